@@ -17,7 +17,10 @@ and for N > 1 the RCCL all-gather of the per-video results (final tubelets + per
 counts).  Workload at N=1 = BASELINE.json configs[1] (+ configs[2]'s tracking on the same video):
 300 frames x 10 000 boxes x 200 classes.  Videos are sharded one per GPU ("weak" scaling).
 
-Prints ONE JSON line (rank 0) with BASELINE.json's metric plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with BASELINE.json's metric.  A plain run sets up, warms up, times the K steps and prints
+the line; `--full` adds everything else the line used to carry (`roofline`, `cpu_baseline`, `timed_check`, the caveat
+legs: other inputs, sizes and configurations, the reference comparisons).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK = 8.0e12          # B/s, MI355X spec (/opt/skills/guides/MI355X_MICROARCH.md)
 METRIC = "boxes/sec whole-node (NMS+temporal-conv+link), 300f\u00d710k-box synth; mAP parity"   # BASELINE.json
+DUMP_ARRAY_BYTES = 4 << 20  # --dump-outputs: at most this much per array (10 arrays + 4 float32 masks: < 64 MB in all)
 
 
 def drop_c_stdio():
@@ -54,6 +58,50 @@ def emit_line(result):
     drop_c_stdio()
     sys.stdout.write(json.dumps(result) + "\n")
     sys.stdout.flush()
+
+
+def _dump_sample(n, k, name):
+    """k of n flat positions (sorted, duplicates dropped) drawn from a seed fixed by the array's name, or None when n <= k:
+    the same positions for every run and every build at the same arguments"""
+    import zlib
+    import numpy as np
+    if n <= k:
+        return None
+    return np.unique(np.random.RandomState(zlib.crc32(name.encode())).randint(0, n, k))
+
+
+def dump_outputs(torch, outdir, keep_idx, keep_cnt, arrays, holes=()):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step -> outdir/<name>.npy.  float32
+    outputs stay float32, everything else (float64, the integer outputs) is written as float64, which holds them exactly.
+    An array of more than DUMP_ARRAY_BYTES is written as a fixed sample of its elements (_dump_sample, flattened); keep_idx
+    as whole (frame, class) lists of a fixed sample of rows, the slots past each list's count as -1 (the step leaves them
+    uninitialised).  Every value written is finite: the tubelet outputs mark the frames a tubelet has no box in with NaN,
+    so an array listed in `holes` is written with those entries as 0 next to <name>_valid.npy (float32, 1 where the value
+    is finite, same sample positions).  arrays: [(name, tensor or None)]."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    cap = keep_idx.shape[-1]
+    rows, cnt = keep_idx.reshape(-1, cap), keep_cnt.reshape(-1)
+    pick = _dump_sample(rows.shape[0], max(1, DUMP_ARRAY_BYTES // (8 * cap)), "keep_idx")
+    if pick is not None:
+        p = torch.from_numpy(pick).to(rows.device)
+        rows, cnt = rows[p], cnt[p]
+    live = torch.arange(cap, device=rows.device)[None, :] < cnt[:, None]
+    arrays = [("keep_idx", torch.where(live, rows, -1)), ("keep_cnt", keep_cnt)] + list(arrays)
+    for name, t in arrays:
+        if t is None:
+            continue
+        dt = torch.float32 if t.dtype == torch.float32 else torch.float64
+        flat = t.reshape(-1)
+        pick = _dump_sample(flat.numel(), DUMP_ARRAY_BYTES // (4 if dt == torch.float32 else 8), name)
+        if pick is not None:
+            flat = flat[torch.from_numpy(pick).to(flat.device)]
+        shape = (flat.numel(),) if pick is not None else tuple(t.shape)
+        if name in holes:
+            ok = torch.isfinite(flat)
+            np.save(os.path.join(outdir, name + "_valid.npy"), ok.to(torch.float32).cpu().numpy().reshape(shape))
+            flat = torch.where(ok, flat, torch.zeros_like(flat))
+        np.save(os.path.join(outdir, name + ".npy"), flat.to(dt).cpu().numpy().reshape(shape))
 
 
 def synth_video_cuda(torch, seed, F, B, C, device, kind="rand"):
@@ -498,7 +546,7 @@ def vid_shape_leg(torch, ops, _lib, dev, taps, V=64, B=300, C=30, T=4):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no torchrun environment: re-execute under torch.distributed.run with N ranks on
+    """`python bench.py --gpus N` with N > 1 and no torchrun environment: run again under torch.distributed.run (a child) with N ranks on
     127.0.0.1 (one rank per GPU over RCCL) -- the same command line the driver would write.  Fewer than N visible devices is an
     error (exit 2), never a silent one-rank run.  Under torchrun the world size comes from the environment; a `--gpus` that
     disagrees with it is reported on stderr and the environment wins (the line's `n_gpus` is always the real world size)."""
@@ -531,7 +579,9 @@ def self_launch(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    # a child process, not exec: this process may already have opened the HIP runtime (device_count above)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -573,13 +623,22 @@ def main():
     ap.add_argument("--check-oracle", action="store_true", help="--videos: check one gathered video against the CPU oracle on rank 0")
     ap.add_argument("--no-sharded-leg", action="store_true", help="skip the default line's configs[3] leg (64 videos sharded, one exchange)")
     ap.add_argument("--sharded-videos", type=int, default=64, help="videos of the default line's configs[3] leg")
-    ap.add_argument("--profile", action="store_true", help="headline step + per-kernel timing only (rocprofv3 runs): no caveat legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the timed outputs against a synchronous run, per-kernel timing + roofline, the CPU "
+                         "baselines, the caveat legs (other inputs, sizes, configurations, reference comparisons); --profile, "
+                         "--no-cpu, --no-coherent, --no-upload and --no-sharded-leg trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; arrays above 4 MiB as a "
+                         "fixed seeded sample; the tubelet outputs' NaN holes as 0 next to <name>_valid.npy)")
+    ap.add_argument("--profile", action="store_true", help="with --full: headline step + per-kernel timing only (rocprofv3 runs): no caveat legs")
     ap.add_argument("--no-coherent", action="store_true", help="skip the coherent-video leg (reported next to value, never part of it)")
     ap.add_argument("--no-upload", action="store_true", help="skip the PCIe-fed pipeline leg (reported next to value, never part of it)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the N > 1 exchange step -- process group, RCCL communicator, all-gather of device tensors from "
                          "every stream -- also in a world of ONE (what a single-GPU box can execute of configs[3])")
     args = ap.parse_args()
+    if args.dump_outputs and args.videos > 0:
+        ap.error("--dump-outputs writes the headline step's outputs; not with --videos")
     self_launch(args)            # plain `python bench.py --gpus N` (no torchrun): becomes N ranks, one per GPU, over RCCL
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         args.no_cpu = True       # the CPU baseline / mAP-parity / PCIe legs are reported at N = 1 only
@@ -682,7 +741,7 @@ def main():
             if not args.no_link and not args.no_rescore:
                 det, tpool, tboxes = ops.rescore_tracks(tracks, ntracks, vb, vs, overlap_thres=args.pool_thres,
                                                         window=args.window, sync=False, ctx=cx)
-                tub = (tracks, ntracks, tpool, tboxes)
+                tub = (tracks, ntracks, tpool, tboxes, anchors, det)
             if (world > 1 or force_x) and exchange:   # the one exchange step: RCCL all-gather of the per-video results over xGMI
                 # (same geometry on every rank: one fixed-shape collective per tensor, nothing the host
                 # has to wait for -- a count exchange would stall the multi-video pipeline)
@@ -737,6 +796,7 @@ def main():
     fence()
     if warm():
         warm()
+    step_no[0] = 0       # (the device is idle here) the last timed step's video depends on --steps and --streams alone
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -767,13 +827,54 @@ def main():
                     "backend": dist.get_backend(), "world": dist.get_world_size(), "own_slot_matches": bool(mine),
                     "note": "HIP events on the step's stream around the two all_gather_into_tensor calls (tubelet boxes + pooled "
                             "scores, kept counts); the collectives run on RCCL's stream, ordered after the step's kernels"}
+    if args.dump_outputs and rank == 0:
+        ki, kc, pooled_t, tub_t, conv_t = out
+        tub_t = tub_t or (None,) * 6
+        dump_outputs(torch, args.dump_outputs, ki, kc,
+                     [("temporal_maxpool", pooled_t), ("temporal_conv", conv_t), ("tracks", tub_t[0]), ("anchors", tub_t[4]),
+                      ("ntracks", tub_t[1]), ("track_det_scores", tub_t[5]), ("track_pooled_scores", tub_t[2]),
+                      ("track_boxes", tub_t[3])],
+                     holes=("tracks", "track_det_scores", "track_pooled_scores", "track_boxes"))
+        del ki, kc, pooled_t, tub_t, conv_t
+    result = None
+    if rank == 0:
+        result = {
+            "metric": METRIC,
+            "value": boxes_per_s, "unit": "boxes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "unpinned_by_nature": "the linking RULE (the reference's trackers are external MATLAB code: the built-in f32 IoU link "
+                                  "stands in), the temporal-convolution taps (external Caffe TCN: a fixed 3-tap filter), the order of "
+                                  "equal scores inside a frame (the reference's argsort is unstable); everything else is pinned to "
+                                  "outputs of the reference (tests/golden)",
+            "config": {"workload": ("configs[1]%s: 1 video/GPU, %d frames x %d boxes x %d classes; per-(frame,class) "
+                                   "NMS thresh %.2f + temporal max-pool w=%d" + ("" if args.no_conv else " + 3-tap temporal convolution") + "%s%s") %
+                                   ("" if args.no_link else "+[2]", F, B, C, args.thresh, args.window,
+                                    "" if args.no_link else "; greedy tubelets: %d tracks/class (stop < %.2f), IoU-link "
+                                    ">= %.2f, spatial max-pool IoU > %.2f + completion + temporal max-pool" %
+                                    (args.max_tracks, args.track_thres, args.link_thres, args.pool_thres),
+                                    "; RCCL all-gather of the final tubelets + kept counts" if (world > 1 or force_x) else ""),
+                       "frames": F, "boxes": B, "classes": C, "scores": args.scores,
+                       "parallelism": "video-per-gpu x%d, %d distinct videos in flight per GPU%s" % (
+                           world, nstreams, ", heavy phases gated one at a time" if args.gate == "heavy" and nstreams > 1 else "")},
+            "exchange": exchange,
+            "per_rank": None if by_rank is None else {
+                "ms_per_step": [t / args.steps * 1e3 for t in by_rank],
+                "boxes_per_s": [F * B * args.steps / t for t in by_rank],
+                "hbm_frac_algorithmic": [F * B * args.steps / t * (16 * C + 16) / HBM_PEAK for t in by_rank],
+                "note": "each rank's own wall time for the K timed steps (its video per step + the exchange); value uses the MAX"},
+            "inputs": ("BASELINE.md section 3 host generator: np.random.RandomState(1000 * 2 + video), integer boxes, scores tie-free per "
+                       "(frame, class)" if (args.inputs == "reference" and args.scores == "rand") else "torch device generator, scores " + args.scores) +
+                      "; HBM-resident when the timed region starts (the PCIe-fed rate is upload_pipeline.boxes_per_s, never `value`)",
+        }
 
+    # ---- --full: everything below runs after the headline and never changes it
     # ---- the TIMED configuration's own results: the last timed step of every stream (asynchronous builds, `--streams` videos
     # in flight on their own streams and contexts) against a synchronous run of the same video on one fresh context, one
     # video at a time on the default stream -- and, below (cpu_baseline.parity_checked_other_video), a video other than
     # the first against the CPU oracle
     timed_check = None
-    if rank == 0:
+    if rank == 0 and args.full:
         torch.cuda.synchronize()
         timed = list(last_out)
         ref_ctx = _lib.Context(local)
@@ -820,8 +921,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- per-kernel timing (HIP events on the kernels' stream), outside the timed region
-    result = None
-    if rank == 0:
+    if rank == 0 and args.full:
         torch.cuda.synchronize()
         step_no[0] = 0
         ctx.set_timing(2)
@@ -1280,31 +1380,7 @@ def main():
             except Exception as e:
                 sharded = {"error": repr(e)[:300]}
 
-        result = {
-            "metric": METRIC,
-            "value": boxes_per_s, "unit": "boxes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "unpinned_by_nature": "the linking RULE (the reference's trackers are external MATLAB code: the built-in f32 IoU link "
-                                  "stands in), the temporal-convolution taps (external Caffe TCN: a fixed 3-tap filter), the order of "
-                                  "equal scores inside a frame (the reference's argsort is unstable); everything else is pinned to "
-                                  "outputs of the reference (tests/golden)",
-            "config": {"workload": ("configs[1]%s: 1 video/GPU, %d frames x %d boxes x %d classes; per-(frame,class) "
-                                   "NMS thresh %.2f + temporal max-pool w=%d" + ("" if args.no_conv else " + 3-tap temporal convolution") + "%s%s") %
-                                   ("" if args.no_link else "+[2]", F, B, C, args.thresh, args.window,
-                                    "" if args.no_link else "; greedy tubelets: %d tracks/class (stop < %.2f), IoU-link "
-                                    ">= %.2f, spatial max-pool IoU > %.2f + completion + temporal max-pool" %
-                                    (args.max_tracks, args.track_thres, args.link_thres, args.pool_thres),
-                                    "; RCCL all-gather of the final tubelets + kept counts" if (world > 1 or force_x) else ""),
-                       "frames": F, "boxes": B, "classes": C, "scores": args.scores,
-                       "parallelism": "video-per-gpu x%d, %d distinct videos in flight per GPU%s" % (
-                           world, nstreams, ", heavy phases gated one at a time" if args.gate == "heavy" and nstreams > 1 else "")},
-            "exchange": exchange,
-            "per_rank": None if by_rank is None else {
-                "ms_per_step": [t / args.steps * 1e3 for t in by_rank],
-                "boxes_per_s": [F * B * args.steps / t for t in by_rank],
-                "hbm_frac_algorithmic": [F * B * args.steps / t * (16 * C + 16) / HBM_PEAK for t in by_rank],
-                "note": "each rank's own wall time for the K timed steps (its video per step + the exchange); value uses the MAX"},
+        result.update({
             "single_video_ms": single_video_ms,          # one video at a time (no videos in flight): the latency of one step
             "value_other_scores": value_other,           # the same step on the other synthetic score distribution
             "value_random_scores": value_random,         # ... with random instead of evenly spaced scores (the sort has real bins to order)
@@ -1318,12 +1394,9 @@ def main():
             "value_other_inputs": ref_inputs,            # the step on the other input generator (device <-> reference host stream)
             "sharded64": sharded,                        # configs[3] at its written size (one exchange per pass, oracle-checked)
             "timed_check": timed_check,
-            "inputs": ("BASELINE.md section 3 host generator: np.random.RandomState(1000 * 2 + video), integer boxes, scores tie-free per "
-                       "(frame, class)" if (args.inputs == "reference" and args.scores == "rand") else "torch device generator, scores " + args.scores) +
-                      "; HBM-resident when the timed region starts (the PCIe-fed rate is upload_pipeline.boxes_per_s, never `value`)",
             "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_allcores": cpu_all, "map_parity": map_par, "pcie": pcie,
             "upload_pipeline": upload,
-        }
+        })
     if world > 1 or force_x:
         dist.barrier()
         dist.destroy_process_group()

@@ -3,7 +3,7 @@
 #   devtools/ab_env.sh <tag> "VAR=a" "VAR=b" ...
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd $R; O=gpurun_out; mkdir -p $O; P=$1; shift
 for rep in 1 2; do i=0; for ev in "$@"; do i=$((i+1))
-  env $ev timeout 300 python bench.py --profile --no-sharded-leg --steps 32 --warmup 8 > $O/${P}_${i}_$rep.json 2> $O/${P}_${i}_$rep.err
+  env $ev timeout 300 python bench.py --full --profile --no-sharded-leg --steps 32 --warmup 8 > $O/${P}_${i}_$rep.json 2> $O/${P}_${i}_$rep.err
   python - <<PY
 import json
 d=json.loads(open("$O/${P}_${i}_$rep.json").read().split("\n")[0])

@@ -6,8 +6,8 @@ O=gpurun_out; mkdir -p $O
 P=$1; shift
 for so in "$@"; do
   n=$(basename $so .so)
-  timeout 300 python devtools/ab_lib.py $so --profile --no-sharded-leg --streams 1 --steps 8 --warmup 3 --inputs device > $O/${P}_${n}_s1.json 2> $O/${P}_${n}_s1.err
-  timeout 300 python devtools/ab_lib.py $so --profile --no-sharded-leg --steps 32 --warmup 8 --inputs device > $O/${P}_${n}_s4.json 2> $O/${P}_${n}_s4.err
+  timeout 300 python devtools/ab_lib.py $so --full --profile --no-sharded-leg --streams 1 --steps 8 --warmup 3 --inputs device > $O/${P}_${n}_s1.json 2> $O/${P}_${n}_s1.err
+  timeout 300 python devtools/ab_lib.py $so --full --profile --no-sharded-leg --steps 32 --warmup 8 --inputs device > $O/${P}_${n}_s4.json 2> $O/${P}_${n}_s4.err
   python - <<PY
 import json
 for tag in ("s1","s4"):

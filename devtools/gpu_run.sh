@@ -20,7 +20,7 @@ cd $R
 O=gpurun_out
 mkdir -p $O
 P=$1; shift
-STEP="python $R/bench.py --profile --no-sharded-leg --streams 1"
+STEP="python $R/bench.py --full --profile --no-sharded-leg --streams 1"
 n=0
 for what in "$@"; do
   case "$what" in
