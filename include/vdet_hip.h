@@ -45,6 +45,10 @@
  *                                                                     series one thread per series (slower, same results)
  *   single-launch h_* calls                n <= 640 rows, t <= 256    larger inputs take the general kernel chain (same results)
  *   link table up front                    B <= 1024                  larger frames scan link steps on demand (same results)
+ *   evaluator: tracks per (frame, class)   T <= 1024                  VDET_EINVAL (vdet_eval_match_tracks[_batch])
+ *   evaluator: gt boxes per (video, frame, class)  <= 256             VDET_EINVAL (vdet_eval_gt_upload)
+ *   evaluator: gt table cells              videos x frames x K < 2^31 VDET_EINVAL;  class slots 1 <= K <= 65536
+ *   evaluator: stream entries              < 2^31 (per add: C*T*F or F*C*cap < 2^31)   VDET_EINVAL
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -442,6 +446,60 @@ int vdet_rescore_tracks(vdet_ctx *ctx, const float *d_tracks, const int32_t *d_n
                         const float *d_scores, int64_t F, int64_t B, int64_t C, int max_tracks,
                         double overlap_thres, int window, double *d_det_score, double *d_pooled,
                         float *d_boxes_out);
+
+/* ---- device evaluator (vdetlib_amd/eval.py on the GPU; ops.DetEvaluator) --------------------------------------------
+ *
+ * Per-class AP / mAP of detections against ground truth, with eval.py's evaluate() as the specification (bit for bit in
+ * the matching, AP up to the order of one f64 sum).  A caller-owned STREAM of (class slot i32, score f64, tp u8) entries
+ * collects the matched detections of every add; restricted to one class, its order is the order eval.py's adapters list
+ * the detections in (tubelets (t, f), keep lists (f, k), video after video), so the stable sort of vdet_eval_ap
+ * reproduces Python's stable sorted().  Class slots: the caller maps its evaluated classes to 0..K-1 (h_col_slot[c] for
+ * score column c; -1 = class not evaluated, its detections are dropped).  rule 0 = VOC (IoU >= iou_thr, arg-max over the
+ * unmatched ground truths, used ones count -1), 1 = ILSVRC VID (per-box threshold min(iou_thr, wh/((w+10)(h+10)))).
+ *
+ * Ground truth: a CSR built once (vdet_eval_gt_upload) from per-box (video index, frame, class slot, box f64) rows in
+ * annotation order; h_vid_nf[v] = frames of video v in the table (boxes of frame >= nf, of a slot outside [0, K) or of a
+ * video outside [0, NV) are not stored -- they can never match but still count in the caller's n_gt).
+ *   d_gt_boxes [G,4] f64 (capacity G), d_gt_off [sum_v nf_v*K + 1] i32, d_vid_meta [NV,2] i64.  Synchronous.
+ * Match calls enqueue one match launch and the order-preserving compaction, append at d_st_*[st_len ..] (capacity st_cap
+ * must hold st_len + every candidate position of the call) and wait once: *h_count = entries appended.
+ * vid: the detections' video in the table, -1 = unknown (every detection a false positive).
+ */
+int vdet_eval_gt_upload(vdet_ctx *ctx, const int32_t *h_vid, const int64_t *h_frame, const int32_t *h_slot, const double *h_boxes,
+                        int64_t G, const int64_t *h_vid_nf, int64_t NV, int K, double *d_gt_boxes, int32_t *d_gt_off,
+                        int64_t *d_vid_meta);
+
+/* Tubelets of one video (vdet_track_volume / vdet_rescore_tracks outputs): d_boxes [C,T,F,box_stride] f32 (5: the track
+ * rows, 4: d_boxes_out), d_scores [C,T,F] f64 (scores_f64) or f32, NaN = no box; tracks t >= d_ntracks[c] are skipped.
+ * Frame f of the volume is frame f + 1 of the table. */
+int vdet_eval_match_tracks(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K,
+                           int rule, double iou_thr, int vid, int64_t F, int64_t C, int T, const float *d_boxes, int box_stride,
+                           const void *d_scores, int scores_f64, const int32_t *d_ntracks, const int32_t *h_col_slot,
+                           int32_t *d_st_slot, double *d_st_score, uint8_t *d_st_tp, int64_t st_len, int64_t st_cap,
+                           int64_t *h_count);
+
+/* vdet_video_batch's tubelets of V videos in ONE match launch: video v's arrays start at element C*T*h_frame_off[v]
+ * ([C,T,F_v] like vdet_eval_match_tracks), d_ntracks [V,C], h_vid [V] its table indices. */
+int vdet_eval_match_tracks_batch(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta,
+                                 int K, int rule, double iou_thr, const int32_t *h_vid, const int64_t *h_frame_off, int64_t V,
+                                 int64_t C, int T, const float *d_boxes, int box_stride, const void *d_scores, int scores_f64,
+                                 const int32_t *d_ntracks, const int32_t *h_col_slot, int32_t *d_st_slot, double *d_st_score,
+                                 uint8_t *d_st_tp, int64_t st_len, int64_t st_cap, int64_t *h_count);
+
+/* NMS survivors (vdet_nms_volume[_topk] / vdet_nms_track_volume / vdet_video_batch): d_boxes [F,B,4], d_scores [F,B,C] or
+ * [F,C,B] f32, d_keep_idx [F,C,cap], d_keep_cnt [F,C].  Every list is walked in its own order; a list that is not
+ * non-increasing in score, a kept NaN score or a count / index out of range latches VDET_EINVAL (vdet_sync). */
+int vdet_eval_match_keep(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K,
+                         int rule, double iou_thr, int vid, const float *d_boxes, const float *d_scores, int layout, int64_t F,
+                         int64_t B, int64_t C, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
+                         const int32_t *h_col_slot, int32_t *d_st_slot, double *d_st_score, uint8_t *d_st_tp, int64_t st_len,
+                         int64_t st_cap, int64_t *h_count);
+
+/* AP of every class slot over a stream of n entries: stable LSD radix sort by (slot asc, score desc; -0.0 == +0.0), then
+ * per slot eval.py's average_precision with n_gt = d_ngt[k] (<= 0: NaN).  d_ap [K] f64.  d_perm [n] i32 or NULL: the
+ * sorted order (stream positions).  Asynchronous. */
+int vdet_eval_ap(vdet_ctx *ctx, const int32_t *d_st_slot, const double *d_st_score, const uint8_t *d_st_tp, int64_t n, int K,
+                 const int64_t *d_ngt, double *d_ap, int32_t *d_perm);
 
 #ifdef __cplusplus
 }

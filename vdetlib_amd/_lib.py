@@ -59,6 +59,14 @@ SYMBOLS = {
     "vdet_temporal_maxpool_f32": (_ci, [_vp, _vp, _vp, _i64, _i64, _ci, _f32]),
     "vdet_temporal_conv_f32": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _ci, _f32, _f32]),
     "vdet_temporal_maxpool_conv_f32": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _ci, _f32, _vp, _f32, _f32]),
+    "vdet_eval_gt_upload": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _ci, _vp, _vp, _vp]),
+    "vdet_eval_match_tracks": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _f64, _ci, _i64, _i64, _ci, _vp, _ci, _vp, _ci, _vp, _vp,
+                                     _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_i64)]),
+    "vdet_eval_match_tracks_batch": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _f64, _vp, _vp, _i64, _i64, _ci, _vp, _ci, _vp, _ci, _vp,
+                                           _vp, _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_i64)]),
+    "vdet_eval_match_keep": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _f64, _ci, _vp, _vp, _ci, _i64, _i64, _i64, _vp, _vp, _i64, _vp,
+                                   _vp, _vp, _vp, _i64, _i64, ctypes.POINTER(_i64)]),
+    "vdet_eval_ap": (_ci, [_vp, _vp, _vp, _vp, _i64, _ci, _vp, _vp, _vp]),
 }
 
 

@@ -28,6 +28,7 @@
 #include "track_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "gemm_kernels.hpp"
+#include "eval_kernels.hpp"
 
 using namespace vdet;
 
@@ -181,6 +182,8 @@ struct vdet_ctx {
     size_t fbatch_in_cap = 0, fbatch_out_cap = 0;
     bool fbatch_attr = false;
     size_t dyn_lds_max = 0;
+    // device evaluator (eval_kernels.hpp): dense per-call match results, compaction counts, radix-sort ping-pong buffers
+    DevBuf ev_tab, ev_dtp, ev_dsc, ev_dslot, ev_bcnt, ev_boff, ev_key[2], ev_val[2], ev_hist;
 };
 
 namespace {
@@ -255,6 +258,7 @@ int translate_status(vdet_ctx *c, int st)
 {
     if (st & kStPoolAsync) return fail(c, VDET_EAGAIN, "adjacency pool overflow in an asynchronous graph build: run the calls again");
     if (st & kStBadOrder) return fail(c, VDET_EINVAL, "a caller-supplied candidate list holds a count or a box index out of range");
+    if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
     if (st & kStPool) return fail(c, VDET_EHIP, "internal: adjacency pool overflow");
@@ -1232,7 +1236,8 @@ int vdet_destroy(vdet_ctx *c)
                       &c->rowz, &c->rowmeta, &c->groupz, &c->adj, &c->comp, &c->origidx, &c->out64,
                       &c->trk_frames, &c->trk_boxes, &c->b1, &c->b2, &c->iou_out, &c->order, &c->ncand, &c->keepidx,
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
-                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab, &c->vidtab, &c->nover, &c->ordncand};
+                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab, &c->vidtab, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
+                      &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -2683,6 +2688,237 @@ int vdet_svm_scores_f32(vdet_ctx *c, const float *h_feat, int64_t n, int64_t k, 
                         float *h_out)
 {
     return svm_scores_impl<float>(c, h_feat, n, k, h_W, h_B, m, h_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device evaluator (eval_kernels.hpp; the specification is vdetlib_amd/eval.py)
+// ---------------------------------------------------------------------------------------------
+int vdet_eval_gt_upload(vdet_ctx *c, const int32_t *h_vid, const int64_t *h_frame, const int32_t *h_slot, const double *h_boxes,
+                        int64_t G, const int64_t *h_vid_nf, int64_t NV, int K, double *d_gt_boxes, int32_t *d_gt_off,
+                        int64_t *d_vid_meta)
+{
+    if (!c) return VDET_EINVAL;
+    if (G < 0 || NV < 0 || K < 1 || K > 65536) return fail(c, VDET_EINVAL, "bad ground-truth table shape");
+    if ((G && (!h_vid || !h_frame || !h_slot || !h_boxes)) || (NV && !h_vid_nf) || !d_gt_off || (NV && !d_vid_meta))
+        return fail(c, VDET_EINVAL, "null buffer");
+    std::vector<int64_t> meta((size_t)NV * 2);
+    int64_t total = 0;
+    for (int64_t v = 0; v < NV; ++v) {
+        if (h_vid_nf[v] < 0) return fail(c, VDET_EINVAL, "negative frame count");
+        meta[2 * v] = total;
+        meta[2 * v + 1] = h_vid_nf[v];
+        total += h_vid_nf[v] * K;
+        if (total > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "ground-truth table too large (videos x frames x classes >= 2^31)");
+    }
+    auto cell = [&](int64_t i) -> int64_t {
+        const int32_t v = h_vid[i], s = h_slot[i];
+        if (v < 0 || v >= NV || s < 0 || s >= K || h_frame[i] < 0 || h_frame[i] >= meta[2 * v + 1]) return -1;
+        return meta[2 * v] + h_frame[i] * K + s;
+    };
+    std::vector<int32_t> off((size_t)total + 1, 0);
+    int64_t placed = 0;
+    for (int64_t i = 0; i < G; ++i) {
+        const int64_t o = cell(i);
+        if (o < 0) continue;
+        if (++off[(size_t)o + 1] > kEvalMaxGt)
+            return fail(c, VDET_EINVAL, "more than %d ground-truth boxes in one (video, frame, class)", kEvalMaxGt);
+        ++placed;
+    }
+    if (placed > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many ground-truth boxes");
+    for (int64_t o = 0; o < total; ++o) off[(size_t)o + 1] += off[(size_t)o];
+    std::vector<int32_t> cur(off.begin(), off.end() - 1);
+    std::vector<double> boxes((size_t)placed * 4);
+    for (int64_t i = 0; i < G; ++i) {           // annotation order within every cell
+        const int64_t o = cell(i);
+        if (o < 0) continue;
+        const int32_t p = cur[(size_t)o]++;
+        for (int q = 0; q < 4; ++q) boxes[(size_t)p * 4 + q] = h_boxes[i * 4 + q];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (placed) HIPCHK(c, hipMemcpyAsync(d_gt_boxes, boxes.data(), boxes.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_gt_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (NV) HIPCHK(c, hipMemcpyAsync(d_vid_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, host_sync(c));        // the host vectors die here
+    return VDET_OK;
+}
+
+static int eval_gt_args(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K, int rule,
+                 double iou_thr, EvGt &g)
+{
+    if (!d_gt_off || !d_vid_meta || K < 1 || K > 65536) return fail(c, VDET_EINVAL, "bad ground-truth CSR");
+    if (rule != 0 && rule != 1) return fail(c, VDET_EINVAL, "rule must be 0 (VOC) or 1 (ILSVRC)");
+    g = EvGt{d_gt_boxes, d_gt_off, d_vid_meta, K, rule, iou_thr};
+    return VDET_OK;
+}
+
+// the dense results of a match launch (c->ev_dtp / ev_dsc / ev_dslot, N entries) -> appended to the stream at st_len, in
+// order; one host wait to learn the count
+static int eval_compact(vdet_ctx *c, int64_t N, int32_t *st_slot, double *st_sc, uint8_t *st_tp, int64_t st_len, int64_t *h_count)
+{
+    const int64_t nb = (N + kEvalTile - 1) / kEvalTile;
+    HIPCHK(c, c->ev_bcnt.reserve((size_t)nb * 8 + 8));
+    HIPCHK(c, c->ev_boff.reserve((size_t)nb * 8 + 8));
+    int64_t *total = c->ev_bcnt.as<int64_t>() + nb;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(eval_count_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_dtp.as<int8_t>(), N,
+                           c->ev_bcnt.as<int64_t>());
+        hipLaunchKernelGGL(eval_scan_kernel<int64_t>, dim3(1), dim3(1024), 0, c->stream, c->ev_bcnt.as<int64_t>(), nb,
+                           c->ev_boff.as<int64_t>(), total);
+        hipLaunchKernelGGL(eval_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_dtp.as<int8_t>(),
+                           c->ev_dsc.as<double>(), c->ev_dslot.as<int32_t>(), N, c->ev_boff.as<int64_t>(), st_len, st_slot, st_sc, st_tp);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_count, total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, host_sync(c));
+    return VDET_OK;
+}
+
+static int eval_dense(vdet_ctx *c, int64_t N)
+{
+    HIPCHK(c, c->ev_dtp.reserve((size_t)N));
+    HIPCHK(c, c->ev_dsc.reserve((size_t)N * 8));
+    HIPCHK(c, c->ev_dslot.reserve((size_t)N * 4));
+    return VDET_OK;
+}
+
+int vdet_eval_match_tracks_batch(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K,
+                                 int rule, double iou_thr, const int32_t *h_vid, const int64_t *h_frame_off, int64_t V, int64_t C,
+                                 int T, const float *d_boxes, int box_stride, const void *d_scores, int scores_f64,
+                                 const int32_t *d_ntracks, const int32_t *h_col_slot, int32_t *d_st_slot, double *d_st_score,
+                                 uint8_t *d_st_tp, int64_t st_len, int64_t st_cap, int64_t *h_count)
+{
+    if (!c) return VDET_EINVAL;
+    EvGt g;
+    int rc = eval_gt_args(c, d_gt_boxes, d_gt_off, d_vid_meta, K, rule, iou_thr, g);
+    if (rc) return rc;
+    if (!h_count || !h_vid || !h_frame_off || !h_col_slot) return fail(c, VDET_EINVAL, "null buffer");
+    *h_count = 0;
+    if (V < 1 || C < 1 || C > 65535 || T < 0 || T > kEvalMaxT || (box_stride != 4 && box_stride != 5))
+        return fail(c, VDET_EINVAL, "bad shape (1 <= C <= 65535, 0 <= T <= %d, box stride 4 or 5)", kEvalMaxT);
+    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame_off must start at 0");
+    for (int64_t v = 0; v < V; ++v)
+        if (h_frame_off[v + 1] <= h_frame_off[v]) return fail(c, VDET_EINVAL, "frame_off must be strictly increasing");
+    const int64_t Ft = h_frame_off[V];
+    const int64_t N = C * T * Ft;
+    if (Ft > 0x7FFFFFF0ll || N > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes");
+    if (T == 0) return VDET_OK;
+    if (!d_boxes || !d_scores || !d_ntracks || !d_st_slot || !d_st_score || !d_st_tp) return fail(c, VDET_EINVAL, "null buffer");
+    if (st_len < 0 || st_len + N > st_cap) return fail(c, VDET_EINVAL, "stream capacity too small (%lld + %lld > %lld)",
+                                                      (long long)st_len, (long long)N, (long long)st_cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    // host tables: column slots [C] i32 | video table indices [V] i32 | frame offsets [V+1] i64
+    const size_t o_vid = ((size_t)C * 4 + 7) & ~(size_t)7, o_off = (o_vid + (size_t)V * 4 + 7) & ~(size_t)7;
+    std::vector<char> tab(o_off + (size_t)(V + 1) * 8);
+    memcpy(tab.data(), h_col_slot, (size_t)C * 4);
+    memcpy(tab.data() + o_vid, h_vid, (size_t)V * 4);
+    memcpy(tab.data() + o_off, h_frame_off, (size_t)(V + 1) * 8);
+    if ((rc = eval_dense(c, N))) return rc;
+    HIPCHK(c, c->ev_tab.reserve(tab.size()));
+    HIPCHK(c, hipMemcpyAsync(c->ev_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    char *tb = c->ev_tab.as<char>();
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(eval_match_tracks_kernel, dim3((unsigned)Ft, (unsigned)C), dim3(64), 0, c->stream, g,
+                           reinterpret_cast<const int64_t *>(tb + o_off), (int)V, reinterpret_cast<const int32_t *>(tb + o_vid), (int)C,
+                           T, d_boxes, box_stride, scores_f64 ? static_cast<const double *>(d_scores) : (const double *)nullptr,
+                           scores_f64 ? (const float *)nullptr : static_cast<const float *>(d_scores), d_ntracks,
+                           reinterpret_cast<const int32_t *>(tb), c->ev_dtp.as<int8_t>(), c->ev_dsc.as<double>(),
+                           c->ev_dslot.as<int32_t>());
+    }
+    HIPCHK(c, hipGetLastError());
+    return eval_compact(c, N, d_st_slot, d_st_score, d_st_tp, st_len, h_count);   // (its host wait also retires `tab`)
+}
+
+int vdet_eval_match_tracks(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K, int rule,
+                           double iou_thr, int vid, int64_t F, int64_t C, int T, const float *d_boxes, int box_stride,
+                           const void *d_scores, int scores_f64, const int32_t *d_ntracks, const int32_t *h_col_slot,
+                           int32_t *d_st_slot, double *d_st_score, uint8_t *d_st_tp, int64_t st_len, int64_t st_cap,
+                           int64_t *h_count)
+{
+    const int64_t foff[2] = {0, F};
+    return vdet_eval_match_tracks_batch(c, d_gt_boxes, d_gt_off, d_vid_meta, K, rule, iou_thr, &vid, foff, 1, C, T, d_boxes,
+                                        box_stride, d_scores, scores_f64, d_ntracks, h_col_slot, d_st_slot, d_st_score, d_st_tp,
+                                        st_len, st_cap, h_count);
+}
+
+int vdet_eval_match_keep(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K, int rule,
+                         double iou_thr, int vid, const float *d_boxes, const float *d_scores, int layout, int64_t F, int64_t B,
+                         int64_t C, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, const int32_t *h_col_slot,
+                         int32_t *d_st_slot, double *d_st_score, uint8_t *d_st_tp, int64_t st_len, int64_t st_cap,
+                         int64_t *h_count)
+{
+    if (!c) return VDET_EINVAL;
+    EvGt g;
+    int rc = eval_gt_args(c, d_gt_boxes, d_gt_off, d_vid_meta, K, rule, iou_thr, g);
+    if (rc) return rc;
+    if (!h_count || !h_col_slot) return fail(c, VDET_EINVAL, "null buffer");
+    *h_count = 0;
+    if (layout != VDET_LAYOUT_FBC && layout != VDET_LAYOUT_FCB) return fail(c, VDET_EINVAL, "bad layout");
+    if (F < 1 || B < 1 || C < 1 || C > 65535 || cap < 0 || B > 0x7FFFFFFF) return fail(c, VDET_EINVAL, "bad shape");
+    const int64_t N = F * C * cap;
+    if (F > 0x7FFFFFF0ll || N > 0x7FFFFFF0ll || F * B * C > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many kept entries");
+    if (cap == 0) return VDET_OK;
+    if (!d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt || !d_st_slot || !d_st_score || !d_st_tp)
+        return fail(c, VDET_EINVAL, "null buffer");
+    if (st_len < 0 || st_len + N > st_cap) return fail(c, VDET_EINVAL, "stream capacity too small (%lld + %lld > %lld)",
+                                                      (long long)st_len, (long long)N, (long long)st_cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if ((rc = eval_dense(c, N))) return rc;
+    if ((rc = upload(c, c->ev_tab, h_col_slot, (size_t)C * 4))) return rc;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(eval_match_keep_kernel, dim3((unsigned)F, (unsigned)C), dim3(64), 0, c->stream, g, vid, (int)C, (int)B,
+                           layout, d_boxes, d_scores, d_keep_idx, d_keep_cnt, cap, c->ev_tab.as<int32_t>(), c->ev_dtp.as<int8_t>(),
+                           c->ev_dsc.as<double>(), c->ev_dslot.as<int32_t>(), &c->d_cnt->status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return eval_compact(c, N, d_st_slot, d_st_score, d_st_tp, st_len, h_count);
+}
+
+int vdet_eval_ap(vdet_ctx *c, const int32_t *d_st_slot, const double *d_st_score, const uint8_t *d_st_tp, int64_t n, int K,
+                 const int64_t *d_ngt, double *d_ap, int32_t *d_perm)
+{
+    if (!c) return VDET_EINVAL;
+    if (n < 0 || n > 0x7FFFFFF0ll || K < 1 || K > 65536) return fail(c, VDET_EINVAL, "bad shape (stream < 2^31, 1 <= K <= 65536)");
+    if (!d_ngt || !d_ap || (n && (!d_st_slot || !d_st_score || !d_st_tp))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    const uint64_t *val = nullptr;
+    if (n) {
+        const int64_t nb = (n + kEvalTile - 1) / kEvalTile;
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, c->ev_key[i].reserve((size_t)n * 8));
+            HIPCHK(c, c->ev_val[i].reserve((size_t)n * 8));
+        }
+        HIPCHK(c, c->ev_hist.reserve((size_t)nb * 256 * 8));
+        uint32_t *hist = c->ev_hist.as<uint32_t>(), *hoff = hist + nb * 256;
+        const int passes = 8 + (K <= 1 ? 0 : (K <= 256 ? 1 : 2));
+        StageTimer tm(c, ST_SORT);
+        hipLaunchKernelGGL(eval_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_st_slot, d_st_score, n,
+                           c->ev_key[0].as<uint64_t>(), c->ev_val[0].as<uint64_t>());
+        int cur = 0;
+        for (int p = 0; p < passes; ++p) {
+            hipLaunchKernelGGL(eval_hist_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_key[cur].as<uint64_t>(),
+                               c->ev_val[cur].as<uint64_t>(), n, p, hist);
+            hipLaunchKernelGGL(eval_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, c->stream, hist, nb * 256, hoff, (uint32_t *)nullptr);
+            hipLaunchKernelGGL(eval_radix_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, c->ev_key[cur].as<uint64_t>(),
+                               c->ev_val[cur].as<uint64_t>(), n, p, hoff, c->ev_key[cur ^ 1].as<uint64_t>(),
+                               c->ev_val[cur ^ 1].as<uint64_t>());
+            cur ^= 1;
+        }
+        val = c->ev_val[cur].as<uint64_t>();
+        if (d_perm)
+            hipLaunchKernelGGL(eval_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, val, n, d_perm);
+    }
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(eval_ap_kernel, dim3((unsigned)K), dim3(256), 0, c->stream, val, d_st_tp, n, d_ngt, d_ap);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
 }
 
 }  // extern "C"

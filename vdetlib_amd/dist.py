@@ -223,3 +223,12 @@ class PackedExchange(object):
             fields.append(buf[off:off + n])
             off = (off + n + 15) // 16 * 16
         return hdr, fields
+
+
+def gather_eval_stream(slot, score, tp, group=None, force=False):
+    """The device evaluator's streams of every rank (ops.DetEvaluator.compute), concatenated RANK-MAJOR: ties between
+    videos are then broken as if one evaluator had been fed rank 0's videos, then rank 1's, ... .  slot int32 [n],
+    score f64 [n], tp uint8 [n]; one ragged all-gather each."""
+    if not _collective(group, force):
+        return slot, score, tp
+    return tuple(torch.cat(all_gather_ragged(t, group, force)) for t in (slot, score, tp))

@@ -483,3 +483,202 @@ def rescore_tracks(tracks, ntracks, boxes, scores, overlap_thres=0.7, window=3, 
     if sync:
         ctx.sync()
     return det, pooled, ob
+
+
+class DetEvaluator(object):
+    """Per-class AP / mAP of device detections (include/vdet_hip.h: the device evaluator); ``vdetlib_amd.eval.evaluate``
+    is the specification -- same matching bit for bit, the same AP up to the order of one f64 sum (< 1e-12).
+
+      ev = DetEvaluator(eval.gt_table_from_annots(annots), classes=None, iou_thr=0.5, rule='voc')
+      ev.add_tracks(video, tracks, ntracks, scores, boxes=None)      # track_volume / rescore_tracks outputs
+      ev.add_keep_lists(video, boxes, scores, keep_idx, keep_cnt)    # nms_volume[_topk] / nms_track_volume survivors
+      ev.add_batch(videos, video_batch(...))                         # all videos of a batch, one match launch
+      aps, mAP = ev.compute()                                        # {class_index: AP}, float
+
+    Every add appends its matched detections to a device stream of (class, score, tp); ``compute`` sorts it stably by
+    (class, score desc), so detections of equal score keep the order of the adds -- the order in which the host
+    evaluator would have to be given the videos.  ``compute(group=...)`` all-gathers the streams of every rank first
+    (rank-major), so each rank builds its evaluator from the FULL ground-truth table and all ranks get the same mAP."""
+
+    def __init__(self, gt_table, classes=None, iou_thr=0.5, rule='voc', device=None):
+        if rule not in ('voc', 'ilsvrc'):
+            raise ValueError("rule must be 'voc' or 'ilsvrc'")
+        self.rule, self.iou_thr = rule, float(iou_thr)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError("expected a CUDA/HIP device (vdetlib_amd has no CPU path)")
+        vid = np.ascontiguousarray(gt_table['video'], dtype=np.int32).reshape(-1)
+        frame = np.ascontiguousarray(gt_table['frame'], dtype=np.int64).reshape(-1)
+        cls = np.asarray(gt_table['class_index'], dtype=np.int64).reshape(-1)
+        bbox = np.ascontiguousarray(gt_table['bbox'], dtype=np.float64).reshape(-1, 4)
+        if not (len(vid) == len(frame) == len(cls) == len(bbox)):
+            raise ValueError("gt_table arrays differ in length")
+        self.videos = list(gt_table['videos'])
+        self._vidx = {v: i for i, v in enumerate(self.videos)}
+        self.classes = sorted(set(int(c) for c in cls)) if classes is None else [int(c) for c in classes]
+        if not self.classes:
+            raise ValueError("no classes to evaluate")
+        self._slot = {c: k for k, c in enumerate(self.classes)}
+        K = len(self.classes)
+        slot = np.array([self._slot.get(int(c), -1) for c in cls], dtype=np.int32)
+        self.n_gt = np.bincount(slot[slot >= 0], minlength=K).astype(np.int64)
+        NV = len(self.videos)
+        nf = np.zeros(max(NV, 1), dtype=np.int64)
+        ok = (slot >= 0) & (frame >= 0) & (vid >= 0) & (vid < NV)
+        if ok.any():
+            np.maximum.at(nf, vid[ok], frame[ok] + 1)
+        nf = nf[:NV]
+        ncell = int(nf.sum()) * K
+        if ncell >= 2 ** 31 - 16:
+            raise ValueError("ground-truth table too large (videos x frames x classes >= 2^31)")
+        dev = self.device
+        self._gt_boxes = torch.empty((max(len(bbox), 1), 4), dtype=torch.float64, device=dev)
+        self._gt_off = torch.empty((ncell + 1,), dtype=torch.int32, device=dev)
+        self._gt_meta = torch.empty((max(NV, 1), 2), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ctx = _ctx_for(self._gt_off, None)
+            ctx.check(ctx.lib.vdet_eval_gt_upload(
+                ctx.h, vid.ctypes.data, frame.ctypes.data, slot.ctypes.data, bbox.ctypes.data, len(vid), nf.ctypes.data, NV, K,
+                self._gt_boxes.data_ptr(), self._gt_off.data_ptr(), self._gt_meta.data_ptr()))
+        self._ngt = torch.from_numpy(self.n_gt).to(dev)
+        self._cls_t = torch.tensor(self.classes, dtype=torch.int64, device=dev)
+        self._n = 0
+        self._st = (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float64, device=dev),
+                    torch.empty(0, dtype=torch.uint8, device=dev))
+
+    # -- stream ------------------------------------------------------------------------------------------------------
+    def _reserve(self, extra):
+        need = self._n + int(extra)
+        if need <= self._st[0].numel():
+            return
+        cap = max(need, 2 * self._st[0].numel(), 1024)
+        new = tuple(torch.empty(cap, dtype=t.dtype, device=self.device) for t in self._st)
+        for a, b in zip(new, self._st):
+            a[:self._n] = b[:self._n]
+        self._st = new
+
+    def _gt_args(self):
+        return (self._gt_boxes.data_ptr(), self._gt_off.data_ptr(), self._gt_meta.data_ptr(), len(self.classes),
+                0 if self.rule == 'voc' else 1, self.iou_thr)
+
+    def _col_slots(self, C, class_base):
+        return np.array([self._slot.get(c + class_base, -1) for c in range(C)], dtype=np.int32)
+
+    def _append(self, call, extra):
+        self._reserve(extra)
+        cnt = ctypes.c_int64(0)
+        st = self._st
+        with torch.cuda.device(self.device):
+            ctx = _ctx_for(st[0], None)
+            ctx.check(call(ctx, (st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), self._n, st[0].numel(), ctypes.byref(cnt))))
+            ctx.sync()          # latched failures (a keep list out of order) surface here, before the stream grows
+        self._n += int(cnt.value)
+        return int(cnt.value)
+
+    def _check(self, *ts):
+        for t in ts:
+            if not t.is_cuda or t.device != self.device:
+                raise ValueError("every tensor must live on the evaluator's GPU (%s)" % self.device)
+
+    def add_tracks(self, video, tracks, ntracks, scores, boxes=None):
+        """Tubelets of one video: tracks [C,T,F,5] f32 (track_volume), ntracks [C] int32, scores [C,T,F] f64 or f32
+        (NaN = no box; e.g. rescore_tracks' pooled), boxes [C,T,F,4] f32 (rescore_tracks' boxes; default: the track
+        boxes).  Returns the number of detections added."""
+        if tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+            raise ValueError("tracks must be float32 [C,T,F,5]")
+        C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+        if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+            raise ValueError("ntracks must be int32 [C]")
+        if scores.dtype not in (torch.float32, torch.float64) or tuple(scores.shape) != (C, T, F):
+            raise ValueError("scores must be float32 / float64 [C,T,F]")
+        if boxes is not None and (boxes.dtype != torch.float32 or tuple(boxes.shape) != (C, T, F, 4)):
+            raise ValueError("boxes must be float32 [C,T,F,4]")
+        self._check(tracks, ntracks, scores, *([boxes] if boxes is not None else []))
+        bx = (tracks if boxes is None else boxes).contiguous()
+        scores, ntracks = scores.contiguous(), ntracks.contiguous()
+        slots = self._col_slots(C, 1)
+        vid = self._vidx.get(video, -1)
+        stride = 5 if boxes is None else 4
+        return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks(
+            ctx.h, *self._gt_args(), vid, F, C, T, bx.data_ptr(), stride, scores.data_ptr(), int(scores.dtype == torch.float64),
+            ntracks.data_ptr(), slots.ctypes.data, *st), C * T * F)
+
+    def add_keep_lists(self, video, boxes, scores, keep_idx, keep_cnt, layout='FBC', class_base=1):
+        """NMS survivors of one video: boxes [F,B,4] f32, scores [F,B,C] ('FBC') / [F,C,B] ('FCB') f32, keep_idx
+        [F,C,cap] int32 (descending score: a list that is not, or a kept NaN score, raises ValueError), keep_cnt [F,C]
+        int32; column c is class c + class_base.  Returns the number of detections added."""
+        if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+            raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+        if keep_idx.dtype != torch.int32 or keep_cnt.dtype != torch.int32 or keep_idx.dim() != 3:
+            raise ValueError("keep_idx must be int32 [F,C,cap], keep_cnt int32 [F,C]")
+        F, C, cap = keep_idx.shape
+        if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4 or tuple(keep_cnt.shape) != (F, C):
+            raise ValueError("boxes [F,B,4], keep_idx [F,C,cap], keep_cnt [F,C]")
+        B = boxes.shape[1]
+        if layout == 'FBC':
+            lay, shp = _lib.LAYOUT_FBC, (F, B, C)
+        elif layout == 'FCB':
+            lay, shp = _lib.LAYOUT_FCB, (F, C, B)
+        else:
+            raise ValueError("layout must be 'FBC' or 'FCB'")
+        if tuple(scores.shape) != shp:
+            raise ValueError("scores must be %s" % ('[F,B,C]' if layout == 'FBC' else '[F,C,B]'))
+        self._check(boxes, scores, keep_idx, keep_cnt)
+        boxes, scores, keep_idx, keep_cnt = boxes.contiguous(), scores.contiguous(), keep_idx.contiguous(), keep_cnt.contiguous()
+        slots = self._col_slots(C, int(class_base))
+        vid = self._vidx.get(video, -1)
+        return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_keep(
+            ctx.h, *self._gt_args(), vid, boxes.data_ptr(), scores.data_ptr(), lay, F, B, C, keep_idx.data_ptr(),
+            keep_cnt.data_ptr(), cap, slots.ctypes.data, *st), F * C * cap)
+
+    def add_batch(self, videos, batch_out):
+        """The re-scored tubelets (``pooled`` scores, ``tboxes`` boxes) of every video of a ``video_batch`` result, in ONE
+        match launch; videos[v] names video v.  Same stream as add_tracks video after video."""
+        off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
+        V = len(off) - 1
+        if len(videos) != V:
+            raise ValueError("one name per video of the batch")
+        if not batch_out.get('pooled'):
+            raise ValueError("video_batch ran without re-scoring (rescore=False): no tubelet scores")
+        nt = batch_out['ntracks']
+        tr0, sc0, bx0 = batch_out['tracks'][0], batch_out['pooled'][0], batch_out['tboxes'][0]
+        C, T = tr0.shape[0], tr0.shape[1]
+        if nt.dtype != torch.int32 or tuple(nt.shape) != (V, C) or sc0.dtype != torch.float64:
+            raise ValueError("not a video_batch result")
+        self._check(nt, sc0, bx0)
+        nt = nt.contiguous()
+        vids = np.array([self._vidx.get(v, -1) for v in videos], dtype=np.int32)
+        slots = self._col_slots(C, 1)
+        Ft = int(off[-1])
+        return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks_batch(
+            ctx.h, *self._gt_args(), vids.ctypes.data, off.ctypes.data, V, C, T, bx0.data_ptr(), 4, sc0.data_ptr(), 1,
+            nt.data_ptr(), slots.ctypes.data, *st), C * T * Ft)
+
+    def stream(self, raw=False):
+        """The stream so far: (class_index int64, score f64, tp bool) device tensors (raw: class slot int32, tp uint8)."""
+        s, sc, tp = (t[:self._n] for t in self._st)
+        if raw:
+            return s, sc, tp
+        return self._cls_t[s.long()], sc, tp.bool()
+
+    def compute(self, group=None, return_order=False):
+        """({class_index: AP}, mAP over the classes with ground truth) -- eval.evaluate's result.  With ``group`` (or an
+        initialised torch.distributed world) the streams of all ranks are gathered first (dist.gather_eval_stream)."""
+        from . import dist as vdist
+        s, sc, tp = vdist.gather_eval_stream(*self.stream(raw=True), group=group)
+        n, K = s.numel(), len(self.classes)
+        ap = torch.empty(K, dtype=torch.float64, device=self.device)
+        perm = torch.empty(max(n, 1), dtype=torch.int32, device=self.device) if return_order else None
+        s, sc, tp = s.contiguous(), sc.contiguous(), tp.contiguous()
+        with torch.cuda.device(self.device):
+            ctx = _ctx_for(ap, None)
+            ctx.check(ctx.lib.vdet_eval_ap(ctx.h, s.data_ptr(), sc.data_ptr(), tp.data_ptr(), n, K, self._ngt.data_ptr(),
+                                           ap.data_ptr(), perm.data_ptr() if perm is not None else None))
+            ctx.sync()
+        v = ap.cpu().numpy()
+        aps = {c: float(v[k]) for k, c in enumerate(self.classes)}
+        valid = [x for x in aps.values() if not np.isnan(x)]
+        res = (aps, float(np.mean(valid)) if valid else float('nan'))
+        if return_order:
+            return res + ((self._cls_t[s.long()], sc, tp.bool(), perm[:n].long()),)
+        return res
