@@ -49,6 +49,14 @@
  *   evaluator: gt boxes per (video, frame, class)  <= 256             VDET_EINVAL (vdet_eval_gt_upload)
  *   evaluator: gt table cells              videos x frames x K < 2^31 VDET_EINVAL;  class slots 1 <= K <= 65536
  *   evaluator: stream entries              < 2^31 (per add: C*T*F or F*C*cap < 2^31)   VDET_EINVAL
+ *   device TCN: layers of a net            1 .. 16                    VDET_EINVAL
+ *   device TCN: channels of a layer        1 .. 4096 (inputs: 1 .. 16 assembled channels; any count up to 4096 for
+ *                                          vdet_tcn_series_f32); the last layer has 2      VDET_EINVAL
+ *   device TCN: kernel size                odd, <= 31                 VDET_EINVAL
+ *   device TCN: series length, net width   none                       series whose activations exceed 48 KiB of LDS are tiled
+ *                                                                     along the series; nets too wide for a 16-position tile keep
+ *                                                                     their activations in global memory (slower, same results)
+ *   device TCN / overlap: videos per call  V <= 65535, C*T*F < 2^31   VDET_EINVAL
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -124,7 +132,8 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * what = 8 -> number of host waits (hipStreamSynchronize) this context has made so far: the asynchronous video
  * step (vdet_set_async) adds none between the entry and the return of the volume entry points;
  * what = 9 -> (frame, class) columns of the last volume sort that the equalised counting sort handed to the LSD
- * radix kernel (tied / quantised / thresholded columns; synchronises the stream), -1 if that sort did not use it.
+ * radix kernel (tied / quantised / thresholded columns; synchronises the stream), -1 if that sort did not use it;
+ * what = 10 -> number of times the device TCN's parameters were uploaded (a call with the resident net uploads nothing).
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant):
@@ -137,6 +146,9 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  *   VDET_DIRECT_LISTS=0   the suppression graph of regular frames of > 384 boxes through the bit matrix (what a context takes for
  *                         good once a row had more neighbours than a direct list slot holds); VDET_DIRECT_CAP=n entries per slot
  *   VDET_ADJ_ROWS=0       (bit-matrix path) the lane-per-row adjacency kernel on every frame (what irregular / small frames take)
+ *   VDET_TCN_TILED=1      device TCN: every series cut into the smallest tiles, 16 positions or the net's halo (what long series
+ *                         and wide nets take)
+ *   VDET_TCN_GLOBAL=1     device TCN: the activations in global memory (what nets too wide for the LDS budget take)
  *   VDET_ATOMIC_RANK=0 / VDET_WAVE_TRANSPOSE=0   the variants selected when the start-up hardware probes fail
  *   VDET_BITS_BUDGET_MB=n bytes of bit-matrix scratch per graph-build batch (default 1024) */
 int vdet_query(vdet_ctx *ctx, int what);
@@ -500,6 +512,64 @@ int vdet_eval_match_keep(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t 
  * sorted order (stream positions).  Asynchronous. */
 int vdet_eval_ap(vdet_ctx *ctx, const int32_t *d_st_slot, const double *d_st_score, const uint8_t *d_st_tp, int64_t n, int K,
                  const int64_t *d_ngt, double *d_ap, int32_t *d_perm);
+
+/* ---- device TCN: the tubelet temporal-convolution scorer (score_conv_cls, vdet/tubelet_cls.py:15-51) ----------------------
+ *
+ * The net (vdetlib_amd/vdet/tcn.py: 1-D "same" convolutions over the tubelet length, ReLU between layers, a 2-way channel
+ * softmax at the end) travels with every call: h_layers [n_layers][3] = (Cout, Cin, K) and h_params = W0 | b0 | W1 | b1 ...
+ * (W [Cout,Cin,K] row-major, f32).  The context keeps the parameters of the last net on the device and uploads only when
+ * the bytes differ (vdet_query(ctx, 10)).  Arithmetic = vdet_conv1d_f32's, element for element (acc = b[co]; ci outer, k
+ * inner; acc = acc + w*x in f32 without contraction; zero padding at the ends of the series), so the results equal the
+ * layer-by-layer path bit for bit, whichever of the paths of the limits table runs.
+ *
+ * Tubelet (c, t): the frames of d_tracks[c, t] whose row is not NaN (column 0), in frame order, compacted (length L);
+ * t >= d_ntracks[c] does not exist.  h_channels [n_channels] selects and orders the net's input channels, one value per
+ * box, rounded once from f64 to f32 like np.asarray(python floats, dtype='float32'):
+ *   0 det_scores   d_det_score [C,T,F] (f64 when det_f64, else f32)        1 track_scores  d_tracks[..., 4]
+ *   2 anchors      (frame - anchor frame) / L in f64, anchor frame = (int)d_anchors[c, t, 0] (1-based)
+ *   3 abs_anchors  its magnitude        4 gt_overlaps  d_gt_overlap [C,T,F] f64        5 labels  gt_overlap >= 0.5 as 0 / 1
+ * (4 / 5 without a d_gt_overlap buffer: VDET_EINVAL).  d_conv_score [C,T,F] f32 = probs[1] at the box's frame, NaN where
+ * the tubelet has no box.  One assembly launch + one network launch; asynchronous, no host wait (a context that changes
+ * nets or batch geometries between calls waits once per change for the copy of the previous table).
+ */
+int vdet_tcn_tracks(vdet_ctx *ctx, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
+                    int n_channels, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                    const float *d_anchors, const void *d_det_score, int det_f64, const double *d_gt_overlap, float *d_conv_score);
+
+/* The same for the V videos of vdet_video_batch's layout in ONE assembly launch and ONE network launch: video v's arrays
+ * start at element C*T*h_frame_off[v] and are [C,T,F_v]; d_ntracks [V,C], d_anchors [V,C,T,3]. */
+int vdet_tcn_tracks_batch(vdet_ctx *ctx, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
+                          int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
+                          const double *d_gt_overlap, float *d_conv_score);
+
+/* The network kernel on T ragged host series: series t is h_x[cin*h_off[t] ...], channel-major [cin, L_t] with
+ * L_t = h_off[t+1] - h_off[t]; h_out[h_off[t] + j] = probs[1] of position j.  Synchronous: one upload, one launch, one
+ * download for all series. */
+int vdet_tcn_series_f32(vdet_ctx *ctx, const float *h_params, const int32_t *h_layers, int n_layers, int cin, const float *h_x,
+                        const int64_t *h_off, int64_t T, float *h_out);
+
+/* Ground-truth overlap of device tubelets (tubelets_overlap, utils/protocol.py:467-489) over the evaluator's table
+ * (vdet_eval_gt_upload; frame f of the volume is frame f + 1 of the table, h_col_slot[c] the class slot of column c):
+ *   d_gt_overlap [C,T,F] f64  the largest IoU (utils/common.py:451-468, vdet_iou_f64's operation order, ground truth first)
+ *                             of the box with the ground-truth boxes of its video, frame and class; 0 when there is none
+ *                             (or the video is unknown: vid -1); NaN where the tubelet has no box;
+ *   d_mean_iou [C,T] f64      the mean over the tubelet's boxes, summed sequentially in frame order (NaN: no tubelet);
+ *   d_gt [C,T] i32            |mean - 1| < DBL_EPSILON (a tubelet lying on a ground-truth track).
+ * The box: d_tracks[..., :4], or d_boxes [C,T,F,4] when not NULL (vdet_rescore_tracks' d_boxes_out); d_tracks always says
+ * where a tubelet has a box.  The f32 coordinates are widened to f64 AS THEY ARE -- the values vdet_eval_match_tracks
+ * matches -- whereas ops.tracks_to_proto truncates them with int(): on integer-valued boxes the two agree bit for bit, on
+ * fractional boxes the device form is the overlap of the untruncated box.  Asynchronous. */
+int vdet_tubelets_overlap(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K,
+                          int vid, int64_t F, int64_t C, int T, const float *d_tracks, const float *d_boxes,
+                          const int32_t *d_ntracks, const int32_t *h_col_slot, double *d_gt_overlap, double *d_mean_iou,
+                          int32_t *d_gt);
+
+/* V videos in vdet_video_batch's layout, one launch: h_vid [V] table indices, d_ntracks [V,C], d_mean_iou / d_gt [V,C,T]. */
+int vdet_tubelets_overlap_batch(vdet_ctx *ctx, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta,
+                                int K, const int32_t *h_vid, const int64_t *h_frame_off, int64_t V, int64_t C, int T,
+                                const float *d_tracks, const float *d_boxes, const int32_t *d_ntracks, const int32_t *h_col_slot,
+                                double *d_gt_overlap, double *d_mean_iou, int32_t *d_gt);
 
 #ifdef __cplusplus
 }

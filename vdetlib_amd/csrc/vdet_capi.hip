@@ -29,6 +29,7 @@
 #include "batch_kernels.hpp"
 #include "gemm_kernels.hpp"
 #include "eval_kernels.hpp"
+#include "tcn_kernels.hpp"
 
 using namespace vdet;
 
@@ -81,6 +82,14 @@ __global__ void fold_pool_kernel(Counters *cnt)
 {
     if (cnt->pool_used > cnt->pool_max) cnt->pool_max = cnt->pool_used;
 }
+
+// a small host table the device reads in an asynchronous call: the host copy lives in the context so it outlives the copy made
+// from it, and a call that brings the same bytes again uploads nothing
+struct StagedTab {
+    DevBuf dev;
+    std::vector<char> host;
+    bool valid = false;
+};
 
 struct NmsPlan {
     std::vector<GroupDesc> groups;   // bits_off is batch-local
@@ -184,6 +193,13 @@ struct vdet_ctx {
     size_t dyn_lds_max = 0;
     // device evaluator (eval_kernels.hpp): dense per-call match results, compaction counts, radix-sort ping-pong buffers
     DevBuf ev_tab, ev_dtp, ev_dsc, ev_dslot, ev_bcnt, ev_boff, ev_key[2], ev_val[2], ev_hist;
+    // device TCN (tcn_kernels.hpp): assembled channels, frame lists, tubelet descriptors, the global-path activations, and the
+    // host tables its asynchronous calls read on the device (net parameters, frame offsets, the overlap call's tables)
+    DevBuf tcn_x, tcn_frames, tcn_base, tcn_len, tcn_scratch;
+    StagedTab tcn_params, tcn_foff, tcn_ovtab;
+    long long tcn_uploads = 0;    // parameter uploads so far (vdet_query 10)
+    bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
+    bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
 };
 
 namespace {
@@ -1166,6 +1182,8 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_DIRECT_CAP")) { const int v = atoi(e); if (v >= 8 && v <= 32760) c->direct_cap = (uint32_t)(v & ~7); }
     if (const char *e = getenv("VDET_BINSORT")) c->binsort = atoi(e) != 0;
     if (const char *e = getenv("VDET_SMALL_LISTS")) c->small_lists = atoi(e) != 0;
+    if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
+    if (const char *e = getenv("VDET_TCN_GLOBAL")) c->tcn_global = atoi(e) != 0;
     {   // probe: do returning LDS atomics resolve same-address lanes in ascending lane order?
         const int npat = 4096;
         std::vector<uint8_t> pats((size_t)npat * 64);
@@ -1237,7 +1255,8 @@ int vdet_destroy(vdet_ctx *c)
                       &c->trk_frames, &c->trk_boxes, &c->b1, &c->b2, &c->iou_out, &c->order, &c->ncand, &c->keepidx,
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab, &c->vidtab, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
-                      &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist};
+                      &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
+                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1290,6 +1309,7 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 2) return c->all_regular ? 1 : 0;
     if (what == 3) return c->wave_transpose ? 1 : 0;
     if (what == 8) return (int)std::min<long long>(c->n_host_syncs, 0x7FFFFFFF);
+    if (what == 10) return (int)std::min<long long>(c->tcn_uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -2919,6 +2939,246 @@ int vdet_eval_ap(vdet_ctx *c, const int32_t *d_st_slot, const double *d_st_score
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device TCN (tcn_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+static int stage_table(vdet_ctx *c, StagedTab &t, const void *src, size_t bytes, bool *uploaded = nullptr)
+{
+    if (uploaded) *uploaded = false;
+    if (t.valid && t.host.size() == bytes && memcmp(t.host.data(), src, bytes) == 0) return VDET_OK;
+    if (!t.host.empty()) HIPCHK(c, host_sync(c));      // (a change of table: the copy made from the old bytes may be in flight)
+    t.valid = false;
+    t.host.assign(static_cast<const char *>(src), static_cast<const char *>(src) + bytes);
+    HIPCHK(c, t.dev.reserve(std::max<size_t>(bytes, 16)));
+    HIPCHK(c, hipMemcpyAsync(t.dev.p, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    t.valid = true;
+    if (uploaded) *uploaded = true;
+    return VDET_OK;
+}
+
+// h_layers [n_layers][3] = (Cout, Cin, K); h_params = W0 | b0 | W1 | b1 | ... (W [Cout, Cin, K] row-major).  The parameters
+// are uploaded when their bytes differ from the resident ones (vdet_query(ctx, 10) counts the uploads).
+static int tcn_net_args(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, int cin, TcnNet &net)
+{
+    if (!h_params || !h_layers) return fail(c, VDET_EINVAL, "null buffer");
+    if (n_layers < 1 || n_layers > kTcnMaxLayers) return fail(c, VDET_EINVAL, "a net has 1 to %d layers", kTcnMaxLayers);
+    if (cin < 1 || cin > kTcnMaxChannels) return fail(c, VDET_EINVAL, "a net has 1 to %d input channels", kTcnMaxChannels);
+    net = TcnNet{};
+    net.n = n_layers; net.cin = cin; net.maxc = cin; net.halo = 0;
+    int64_t off = 0;
+    int prev = cin;
+    for (int i = 0; i < n_layers; ++i) {
+        const int co = h_layers[3 * i], ci = h_layers[3 * i + 1], k = h_layers[3 * i + 2];
+        if (co < 1 || co > kTcnMaxChannels) return fail(c, VDET_EINVAL, "layer %d: 1 to %d channels", i, kTcnMaxChannels);
+        if (ci != prev) return fail(c, VDET_EINVAL, "layer shapes do not chain: layer %d takes %d channels after %d", i, ci, prev);
+        if (k < 1 || k % 2 != 1 || k > kTcnMaxK) return fail(c, VDET_EINVAL, "layer %d: the kernel size must be odd and <= %d", i, kTcnMaxK);
+        net.l[i].cin = ci; net.l[i].cout = co; net.l[i].k = k;
+        net.l[i].woff = (int)off; off += (int64_t)co * ci * k;
+        net.l[i].boff = (int)off; off += co;
+        if (off > 0x7FFFFFF0ll / 4) return fail(c, VDET_EINVAL, "net too large");
+        net.maxc = std::max(net.maxc, co);
+        net.halo += k / 2;
+        prev = co;
+    }
+    if (prev != 2) return fail(c, VDET_EINVAL, "the last layer must produce 2 channels (probs[:, 1, :] is the score)");
+    int rem = 0;
+    for (int i = n_layers - 1; i >= 0; --i) { net.l[i].rem = rem; rem += net.l[i].k / 2; }
+    bool up = false;
+    const int rc = stage_table(c, c->tcn_params, h_params, (size_t)off * 4, &up);
+    if (up) ++c->tcn_uploads;
+    return rc;
+}
+
+// The network launch over ntub tubelet descriptors; Lmax bounds every series length.  Path by size (DESIGN.md "Device TCN"):
+// whole series in LDS; else tiles of the largest width the LDS budget holds; else (net too wide for a useful tile) the
+// global-memory activations, tiled so that the scratch stays within 256 MiB.
+static int tcn_launch_net(vdet_ctx *c, const TcnNet &net, const float *d_x, const int32_t *d_frames, const int64_t *d_base,
+                          const int32_t *d_len, int64_t ntub, int64_t Lmax, float *d_out)
+{
+    if (ntub <= 0) return VDET_OK;
+    const int lmax = (int)std::max<int64_t>(std::min<int64_t>(Lmax, 0x3FFFFFF0), 1);
+    const int min_tile = std::max(kTcnMinTile, 2 * net.halo);
+    const int64_t per_pos = (int64_t)8 * net.maxc;            // two buffers x maxc floats per staged position
+    const int64_t fit = kTcnLdsBudget / per_pos - 2 * net.halo;   // widest tile the LDS budget holds
+    const float *params = c->tcn_params.dev.as<float>();
+    StageTimer tm(c, ST_OTHER);
+    if (!c->tcn_global && fit >= std::min(lmax, min_tile)) {
+        int tile = (int)std::min<int64_t>(fit, lmax);
+        if (c->tcn_tiled) tile = std::min(tile, min_tile);
+        const size_t lds = (size_t)per_pos * (tile + 2 * net.halo);
+        const unsigned grid = (unsigned)std::min<int64_t>(ntub, (int64_t)64 * c->n_cu);
+        hipLaunchKernelGGL(tcn_net_kernel<false>, dim3(grid), dim3(kTcnThreads), lds, c->stream, net, params, d_x, d_frames, d_base,
+                           d_len, ntub, tile, (float *)nullptr, d_out);
+    } else {
+        int tile = std::min(lmax, std::max(256, min_tile));
+        if (c->tcn_tiled) tile = std::min(tile, min_tile);
+        const size_t per_wg = (size_t)per_pos * (tile + 2 * net.halo);
+        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ntub, (int64_t)2 * c->n_cu), ((int64_t)256 << 20) / (int64_t)per_wg));
+        HIPCHK(c, c->tcn_scratch.reserve(per_wg * (size_t)grid));
+        hipLaunchKernelGGL(tcn_net_kernel<true>, dim3((unsigned)grid), dim3(kTcnThreads), 0, c->stream, net, params, d_x, d_frames,
+                           d_base, d_len, ntub, tile, c->tcn_scratch.as<float>(), d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+static int check_frame_off(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t *Ftot, int64_t *Fmax)
+{
+    if (!h_frame_off || V < 1 || V > 65535) return fail(c, VDET_EINVAL, "1 to 65535 videos with their frame offsets");
+    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame_off must start at 0");
+    *Fmax = 0;
+    for (int64_t v = 0; v < V; ++v) {
+        if (h_frame_off[v + 1] <= h_frame_off[v]) return fail(c, VDET_EINVAL, "frame_off must be strictly increasing");
+        *Fmax = std::max(*Fmax, h_frame_off[v + 1] - h_frame_off[v]);
+    }
+    *Ftot = h_frame_off[V];
+    return VDET_OK;
+}
+
+int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
+                          int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
+                          const double *d_gt_overlap, float *d_conv_score)
+{
+    if (!c) return VDET_EINVAL;
+    int64_t Ft = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax);
+    if (rc) return rc;
+    if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if (!h_channels || n_channels < 1 || n_channels > 16) return fail(c, VDET_EINVAL, "1 to 16 input channels");
+    TcnChannels ch{};
+    ch.n = n_channels;
+    bool need_gt = false, need_det = false;
+    for (int q = 0; q < n_channels; ++q) {
+        if (h_channels[q] < 0 || h_channels[q] >= kChCount) return fail(c, VDET_EINVAL, "unknown input channel code %d", h_channels[q]);
+        ch.code[q] = h_channels[q];
+        need_gt = need_gt || h_channels[q] == kChGtOverlap || h_channels[q] == kChLabel;
+        need_det = need_det || h_channels[q] == kChDet;
+    }
+    if (need_gt && !d_gt_overlap) return fail(c, VDET_EINVAL, "the net reads gt_overlaps / labels: a gt_overlap buffer is needed");
+    const int64_t N = C * T * Ft;
+    if (N > 0x7FFFFFF0ll || N * n_channels > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_anchors || (need_det && !d_det_score) || !d_conv_score) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    TcnNet net;
+    if ((rc = tcn_net_args(c, h_params, h_layers, n_layers, n_channels, net))) return rc;
+    const int64_t *d_foff = nullptr;
+    if (V > 1) {
+        if ((rc = stage_table(c, c->tcn_foff, h_frame_off, (size_t)(V + 1) * 8))) return rc;
+        d_foff = c->tcn_foff.dev.as<int64_t>();
+    }
+    const int64_t ntub = V * C * T;
+    HIPCHK(c, c->tcn_x.reserve((size_t)N * n_channels * 4));
+    HIPCHK(c, c->tcn_frames.reserve((size_t)N * 4));
+    HIPCHK(c, c->tcn_base.reserve((size_t)ntub * 8));
+    HIPCHK(c, c->tcn_len.reserve((size_t)ntub * 4));
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(tcn_assemble_kernel, dim3((unsigned)(C * T), (unsigned)V), dim3(64), 0, c->stream, d_tracks, d_ntracks, d_anchors,
+                           det_f64 ? static_cast<const double *>(d_det_score) : (const double *)nullptr,
+                           det_f64 ? (const float *)nullptr : static_cast<const float *>(d_det_score), d_gt_overlap, d_foff, Ft, (int)C, T,
+                           ch, c->tcn_x.as<float>(), c->tcn_frames.as<int32_t>(), c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(),
+                           d_conv_score);
+    }
+    HIPCHK(c, hipGetLastError());
+    return tcn_launch_net(c, net, c->tcn_x.as<float>(), c->tcn_frames.as<int32_t>(), c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(),
+                          ntub, Fmax, d_conv_score);
+}
+
+int vdet_tcn_tracks(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
+                    int n_channels, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                    const float *d_anchors, const void *d_det_score, int det_f64, const double *d_gt_overlap, float *d_conv_score)
+{
+    const int64_t foff[2] = {0, F};
+    return vdet_tcn_tracks_batch(c, h_params, h_layers, n_layers, h_channels, n_channels, foff, 1, C, T, d_tracks, d_ntracks, d_anchors,
+                                 d_det_score, det_f64, d_gt_overlap, d_conv_score);
+}
+
+int vdet_tcn_series_f32(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, int cin, const float *h_x,
+                        const int64_t *h_off, int64_t T, float *h_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (T < 0 || (T && !h_off)) return fail(c, VDET_EINVAL, "bad series table");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    TcnNet net;
+    int rc = tcn_net_args(c, h_params, h_layers, n_layers, cin, net);
+    if (rc) return rc;
+    if (T == 0) return VDET_OK;
+    if (h_off[0] != 0) return fail(c, VDET_EINVAL, "series offsets must start at 0");
+    std::vector<int32_t> len((size_t)T);
+    int64_t Lmax = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        const int64_t l = h_off[t + 1] - h_off[t];
+        if (l < 0 || l > 0x3FFFFFF0ll) return fail(c, VDET_EINVAL, "series offsets must not decrease");
+        len[(size_t)t] = (int32_t)l;
+        Lmax = std::max(Lmax, l);
+    }
+    const int64_t n = h_off[T];
+    if (n == 0) return VDET_OK;
+    if (n * cin > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many series elements");
+    if (!h_x || !h_out) return fail(c, VDET_EINVAL, "null buffer");
+    if ((rc = upload(c, c->tmp[0], h_x, (size_t)n * cin * 4))) return rc;
+    if ((rc = upload(c, c->tmp[1], h_off, (size_t)T * 8))) return rc;
+    if ((rc = upload(c, c->tmp[2], len.data(), (size_t)T * 4))) return rc;
+    HIPCHK(c, c->tmp[3].reserve((size_t)n * 4));
+    if ((rc = tcn_launch_net(c, net, c->tmp[0].as<float>(), nullptr, c->tmp[1].as<int64_t>(), c->tmp[2].as<int32_t>(), T, Lmax,
+                             c->tmp[3].as<float>())))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(h_out, c->tmp[3].p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, host_sync(c));
+    return VDET_OK;
+}
+
+int vdet_tubelets_overlap_batch(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K,
+                                const int32_t *h_vid, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                                const float *d_boxes, const int32_t *d_ntracks, const int32_t *h_col_slot, double *d_gt_overlap,
+                                double *d_mean_iou, int32_t *d_gt)
+{
+    if (!c) return VDET_EINVAL;
+    EvGt g;
+    int rc = eval_gt_args(c, d_gt_boxes, d_gt_off, d_vid_meta, K, 0, 0.5, g);
+    if (rc) return rc;
+    int64_t Ft = 0, Fmax = 0;
+    if ((rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax))) return rc;
+    if (!h_vid || !h_col_slot) return fail(c, VDET_EINVAL, "null buffer");
+    if (C < 1 || C > 65535 || T < 0 || C * std::max(T, 1) * Ft > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_gt_overlap || !d_mean_iou || !d_gt) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    // host tables: frame offsets [V+1] i64 | column slots [C] i32 | video table indices [V] i32.  One video travels in the
+    // kernel arguments, so that videos of different lengths one after the other keep the resident table (the column slots)
+    const bool one = V == 1;
+    const size_t o_slot = one ? 0 : (size_t)(V + 1) * 8, o_vid = o_slot + (size_t)C * 4;
+    std::vector<char> tab(o_vid + (one ? 0 : (size_t)V * 4));
+    if (!one) memcpy(tab.data(), h_frame_off, o_slot);
+    memcpy(tab.data() + o_slot, h_col_slot, (size_t)C * 4);
+    if (!one) memcpy(tab.data() + o_vid, h_vid, (size_t)V * 4);
+    if ((rc = stage_table(c, c->tcn_ovtab, tab.data(), tab.size()))) return rc;
+    const char *tb = c->tcn_ovtab.dev.as<char>();
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(tubelets_overlap_kernel, dim3((unsigned)(C * T), (unsigned)V), dim3(64), 0, c->stream, g,
+                           one ? (const int64_t *)nullptr : reinterpret_cast<const int64_t *>(tb), Ft,
+                           one ? (const int32_t *)nullptr : reinterpret_cast<const int32_t *>(tb + o_vid), h_vid[0], (int)C, T,
+                           d_tracks, d_boxes, d_ntracks, reinterpret_cast<const int32_t *>(tb + o_slot), d_gt_overlap, d_mean_iou, d_gt);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_tubelets_overlap(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d_gt_off, const int64_t *d_vid_meta, int K, int vid,
+                          int64_t F, int64_t C, int T, const float *d_tracks, const float *d_boxes, const int32_t *d_ntracks,
+                          const int32_t *h_col_slot, double *d_gt_overlap, double *d_mean_iou, int32_t *d_gt)
+{
+    const int64_t foff[2] = {0, F};
+    return vdet_tubelets_overlap_batch(c, d_gt_boxes, d_gt_off, d_vid_meta, K, &vid, foff, 1, C, T, d_tracks, d_boxes, d_ntracks,
+                                       h_col_slot, d_gt_overlap, d_mean_iou, d_gt);
 }
 
 }  // extern "C"

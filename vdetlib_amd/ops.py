@@ -485,6 +485,185 @@ def rescore_tracks(tracks, ntracks, boxes, scores, overlap_thres=0.7, window=3, 
     return det, pooled, ob
 
 
+def _tcn_net_args(net):
+    from .vdet.tcn import TCNNet
+    if not isinstance(net, TCNNet):
+        raise ValueError("net must be a vdetlib_amd.vdet.tcn.TCNNet")
+    params, shapes = net.packed()
+    codes = net.device_channels()
+    return params, shapes, codes
+
+
+def _tcn_check(tracks, ntracks, anchors, det_score, gt_overlap, V, C, T, n, codes):
+    """Shared validation of tcn_tracks / tcn_tracks_batch: flat element counts ``n`` = C*T*F_total."""
+    if tracks.dtype != torch.float32 or tracks.numel() != n * 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    if ntracks.dtype != torch.int32 or ntracks.numel() != V * C:
+        raise ValueError("ntracks must be int32 [C] (batch: [V,C])")
+    if anchors.dtype != torch.float32 or anchors.numel() != V * C * T * 3:
+        raise ValueError("anchors must be float32 [C,T,3] (batch: [V,C,T,3])")
+    if det_score.dtype not in (torch.float32, torch.float64) or det_score.numel() != n:
+        raise ValueError("det_score must be float32 / float64 [C,T,F]")
+    if gt_overlap is not None and (gt_overlap.dtype != torch.float64 or gt_overlap.numel() != n):
+        raise ValueError("gt_overlap must be float64 [C,T,F]")
+    if gt_overlap is None and any(int(q) in (4, 5) for q in codes):
+        raise ValueError("the net reads gt_overlaps / labels: pass gt_overlap (ops.tubelets_overlap)")
+    for t in (tracks, ntracks, anchors, det_score) + (() if gt_overlap is None else (gt_overlap,)):
+        if not t.is_cuda or t.device != tracks.device:
+            raise ValueError("tracks, ntracks, anchors, det_score and gt_overlap must live on the same GPU")
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+
+
+def tcn_tracks(net, tracks, ntracks, anchors, det_score, gt_overlap=None, sync=True, ctx=None):
+    """The tubelet temporal-convolution scorer (score_conv_cls, vdet/tubelet_cls.py:15-51) on device tubelets: channel
+    assembly and every layer of ``net`` (a ``vdet.tcn.TCNNet`` whose inputs are one-channel blobs among det_scores,
+    track_scores, anchors, abs_anchors, gt_overlaps, labels) in two launches for ALL tubelets of the video.
+
+    tracks [C,T,F,5] f32 / ntracks [C] int32 / anchors [C,T,3] f32 (track_volume, nms_track_volume), det_score [C,T,F] f64
+    or f32 (rescore_tracks' det_score or pooled), gt_overlap [C,T,F] f64 (tubelets_overlap) when the net reads it.
+    Returns conv_score [C,T,F] f32: probs[1] per box, NaN where there is none -- bit for bit what ``score_conv_cls`` writes
+    on the protocol dicts of the same tensors; feeds ``DetEvaluator.add_tracks(..., scores=conv_score)`` as is."""
+    params, shapes, codes = _tcn_net_args(net)
+    if tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if tuple(ntracks.shape) != (C,) or tuple(anchors.shape) != (C, T, 3) or tuple(det_score.shape) != (C, T, F) or \
+            (gt_overlap is not None and tuple(gt_overlap.shape) != (C, T, F)):
+        raise ValueError("ntracks [C], anchors [C,T,3], det_score / gt_overlap [C,T,F]")
+    if F < 1:
+        raise ValueError("a video needs at least one frame")
+    tracks, ntracks, anchors, det_score = tracks.contiguous(), ntracks.contiguous(), anchors.contiguous(), det_score.contiguous()
+    gt_overlap = None if gt_overlap is None else gt_overlap.contiguous()
+    _tcn_check(tracks, ntracks, anchors, det_score, gt_overlap, 1, C, T, C * T * F, codes)
+    ctx = _ctx_for(tracks, ctx)
+    out = torch.empty((C, T, F), dtype=torch.float32, device=tracks.device)
+    ctx.check(ctx.lib.vdet_tcn_tracks(
+        ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), codes.ctypes.data, len(codes), F, C, T, tracks.data_ptr(),
+        ntracks.data_ptr(), anchors.data_ptr(), det_score.data_ptr(), int(det_score.dtype == torch.float64),
+        gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
+    if sync:
+        ctx.sync()
+    return out
+
+
+def _batch_flat(views, per):
+    """The flat buffer behind video_batch's per-video views (they are consecutive slices of one allocation)."""
+    total = sum(v.numel() for v in views)
+    flat = torch.as_strided(views[0], (total,), (1,))
+    if views[-1].data_ptr() != views[0].data_ptr() + (total - views[-1].numel()) * views[0].element_size():
+        raise ValueError("not a video_batch result: the per-video views are not consecutive")
+    return flat
+
+
+def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, ctx=None):
+    """``tcn_tracks`` for every video of a ``video_batch`` result in ONE assembly launch and ONE network launch.
+    ``series``: which re-scored series feeds det_scores ('det' or 'pooled'); gt_overlap: the flat f64 buffer
+    ``tubelets_overlap_batch`` returns.  Returns the list of per-video conv_score [C,T,F_v] f32 views."""
+    params, shapes, codes = _tcn_net_args(net)
+    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
+    V = len(off) - 1
+    if series not in ('det', 'pooled') or not batch_out.get(series):
+        raise ValueError("series must be 'det' or 'pooled' of a video_batch result that ran the re-scoring")
+    tv, sv = batch_out['tracks'], batch_out[series]
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    Ft = int(off[-1])
+    tracks, det = _batch_flat(tv, 5), _batch_flat(sv, 1)
+    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
+    if tuple(ntracks.shape) != (V, C) or tuple(anchors.shape) != (V, C, T, 3):
+        raise ValueError("not a video_batch result")
+    _tcn_check(tracks, ntracks, anchors, det, gt_overlap, V, C, T, C * T * Ft, codes)
+    ctx = _ctx_for(tracks, ctx)
+    out = torch.empty((C * T * Ft,), dtype=torch.float32, device=tracks.device)
+    ctx.check(ctx.lib.vdet_tcn_tracks_batch(
+        ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), codes.ctypes.data, len(codes), off.ctypes.data, V, C, T,
+        tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), det.data_ptr(), int(det.dtype == torch.float64),
+        gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
+    if sync:
+        ctx.sync()
+    return [out[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
+
+
+def _evaluator_of(gt):
+    return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
+
+
+def tubelets_overlap(gt, video, tracks, ntracks, boxes=None, sync=True, ctx=None):
+    """``tubelets_overlap`` (utils/protocol.py:467-489) on device tubelets, against the ground truth a ``DetEvaluator``
+    holds on the device (``gt``: the evaluator -- both then share one copy of the table -- or a gt_table dict, which is
+    uploaded for this call).  tracks [C,T,F,5] f32 (column c = class c + 1), ntracks [C] int32, boxes [C,T,F,4] f32 to
+    measure instead of the track rows (rescore_tracks' boxes).  The f32 coordinates are used as they are (no int()
+    truncation, see include/vdet_hip.h).  Returns (gt_overlap [C,T,F] f64, NaN where no box; mean_iou [C,T] f64;
+    gt [C,T] int32 flags)."""
+    ev = _evaluator_of(gt)
+    if tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if boxes is not None and (boxes.dtype != torch.float32 or tuple(boxes.shape) != (C, T, F, 4)):
+        raise ValueError("boxes must be float32 [C,T,F,4]")
+    if F < 1:
+        raise ValueError("a video needs at least one frame")
+    ev._check(tracks, ntracks, *([boxes] if boxes is not None else []))
+    tracks, ntracks = tracks.contiguous(), ntracks.contiguous()
+    boxes = None if boxes is None else boxes.contiguous()
+    dev = tracks.device
+    ov = torch.empty((C, T, F), dtype=torch.float64, device=dev)
+    mean = torch.empty((C, T), dtype=torch.float64, device=dev)
+    flag = torch.empty((C, T), dtype=torch.int32, device=dev)
+    slots = ev._col_slots(C, 1)
+    ctx = _ctx_for(tracks, ctx)
+    gtb, gto, gtm, K = ev.device_table()
+    ctx.check(ctx.lib.vdet_tubelets_overlap(
+        ctx.h, gtb.data_ptr(), gto.data_ptr(), gtm.data_ptr(), K, ev._vidx.get(video, -1), F, C, T, tracks.data_ptr(),
+        boxes.data_ptr() if boxes is not None else None, ntracks.data_ptr(), slots.ctypes.data, ov.data_ptr(), mean.data_ptr(),
+        flag.data_ptr()))
+    if sync:
+        ctx.sync()
+    return ov, mean, flag
+
+
+def tubelets_overlap_batch(gt, videos, batch_out, use_tboxes=False, sync=True, ctx=None):
+    """``tubelets_overlap`` for every video of a ``video_batch`` result in one launch.  Returns (gt_overlap: flat f64
+    buffer in the batch layout -- what ``tcn_tracks_batch`` takes --, its per-video [C,T,F_v] views, mean_iou [V,C,T],
+    gt [V,C,T])."""
+    ev = _evaluator_of(gt)
+    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
+    V = len(off) - 1
+    if len(videos) != V:
+        raise ValueError("one name per video of the batch")
+    tv = batch_out['tracks']
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    Ft = int(off[-1])
+    tracks = _batch_flat(tv, 5)
+    boxes = None
+    if use_tboxes:
+        if not batch_out.get('tboxes'):
+            raise ValueError("video_batch ran without re-scoring (rescore=False): no tboxes")
+        boxes = _batch_flat(batch_out['tboxes'], 4)
+    ntracks = batch_out['ntracks'].contiguous()
+    if tracks.dtype != torch.float32 or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
+        raise ValueError("not a video_batch result")
+    ev._check(tracks, ntracks)
+    dev = tracks.device
+    ov = torch.empty((C * T * Ft,), dtype=torch.float64, device=dev)
+    mean = torch.empty((V, C, T), dtype=torch.float64, device=dev)
+    flag = torch.empty((V, C, T), dtype=torch.int32, device=dev)
+    slots = ev._col_slots(C, 1)
+    vids = np.array([ev._vidx.get(v, -1) for v in videos], dtype=np.int32)
+    ctx = _ctx_for(tracks, ctx)
+    gtb, gto, gtm, K = ev.device_table()
+    ctx.check(ctx.lib.vdet_tubelets_overlap_batch(
+        ctx.h, gtb.data_ptr(), gto.data_ptr(), gtm.data_ptr(), K, vids.ctypes.data, off.ctypes.data, V, C, T, tracks.data_ptr(),
+        boxes.data_ptr() if boxes is not None else None, ntracks.data_ptr(), slots.ctypes.data, ov.data_ptr(), mean.data_ptr(),
+        flag.data_ptr()))
+    if sync:
+        ctx.sync()
+    views = [ov[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
+    return ov, views, mean, flag
+
+
 class DetEvaluator(object):
     """Per-class AP / mAP of device detections (include/vdet_hip.h: the device evaluator); ``vdetlib_amd.eval.evaluate``
     is the specification -- same matching bit for bit, the same AP up to the order of one f64 sum (< 1e-12).
@@ -560,6 +739,11 @@ class DetEvaluator(object):
     def _gt_args(self):
         return (self._gt_boxes.data_ptr(), self._gt_off.data_ptr(), self._gt_meta.data_ptr(), len(self.classes),
                 0 if self.rule == 'voc' else 1, self.iou_thr)
+
+    def device_table(self):
+        """The uploaded ground-truth CSR (gt_boxes [G,4] f64, gt_off int32, vid_meta [NV,2] int64 device tensors, K class
+        slots): shared with ``ops.tubelets_overlap`` so that the table lives on the device once."""
+        return self._gt_boxes, self._gt_off, self._gt_meta, len(self.classes)
 
     def _col_slots(self, C, class_base):
         return np.array([self._slot.get(c + class_base, -1) for c in range(C)], dtype=np.int32)

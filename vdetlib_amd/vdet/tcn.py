@@ -72,6 +72,55 @@ class TCNNet(object):
             arrs['b%d' % i] = b
         np.savez(path, **arrs)
 
+    # channel codes of include/vdet_hip.h (vdet_tcn_tracks): the blob names the device assembly knows
+    DEVICE_CHANNELS = {'det_scores': 0, 'track_scores': 1, 'anchors': 2, 'abs_anchors': 3, 'gt_overlaps': 4, 'labels': 5}
+
+    def packed(self):
+        """(params f32 = W0 | b0 | W1 | b1 ..., layers int32 [n,3] = (Cout, Cin, K)): the form the one-launch entry points
+        take (vdet_tcn_tracks, vdet_tcn_series_f32).  Built once and kept, so that the library finds the same bytes at
+        the same address on every call; a net whose ``layers`` were edited in place needs a fresh TCNNet."""
+        if getattr(self, '_packed', None) is None:
+            params = np.concatenate([a.ravel() for w, b in self.layers for a in (w, b)]).astype(np.float32)
+            shapes = np.array([w.shape for w, _ in self.layers], dtype=np.int32).reshape(-1, 3)
+            self._packed = (np.ascontiguousarray(params), np.ascontiguousarray(shapes))
+        return self._packed
+
+    def device_channels(self):
+        """The input list as channel codes of the device assembly; ValueError for blobs it cannot assemble
+        (``all_scores`` / ``feats``, multi-channel blobs, unknown names)."""
+        codes = []
+        for name, ch in self.inputs:
+            if name not in self.DEVICE_CHANNELS or ch != 1:
+                raise ValueError("the device TCN assembles one-channel blobs named %s; got %r with %d channel(s)"
+                                 % (sorted(self.DEVICE_CHANNELS), name, ch))
+            codes.append(self.DEVICE_CHANNELS[name])
+        return np.array(codes, dtype=np.int32)
+
+    def forward_series(self, series, ctx=None):
+        """The net on many series in ONE launch (vdet_tcn_series_f32): ``series`` is a list of float32 arrays
+        [Cin, L_t] (the channels in ``inputs`` order); returns the list of probs[1] arrays [L_t] -- what ``forward()``
+        gives as ``['probs'][0, 1]`` series by series, bit for bit."""
+        cin = sum(c for _, c in self.inputs)
+        xs = []
+        for x in series:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            if x.ndim != 2 or x.shape[0] != cin:
+                raise ValueError("every series must be [%d, L]; got %r" % (cin, x.shape))
+            xs.append(x)
+        lens = np.array([x.shape[1] for x in xs], dtype=np.int64)
+        off = np.zeros(len(xs) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        flat = np.concatenate([x.ravel() for x in xs]) if xs else np.zeros(0, np.float32)
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        out = np.empty(int(off[-1]), dtype=np.float32)
+        params, shapes = self.packed()
+        if ctx is None:
+            ctx = _lib.get_context()
+            ctx.reset_stream()
+        ctx.check(ctx.lib.vdet_tcn_series_f32(ctx.h, params.ctypes.data, shapes.ctypes.data, len(self.layers), cin,
+                                              flat.ctypes.data, off.ctypes.data, len(xs), out.ctypes.data))
+        return [out[off[i]:off[i + 1]] for i in range(len(xs))]
+
     def forward(self):
         L = self.blobs[self.inputs[0][0]].shape[3]
         x = np.concatenate([np.asarray(self.blobs[n].data, dtype=np.float32).reshape(c, L) for n, c in self.inputs], 0)

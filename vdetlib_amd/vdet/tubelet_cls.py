@@ -63,6 +63,31 @@ def score_conv_cls(score_proto, net):
     return out
 
 
+def score_conv_cls_batched(score_proto, net):
+    """``score_conv_cls`` for a ``vdetlib_amd.vdet.tcn.TCNNet`` with ALL tubelets of the proto in one launch
+    (``TCNNet.forward_series``): same channel assembly, same ``conv_score`` values bit for bit, same return value.  The
+    net's blobs are not touched (``score_conv_cls`` itself keeps the per-tubelet pycaffe contract)."""
+    from .tcn import TCNNet
+    if not isinstance(net, TCNNet):
+        raise TypeError("score_conv_cls_batched needs a vdetlib_amd.vdet.tcn.TCNNet (any pycaffe-like net: score_conv_cls)")
+    out = copy.copy(score_proto)
+    print("{}: {} tubelet(s).".format(score_proto['video'], len(out['tubelets'])))
+    blob_names = set(net.blobs.keys())
+    series = []
+    for tubelet in out['tubelets']:
+        channels, length = _tcn_channels(tubelet, blob_names)
+        rows = []
+        for name, ch in net.inputs:
+            if name not in channels:
+                raise ValueError("the net reads a blob %r that score_conv_cls does not assemble" % name)
+            rows.append(np.asarray(channels[name], dtype='float32').reshape(ch, length))
+        series.append(np.concatenate(rows, 0))
+    for tubelet, probs in zip(out['tubelets'], net.forward_series(series)):
+        for box, p in zip(tubelet['boxes'], probs):
+            box['conv_score'] = float(p)
+    return out
+
+
 def scoring_tracks(vid_proto, track_proto, annot_proto, sc_method, net, class_idx):
     """:263-273"""
     assert vid_proto['video'] == track_proto['video']
