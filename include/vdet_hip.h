@@ -57,6 +57,9 @@
  *                                                                     along the series; nets too wide for a 16-position tile keep
  *                                                                     their activations in global memory (slower, same results)
  *   device TCN / overlap: videos per call  V <= 65535, C*T*F < 2^31   VDET_EINVAL
+ *   device interpolation: series per call  <= 4                       VDET_EINVAL
+ *   device interpolation: rows, frames, stride  none (V <= 65535, C*T*F < 2^31 on both axes)   VDET_EINVAL; one path for
+ *                                                                     every size: the kernel keeps no knot list
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -570,6 +573,51 @@ int vdet_tubelets_overlap_batch(vdet_ctx *ctx, const double *d_gt_boxes, const i
                                 int K, const int32_t *h_vid, const int64_t *h_frame_off, int64_t V, int64_t C, int T,
                                 const float *d_tracks, const float *d_boxes, const int32_t *d_ntracks, const int32_t *h_col_slot,
                                 double *d_gt_overlap, double *d_mean_iou, int32_t *d_gt);
+
+/* ---- device interpolation: strided / holey tubelets back to every frame (score_proto_interpolation,
+ *      vdet/tubelet_cls.py:416-490) -----------------------------------------------------------------------------------------
+ *
+ * The inputs live on a SAMPLED frame axis of Fs rows (vdet_track_volume / vdet_rescore_tracks run on every stride-th frame
+ * of the video, or any [C,T,Fs,...] tubelets with NaN rows); row i is the dense 1-based frame h_frames[i] (strictly
+ * ascending, >= 1, <= F; NULL: i + 1, which needs F >= Fs).  The outputs live on the dense axis of F frames.
+ * KNOTS of slot (c, t): the rows whose d_tracks column 0 is not NaN, t < d_ntracks[c].  With L knots:
+ *   L == 0 (or t >= d_ntracks[c], whatever the rows hold)   every output NaN;
+ *   L == 1   the one box copied to its frame, NaN elsewhere (the reference copies tubelets of < 2 boxes, :452-454);
+ *   L >= 2   frames lo..hi, lo / hi = first / last knot frame with the end rule lo == 2 -> 1, hi == F - 1 -> F
+ *            (:472-475), NaN elsewhere.  Arithmetic = vdet_series_interp_f64's in f64, operation for operation, without
+ *            contraction: the knot's own value at a knot; else slope = (y[j+1]-y[j])/(x[j+1]-x[j]), slope*(x-x[j]) + y[j]
+ *            from the LEFT knot; frame 1 below the knots y[0] + (x-x[0])*(y[1]-y[0])/(x[1]-x[0]); frame F above them
+ *            y[-1] + (x-x[-1])*(y[-1]-y[-2])/(x[-1]-x[-2]).  A NaN in a knot's field flows through that arithmetic.
+ * Fields, all interpolated by that one rule:
+ *   the box        d_boxes [C,T,Fs,4] f32 when not NULL (vdet_rescore_tracks' d_boxes_out), else d_tracks[..., :4]; the
+ *                  f32 values widened to f64 AS THEY ARE (no int(), as in vdet_tubelets_overlap)
+ *                  -> d_boxes64 [C,T,F,4] f64;  d_tboxes [C,T,F,4] f32 and d_tracks_out[..., :4] = that, rounded once
+ *   n_series <= 4  h_series[q]: DEVICE pointers [C,T,Fs], all f64 (series_f64) or all f32 -- each a det_score field of the
+ *                  reference -> d_series_out [n_series][C*T*F] f64 (batch: F = all dense frames of the call): series q
+ *                  starts at element q*C*T*F and is laid out like every other [C,T,F] output
+ *   the anchor     h_frames[i] - h_frames[(int)d_anchors[c,t,0] - 1], the offset in dense frames (the reference's
+ *                  tracks_proto_from_boxes(..., start_frame, step)) -> d_anchor [C,T,F] f64 (NaN when the anchor row is
+ *                  not a row of the video)
+ *   track score    d_tracks[..., 4] -> d_tracks_out[..., 4] f32, rounded once.  BUILD-DEFINED: the reference's interpolated
+ *                  boxes carry no track_score; the device TCN reads one per box, so it is interpolated like a score.
+ * d_tracks_out [C,T,F,5] rows are NaN exactly where the tubelet has no dense box.  d_anchors_out [C,T,3] f32: column 0 is
+ * the anchor's dense frame number (copied unchanged for t >= d_ntracks[c] or an anchor row outside the video), columns 1-2
+ * copied.  Every output element is written by the ONE launch of the call (no fill pass).  Asynchronous, no host wait
+ * (h_frames and the offsets are staged in the context; a change of table waits once for the copy of the previous one).
+ */
+int vdet_interp_tracks(vdet_ctx *ctx, int64_t Fs, int64_t F, const int32_t *h_frames, int64_t C, int T, const float *d_tracks,
+                       const float *d_boxes, const int32_t *d_ntracks, const float *d_anchors, const void *const *h_series,
+                       int n_series, int series_f64, float *d_tracks_out, double *d_boxes64, float *d_tboxes,
+                       double *d_series_out, double *d_anchor, float *d_anchors_out);
+
+/* The same for V videos in vdet_video_batch's layout, one launch: the inputs of video v start at element
+ * C*T*h_sframe_off[v] and are [C,T,Fs_v], its outputs at C*T*h_frame_off[v] and are [C,T,F_v]; h_frames [h_sframe_off[V]]
+ * (ascending inside each video, or NULL), d_ntracks [V,C], d_anchors / d_anchors_out [V,C,T,3]. */
+int vdet_interp_tracks_batch(vdet_ctx *ctx, const int64_t *h_sframe_off, const int64_t *h_frame_off, int64_t V,
+                             const int32_t *h_frames, int64_t C, int T, const float *d_tracks, const float *d_boxes,
+                             const int32_t *d_ntracks, const float *d_anchors, const void *const *h_series, int n_series,
+                             int series_f64, float *d_tracks_out, double *d_boxes64, float *d_tboxes,
+                             double *d_series_out, double *d_anchor, float *d_anchors_out);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@
 #include "gemm_kernels.hpp"
 #include "eval_kernels.hpp"
 #include "tcn_kernels.hpp"
+#include "interp_kernels.hpp"
 
 using namespace vdet;
 
@@ -200,6 +201,7 @@ struct vdet_ctx {
     long long tcn_uploads = 0;    // parameter uploads so far (vdet_query 10)
     bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
     bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
+    StagedTab interp_tab;         // device interpolation (interp_kernels.hpp): frame offsets and the frame table of the last call
 };
 
 namespace {
@@ -1256,7 +1258,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab, &c->vidtab, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
-                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev};
+                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -3179,6 +3181,99 @@ int vdet_tubelets_overlap(vdet_ctx *c, const double *d_gt_boxes, const int32_t *
     const int64_t foff[2] = {0, F};
     return vdet_tubelets_overlap_batch(c, d_gt_boxes, d_gt_off, d_vid_meta, K, &vid, foff, 1, C, T, d_tracks, d_boxes, d_ntracks,
                                        h_col_slot, d_gt_overlap, d_mean_iou, d_gt);
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// Device interpolation (interp_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_interp_tracks_batch(vdet_ctx *c, const int64_t *h_sframe_off, const int64_t *h_frame_off, int64_t V, const int32_t *h_frames,
+                             int64_t C, int T, const float *d_tracks, const float *d_boxes, const int32_t *d_ntracks,
+                             const float *d_anchors, const void *const *h_series, int n_series, int series_f64, float *d_tracks_out,
+                             double *d_boxes64, float *d_tboxes, double *d_series_out, double *d_anchor, float *d_anchors_out)
+{
+    if (!c) return VDET_EINVAL;
+    int64_t Fst = 0, Fsmax = 0, Ft = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_sframe_off, V, &Fst, &Fsmax);
+    if (rc) return rc;
+    if ((rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax))) return rc;
+    if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if (n_series < 0 || n_series > kInterpMaxSeries) return fail(c, VDET_EINVAL, "0 to %d series", kInterpMaxSeries);
+    if (C * std::max(T, 1) * Ft > 0x7FFFFFF0ll || C * std::max(T, 1) * Fst > 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31)");
+    for (int64_t v = 0; v < V; ++v) {
+        const int64_t s0 = h_sframe_off[v], fs = h_sframe_off[v + 1] - s0, f = h_frame_off[v + 1] - h_frame_off[v];
+        if (!h_frames) {
+            if (f < fs) return fail(c, VDET_EINVAL, "video %lld: %lld dense frames for %lld rows", (long long)v, (long long)f, (long long)fs);
+            continue;
+        }
+        for (int64_t i = 0; i < fs; ++i) {
+            const int64_t x = h_frames[s0 + i];
+            if (x < 1 || (i && x <= h_frames[s0 + i - 1]))
+                return fail(c, VDET_EINVAL, "video %lld: frames must be >= 1 and strictly ascending", (long long)v);
+        }
+        if (h_frames[s0 + fs - 1] > f)
+            return fail(c, VDET_EINVAL, "video %lld: frame %d lies beyond its %lld dense frames", (long long)v, (int)h_frames[s0 + fs - 1], (long long)f);
+    }
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_anchors || !d_tracks_out || !d_boxes64 || !d_tboxes || !d_anchor || !d_anchors_out ||
+        (n_series && (!h_series || !d_series_out)))
+        return fail(c, VDET_EINVAL, "null buffer");
+    InterpArgs a{};
+    for (int q = 0; q < n_series; ++q) {
+        if (!h_series[q]) return fail(c, VDET_EINVAL, "null buffer");
+        a.series[q] = h_series[q];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    // host tables: sampled offsets [V+1] i64 | dense offsets [V+1] i64 (both only for V > 1) | frames [Fs] i32 (when given).
+    // One video on an identity axis travels in the kernel arguments alone.
+    const bool many = V > 1;
+    const size_t o_fr = many ? (size_t)(V + 1) * 16 : 0;
+    if (many || h_frames) {
+        std::vector<char> tab(o_fr + (h_frames ? (size_t)Fst * 4 : 0));
+        if (many) {
+            memcpy(tab.data(), h_sframe_off, (size_t)(V + 1) * 8);
+            memcpy(tab.data() + (size_t)(V + 1) * 8, h_frame_off, (size_t)(V + 1) * 8);
+        }
+        if (h_frames) memcpy(tab.data() + o_fr, h_frames, (size_t)Fst * 4);
+        if ((rc = stage_table(c, c->interp_tab, tab.data(), tab.size()))) return rc;
+        const char *tb = c->interp_tab.dev.as<char>();
+        if (many) {
+            a.soff = reinterpret_cast<const int64_t *>(tb);
+            a.doff = a.soff + (V + 1);
+        }
+        if (h_frames) a.frames = reinterpret_cast<const int32_t *>(tb + o_fr);
+    }
+    a.tracks = d_tracks; a.boxes = d_boxes; a.ntracks = d_ntracks; a.anchors = d_anchors;
+    a.nser = n_series; a.oseries = d_series_out; a.N = C * T * Ft;
+    a.Fs1 = (int)Fst; a.F1 = (int)Ft; a.C = (int)C; a.T = T;
+    a.otracks = d_tracks_out; a.boxes64 = d_boxes64; a.tboxes = d_tboxes; a.oanchor = d_anchor; a.oanchors = d_anchors_out;
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)(C * T), (unsigned)V);
+#define VDET_INTERP_LAUNCH(N_)                                                                              \
+    case N_:                                                                                                \
+        if (series_f64) hipLaunchKernelGGL((interp_tracks_kernel<N_, true>), grid, dim3(64), 0, c->stream, a);  \
+        else hipLaunchKernelGGL((interp_tracks_kernel<N_, false>), grid, dim3(64), 0, c->stream, a);            \
+        break;
+        switch (n_series) {
+            VDET_INTERP_LAUNCH(0) VDET_INTERP_LAUNCH(1) VDET_INTERP_LAUNCH(2) VDET_INTERP_LAUNCH(3) VDET_INTERP_LAUNCH(4)
+        }
+#undef VDET_INTERP_LAUNCH
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_interp_tracks(vdet_ctx *c, int64_t Fs, int64_t F, const int32_t *h_frames, int64_t C, int T, const float *d_tracks,
+                       const float *d_boxes, const int32_t *d_ntracks, const float *d_anchors, const void *const *h_series,
+                       int n_series, int series_f64, float *d_tracks_out, double *d_boxes64, float *d_tboxes,
+                       double *d_series_out, double *d_anchor, float *d_anchors_out)
+{
+    const int64_t soff[2] = {0, Fs}, doff[2] = {0, F};
+    return vdet_interp_tracks_batch(c, soff, doff, 1, h_frames, C, T, d_tracks, d_boxes, d_ntracks, d_anchors, h_series, n_series,
+                                    series_f64, d_tracks_out, d_boxes64, d_tboxes, d_series_out, d_anchor, d_anchors_out);
 }
 
 }  // extern "C"

@@ -584,6 +584,169 @@ def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, c
     return [out[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
 
 
+def _interp_frames(frames, off, num_frames):
+    """The host tables of interpolate_tracks[_batch]: frames (flat int32, or None: identity) and the dense frame counts
+    [V], checked per video against the sampled offsets ``off``."""
+    V = len(off) - 1
+    nf = np.ascontiguousarray(num_frames, dtype=np.int64).reshape(-1)
+    if nf.size != V:
+        raise ValueError("num_frames: one dense frame count per video")
+    if frames is None:
+        if np.any(nf < np.diff(off)):
+            raise ValueError("num_frames must not be smaller than the number of rows when frames is None")
+        return None, nf
+    fr = np.asarray(frames.cpu() if hasattr(frames, 'cpu') else frames)
+    if fr.dtype.kind not in 'iu' or fr.ndim != 1:
+        raise ValueError("frames must be a 1-D integer array of dense 1-based frame numbers")
+    if fr.size != int(off[-1]):
+        raise ValueError("frames must name the dense frame of every row (%d rows, %d frames)" % (int(off[-1]), fr.size))
+    fr = fr.astype(np.int64)
+    if np.any(fr[off[:-1]] < 1):
+        raise ValueError("frames are 1-based: the first frame of a video must be >= 1")
+    inner = np.ones(max(fr.size - 1, 0), dtype=bool)
+    inner[off[1:-1] - 1] = False                      # the step from one video's last row to the next one's first
+    if np.any((np.diff(fr) <= 0) & inner):
+        raise ValueError("frames must be strictly ascending inside a video")
+    if np.any(nf < fr[off[1:] - 1]):
+        raise ValueError("num_frames is smaller than the last frame of a video")
+    return np.ascontiguousarray(fr, dtype=np.int32), nf
+
+
+def _interp_series(series, n, device):
+    if torch.is_tensor(series):
+        series = (series,)
+    series = tuple(series)
+    if len(series) > 4:
+        raise ValueError("at most 4 series per call")
+    for x in series:
+        if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.float64) or x.numel() != n:
+            raise ValueError("every series must be a float32 / float64 tensor [C,T,Fs]")
+        if x.dtype != series[0].dtype:
+            raise ValueError("the series of one call must share one dtype")
+        if not x.is_cuda or x.device != device:
+            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    return tuple(x.contiguous() for x in series)
+
+
+def _interp_call(ctx, single, soff, doff, fr, C, T, tracks, boxes, ntracks, anchors, series, sync):
+    """Allocate the dense outputs (flat, batch layout) and enqueue the one launch."""
+    dev = tracks.device
+    V, N = len(doff) - 1, C * T * int(doff[-1])
+    if N >= 2 ** 31 - 16 or C * T * int(soff[-1]) >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31)")
+    out_tr = torch.empty((N * 5,), dtype=torch.float32, device=dev)
+    b64 = torch.empty((N * 4,), dtype=torch.float64, device=dev)
+    tb = torch.empty((N * 4,), dtype=torch.float32, device=dev)
+    ser = torch.empty((len(series), N), dtype=torch.float64, device=dev)
+    anchor = torch.empty((N,), dtype=torch.float64, device=dev)
+    oan = torch.empty((V, C, T, 3), dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in series])
+    f64 = int(bool(series) and series[0].dtype == torch.float64)
+    tail = (C, T, tracks.data_ptr(), boxes.data_ptr() if boxes is not None else None, ntracks.data_ptr(), anchors.data_ptr(), ptrs,
+            len(series), f64, out_tr.data_ptr(), b64.data_ptr(), tb.data_ptr(), ser.data_ptr(), anchor.data_ptr(), oan.data_ptr())
+    frp = fr.ctypes.data if fr is not None else None
+    if single:
+        ctx.check(ctx.lib.vdet_interp_tracks(ctx.h, int(soff[-1]), int(doff[-1]), frp, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_interp_tracks_batch(ctx.h, soff.ctypes.data, doff.ctypes.data, V, frp, *tail))
+    if sync:
+        ctx.sync()
+    return out_tr, b64, tb, ser, anchor, oan
+
+
+def interpolate_tracks(tracks, ntracks, anchors, series, boxes=None, frames=None, num_frames=None, sync=True, ctx=None):
+    """``score_proto_interpolation`` (vdet/tubelet_cls.py:416-490) on device tubelets: tubelets tracked and re-scored on
+    every stride-th frame (``nms_track_volume`` / ``rescore_tracks`` on ``boxes[::stride]``, ``scores[::stride]``), or
+    tubelets with holes (NaN rows), back to EVERY frame of the video -- all tubelets in one launch, no host wait.
+
+    tracks [C,T,Fs,5] f32 / ntracks [C] int32 / anchors [C,T,3] f32 on the sampled axis; row i is the dense 1-based frame
+    ``frames[i]`` (strictly ascending ints; None: i + 1, the axis is dense already and only holes are filled);
+    ``num_frames`` = F, the frames of the dense video (default: the last of ``frames``, else Fs).  ``series``: up to 4
+    tensors [C,T,Fs], all f64 or all f32 (rescore_tracks' det_score / pooled, a conv_score ...); ``boxes`` [C,T,Fs,4] f32
+    to interpolate instead of the track boxes (rescore_tracks' boxes).  Semantics per tubelet, arithmetic and the end rule:
+    include/vdet_hip.h (vdet_interp_tracks) -- bit for bit oracle.tubelet_interpolation on the same numbers.
+
+    Returns a dict: ``tracks`` [C,T,F,5] f32 (interpolated box and track score, each rounded once from f64; NaN rows where
+    the tubelet has no dense box), ``boxes64`` [C,T,F,4] f64, ``tboxes`` [C,T,F,4] f32 (boxes64 rounded once), ``series``
+    (tuple of [C,T,F] f64), ``anchor`` [C,T,F] f64 (offset from the anchor in dense frames), ``anchors`` [C,T,3] f32
+    (column 0 = the anchor's dense frame number), ``ntracks``.  The track score is interpolated like a score (the
+    reference's interpolated boxes have none: build-defined)."""
+    if not torch.is_tensor(tracks) or tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,Fs,5]")
+    C, T, Fs = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if Fs < 1 or C < 1:
+        raise ValueError("a video needs at least one frame and one class")
+    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if anchors.dtype != torch.float32 or tuple(anchors.shape) != (C, T, 3):
+        raise ValueError("anchors must be float32 [C,T,3]")
+    if boxes is not None and (boxes.dtype != torch.float32 or tuple(boxes.shape) != (C, T, Fs, 4)):
+        raise ValueError("boxes must be float32 [C,T,Fs,4]")
+    for x in (tracks, ntracks, anchors) + (() if boxes is None else (boxes,)):
+        if not x.is_cuda or x.device != tracks.device:
+            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    series = _interp_series(series, C * T * Fs, tracks.device)
+    for x in series:
+        if tuple(x.shape) != (C, T, Fs):
+            raise ValueError("every series must be a float32 / float64 tensor [C,T,Fs]")
+    soff = np.array([0, Fs], dtype=np.int64)
+    if num_frames is None:
+        last = np.asarray(frames.cpu() if hasattr(frames, 'cpu') else frames).reshape(-1)[-1:] if frames is not None else []
+        num_frames = int(last[0]) if len(last) else Fs
+    fr, nf = _interp_frames(frames, soff, [int(num_frames)])
+    doff = np.array([0, int(nf[0])], dtype=np.int64)
+    tracks, ntracks, anchors = tracks.contiguous(), ntracks.contiguous(), anchors.contiguous()
+    boxes = None if boxes is None else boxes.contiguous()
+    ctx = _ctx_for(tracks, ctx)
+    out_tr, b64, tb, ser, anchor, oan = _interp_call(ctx, True, soff, doff, fr, C, T, tracks, boxes, ntracks, anchors, series, sync)
+    F = int(nf[0])
+    return dict(tracks=out_tr.view(C, T, F, 5), boxes64=b64.view(C, T, F, 4), tboxes=tb.view(C, T, F, 4),
+                series=tuple(ser[q].view(C, T, F) for q in range(len(series))), anchor=anchor.view(C, T, F),
+                anchors=oan.view(C, T, 3), ntracks=ntracks)
+
+
+def interpolate_tracks_batch(batch_out, frames, num_frames, sync=True, ctx=None):
+    """``interpolate_tracks`` for every video of a ``video_batch`` result that was computed on SAMPLED frames, in one
+    launch: ``frames`` flat [Fs_total] ints (the dense 1-based frame of every row, ascending inside each video; None:
+    identity), ``num_frames`` [V] the dense frame counts.  The re-scored ``det`` / ``pooled`` series and ``tboxes`` are
+    interpolated when the batch has them (else the track boxes, no series).  Returns a dict in ``video_batch``'s layout on
+    the DENSE axis -- ``tracks`` / ``det`` / ``pooled`` / ``tboxes`` as consecutive per-video views of one allocation,
+    ``anchors`` [V,C,T,3], ``ntracks`` [V,C], the dense ``frame_off`` -- plus ``boxes64`` and ``anchor`` views, so that
+    ``tcn_tracks_batch``, ``tubelets_overlap_batch(use_tboxes=True)`` and ``DetEvaluator.add_batch`` take it unchanged."""
+    soff = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
+    V = len(soff) - 1
+    tv = batch_out['tracks']
+    if V < 1 or len(tv) != V or soff[0] != 0 or np.any(np.diff(soff) <= 0):
+        raise ValueError("not a video_batch result")
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    tracks = _batch_flat(tv, 5)
+    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
+    if tracks.dtype != torch.float32 or tracks.numel() != C * T * int(soff[-1]) * 5 or ntracks.dtype != torch.int32 or \
+            tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or tuple(anchors.shape) != (V, C, T, 3):
+        raise ValueError("not a video_batch result")
+    rescored = bool(batch_out.get('pooled'))
+    series = _interp_series((_batch_flat(batch_out['det'], 1), _batch_flat(batch_out['pooled'], 1)) if rescored else (),
+                            C * T * int(soff[-1]), tracks.device)
+    boxes = _batch_flat(batch_out['tboxes'], 4) if rescored else None
+    for x in (ntracks, anchors) + (() if boxes is None else (boxes,)):
+        if not x.is_cuda or x.device != tracks.device:
+            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    fr, nf = _interp_frames(frames, soff, num_frames)
+    doff = np.concatenate([[0], np.cumsum(nf)]).astype(np.int64)
+    ctx = _ctx_for(tracks, ctx)
+    out_tr, b64, tb, ser, anchor, oan = _interp_call(ctx, False, soff, doff, fr, C, T, tracks, boxes, ntracks, anchors, series, sync)
+
+    def views(flat, per):
+        shape = (lambda fv: (C, T, fv, per)) if per > 1 else (lambda fv: (C, T, fv))
+        return [flat[C * T * per * int(doff[v]): C * T * per * int(doff[v + 1])].view(*shape(int(doff[v + 1] - doff[v]))) for v in range(V)]
+
+    out = dict(tracks=views(out_tr, 5), tboxes=views(tb, 4), boxes64=views(b64, 4), anchor=views(anchor, 1), anchors=oan,
+               ntracks=ntracks, frame_off=doff, det=[], pooled=[])
+    if rescored:
+        out.update(det=views(ser[0], 1), pooled=views(ser[1], 1))
+    return out
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 
