@@ -85,11 +85,23 @@ __global__ void fold_pool_kernel(Counters *cnt)
 }
 
 // a small host table the device reads in an asynchronous call: the host copy lives in the context so it outlives the copy made
-// from it, and a call that brings the same bytes again uploads nothing
+// from it, and a call that brings the same bytes again uploads nothing (stage_table / stage_keyed)
 struct StagedTab {
     DevBuf dev;
-    std::vector<char> host;
+    std::vector<char> host;       // what the device holds (the source of the last copy)
+    std::vector<char> key;        // stage_keyed: the bytes the table was built from, compared instead of the table itself
     bool valid = false;
+    long long uploads = 0;        // copies made so far
+};
+
+// which sorted lists c->order / c->ncand hold (thr takes part only under use_thr)
+struct ListsKey {
+    const void *scores = nullptr;
+    int64_t C = 0;
+    int layout = -1, use_thr = 0;
+    float thr = 0;
+    int topk = 0;
+    bool operator==(const ListsKey &o) const { return scores == o.scores && C == o.C && layout == o.layout && use_thr == o.use_thr && (!use_thr || thr == o.thr) && topk == o.topk; }
 };
 
 struct NmsPlan {
@@ -130,8 +142,9 @@ struct vdet_ctx {
     int last_launches[ST_COUNT] = {0};
     bool sort_attr_set = false;
     // opt-in reuse of the per-video preparation (graph + sorted lists) between d_* calls
+    // (owned by the prep-cache helpers next to volume_plan: nothing else reads prep or sets a flag; anyone may clear one)
     bool cache_enabled = false;
-    struct PrepKey { const void *boxes = nullptr, *scores = nullptr; int64_t F = 0, B = 0, C = 0; float t32 = 0; int layout = -1, use_thr = 0; float thr = 0; int topk = 0; } prep;
+    struct PrepKey { const void *boxes = nullptr; int64_t F = 0, B = 0; float t32 = 0; ListsKey lists; } prep;
     bool graph_valid = false, lists_valid = false;
     // class-major sort keys left in c->tkeys by vdet_volume_pass (reused like the other prep, cache on)
     struct KeySrc { const void *scores = nullptr; int64_t F = 0, B = 0, C = 0; int use_thr = 0; float thr = 0; } keysrc;
@@ -172,11 +185,7 @@ struct vdet_ctx {
     bool wmeta16_built = false;   // ... and adj_rows_kernel the 16-byte form of the records of integer frames
     bool wmeta_built = false;     // ... which also wrote the packed walk's records (WalkMeta) of the regular frames
     bool last_sort_binned = false;   // the last per-(frame, class) sort went through binsort_kernel (vdet_query 9)
-    DevBuf vidtab;                // batched videos: {first frame, frames} per video
-    std::vector<VidDesc> h_vids, h_vids_stage;   // the resident table (empty: none) / the source of the copy in flight
-    DevBuf segtab;                // batched videos: per-frame {first, one past last} frame of its video
-    std::vector<int2> h_seg;
-    std::vector<int64_t> h_seg_off;   // the offsets h_seg / segtab were built from
+    StagedTab vidtab, segtab;     // batched videos, keyed by the frame offsets: {first frame, frames} per video / per frame {first, one past last} of its video
     DevBuf sortctl;               // binsort_kernel's work counter + the list of problems it handed to the LSD kernel
     DevBuf nover;                 // vdet_det_nms_volume: candidates per list before the topk cut
     DevBuf ordncand;              // vdet_nms_volume_ordered: the caller's counts after check_order_kernel
@@ -197,8 +206,7 @@ struct vdet_ctx {
     // device TCN (tcn_kernels.hpp): assembled channels, frame lists, tubelet descriptors, the global-path activations, and the
     // host tables its asynchronous calls read on the device (net parameters, frame offsets, the overlap call's tables)
     DevBuf tcn_x, tcn_frames, tcn_base, tcn_len, tcn_scratch;
-    StagedTab tcn_params, tcn_foff, tcn_ovtab;
-    long long tcn_uploads = 0;    // parameter uploads so far (vdet_query 10)
+    StagedTab tcn_params, tcn_foff, tcn_ovtab;      // (tcn_params.uploads: vdet_query 10)
     bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
     bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
     StagedTab interp_tab;         // device interpolation (interp_kernels.hpp): frame offsets and the frame table of the last call
@@ -255,6 +263,53 @@ struct StageTimer {
 };
 
 void timing_reset(vdet_ctx *c) { if (!c->timing_accumulate) c->ev_used = 0; }
+
+// StagedTab, the miss: fill(host bytes) writes the new table.  A change waits for the stream once (the copy made from the old
+// bytes may be in flight); the table is resident only once its copy is enqueued, so a failed reserve or copy leaves none.
+template <typename Fill> int stage_upload(vdet_ctx *c, StagedTab &t, size_t bytes, Fill fill)
+{
+    t.valid = false;
+    if (!t.host.empty()) HIPCHK(c, host_sync(c));
+    t.host.resize(bytes);
+    fill(t.host.data());
+    HIPCHK(c, t.dev.reserve(std::max<size_t>(bytes, 16)));
+    if (bytes) HIPCHK(c, hipMemcpyAsync(t.dev.p, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    t.valid = true;
+    ++t.uploads;
+    return VDET_OK;
+}
+
+// the table IS the caller's bytes: the same bytes again cost neither a wait nor a copy
+int stage_table(vdet_ctx *c, StagedTab &t, const void *src, size_t bytes)
+{
+    if (t.valid && t.host.size() == bytes && memcmp(t.host.data(), src, bytes) == 0) return VDET_OK;
+    return stage_upload(c, t, bytes, [&](char *dst) { memcpy(dst, src, bytes); });
+}
+
+// the table is BUILT from the caller's bytes (O(frames) from O(videos) offsets): the same key again does not even build it
+template <typename Fill> int stage_keyed(vdet_ctx *c, StagedTab &t, const void *key, size_t key_bytes, size_t bytes, Fill fill)
+{
+    if (t.valid && t.key.size() == key_bytes && memcmp(t.key.data(), key, key_bytes) == 0) return VDET_OK;
+    t.valid = false;
+    t.key.assign(static_cast<const char *>(key), static_cast<const char *>(key) + key_bytes);
+    return stage_upload(c, t, bytes, fill);
+}
+
+// THE check of the frame offsets of V concatenated videos: from 0, increasing -- strictly unless allow_empty; max_videos > 0 caps V
+int check_frame_off(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, bool allow_empty, int64_t max_videos, int64_t *Ftot, int64_t *Fmax)
+{
+    if (!h_frame_off || V < 1) return fail(c, VDET_EINVAL, "at least one video with its frame offsets");
+    if (max_videos > 0 && V > max_videos) return fail(c, VDET_EINVAL, "at most %lld videos in one call", (long long)max_videos);
+    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame_off must start at 0");
+    *Fmax = 0;
+    for (int64_t v = 0; v < V; ++v) {
+        const int64_t f = h_frame_off[v + 1] - h_frame_off[v];
+        if (f < (allow_empty ? 0 : 1)) return fail(c, VDET_EINVAL, "frame_off must %s", allow_empty ? "not decrease" : "be strictly increasing");
+        *Fmax = std::max(*Fmax, f);
+    }
+    *Ftot = h_frame_off[V];
+    return VDET_OK;
+}
 
 // smallest float32 f with (double)f >= thresh: "(double)ovr_f32 >= thresh" <=> "ovr_f32 >= f"
 float thresh_to_f32(double thresh)
@@ -382,6 +437,114 @@ NmsPlan &volume_plan(vdet_ctx *c, int64_t F, int64_t B)
     c->vplan_F = F; c->vplan_B = B; c->vplan_budget = c->bits_budget;
     c->vplan_valid = false;
     return c->vplan;
+}
+
+// calls that need only the group table of a volume (one group of B boxes per frame) on the device; tiles / pairs follow
+// with the next graph build
+int volume_groups(vdet_ctx *c, int64_t F, int64_t B)
+{
+    NmsPlan &pl = volume_plan(c, F, B);
+    c->host_groups = &pl.groups;
+    HIPCHK(c, c->groups.reserve((size_t)F * sizeof(GroupDesc)));
+    if (!c->vplan_valid)
+        HIPCHK(c, hipMemcpyAsync(c->groups.p, pl.groups.data(), (size_t)F * sizeof(GroupDesc), hipMemcpyHostToDevice, c->stream));
+    return VDET_OK;
+}
+
+int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, double thresh, bool volume);
+
+// ---- the prep cache: c->prep, graph_valid and lists_valid are read, and set, only here
+// Make the resident suppression graph the one of these boxes at this threshold.  reuse: the resident one may serve, when the
+// cache is on and its key matches -- the threshold bit for bit, so that a NaN threshold equals itself; *reused says so.
+int ensure_volume_graph(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, double nms_thres, bool reuse, bool *reused = nullptr)
+{
+    const float t32 = thresh_to_f32(nms_thres);
+    const bool same = reuse && c->cache_enabled && c->graph_valid && c->prep.boxes == d_boxes && c->prep.F == F && c->prep.B == B &&
+                      memcmp(&c->prep.t32, &t32, 4) == 0;
+    if (reused) *reused = same;
+    if (same) return VDET_OK;
+    c->graph_valid = c->lists_valid = c->nodes_valid = false;     // (the recorded track nodes point into the lists rewritten now)
+    const int rc = build_graph(c, reinterpret_cast<const float4 *>(d_boxes), volume_plan(c, F, B), t32, nms_thres, true);
+    if (rc) return rc;
+    c->prep.boxes = d_boxes; c->prep.F = F; c->prep.B = B; c->prep.t32 = t32;
+    c->graph_valid = true;
+    return VDET_OK;
+}
+
+// are the resident sorted lists those of key, made on a volume of F x B?
+bool lists_match(const vdet_ctx *c, const ListsKey &key, int64_t F, int64_t B) { return c->lists_valid && c->prep.F == F && c->prep.B == B && c->prep.lists == key; }
+void set_lists(vdet_ctx *c, const ListsKey &key) { c->prep.lists = key; c->lists_valid = true; }
+
+// vdet_rescore_tracks: do gflags / the x-index describe these boxes (left by the graph build of the same volume)?
+bool index_matches(const vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B)
+{
+    return c->cache_enabled && c->graph_valid && c->index_valid && c->prep.boxes == d_boxes && c->prep.F == F && c->prep.B == B && c->index_boxes == d_boxes;
+}
+
+// ... and are these the tracks of the last tracking call on this context, same boxes, with the graph they were made on (same
+// threshold) still in place?  Then c->tracknode says which proposal every tubelet box is.
+bool nodes_match(const vdet_ctx *c, const float *d_tracks, const float *d_boxes, int64_t F, int64_t B, int64_t C, int T)
+{
+    const float nt = thresh_to_f32(c->nodekey.nms_thres);
+    return c->cache_enabled && c->nodes_valid && c->graph_valid && c->nodekey.tracks == d_tracks && c->nodekey.boxes == d_boxes &&
+           c->prep.boxes == d_boxes && c->nodekey.F == F && c->nodekey.B == B && c->nodekey.C == C && c->nodekey.T == T &&
+           c->prep.F == F && c->prep.B == B && memcmp(&c->prep.t32, &nt, 4) == 0;
+}
+
+// re-scoring may take a tubelet box's candidates from its proposal's graph neighbours: with the regular-frame flags and
+// overlap_thres well above the graph's threshold
+bool rescore_from_graph(const uint32_t *group_flags, double nms_thres, double overlap_thres)
+{
+    return group_flags && overlap_thres - nms_thres > 0.05 && nms_thres > 0.0 && overlap_thres < 1.0;
+}
+
+// ---- the tracking workspace of vdet_nms_track_volume (n_states = C) and vdet_video_batch (n_states = V * C)
+struct TrackWork {
+    const uint32_t *flags;        // regular-frame flags, or null: only when the graph in place ran K0 + the frame index
+    FrameIndex ix;                // ... and the x-index for the link windows, when there is one
+    bool filled;                  // small frames: the whole link table is filled up front, nothing is predicted
+    float link_t32;
+    int reach, mask_words, lazy;
+    bool need_suppress;           // the eager track_det_nms pass, for the lists the pick does not maintain
+};
+
+// (the scalars first: how many warm chains a call wants depends on them.  reach_unbounded: the caller's kernels' "no max_frames")
+TrackWork track_work(vdet_ctx *c, int64_t B, double link_thres, int max_frames, int reach_unbounded)
+{
+    TrackWork w{};
+    w.flags = c->sym_built ? c->gflags.as<uint32_t>() : nullptr;
+    if (w.flags && c->index_valid && !c->no_index) w.ix = frame_index_of(c);
+    w.filled = B <= kLinkFillMax && w.ix.xbox != nullptr;
+    w.link_t32 = thresh_to_f32(link_thres);
+    w.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : reach_unbounded;
+    w.mask_words = (int)((((size_t)4 * ((B + 31) / 32) + 15) & ~(size_t)15) / 4);
+    w.lazy = c->no_lazy ? 0 : 1;
+    // (when the host does not know whether every frame is regular -- asynchronous build -- the kernel asks the device)
+    w.need_suppress = !w.lazy || !w.flags || !c->all_regular;
+    return w;
+}
+
+// reserve and clear: recorded nodes (0xFF: none), one link memo per call (a link step depends on the boxes and link_thres
+// only), and -- with tracks to make -- wm warm chains per state, the visited marks and the lazy-list state of the pick
+// (t1 | head | nkp | pos, [F*C] int32 each)
+int track_scratch(vdet_ctx *c, int64_t Ftot, int64_t B, int64_t C, int T, int wm, int64_t n_states)
+{
+    auto cleared = [&](DevBuf &b, int byte, size_t bytes) {
+        const hipError_t e = b.reserve(bytes);
+        return e != hipSuccess ? e : hipMemsetAsync(b.p, byte, bytes, c->stream);
+    };
+    c->nodes_valid = false;
+    HIPCHK(c, cleared(c->tracknode, 0xFF, (size_t)std::max<int64_t>(C * T * Ftot, 1) * 4));
+    HIPCHK(c, cleared(c->linkmemo, 0, (size_t)2 * Ftot * B * 8));
+    HIPCHK(c, cleared(c->linkstats, 0, 16));
+    HIPCHK(c, c->tstate.reserve((size_t)n_states * sizeof(TrackState)));
+    if (T == 0) return VDET_OK;
+    HIPCHK(c, c->linkwarm.reserve((size_t)n_states * wm * 4));
+    HIPCHK(c, c->linkchains.reserve((size_t)C * wm * Ftot * 5 * 4));
+    HIPCHK(c, cleared(c->linknodes, 0xFF, (size_t)C * wm * Ftot * 4));
+    HIPCHK(c, cleared(c->visited, 0, (size_t)(Ftot * C)));
+    HIPCHK(c, cleared(c->heads, 0, (size_t)(Ftot * C) * 16));
+    return VDET_OK;
 }
 
 // host-buffer entry points: their group table dies with the call
@@ -566,7 +729,7 @@ int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, doub
                                    bits_b, c->rowz.as<uint32_t>(), c->rowmeta.as<uint2>(),
                                    c->adj.as<uint16_t>(), &c->d_cnt->pool_used, pool_cap,
                                    &c->d_cnt->status, use_sym ? c->gflags.as<uint32_t>() : (const uint32_t *)nullptr,
-                                   use_sym ? frame_index_of(c) : FrameIndex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0}, one_minus_t,
+                                   use_sym ? frame_index_of(c) : FrameIndex{}, one_minus_t,
                                    async ? (kStPool | kStPoolAsync) : kStPool,
                                    c->wmeta_built ? c->wmeta.as<WalkMeta>() : (WalkMeta *)nullptr,
                                    use_sym ? c->reachtab.as<float2>() : (const float2 *)nullptr, rows_path ? 1 : 0);
@@ -644,6 +807,26 @@ struct SortWalkArgs {
     int32_t *keep_cnt;
     int64_t cap;
 };
+
+// an [F,B,C] score volume through the transposed keys: only the descending lists per (frame, class) ...
+SortWalkArgs volume_sort_args(int64_t F, int64_t B, int64_t C, const float *d_scores)
+{
+    SortWalkArgs a{};
+    a.sort_only = true;
+    a.mode = 0; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
+    a.scores = d_scores;
+    return a;
+}
+
+// ... and only the walk over them (the lists stay in place)
+SortWalkArgs volume_walk_args(int64_t F, int64_t B, int64_t C, const float *d_scores, int32_t *keep_idx, int32_t *keep_cnt, int64_t cap)
+{
+    SortWalkArgs a = volume_sort_args(F, B, C, d_scores);
+    a.sort_only = false;
+    a.walk_only = true;
+    a.keep_idx = keep_idx; a.keep_cnt = keep_cnt; a.cap = cap;
+    return a;
+}
 
 int sort_comp_desc(vdet_ctx *c, uint32_t n);
 
@@ -1256,7 +1439,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->rowz, &c->rowmeta, &c->groupz, &c->adj, &c->comp, &c->origidx, &c->out64,
                       &c->trk_frames, &c->trk_boxes, &c->b1, &c->b2, &c->iou_out, &c->order, &c->ncand, &c->keepidx,
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
-                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab, &c->vidtab, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
+                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev};
     for (DevBuf *b : bufs) b->release();
@@ -1311,7 +1494,7 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 2) return c->all_regular ? 1 : 0;
     if (what == 3) return c->wave_transpose ? 1 : 0;
     if (what == 8) return (int)std::min<long long>(c->n_host_syncs, 0x7FFFFFFF);
-    if (what == 10) return (int)std::min<long long>(c->tcn_uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
+    if (what == 10) return (int)std::min<long long>(c->tcn_params.uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -1626,31 +1809,19 @@ int vdet_nms_volume_topk(vdet_ctx *c, const float *d_boxes, const float *d_score
         HIPCHK(c, hipMemsetAsync(d_keep_cnt, 0, (size_t)(F * C) * 4, c->stream));
         return VDET_OK;
     }
-    const float t32 = thresh_to_f32(thresh);
-    const bool same_geo = c->cache_enabled && c->graph_valid && c->prep.boxes == d_boxes && c->prep.F == F &&
-                          c->prep.B == B && memcmp(&c->prep.t32, &t32, 4) == 0;
-    const bool same_lists = same_geo && c->lists_valid && c->prep.scores == d_scores && c->prep.C == C &&
-                            c->prep.layout == layout && c->prep.use_thr == use_score_thresh &&
-                            (!use_score_thresh || c->prep.thr == score_thresh) && c->prep.topk == topk;
-    int rc;
-    if (!same_geo) {
-        c->graph_valid = c->lists_valid = false;
-        rc = build_graph(c, reinterpret_cast<const float4 *>(d_boxes), volume_plan(c, F, B), t32, thresh, true);
-        if (rc) return rc;
-        c->prep.boxes = d_boxes; c->prep.F = F; c->prep.B = B; c->prep.t32 = t32;
-        c->graph_valid = true;
-    }
+    bool same_geo = false;
+    int rc = ensure_volume_graph(c, d_boxes, F, B, thresh, true, &same_geo);
+    if (rc) return rc;
+    const ListsKey key{d_scores, C, layout, use_score_thresh, score_thresh, topk};
     SortWalkArgs a{};
-    a.walk_only = same_lists;
+    a.walk_only = same_geo && lists_match(c, key, F, B);
     a.mode = layout; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
     a.scores = d_scores;
     a.use_thr = use_score_thresh; a.thr = score_thresh; a.topk = topk;
     a.keep_idx = d_keep_idx; a.keep_cnt = d_keep_cnt; a.cap = cap;
     rc = launch_sort_walk(c, a, (int)B, F * C * B);
     if (rc) return rc;
-    c->prep.scores = d_scores; c->prep.C = C; c->prep.layout = layout; c->prep.use_thr = use_score_thresh;
-    c->prep.thr = score_thresh; c->prep.topk = topk;
-    c->lists_valid = true;
+    set_lists(c, key);
     return VDET_OK;
 }
 
@@ -1678,22 +1849,15 @@ int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores
     }
     if (!d_boxes || !d_scores) return fail(c, VDET_EINVAL, "null buffer");
     if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
-    // only the group table (one group of B boxes per frame) is needed: no suppression graph is shared between classes here
-    NmsPlan &pl = volume_plan(c, F, B);
-    c->host_groups = &pl.groups;
-    HIPCHK(c, c->groups.reserve((size_t)F * sizeof(GroupDesc)));
-    if (!c->vplan_valid)
-        HIPCHK(c, hipMemcpyAsync(c->groups.p, pl.groups.data(), (size_t)F * sizeof(GroupDesc), hipMemcpyHostToDevice, c->stream));
+    // (no suppression graph is shared between classes here)
+    int rc = volume_groups(c, F, B);
+    if (rc) return rc;
     c->lists_valid = false;          // (the context's lists become the selections)
     HIPCHK(c, c->nover.reserve((size_t)(F * K) * 4));
-    SortWalkArgs a{};
-    a.sort_only = true;
-    a.mode = 0; a.P = (int)(F * K); a.B = (int)B; a.C = (int)K;
-    a.scores = d_scores;
+    SortWalkArgs a = volume_sort_args(F, B, K, d_scores);
     a.use_thr = use_score_thresh ? 1 : 0; a.thr = score_thresh; a.topk = topk;
     a.nover_out = c->nover.as<int32_t>();
-    const int rc = launch_sort_walk(c, a, (int)B, F * K * B);
-    if (rc) return rc;
+    if ((rc = launch_sort_walk(c, a, (int)B, F * K * B))) return rc;
     DetNmsParams dp{};
     dp.boxes = reinterpret_cast<const float4 *>(d_boxes); dp.scores = d_scores;
     dp.F = (int)F; dp.B = (int)B; dp.K = (int)K; dp.class0 = class0;
@@ -1727,16 +1891,8 @@ int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d
     }
     if (!d_boxes || !d_order || !d_ncand) return fail(c, VDET_EINVAL, "null buffer");
     if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
-    const float t32 = thresh_to_f32(thresh);
-    const bool same_geo = c->cache_enabled && c->graph_valid && c->prep.boxes == d_boxes && c->prep.F == F &&
-                          c->prep.B == B && memcmp(&c->prep.t32, &t32, 4) == 0;
-    if (!same_geo) {
-        c->graph_valid = c->lists_valid = false;
-        const int rc = build_graph(c, reinterpret_cast<const float4 *>(d_boxes), volume_plan(c, F, B), t32, thresh, true);
-        if (rc) return rc;
-        c->prep.boxes = d_boxes; c->prep.F = F; c->prep.B = B; c->prep.t32 = t32;
-        c->graph_valid = true;
-    }
+    const int rc = ensure_volume_graph(c, d_boxes, F, B, thresh, true);
+    if (rc) return rc;
     // the lists are the caller's: counts / indices out of range latch VDET_EINVAL (vdet_sync) and the list is walked as empty
     HIPCHK(c, c->ordncand.reserve((size_t)(F * C) * 4));
     hipLaunchKernelGGL(check_order_kernel, dim3((unsigned)((F * C + 3) / 4)), dim3(256), 0, c->stream, d_order, d_ncand, (int)(F * C), (int)B,
@@ -1765,12 +1921,8 @@ int vdet_argsort_volume(vdet_ctx *c, const float *d_scores, int layout, int64_t 
         HIPCHK(c, hipMemsetAsync(d_ncand, 0, (size_t)(F * C) * 4, c->stream));
         return VDET_OK;
     }
-    // only the group table (one group of B boxes per frame) is needed; tiles / pairs follow with the next graph build
-    NmsPlan &pl = volume_plan(c, F, B);
-    c->host_groups = &pl.groups;
-    HIPCHK(c, c->groups.reserve((size_t)F * sizeof(GroupDesc)));
-    if (!c->vplan_valid)
-        HIPCHK(c, hipMemcpyAsync(c->groups.p, pl.groups.data(), (size_t)F * sizeof(GroupDesc), hipMemcpyHostToDevice, c->stream));
+    const int rc = volume_groups(c, F, B);
+    if (rc) return rc;
     c->lists_valid = false;          // (c->tkeys, which the context's own lists are read with, is rewritten)
     SortWalkArgs a{};
     a.sort_only = true;
@@ -1807,99 +1959,61 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     const float t32 = thresh_to_f32(nms_thres);
-    const bool same_geo = c->cache_enabled && c->graph_valid && c->prep.boxes == d_boxes && c->prep.F == F &&
-                          c->prep.B == B && memcmp(&c->prep.t32, &t32, 4) == 0;
-    const bool same_lists = same_geo && c->lists_valid && c->prep.scores == d_scores && c->prep.C == C &&
-                            c->prep.layout == VDET_LAYOUT_FBC && c->prep.use_thr == 0 && c->prep.topk == 0;
-    int rc;
-    if (!same_geo) {
-        c->graph_valid = c->lists_valid = false;
-        rc = build_graph(c, reinterpret_cast<const float4 *>(d_boxes), volume_plan(c, F, B), t32, nms_thres, true);
-        if (rc) return rc;
-        c->prep.boxes = d_boxes; c->prep.F = F; c->prep.B = B; c->prep.t32 = t32;
-        c->graph_valid = true;
-    }
-    if (!same_lists) {
+    bool same_geo = false;
+    int rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, true, &same_geo);
+    if (rc) return rc;
+    if (!(same_geo && lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, 0, 0.f, 0}, F, B))) {
         // descending lists per (frame, class): always through the transposed keys (pick needs them)
-        SortWalkArgs a{};
-        a.sort_only = true;
-        a.mode = 0; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
-        a.scores = d_scores;
-        rc = launch_sort_walk(c, a, (int)B, F * C * B);
+        rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B);
         if (rc) return rc;
     }
     // regular-frame fast paths (lazy lists, x-window link): only when THIS graph build (or the cached
     // one being reused) ran K0 + the frame index -- gflags / the index are stale otherwise
-    const bool regular_ok = c->sym_built;
-    const float link_t32 = thresh_to_f32(link_thres);
-    const int reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)F;
-    const uint32_t *w_flags = regular_ok ? c->gflags.as<uint32_t>() : nullptr;
-    FrameIndex w_ix{nullptr, nullptr, nullptr, nullptr};
-    if (w_flags && c->index_valid && !c->no_index) w_ix = frame_index_of(c);
-    c->nodes_valid = false;
-    HIPCHK(c, c->tracknode.reserve((size_t)std::max<int64_t>(C * max_tracks * F, 1) * 4));
-    HIPCHK(c, hipMemsetAsync(c->tracknode.p, 0xFF, (size_t)std::max<int64_t>(C * max_tracks * F, 1) * 4, c->stream));
+    const TrackWork w = track_work(c, B, link_thres, max_frames, (int)F);
+    // small frames (filled): the whole link table up front (every node's window scan, chip-filling) -- then no step of any
+    // chain is ever scanned again, whatever the anchors turn out to be.
+    // Warm the memo otherwise: the chains of every class's likely anchors, all at once (the chip is full instead of
+    // running 2 C latency-bound blocks per track); the tracking loop below then mostly walks known steps.  + slots for
+    // the anchors of COHERENT videos (track_warm_anchors_body: filled only when a class's raw candidates repeat each
+    // other's objects across frames; empty -- and free -- otherwise)
+    const int wm_raw = std::min(max_tracks + 6, 24);       // (measured: 16 of 10 tracks)
+    const bool coherent_slots = F <= 512 && w.flags && !w.filled;
+    const int wm = coherent_slots ? std::min(wm_raw + max_tracks, 32) : wm_raw;
+    if ((rc = track_scratch(c, F, B, C, max_tracks, wm, C))) return rc;
     int materialized = 0;            // warm chains per class whose tubelets are written out (0: none)
-    // one link memo per call: a link step depends on the video's boxes and link_thres only
-    HIPCHK(c, c->linkmemo.reserve((size_t)2 * F * B * 8));
-    HIPCHK(c, c->linkstats.reserve(16));
-    HIPCHK(c, hipMemsetAsync(c->linkmemo.p, 0, (size_t)2 * F * B * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->linkstats.p, 0, 16, c->stream));
     if (max_tracks > 0) {
-        // small frames: the whole link table up front (every node's window scan, chip-filling) -- then no step of any chain
-        // is ever scanned again, whatever the anchors turn out to be
-        const bool filled = B <= kLinkFillMax && w_ix.xbox != nullptr;
-        // warm the memo otherwise: the chains of every class's likely anchors, all at once (the chip is full instead of
-        // running 2 C latency-bound blocks per track); the tracking loop below then mostly walks known steps.  + slots for
-        // the anchors of COHERENT videos (track_warm_anchors_body: filled only when a class's raw candidates repeat each
-        // other's objects across frames; empty -- and free -- otherwise)
-        const int wm_raw = std::min(max_tracks + 6, 24);       // (measured: 16 of 10 tracks)
-        const bool coherent_slots = F <= 512 && regular_ok && !filled;
-        const int wm = coherent_slots ? std::min(wm_raw + max_tracks, 32) : wm_raw;
         StageTimer tm(c, ST_TLINK);
-        if (filled)
+        if (w.filled)
             hipLaunchKernelGGL(link_fill_frame_kernel, dim3((unsigned)F, 2), dim3((unsigned)(64 * ((B + 63) / 64))), link_fill_lds_bytes((int)B), c->stream,
-                               reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, link_t32, w_flags, w_ix, link_thres,
+                               reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, w.link_t32, w.flags, w.ix, link_thres,
                                c->linkmemo.as<unsigned long long>());
-        HIPCHK(c, c->linkwarm.reserve((size_t)C * wm * 4));
         hipLaunchKernelGGL(track_warm_anchors_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, c->tkeys.as<uint32_t>(),
                            c->order.as<uint16_t>(), c->ncand.as<int32_t>(), (int)F, (int)B, (int)C, d_scores, thres, wm,
                            c->linkwarm.as<int32_t>(),
                            WarmExtra{coherent_slots ? reinterpret_cast<const float4 *>(d_boxes) : nullptr, t32, wm_raw, max_tracks});
-        if (!filled) {
+        if (!w.filled) {
             // longest chains first, then every (chain, direction) as one block of the warm-up launch
             HIPCHK(c, c->linkorder.reserve((size_t)C * wm * 2 * 4));
             hipLaunchKernelGGL(warm_order_kernel, dim3(1), dim3(1024), 0, c->stream, c->linkwarm.as<int32_t>(), (int)(C * wm), (int)F, (int)B,
-                               reach, c->linkorder.as<int32_t>());
+                               w.reach, c->linkorder.as<int32_t>());
             hipLaunchKernelGGL((track_link_memo_kernel<256, 1, 8>), dim3((unsigned)(C * wm), 2), dim3(256), 0, c->stream,
-                               reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, max_tracks, link_t32, reach,
-                               (const TrackState *)nullptr, (float *)nullptr, w_flags, w_ix, link_thres,
+                               reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, max_tracks, w.link_t32, w.reach,
+                               (const TrackState *)nullptr, (float *)nullptr, w.flags, w.ix, link_thres,
                                c->linkmemo.as<unsigned long long>(), c->linkstats.as<unsigned int>(), c->linkwarm.as<int32_t>(),
                                (int32_t *)nullptr, (const int32_t *)c->linkorder.as<int32_t>());
         }
         // every step of the warm chains is known now: write each predicted anchor's tubelet ONCE (one wave walks a chain; all
         // of them side by side), for the tracking loop to copy
-        HIPCHK(c, c->linkchains.reserve((size_t)C * wm * F * 5 * 4));
-        HIPCHK(c, c->linknodes.reserve((size_t)C * wm * F * 4));
-        HIPCHK(c, hipMemsetAsync(c->linknodes.p, 0xFF, (size_t)C * wm * F * 4, c->stream));
         hipLaunchKernelGGL((track_link_memo_kernel<64, 2, 8>), dim3((unsigned)(C * wm), 2), dim3(64), 0, c->stream,
-                           reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, max_tracks, link_t32, reach,
-                           (const TrackState *)nullptr, c->linkchains.as<float>(), w_flags, w_ix, link_thres,
+                           reinterpret_cast<const float4 *>(d_boxes), (int)F, (int)B, max_tracks, w.link_t32, w.reach,
+                           (const TrackState *)nullptr, c->linkchains.as<float>(), w.flags, w.ix, link_thres,
                            c->linkmemo.as<unsigned long long>(), (unsigned int *)nullptr, c->linkwarm.as<int32_t>(),
                            c->linknodes.as<int32_t>(), (const int32_t *)nullptr);
         materialized = wm;
     }
-    if (want_nms) {                  // the NMS survivors: one walk over the lists, before they are consumed
-        SortWalkArgs a{};
-        a.walk_only = true;
-        a.mode = 0; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
-        a.scores = d_scores;
-        a.keep_idx = d_keep_idx; a.keep_cnt = d_keep_cnt; a.cap = cap;
-        rc = launch_sort_walk(c, a, (int)B, F * C * B);
-        if (rc) return rc;
-    }
+    // the NMS survivors: one walk over the lists, before they are consumed
+    if (want_nms && (rc = launch_sort_walk(c, volume_walk_args(F, B, C, d_scores, d_keep_idx, d_keep_cnt, cap), (int)B, F * C * B))) return rc;
     c->lists_valid = false;          // the lists are consumed (compacted in place) below
-    HIPCHK(c, c->tstate.reserve((size_t)C * sizeof(TrackState)));
     TrackState *st = c->tstate.as<TrackState>();
     const unsigned cg = (unsigned)((C + 63) / 64);
     hipLaunchKernelGGL(track_init_kernel, dim3(cg), dim3(64), 0, c->stream, st, (int)C);
@@ -1915,31 +2029,20 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
     sp.row_meta = c->rowmeta.as<uint2>();
     sp.adj = c->adj.as<uint16_t>();
     sp.group_z = c->groupz.as<uint32_t>();
-    sp.group_flags = regular_ok ? c->gflags.as<uint32_t>() : nullptr;
-    sp.ix = FrameIndex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    if (sp.group_flags && c->index_valid && !c->no_index) sp.ix = frame_index_of(c);   // built by build_graph
+    sp.group_flags = w.flags; sp.ix = w.ix;      // (built by build_graph)
     sp.thres = nms_thres;
     sp.lists = c->order.as<uint16_t>();
     sp.cnt = c->ncand.as<int32_t>();
-    HIPCHK(c, c->visited.reserve((size_t)(F * C)));
-    HIPCHK(c, hipMemsetAsync(c->visited.p, 0, (size_t)(F * C), c->stream));
     sp.visited = c->visited.as<uint8_t>();
     sp.st = st;
     sp.tracks = d_tracks;
     sp.t32 = t32;
     sp.status = &c->d_cnt->status;
-    sp.mask_words = (int)((((size_t)4 * ((B + 31) / 32) + 15) & ~(size_t)15) / 4);
-    sp.lazy = c->no_lazy ? 0 : 1;
-    // lazy-list state of the pick: t1 | head | nkp | pos, [F*C] int32 each
-    HIPCHK(c, c->heads.reserve((size_t)(F * C) * 16));
-    HIPCHK(c, hipMemsetAsync(c->heads.p, 0, (size_t)(F * C) * 16, c->stream));
+    sp.mask_words = w.mask_words; sp.lazy = w.lazy;
     LazyLists lz{};
     lz.boxes = sp.boxes; lz.tracks = d_tracks; lz.t32 = t32;
     lz.t1 = c->heads.as<int32_t>(); lz.head = lz.t1 + F * C; lz.nkp = lz.head + F * C; lz.pos = lz.nkp + F * C;
     lz.group_flags = sp.lazy ? sp.group_flags : nullptr;
-    // the eager track_det_nms pass is only needed for the lists the pick does not maintain; when the
-    // host does not know whether every frame is regular (asynchronous build) the kernel asks the device
-    const bool need_suppress = !sp.lazy || !sp.group_flags || !c->all_regular;
     sp.n_irregular = &c->d_cnt->irregular;
     // predicted anchors: their tubelets exist already, the loop copies them
     ResolveArgs rv{c->linkwarm.as<int32_t>(), materialized, c->linkchains.as<float>(), c->linknodes.as<int32_t>(), d_tracks,
@@ -1949,10 +2052,10 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
         LoopArgs la{};
         la.keys = c->tkeys.as<uint32_t>(); la.lists = c->order.as<uint16_t>(); la.cnt = c->ncand.as<int32_t>();
         la.scores = d_scores; la.thres = thres; la.link_thres = link_thres; la.anchors = d_anchors;
-        la.link_t32 = link_t32; la.reach = reach;
+        la.link_t32 = w.link_t32; la.reach = w.reach;
         la.memo = c->linkmemo.as<unsigned long long>(); la.stats = c->linkstats.as<unsigned int>();
         la.nodes = c->tracknode.as<int32_t>(); la.ntracks_out = d_ntracks;
-        la.need_suppress = need_suppress ? 1 : 0;
+        la.need_suppress = w.need_suppress ? 1 : 0;
         StageTimer tm(c, ST_TLOOP);
         hipLaunchKernelGGL(track_loop_kernel, dim3((unsigned)C), dim3(256), (size_t)sp.mask_words * 16, c->stream, la, lz, rv, sp);
     }
@@ -1979,47 +2082,23 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     if (!c) return VDET_EINVAL;
     const bool want_nms = d_keep_cnt != nullptr, want_rescore = d_pooled != nullptr;
     if (want_nms && (cap < 0 || (cap > 0 && !d_keep_idx))) return fail(c, VDET_EINVAL, "null output");
-    if (V <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || !h_frame_off) return fail(c, VDET_EINVAL, "bad shape");
+    if (B <= 0 || C <= 0 || max_tracks < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (!d_boxes || !d_scores || !d_ntracks || (max_tracks > 0 && (!d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
     if (want_rescore && (!d_det_score || !d_boxes_out)) return fail(c, VDET_EINVAL, "null buffer");
     if (want_rescore && (window < 1 || window % 2 != 1)) return fail(c, VDET_EINVAL, "Window size must be odd!");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
     if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
-    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame offsets must start at 0");
-    int64_t Fmax = 0;
-    for (int64_t v = 0; v < V; ++v) {
-        if (h_frame_off[v + 1] <= h_frame_off[v]) return fail(c, VDET_EINVAL, "every video needs at least one frame");
-        Fmax = std::max(Fmax, h_frame_off[v + 1] - h_frame_off[v]);
-    }
-    const int64_t F = h_frame_off[V];
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 0, &F, &Fmax);
+    if (rc) return rc;
     if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll || V * C > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     const float t32 = thresh_to_f32(nms_thres);
-    int rc;
-    // ---- the batch as one volume of F frames: graph, sorted lists, NMS survivors
-    c->graph_valid = c->lists_valid = c->nodes_valid = false;
-    rc = build_graph(c, reinterpret_cast<const float4 *>(d_boxes), volume_plan(c, F, B), t32, nms_thres, true);
-    if (rc) return rc;
-    c->prep.boxes = d_boxes; c->prep.F = F; c->prep.B = B; c->prep.t32 = t32;
-    c->graph_valid = true;
-    {
-        SortWalkArgs a{};
-        a.sort_only = true;
-        a.mode = 0; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
-        a.scores = d_scores;
-        rc = launch_sort_walk(c, a, (int)B, F * C * B);
-        if (rc) return rc;
-    }
-    if (want_nms) {
-        SortWalkArgs a{};
-        a.walk_only = true;
-        a.mode = 0; a.P = (int)(F * C); a.B = (int)B; a.C = (int)C;
-        a.scores = d_scores;
-        a.keep_idx = d_keep_idx; a.keep_cnt = d_keep_cnt; a.cap = cap;
-        rc = launch_sort_walk(c, a, (int)B, F * C * B);
-        if (rc) return rc;
-    }
+    // ---- the batch as one volume of F frames: graph (always rebuilt), sorted lists, NMS survivors
+    if ((rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, false))) return rc;
+    if ((rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B))) return rc;
+    if (want_nms && (rc = launch_sort_walk(c, volume_walk_args(F, B, C, d_scores, d_keep_idx, d_keep_cnt, cap), (int)B, F * C * B))) return rc;
     c->lists_valid = false;          // consumed by the tracking below
     HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)(V * C) * 4, c->stream));
     if (max_tracks == 0) {
@@ -2027,55 +2106,23 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
         return VDET_OK;
     }
     // ---- per video: tracking (+ re-scoring) on its frame range
-    const bool regular_ok = c->sym_built;
-    const float link_t32 = thresh_to_f32(link_thres);
-    const uint32_t *g_flags = regular_ok ? c->gflags.as<uint32_t>() : nullptr;
-    const bool have_ix = g_flags && c->index_valid && !c->no_index;
-    const int T = max_tracks;
-    const int wm = std::min(T + 6, 24);
-    HIPCHK(c, c->tracknode.reserve((size_t)(C * T * F) * 4));
-    HIPCHK(c, hipMemsetAsync(c->tracknode.p, 0xFF, (size_t)(C * T * F) * 4, c->stream));
-    HIPCHK(c, c->linkmemo.reserve((size_t)2 * F * B * 8));
-    HIPCHK(c, c->linkstats.reserve(16));
-    HIPCHK(c, hipMemsetAsync(c->linkmemo.p, 0, (size_t)2 * F * B * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->linkstats.p, 0, 16, c->stream));
-    HIPCHK(c, c->linkwarm.reserve((size_t)V * C * wm * 4));
-    HIPCHK(c, c->linkchains.reserve((size_t)C * wm * F * 5 * 4));
-    HIPCHK(c, c->linknodes.reserve((size_t)C * wm * F * 4));
-    HIPCHK(c, hipMemsetAsync(c->linknodes.p, 0xFF, (size_t)C * wm * F * 4, c->stream));
-    HIPCHK(c, c->tstate.reserve((size_t)(V * C) * sizeof(TrackState)));
+    const TrackWork w = track_work(c, B, link_thres, max_frames, -1);
+    const int T = max_tracks, wm = std::min(T + 6, 24);
+    if ((rc = track_scratch(c, F, B, C, T, wm, V * C))) return rc;
     hipLaunchKernelGGL(track_init_kernel, dim3((unsigned)((V * C + 63) / 64)), dim3(64), 0, c->stream, c->tstate.as<TrackState>(), (int)(V * C));
-    HIPCHK(c, c->visited.reserve((size_t)(F * C)));
-    HIPCHK(c, hipMemsetAsync(c->visited.p, 0, (size_t)(F * C), c->stream));
-    HIPCHK(c, c->heads.reserve((size_t)(F * C) * 16));
-    HIPCHK(c, hipMemsetAsync(c->heads.p, 0, (size_t)(F * C) * 16, c->stream));
-    const bool need_suppress = c->no_lazy || !g_flags || !c->all_regular;
-    const int mask_words = (int)((((size_t)4 * ((B + 31) / 32) + 15) & ~(size_t)15) / 4);
     // ---- all videos side by side: one launch per stage, the video is a grid dimension (batch_kernels.hpp)
-    {
-        // the {first frame, frames} table: uploaded only when it differs from the resident one (the host copy must not be
-        // rewritten under a copy in flight, so a change waits for the stream once; the same offsets again cost nothing)
-        bool same_tab = c->vidtab.p != nullptr && c->h_vids.size() == (size_t)V;
-        for (int64_t v = 0; same_tab && v < V; ++v)
-            same_tab = c->h_vids[(size_t)v].f0 == (int32_t)h_frame_off[v] && c->h_vids[(size_t)v].F == (int32_t)(h_frame_off[v + 1] - h_frame_off[v]);
-        if (!same_tab) {
-            (void)host_sync(c);
-            c->h_vids.clear();           // (committed below, once the copy is enqueued: a failure must not leave a "resident" table)
-            std::vector<VidDesc> tab((size_t)V);
-            for (int64_t v = 0; v < V; ++v) tab[(size_t)v] = VidDesc{(int32_t)h_frame_off[v], (int32_t)(h_frame_off[v + 1] - h_frame_off[v])};
-            HIPCHK(c, c->vidtab.reserve((size_t)V * sizeof(VidDesc)));
-            c->h_vids_stage.swap(tab);   // the copy's source must outlive it
-            HIPCHK(c, hipMemcpyAsync(c->vidtab.p, c->h_vids_stage.data(), (size_t)V * sizeof(VidDesc), hipMemcpyHostToDevice, c->stream));
-            c->h_vids = c->h_vids_stage;
-        }
-    }
+    // the {first frame, frames} table: built and uploaded only when the offsets differ from those of the resident one
+    rc = stage_keyed(c, c->vidtab, h_frame_off, (size_t)(V + 1) * 8, (size_t)V * sizeof(VidDesc), [&](char *dst) {
+        VidDesc *tab = reinterpret_cast<VidDesc *>(dst);
+        for (int64_t v = 0; v < V; ++v) tab[v] = VidDesc{(int32_t)h_frame_off[v], (int32_t)(h_frame_off[v + 1] - h_frame_off[v])};
+    });
+    if (rc) return rc;
     BatchTrack bt{};
-    bt.vids = c->vidtab.as<VidDesc>();
+    bt.vids = c->vidtab.dev.as<VidDesc>();
     bt.Ftot = (int)F; bt.B = (int)B; bt.C = (int)C; bt.T = T; bt.wm = wm;
     bt.boxes = reinterpret_cast<const float4 *>(d_boxes); bt.scores = d_scores;
     bt.keys = c->tkeys.as<uint32_t>(); bt.lists = c->order.as<uint16_t>(); bt.cnt = c->ncand.as<int32_t>();
-    bt.group_flags = g_flags;
-    bt.ix = have_ix ? frame_index_of(c) : FrameIndex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    bt.group_flags = w.flags; bt.ix = w.ix;
     bt.memo = c->linkmemo.as<unsigned long long>(); bt.stats = c->linkstats.as<unsigned int>();
     bt.warm = c->linkwarm.as<int32_t>(); bt.chains = c->linkchains.as<float>(); bt.chain_nodes = c->linknodes.as<int32_t>();
     bt.track_nodes = c->tracknode.as<int32_t>();
@@ -2085,13 +2132,12 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     bt.groups = c->groups.as<GroupDesc>(); bt.row_meta = c->rowmeta.as<uint2>(); bt.adj = c->adj.as<uint16_t>();
     bt.group_z = c->groupz.as<uint32_t>();
     bt.thres = thres; bt.link_thres = link_thres; bt.nms_thres = nms_thres;
-    bt.link_t32 = link_t32; bt.t32 = t32;
-    bt.reach_all = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : -1;
-    bt.need_suppress = need_suppress ? 1 : 0; bt.lazy = c->no_lazy ? 0 : 1; bt.mask_words = mask_words;
+    bt.link_t32 = w.link_t32; bt.t32 = t32; bt.reach_all = w.reach;
+    bt.need_suppress = w.need_suppress ? 1 : 0; bt.lazy = w.lazy; bt.mask_words = w.mask_words;
     bt.status = &c->d_cnt->status; bt.n_irregular = &c->d_cnt->irregular;
     {
         StageTimer tm(c, ST_TLINK);
-        if (B <= kLinkFillMax && have_ix) {
+        if (w.filled) {
             // the whole link table of every video: no chain ever scans, whatever its anchor -- so nothing is predicted or
             // materialised either
             hipLaunchKernelGGL(batch_link_fill_frame_kernel, dim3((unsigned)Fmax, 2, (unsigned)V), dim3((unsigned)(64 * ((B + 63) / 64))),
@@ -2105,14 +2151,14 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     }
     {
         StageTimer tm(c, ST_TLOOP);
-        hipLaunchKernelGGL(batch_loop_kernel, dim3((unsigned)C, (unsigned)V), dim3(256), (size_t)mask_words * 16, c->stream, bt);
+        hipLaunchKernelGGL(batch_loop_kernel, dim3((unsigned)C, (unsigned)V), dim3(256), (size_t)w.mask_words * 16, c->stream, bt);
     }
     if (want_rescore) {
         {
             StageTimer tm(c, ST_RSPATIAL);
             // candidates from the suppression graph wherever the tracking loop recorded the proposal a tubelet box came from (as
             // vdet_rescore_tracks does; needs overlap_thres well above the graph's threshold), the window scan for the rest
-            const bool use_adj = g_flags && overlap_thres - nms_thres > 0.05 && nms_thres > 0.0 && overlap_thres < 1.0;
+            const bool use_adj = rescore_from_graph(w.flags, nms_thres, overlap_thres);
             if (use_adj) {
                 const int64_t nb = F * C * T;
                 HIPCHK(c, c->rtodo.reserve((size_t)nb * 8 + 16));
@@ -2153,29 +2199,21 @@ int vdet_rescore_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntr
     if (nb > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    FrameIndex ix{nullptr, nullptr, nullptr, nullptr};
+    FrameIndex ix{};
     const uint32_t *flags = nullptr;
     if (!c->no_index && !c->force_general && (size_t)8 * B + 24 * 1024 <= c->max_lds) {   // (the x1 sort must fit the LDS)
         // per-frame regular flags + x-sorted index: reused from the graph build of the same boxes
         // when the cache is on, else rebuilt here (cheap: one 3 M-key sort)
-        const bool have = c->cache_enabled && c->graph_valid && c->index_valid && c->prep.boxes == d_boxes &&
-                          c->prep.F == F && c->prep.B == B && c->index_boxes == d_boxes;
-        if (!have) {
+        if (!index_matches(c, d_boxes, F, B)) {
             c->graph_valid = c->lists_valid = c->index_valid = false;       // gflags / the index are rewritten
-            NmsPlan &pl = volume_plan(c, F, B);
-            c->host_groups = &pl.groups;
-            HIPCHK(c, c->groups.reserve((size_t)F * sizeof(GroupDesc)));
+            int rc = volume_groups(c, F, B);
+            if (rc) return rc;
             HIPCHK(c, c->gflags.reserve((size_t)F * 4));
-            if (!c->vplan_valid) {
-                // (only the group table is needed here; tiles / pairs follow with the next graph build)
-                HIPCHK(c, hipMemcpyAsync(c->groups.p, pl.groups.data(), (size_t)F * sizeof(GroupDesc), hipMemcpyHostToDevice, c->stream));
-            }
             c->sym_built = false;
             hipLaunchKernelGGL(frame_flags_kernel, dim3((unsigned)F), dim3(256), 0, c->stream,
                                reinterpret_cast<const float4 *>(d_boxes), c->groups.as<GroupDesc>(), c->gflags.as<uint32_t>(),
                                &c->d_cnt->irregular);
-            const int rc = build_frame_index(c, reinterpret_cast<const float4 *>(d_boxes), F * B, F, (int)B);
-            if (rc) return rc;
+            if ((rc = build_frame_index(c, reinterpret_cast<const float4 *>(d_boxes), F * B, F, (int)B))) return rc;
         }
         ix = frame_index_of(c);
         flags = c->gflags.as<uint32_t>();
@@ -2184,13 +2222,7 @@ int vdet_rescore_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntr
         StageTimer tm(c, ST_RSPATIAL);
         // the tracks of the last tracking call on this context, same boxes, graph still in place (cache contract):
         // candidates from the suppression graph (see the kernel); needs overlap_thres well above the graph's threshold
-        const bool use_adj = flags && c->cache_enabled && c->nodes_valid && c->graph_valid &&
-                             c->nodekey.tracks == d_tracks && c->nodekey.boxes == d_boxes && c->prep.boxes == d_boxes &&
-                             c->nodekey.F == F && c->nodekey.B == B && c->nodekey.C == C && c->nodekey.T == max_tracks &&
-                             c->prep.F == F && c->prep.B == B && overlap_thres - c->nodekey.nms_thres > 0.05 &&
-                             c->nodekey.nms_thres > 0.0 && overlap_thres < 1.0 &&
-                             // ... and the resident graph is the one the tracks were made on (same threshold)
-                             [&] { const float nt = thresh_to_f32(c->nodekey.nms_thres); return memcmp(&c->prep.t32, &nt, 4) == 0; }();
+        const bool use_adj = nodes_match(c, d_tracks, d_boxes, F, B, C, max_tracks) && rescore_from_graph(flags, c->nodekey.nms_thres, overlap_thres);
         const double min_self = use_adj ? 1.0 - (overlap_thres - c->nodekey.nms_thres) + 0.02 : 2.0;
         const int32_t *todo = nullptr;
         const unsigned int *todo_cnt = nullptr;
@@ -2561,23 +2593,17 @@ int vdet_volume_pass(vdet_ctx *c, const float *d_scores, int64_t F, int64_t B, i
 // frame offsets of V concatenated videos -> per-frame {first, one past last} table on the device (kept in the context)
 static int upload_segments(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t *Ftot)
 {
-    if (!h_frame_off || V <= 0 || h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame offsets must start at 0");
-    for (int64_t v = 0; v < V; ++v)
-        if (h_frame_off[v + 1] < h_frame_off[v]) return fail(c, VDET_EINVAL, "frame offsets must not decrease");
-    const int64_t F = h_frame_off[V];
+    int64_t F = 0, Fmax = 0;
+    const int rc = check_frame_off(c, h_frame_off, V, true, 0, &F, &Fmax);      // (a video without frames is fine here)
+    if (rc) return rc;
     if (F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many frames");
     *Ftot = F;
-    // the per-frame {first, one past last} table: rebuilt and uploaded only when the offsets differ from the resident ones
-    if (c->segtab.p && c->h_seg_off.size() == (size_t)V + 1 && std::equal(c->h_seg_off.begin(), c->h_seg_off.end(), h_frame_off)) return VDET_OK;
-    (void)host_sync(c);      // (an earlier copy from the host table may be in flight)
-    c->h_seg_off.clear();    // (committed below, once the copy is enqueued: a failure must not leave a "resident" table)
-    c->h_seg.resize((size_t)std::max<int64_t>(F, 1));
-    for (int64_t v = 0; v < V; ++v)
-        for (int64_t f = h_frame_off[v]; f < h_frame_off[v + 1]; ++f) c->h_seg[(size_t)f] = make_int2((int)h_frame_off[v], (int)h_frame_off[v + 1]);
-    HIPCHK(c, c->segtab.reserve(c->h_seg.size() * sizeof(int2)));
-    if (F) HIPCHK(c, hipMemcpyAsync(c->segtab.p, c->h_seg.data(), (size_t)F * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    c->h_seg_off.assign(h_frame_off, h_frame_off + V + 1);
-    return VDET_OK;
+    // O(F) to build: keyed by the O(V) offsets, so the same offsets again neither build nor upload it
+    return stage_keyed(c, c->segtab, h_frame_off, (size_t)(V + 1) * 8, (size_t)F * sizeof(int2), [&](char *dst) {
+        int2 *seg = reinterpret_cast<int2 *>(dst);
+        for (int64_t v = 0; v < V; ++v)
+            for (int64_t f = h_frame_off[v]; f < h_frame_off[v + 1]; ++f) seg[f] = make_int2((int)h_frame_off[v], (int)h_frame_off[v + 1]);
+    });
 }
 
 int vdet_volume_pass_batch(vdet_ctx *c, const float *d_scores, const int64_t *h_frame_off, int64_t V, int64_t B, int64_t C,
@@ -2590,7 +2616,7 @@ int vdet_volume_pass_batch(vdet_ctx *c, const float *d_scores, const int64_t *h_
     const int rc = upload_segments(c, h_frame_off, V, &F);
     if (rc) return rc;
     return volume_pass_impl(c, d_scores, F, B, C, window, pad_max, h_taps, bias, pad_conv, d_out_max, d_out_conv, use_score_thresh,
-                            score_thresh, c->segtab.as<int2>());
+                            score_thresh, c->segtab.dev.as<int2>());
 }
 
 static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64_t B, int64_t C, int window, float pad_max,
@@ -2630,9 +2656,7 @@ static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64
     timing_reset(c);
     // c->tkeys is rewritten (and possibly reallocated) below: sorted lists stay valid only if they are the lists of
     // exactly these keys (the tracking kernels read keys and lists together)
-    if (!(c->prep.scores == d_scores && c->prep.F == F && c->prep.B == B && c->prep.C == C && c->prep.layout == VDET_LAYOUT_FBC &&
-          c->prep.topk == 0 && c->prep.use_thr == (use_score_thresh ? 1 : 0) && (!use_score_thresh || c->prep.thr == score_thresh)))
-        c->lists_valid = false;
+    if (!lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, use_score_thresh ? 1 : 0, score_thresh, 0}, F, B)) c->lists_valid = false;
     HIPCHK(c, c->tkeys.reserve((size_t)(F * C * B) * 4));
     Taps taps{};
     if (conv) for (int k = 0; k < window; ++k) taps.w[k] = h_taps[k];
@@ -2818,10 +2842,8 @@ int vdet_eval_match_tracks_batch(vdet_ctx *c, const double *d_gt_boxes, const in
     *h_count = 0;
     if (V < 1 || C < 1 || C > 65535 || T < 0 || T > kEvalMaxT || (box_stride != 4 && box_stride != 5))
         return fail(c, VDET_EINVAL, "bad shape (1 <= C <= 65535, 0 <= T <= %d, box stride 4 or 5)", kEvalMaxT);
-    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame_off must start at 0");
-    for (int64_t v = 0; v < V; ++v)
-        if (h_frame_off[v + 1] <= h_frame_off[v]) return fail(c, VDET_EINVAL, "frame_off must be strictly increasing");
-    const int64_t Ft = h_frame_off[V];
+    int64_t Ft = 0, Fmax = 0;
+    if ((rc = check_frame_off(c, h_frame_off, V, false, 0, &Ft, &Fmax))) return rc;
     const int64_t N = C * T * Ft;
     if (Ft > 0x7FFFFFF0ll || N > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     if (T == 0) return VDET_OK;
@@ -2946,20 +2968,6 @@ int vdet_eval_ap(vdet_ctx *c, const int32_t *d_st_slot, const double *d_st_score
 // ---------------------------------------------------------------------------------------------
 // Device TCN (tcn_kernels.hpp)
 // ---------------------------------------------------------------------------------------------
-static int stage_table(vdet_ctx *c, StagedTab &t, const void *src, size_t bytes, bool *uploaded = nullptr)
-{
-    if (uploaded) *uploaded = false;
-    if (t.valid && t.host.size() == bytes && memcmp(t.host.data(), src, bytes) == 0) return VDET_OK;
-    if (!t.host.empty()) HIPCHK(c, host_sync(c));      // (a change of table: the copy made from the old bytes may be in flight)
-    t.valid = false;
-    t.host.assign(static_cast<const char *>(src), static_cast<const char *>(src) + bytes);
-    HIPCHK(c, t.dev.reserve(std::max<size_t>(bytes, 16)));
-    HIPCHK(c, hipMemcpyAsync(t.dev.p, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    t.valid = true;
-    if (uploaded) *uploaded = true;
-    return VDET_OK;
-}
-
 // h_layers [n_layers][3] = (Cout, Cin, K); h_params = W0 | b0 | W1 | b1 | ... (W [Cout, Cin, K] row-major).  The parameters
 // are uploaded when their bytes differ from the resident ones (vdet_query(ctx, 10) counts the uploads).
 static int tcn_net_args(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, int cin, TcnNet &net)
@@ -2987,10 +2995,7 @@ static int tcn_net_args(vdet_ctx *c, const float *h_params, const int32_t *h_lay
     if (prev != 2) return fail(c, VDET_EINVAL, "the last layer must produce 2 channels (probs[:, 1, :] is the score)");
     int rem = 0;
     for (int i = n_layers - 1; i >= 0; --i) { net.l[i].rem = rem; rem += net.l[i].k / 2; }
-    bool up = false;
-    const int rc = stage_table(c, c->tcn_params, h_params, (size_t)off * 4, &up);
-    if (up) ++c->tcn_uploads;
-    return rc;
+    return stage_table(c, c->tcn_params, h_params, (size_t)off * 4);
 }
 
 // The network launch over ntub tubelet descriptors; Lmax bounds every series length.  Path by size (DESIGN.md "Device TCN"):
@@ -3026,19 +3031,6 @@ static int tcn_launch_net(vdet_ctx *c, const TcnNet &net, const float *d_x, cons
     return VDET_OK;
 }
 
-static int check_frame_off(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t *Ftot, int64_t *Fmax)
-{
-    if (!h_frame_off || V < 1 || V > 65535) return fail(c, VDET_EINVAL, "1 to 65535 videos with their frame offsets");
-    if (h_frame_off[0] != 0) return fail(c, VDET_EINVAL, "frame_off must start at 0");
-    *Fmax = 0;
-    for (int64_t v = 0; v < V; ++v) {
-        if (h_frame_off[v + 1] <= h_frame_off[v]) return fail(c, VDET_EINVAL, "frame_off must be strictly increasing");
-        *Fmax = std::max(*Fmax, h_frame_off[v + 1] - h_frame_off[v]);
-    }
-    *Ftot = h_frame_off[V];
-    return VDET_OK;
-}
-
 int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
                           int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
                           const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
@@ -3046,7 +3038,7 @@ int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_l
 {
     if (!c) return VDET_EINVAL;
     int64_t Ft = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax);
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
     if (rc) return rc;
     if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
     if (!h_channels || n_channels < 1 || n_channels > 16) return fail(c, VDET_EINVAL, "1 to 16 input channels");
@@ -3146,7 +3138,7 @@ int vdet_tubelets_overlap_batch(vdet_ctx *c, const double *d_gt_boxes, const int
     int rc = eval_gt_args(c, d_gt_boxes, d_gt_off, d_vid_meta, K, 0, 0.5, g);
     if (rc) return rc;
     int64_t Ft = 0, Fmax = 0;
-    if ((rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax))) return rc;
+    if ((rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax))) return rc;
     if (!h_vid || !h_col_slot) return fail(c, VDET_EINVAL, "null buffer");
     if (C < 1 || C > 65535 || T < 0 || C * std::max(T, 1) * Ft > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
     if (T == 0) return VDET_OK;
@@ -3194,9 +3186,9 @@ int vdet_interp_tracks_batch(vdet_ctx *c, const int64_t *h_sframe_off, const int
 {
     if (!c) return VDET_EINVAL;
     int64_t Fst = 0, Fsmax = 0, Ft = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_sframe_off, V, &Fst, &Fsmax);
+    int rc = check_frame_off(c, h_sframe_off, V, false, 65535, &Fst, &Fsmax);
     if (rc) return rc;
-    if ((rc = check_frame_off(c, h_frame_off, V, &Ft, &Fmax))) return rc;
+    if ((rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax))) return rc;
     if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
     if (n_series < 0 || n_series > kInterpMaxSeries) return fail(c, VDET_EINVAL, "0 to %d series", kInterpMaxSeries);
     if (C * std::max(T, 1) * Ft > 0x7FFFFFF0ll || C * std::max(T, 1) * Fst > 0x7FFFFFF0ll)
