@@ -60,6 +60,9 @@
  *   device interpolation: series per call  <= 4                       VDET_EINVAL
  *   device interpolation: rows, frames, stride  none (V <= 65535, C*T*F < 2^31 on both axes)   VDET_EINVAL; one path for
  *                                                                     every size: the kernel keeps no knot list
+ *   device anchor route: slots, frames     C*T*F < 2^31, B <= 32767   VDET_EINVAL; an anchor frame outside 0..F: VDET_EINVAL
+ *                                                                     latched (vdet_sync).  One path for every size: a link
+ *                                                                     step scans the whole frame
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -618,6 +621,45 @@ int vdet_interp_tracks_batch(vdet_ctx *ctx, const int64_t *h_sframe_off, const i
                              const int32_t *d_ntracks, const float *d_anchors, const void *const *h_series, int n_series,
                              int series_f64, float *d_tracks_out, double *d_boxes64, float *d_tboxes,
                              double *d_series_out, double *d_anchor, float *d_anchors_out);
+
+/* ---- device anchor route: tubelets from caller-supplied anchors (track_from_det, vdet/track.py:109-119) and the anchor
+ *      detection's score on every box of the tubelet (anchor_propagate, vdet/tubelet_cls.py:353-383) ---------------------
+ *
+ * vdet_track_from_anchors: slot (c, t) of d_anchor_frames [C,T] int32 (1-based frame, 0 = empty slot) / d_anchor_boxes
+ * [C,T,4] f32 / d_anchor_scores [C,T] f32 (or NULL) is one anchor; C is only a grouping axis (linking does not depend on
+ * the class).  The tubelet of a live slot is what vdet_track_volume's built-in tracker makes from that BOX: the anchor row
+ * is (int-truncated box, 1.0); the chain runs forward, then backward; a step scores every box of the next frame with the
+ * f32 IoU of utils/nms.pyx (the current box as the "i" box), NaN IoUs are out of the running, the best wins, ties go to
+ * the lowest box index; it stops when every IoU is NaN, when the best is < link_thres, at the video's end or after
+ * ceil((max_frames+1)/2) - 1 steps (max_frames <= 0: no limit); the new current box is the truncated proposal, its row
+ * (truncated box, IoU).  Rows not reached are NaN.
+ *   d_tracks  [C,T,F,5] f32   every row written by the ONE launch of the call (no fill pass); all NaN for an empty slot
+ *   d_anchors [C,T,3]   f32   (frame, -1, score or 0)
+ *   d_ntracks [C]       int32 1 + the last live slot of the class (an empty slot below it is a tubelet without boxes)
+ * An anchor frame outside 0..F is latched (VDET_EINVAL at vdet_sync); its slot is written as an empty one.  Asynchronous, no
+ * host wait, no host table.  Reads and writes nothing of the context's cached graph, lists, index or link memo.
+ */
+int vdet_track_from_anchors(vdet_ctx *ctx, const float *d_boxes, int64_t F, int64_t B, const int32_t *d_anchor_frames,
+                            const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, double link_thres,
+                            int max_frames, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+/* d_tracks / d_ntracks / d_anchors of vdet_track_from_anchors, vdet_track_volume or vdet_nms_track_volume; d_boxes [F,B,4],
+ * d_scores [F,B,C] f32.  Slot (c, t), t < d_ntracks[c], fa = (int)d_anchors[c,t,0] in 1..F, anchor row not NaN:
+ *   ov = utils/common.py:451-468 iou (f64, +1 convention, inter / (a1 + a2 - inter); a zero union is NaN as in numpy, not an
+ *        error) of d_tracks[c,t,fa-1,:4] -- widened to f64 as it is -- against the B boxes of frame fa;
+ *   d_best[c,t] = np.argmax(ov): the first maximum, a NaN counts as the maximum, the first NaN wins;
+ *   d_det_score[c,t,f] = (double)d_scores[fa-1, best, c] on every frame whose track row is not NaN, NaN elsewhere.
+ * Every other slot (t >= d_ntracks[c], frame 0, a NaN anchor row): d_det_score NaN, d_best -1.  A live slot whose anchor
+ * frame is neither 0 nor in 1..F is latched (VDET_EINVAL at vdet_sync).  One launch writes every output element. */
+int vdet_anchor_propagate_tracks(vdet_ctx *ctx, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                                 const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int T,
+                                 double *d_det_score, int32_t *d_best);
+
+/* The arg-max of the dict-level anchor_propagate on host tables, all anchors of a call in one launch (synchronous):
+ * h_best[n] = np.argmax(iou([h_anchor_boxes[n]], h_det_boxes[h_group_off[g] .. h_group_off[g+1]))), g = h_group[n] the
+ * anchor's frame slot; -1 for a frame slot without detections.  All f64. */
+int vdet_anchor_argmax_f64(vdet_ctx *ctx, const double *h_anchor_boxes, const int32_t *h_group, int64_t N,
+                           const double *h_det_boxes, const int64_t *h_group_off, int64_t G, int64_t *h_best);
 
 #ifdef __cplusplus
 }

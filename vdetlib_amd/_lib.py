@@ -75,6 +75,9 @@ SYMBOLS = {
     "vdet_interp_tracks": (_ci, [_vp, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_interp_tracks_batch": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),
+    "vdet_track_from_anchors": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _f64, _ci, _vp, _vp, _vp]),
+    "vdet_anchor_propagate_tracks": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp]),
+    "vdet_anchor_argmax_f64": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

@@ -31,6 +31,7 @@
 #include "eval_kernels.hpp"
 #include "tcn_kernels.hpp"
 #include "interp_kernels.hpp"
+#include "anchor_kernels.hpp"
 
 using namespace vdet;
 
@@ -331,6 +332,7 @@ int translate_status(vdet_ctx *c, int st)
 {
     if (st & kStPoolAsync) return fail(c, VDET_EAGAIN, "adjacency pool overflow in an asynchronous graph build: run the calls again");
     if (st & kStBadOrder) return fail(c, VDET_EINVAL, "a caller-supplied candidate list holds a count or a box index out of range");
+    if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -3266,6 +3268,94 @@ int vdet_interp_tracks(vdet_ctx *c, int64_t Fs, int64_t F, const int32_t *h_fram
     const int64_t soff[2] = {0, Fs}, doff[2] = {0, F};
     return vdet_interp_tracks_batch(c, soff, doff, 1, h_frames, C, T, d_tracks, d_boxes, d_ntracks, d_anchors, h_series, n_series,
                                     series_f64, d_tracks_out, d_boxes64, d_tboxes, d_series_out, d_anchor, d_anchors_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device anchor route (anchor_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_track_from_anchors(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, const int32_t *d_anchor_frames,
+                            const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, double link_thres,
+                            int max_frames, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
+    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31)");
+    if (!d_boxes || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (T == 0) {
+        HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
+        return VDET_OK;
+    }
+    AnchorLinkArgs a{};
+    a.boxes = reinterpret_cast<const float4 *>(d_boxes);
+    a.F = (int)F; a.B = (int)B; a.C = (int)C; a.T = T;
+    a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
+    a.link_t32 = thresh_to_f32(link_thres);
+    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)F;
+    a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
+    a.status = &c->d_cnt->status;
+    {
+        StageTimer tm(c, ST_TLINK);
+        hipLaunchKernelGGL(anchor_link_kernel, dim3((unsigned)(C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_anchor_propagate_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                                 const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int T,
+                                 double *d_det_score, int32_t *d_best)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
+    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31)");
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_anchors || !d_boxes || !d_scores || !d_det_score || !d_best) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(anchor_propagate_kernel, dim3((unsigned)(C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks, d_anchors,
+                           d_boxes, d_scores, (int)F, (int)B, (int)C, T, d_det_score, d_best, &c->d_cnt->status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_anchor_argmax_f64(vdet_ctx *c, const double *h_anchor_boxes, const int32_t *h_group, int64_t N, const double *h_det_boxes,
+                           const int64_t *h_group_off, int64_t G, int64_t *h_best)
+{
+    if (!c || N < 0 || G < 0) return VDET_EINVAL;
+    if (N == 0) return VDET_OK;
+    if (N > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many anchors");
+    if (!h_anchor_boxes || !h_group || !h_group_off || !h_best || G == 0) return fail(c, VDET_EINVAL, "null buffer");
+    if (h_group_off[0] != 0) return fail(c, VDET_EINVAL, "group_off must start at 0");
+    for (int64_t g = 0; g < G; ++g)
+        if (h_group_off[g + 1] < h_group_off[g]) return fail(c, VDET_EINVAL, "group_off must not decrease");
+    const int64_t M = h_group_off[G];
+    if (M && !h_det_boxes) return fail(c, VDET_EINVAL, "null buffer");
+    for (int64_t n = 0; n < N; ++n)
+        if (h_group[n] < 0 || h_group[n] >= G) return fail(c, VDET_EINVAL, "anchor frame slot out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    int rc;
+    if ((rc = upload(c, c->tmp[0], h_anchor_boxes, (size_t)N * 32))) return rc;
+    if ((rc = upload(c, c->tmp[1], h_group, (size_t)N * 4))) return rc;
+    if ((rc = upload(c, c->tmp[2], h_det_boxes, (size_t)M * 32))) return rc;
+    if ((rc = upload(c, c->tmp[3], h_group_off, (size_t)(G + 1) * 8))) return rc;
+    HIPCHK(c, c->tmp[4].reserve((size_t)N * 8));
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(anchor_argmax_f64_kernel, dim3((unsigned)N), dim3(kAnchorLT), 0, c->stream, c->tmp[0].as<double>(),
+                           c->tmp[1].as<int32_t>(), c->tmp[2].as<double>(), c->tmp[3].as<int64_t>(), c->tmp[4].as<int64_t>());
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_best, c->tmp[4].p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, host_sync(c));
+    return VDET_OK;
 }
 
 }  // extern "C"

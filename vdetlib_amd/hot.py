@@ -45,6 +45,27 @@ def spatial_maxpool(tub_boxes, tub_group, det_boxes_list, det_scores_list, thres
     return out_idx, out_score
 
 
+def anchor_argmax(anchor_boxes, anchor_group, det_boxes_list):
+    """anchor_boxes [N,4], anchor_group [N] (index into det_boxes_list: one [n,4] array per frame slot).  Returns int64 [N]:
+    ``np.argmax(iou([anchor], det_boxes))`` of every anchor (first maximum, a NaN overlap counts as the maximum), all in ONE
+    launch; -1 for a frame slot without detections."""
+    ab = np.ascontiguousarray(np.asarray(anchor_boxes).astype('float').reshape(-1, 4))
+    ag = np.ascontiguousarray(anchor_group, dtype=np.int32)
+    N = ab.shape[0]
+    best = np.full(N, -1, dtype=np.int64)
+    if N == 0:
+        return best
+    off = _offsets([len(b) for b in det_boxes_list])
+    db = np.zeros((max(int(off[-1]), 1), 4), dtype=np.float64)
+    for g, b in enumerate(det_boxes_list):
+        if len(b):
+            db[off[g]:off[g + 1]] = np.asarray(b).astype('float').reshape(-1, 4)
+    ctx = _ctx()
+    ctx.check(ctx.lib.vdet_anchor_argmax_f64(ctx.h, ab.ctypes.data, ag.ctypes.data, N, db.ctypes.data, off.ctypes.data,
+                                             len(det_boxes_list), best.ctypes.data))
+    return best
+
+
 def series_completion(series_list):
     """do_score_completion on a list of 1-D score sequences; returns new float64 arrays.
     IndexError where the reference raises it."""

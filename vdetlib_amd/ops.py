@@ -485,6 +485,93 @@ def rescore_tracks(tracks, ntracks, boxes, scores, overlap_thres=0.7, window=3, 
     return det, pooled, ob
 
 
+def track_from_anchors(boxes, anchor_frames, anchor_boxes, anchor_scores=None, link_thres=0.5, max_frames=0, sync=True,
+                       ctx=None):
+    """Tubelets from caller-supplied anchors: the array form of track_from_det (vdet/track.py:109-119) with the built-in
+    IoU-linking tracker as ``track_method`` -- every anchor is tracked, nothing is suppressed.
+
+    boxes [F,B,4] f32; anchor_frames [C,T] int32 (1-based, 0 = empty slot), anchor_boxes [C,T,4] f32, anchor_scores [C,T]
+    f32 or None, all on the boxes' GPU.  C is only a grouping axis (C = 1: class-agnostic).  A live slot's rows are what
+    ``track_volume`` makes from an anchor with that (int-truncated) box.  Returns, in ``track_volume``'s layout,
+      tracks  [C,T,F,5] f32 rows (x1,y1,x2,y2,score), NaN where a tubelet has no box (an empty slot: everywhere),
+      anchors [C,T,3] f32 (frame, -1, score or 0),  ntracks [C] int32 = 1 + the last live slot of the class.
+    ValueError for an anchor frame outside 0..F (reported when the call, or a later ``ctx.sync()``, waits)."""
+    if boxes.dtype != torch.float32 or anchor_boxes.dtype != torch.float32 or \
+            (anchor_scores is not None and anchor_scores.dtype != torch.float32):
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if anchor_frames.dtype != torch.int32:
+        raise ValueError("anchor_frames must be int32")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4]")
+    F, B = boxes.shape[0], boxes.shape[1]
+    if F < 1 or B < 1:
+        raise ValueError("boxes must hold at least one frame and one box per frame")
+    if anchor_frames.dim() != 2:
+        raise ValueError("anchor_frames must be [C,T]")
+    C, T = anchor_frames.shape
+    if C < 1:
+        raise ValueError("anchor_frames must be [C,T] with C >= 1")
+    if tuple(anchor_boxes.shape) != (C, T, 4):
+        raise ValueError("anchor_boxes must be [C,T,4]")
+    if anchor_scores is not None and tuple(anchor_scores.shape) != (C, T):
+        raise ValueError("anchor_scores must be [C,T]")
+    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("boxes, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    boxes, anchor_frames, anchor_boxes = boxes.contiguous(), anchor_frames.contiguous(), anchor_boxes.contiguous()
+    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
+    tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=boxes.device)
+    anchors = torch.empty((C, T, 3), dtype=torch.float32, device=boxes.device)
+    ntracks = torch.empty((C,), dtype=torch.int32, device=boxes.device)
+    ctx.check(ctx.lib.vdet_track_from_anchors(
+        ctx.h, boxes.data_ptr(), F, B, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+        anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, float(link_thres), int(max_frames),
+        tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
+    if sync:
+        ctx.sync()
+    return tracks, anchors, ntracks
+
+
+def anchor_propagate_tracks(tracks, ntracks, anchors, boxes, scores, sync=True, ctx=None):
+    """anchor_propagate (vdet/tubelet_cls.py:353-383) on device tubelets: per slot, the detection of the anchor frame that
+    overlaps the anchor box most (f64 ``iou``, ``np.argmax``: first maximum, a NaN overlap counts as the maximum) lends its
+    class score to every box of the tubelet.
+
+    tracks [C,T,F,5] f32 / ntracks [C] int32 / anchors [C,T,3] f32 (track_from_anchors, track_volume, nms_track_volume),
+    boxes [F,B,4] f32, scores [F,B,C] f32.  Returns (det_score [C,T,F] f64: the score where the tubelet has a box, NaN
+    elsewhere; best [C,T] int32: the detection's index on the anchor frame, -1 for a slot without anchor box)."""
+    if tracks.dtype != torch.float32 or anchors.dtype != torch.float32 or boxes.dtype != torch.float32 or \
+            scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if ntracks.dtype != torch.int32:
+        raise ValueError("ntracks must be int32")
+    if tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4]")
+    B = boxes.shape[1]
+    if F < 1 or B < 1 or C < 1:
+        raise ValueError("at least one class, one frame and one box per frame")
+    if tuple(scores.shape) != (F, B, C):
+        raise ValueError("scores must be [F,B,C]")
+    if tuple(ntracks.shape) != (C,) or tuple(anchors.shape) != (C, T, 3):
+        raise ValueError("ntracks must be [C], anchors [C,T,3]")
+    for t in (tracks, ntracks, anchors, scores):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("tracks, ntracks, anchors, boxes and scores must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    det = torch.empty((C, T, F), dtype=torch.float64, device=boxes.device)
+    best = torch.empty((C, T), dtype=torch.int32, device=boxes.device)
+    ctx.check(ctx.lib.vdet_anchor_propagate_tracks(
+        ctx.h, tracks.contiguous().data_ptr(), ntracks.contiguous().data_ptr(), anchors.contiguous().data_ptr(),
+        boxes.contiguous().data_ptr(), scores.contiguous().data_ptr(), F, B, C, T, det.data_ptr(), best.data_ptr()))
+    if sync:
+        ctx.sync()
+    return det, best
+
+
 def _tcn_net_args(net):
     from .vdet.tcn import TCNNet
     if not isinstance(net, TCNNet):

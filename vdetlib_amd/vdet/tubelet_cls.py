@@ -12,7 +12,6 @@ from collections import defaultdict
 import numpy as np
 
 from ..utils.protocol import tubelets_overlap, tubelets_proto_from_tracks_proto
-from ..utils.common import iou
 from ..utils.log import logger as logging
 from .dataset import imagenet_vdet_classes
 from .. import hot
@@ -203,13 +202,29 @@ def anchor_propagate(vid_proto, track_proto, det_proto, class_idx):
     logging.info("Propagating anchor scores in {} for {}...".format(vid_proto['video'],
                                                                      imagenet_vdet_classes[class_idx]))
     dets = _ClassDetsByFrame(det_proto, class_idx)
+    # overlap + arg-max of ALL tubelets of the call in one device call: the anchor frames' detections, each frame once
+    slots, det_boxes_list, anchor_boxes, anchor_group, det_scores_of = {}, [], [], [], []
     for tubelet in tubelets_proto:
         anchors = [box for box in tubelet['boxes'] if box['anchor'] == 0]
         assert len(anchors) == 1
-        det_boxes, det_scores = dets(anchors[0]['frame'])
-        best = int(np.argmax(iou([anchors[0]['bbox']], det_boxes)[0]))
+        frame_id = anchors[0]['frame']
+        det_boxes, det_scores = dets(frame_id)
+        abox = np.asarray([anchors[0]['bbox']]).astype('float')
+        det_boxes = np.asarray(det_boxes).astype('float')
+        if abox.ndim != 2 or det_boxes.ndim != 2 or abox.shape[1] < 4 or det_boxes.shape[1] < 4:
+            raise IndexError("boxes must be [n,4]")              # what iou([bbox], det_boxes) raises
+        if det_boxes.shape[0] == 0:
+            raise ValueError("attempt to get argmax of an empty sequence")
+        if frame_id not in slots:
+            slots[frame_id] = len(det_boxes_list)
+            det_boxes_list.append(det_boxes[:, :4])
+        anchor_boxes.append(abox[0, :4])
+        anchor_group.append(slots[frame_id])
+        det_scores_of.append(det_scores)
+    best = hot.anchor_argmax(anchor_boxes, anchor_group, det_boxes_list) if anchor_boxes else []
+    for tubelet, det_scores, k in zip(tubelets_proto, det_scores_of, best):
         for box in tubelet['boxes']:
-            box['det_score'] = det_scores[best]
+            box['det_score'] = det_scores[int(k)]
     return {'video': vid_proto['video'], 'method': "anchor_propagate", 'tubelets': tubelets_proto}
 
 
