@@ -7,6 +7,12 @@ x 200 classes) with 2 000 anchors, 10 per class: the anchors ops.nms_track_volum
      det_proto holds the anchor frames' detections only (the whole video cannot travel as dicts);
  (b) the new calls: HIP-event time and wall time per call, median [min .. max] of R calls after W warm-up calls;
  (c) nms_track_volume on the same video: vdet_last_timing_ms' track_link / track_loop / track_pick stages, for scale.
+
+ (d) --select: ops.top_anchors (choosing the anchors on the device) on the same video -- video mode T = 10 and T = 100, frame
+     mode top_num = 1 -- and on the 64-video VID-shape batch (T = 10, with the batch link and propagate calls behind it),
+     each next to what a caller could do before: scores.permute(2,0,1).reshape(C,-1).topk(T) + the box gather on the same
+     GPU (no stable tie rule), and protocol.top_detections over the dicts of --host-classes classes, scaled to all classes.
+     "volume_tb_s" is the bytes of the score volume divided by the event time (DESIGN section 8's roofline is 8 TB/s).
 Prints one JSON line."""
 import json
 import os
@@ -54,18 +60,77 @@ def dict_route(name, boxes_h, scores_h, frames, ab, n_cls, F):
     return t_track, t_prop, n, out
 
 
+def torch_route(boxes, scores, T, frame_mode):
+    """what a caller can do without ops.top_anchors: a transposed copy, torch.topk, the box gather"""
+    F, B, C = scores.shape
+    if frame_mode:
+        v, i = scores.permute(2, 0, 1).topk(T, dim=2)            # [C,F,T]
+        f = torch.arange(F, device=scores.device)[None, :, None].expand_as(i)
+        return (f + 1).reshape(C, -1), boxes[f, i].reshape(C, -1, 4), v.reshape(C, -1), i.reshape(C, -1)
+    v, i = scores.permute(2, 0, 1).reshape(C, -1).topk(T)
+    f, b = i // B, i % B
+    return f + 1, boxes[f, b], v, b
+
+
+def select_legs(res, boxes, scores, a):
+    from vdetlib_amd.utils import protocol
+    F, B, C = scores.shape
+    vol = scores.numel() * 4
+    legs = {}
+    for name, T, mode in (("video_T10", 10, 'video'), ("video_T100", 100, 'video'), ("frame_top1", 1, 'frame')):
+        ev, wall = device_times(lambda s: ops.top_anchors(boxes, scores, T, mode=mode, sync=s), a.reps, a.warmup)
+        tev, _ = device_times(lambda s: (torch_route(boxes, scores, T, mode == 'frame'), torch.cuda.synchronize() if s else None),
+                              a.reps, a.warmup)
+        mine = ops.top_anchors(boxes, scores, T, mode=mode)
+        theirs = torch_route(boxes, scores, T, mode == 'frame')
+        legs[name] = {"event_ms": ev, "wall_ms": wall, "torch_topk_event_ms": tev,
+                      "volume_tb_s": round(vol / (ev["median"] * 1e-3) / 1e12, 3),
+                      "same_scores_as_torch": bool(torch.equal(mine[2], theirs[2]))}
+    # the host route on a few classes of a slice the dicts can hold, scaled by detections and classes
+    ncls, Fh = max(1, min(a.host_classes, C)), min(F, 3)
+    sh = scores[:Fh, :, :ncls].cpu().numpy()
+    bh = boxes[:Fh].cpu().numpy()
+    dets = {'video': 'c2', 'detections': [{'frame': f + 1, 'bbox': bh[f, b].tolist(),
+                                            'scores': [{'class_index': c, 'score': float(sh[f, b, c])} for c in range(ncls)]}
+                                           for f in range(Fh) for b in range(B)]}
+    t0 = time.perf_counter()
+    for c in range(ncls):
+        protocol.top_detections(dets, 10, c)
+    legs["host_top_detections_s_scaled"] = round((time.perf_counter() - t0) * (F / Fh) * (C / ncls), 2)
+    legs["host_top_detections_timed"] = {"frames": Fh, "classes": ncls}
+    # the 64-video VID-shape batch: select, link, propagate
+    vb, vs, off = bench.synth_vid_batch(torch, boxes.device, 64)
+    sel = lambda s: ops.top_anchors(vb, vs, 10, frame_off=off, sync=s)
+    fr, ab, sc, _ = sel(True)
+    link = lambda s: ops.track_from_anchors_batch(vb, off, fr, ab, sc, sync=s)
+    out = link(True)
+    prop = lambda s: ops.anchor_propagate_tracks_batch(out, vb, vs, sync=s)
+    batch = {"videos": len(off) - 1, "frames": int(off[-1]), "boxes_per_frame": int(vb.shape[1]), "classes": int(vs.shape[2])}
+    for name, fn in (("top_anchors", sel), ("track_from_anchors_batch", link), ("anchor_propagate_tracks_batch", prop)):
+        ev, wall = device_times(fn, a.reps, a.warmup)
+        batch[name] = {"event_ms": ev, "wall_ms": wall}
+    batch["top_anchors"]["volume_tb_s"] = round(vs.numel() * 4 / (batch["top_anchors"]["event_ms"]["median"] * 1e-3) / 1e12, 3)
+    legs["vid_batch"] = batch
+    res["d_top_anchors"] = legs
+
+
 def main():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-classes", type=int, default=2)
+    ap.add_argument("--select", action="store_true", help="only the top_anchors legs (d)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     res = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup}
     F, B, C, T = 300, 10000, 200, 10
     boxes, scores = bench.synth_video_cuda(torch, 2000, F, B, C, dev)
+    if a.select:
+        select_legs(res, boxes, scores, a)
+        print(json.dumps(res))
+        return
     # ---- (c) the greedy tracker: its anchors, its tubelets, its stage times
     cx = _lib.get_context(0)
     ops.nms_track_volume(boxes, scores, max_tracks=T, pad=False)

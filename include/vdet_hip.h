@@ -63,6 +63,12 @@
  *   device anchor route: slots, frames     C*T*F < 2^31, B <= 32767   VDET_EINVAL; an anchor frame outside 0..F: VDET_EINVAL
  *                                                                     latched (vdet_sync).  One path for every size: a link
  *                                                                     step scans the whole frame
+ *   device anchor selection: slots         1 <= top_num <= 1024 per (video, class); <= 128 per (frame, class) in frame mode
+ *                                                                     VDET_EINVAL (the evaluator's tracks-per-class limit /
+ *                                                                     vdet_det_nms_volume's top-k limit).  One path for every
+ *                                                                     top_num: selection by threshold, then a sort of <= top_num
+ *   device anchor selection / batch forms  B <= 32767, F*B < 2^31 - 16, V <= 65535 (frame mode: F <= 65535), C*T*F < 2^31
+ *                                                                     VDET_EINVAL
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -139,7 +145,9 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * step (vdet_set_async) adds none between the entry and the return of the volume entry points;
  * what = 9 -> (frame, class) columns of the last volume sort that the equalised counting sort handed to the LSD
  * radix kernel (tied / quantised / thresholded columns; synchronises the stream), -1 if that sort did not use it;
- * what = 10 -> number of times the device TCN's parameters were uploaded (a call with the resident net uploads nothing).
+ * what = 10 -> number of times the device TCN's parameters were uploaded (a call with the resident net uploads nothing);
+ * what = 11 -> number of times the per-video table of vdet_top_anchors (batch form), vdet_track_from_anchors_batch and
+ * vdet_anchor_propagate_tracks_batch was staged (calls with the same frame offsets stage it once).
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant):
@@ -660,6 +668,47 @@ int vdet_anchor_propagate_tracks(vdet_ctx *ctx, const float *d_tracks, const int
  * anchor's frame slot; -1 for a frame slot without detections.  All f64. */
 int vdet_anchor_argmax_f64(vdet_ctx *ctx, const double *h_anchor_boxes, const int32_t *h_group, int64_t N,
                            const double *h_det_boxes, const int64_t *h_group_off, int64_t G, int64_t *h_best);
+
+/* ---- device anchor selection: top_detections / frame_top_detections (utils/protocol.py:330-351) as arrays, every class
+ *      (and every video of a batch) in one call; its outputs are vdet_track_from_anchors' inputs -------------------------
+ *
+ * d_boxes [F,B,4] f32 (16-byte aligned), d_scores [F,B,C] f32, class innermost.  A candidate of class c is a detection whose
+ * score is not NaN and -- use_score_thresh != 0 -- is > (float)score_thresh (f32 compare, as vdet_nms_volume_topk).  Candidates
+ * are ordered by descending score, equal scores (-0.0 == +0.0) by ascending flat index f*B + b (Python's stable
+ * sorted(..., reverse=True) over a frame-major proto).  NOT mirrored: the reference returns a proto of fewer than top_num
+ * detections unsorted; this call always sorts.
+ *   mode 0 (video): T = top_num <= 1024; slot (c, t) is the t-th candidate of class c.  h_frame_off = NULL: one video, outputs
+ *     [C,T]; no host table.  h_frame_off [V+1]: V videos, outputs [V,C,T], the selection runs inside each video's frames and
+ *     frames are local to the video (as vdet_video_batch's anchors).
+ *   mode 1 (frame): top_num <= 128, T = F*top_num, outputs [C,T]; slot (c, f*top_num + r) is the r-th candidate of frame f.
+ *     h_frame_off must be NULL.
+ *   d_anchor_frames int32 (1-based, 0 = empty slot), d_anchor_boxes [..,4] f32 (the proposal's box as it is: the link call
+ *   truncates), d_anchor_scores f32, d_anchor_index int32 (box index in its frame, -1 = empty).  An empty slot's box and score
+ *   are 0.  Every element is written by the call's own kernels (no fill pass).
+ * Asynchronous: no host wait; the single-video and frame forms stage no host table, the batch form the per-video table keyed
+ * by the offsets (vdet_query 11).  Scratch is O(V*C*(256 + segments + T)): no transposed or keyed copy of the volume.  Reads
+ * and writes nothing of the context's cached graph, lists, index or link memo. */
+int vdet_top_anchors(vdet_ctx *ctx, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int top_num,
+                     int mode, int use_score_thresh, double score_thresh, const int64_t *h_frame_off, int64_t V,
+                     int32_t *d_anchor_frames, float *d_anchor_boxes, float *d_anchor_scores, int32_t *d_anchor_index);
+
+/* vdet_track_from_anchors for V videos in ONE launch: d_boxes [Ftot,B,4] holds the videos' frames one after the other
+ * (h_frame_off [V+1]); d_anchor_frames [V,C,T] (1-based inside the video) / d_anchor_boxes [V,C,T,4] / d_anchor_scores [V,C,T] or
+ * NULL.  A chain stops at its own video's first and last frame.  Outputs in vdet_video_batch's layout: d_tracks is one flat
+ * buffer of C*T*Ftot*5 floats, video v's [C,T,F_v,5] block at element C*T*5*h_frame_off[v]; d_anchors [V,C,T,3]; d_ntracks
+ * [V,C].  Per video the bits are vdet_track_from_anchors' on that video alone.  An anchor frame outside 0..F_v is latched
+ * (VDET_EINVAL at vdet_sync), its slot written as an empty one.  The per-video table is staged keyed by the offsets: the same
+ * offsets again neither wait nor copy. */
+int vdet_track_from_anchors_batch(vdet_ctx *ctx, const float *d_boxes, const int64_t *h_frame_off, int64_t V, int64_t B,
+                                  const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores,
+                                  int64_t C, int T, double link_thres, int max_frames, float *d_tracks, float *d_anchors,
+                                  int32_t *d_ntracks);
+
+/* vdet_anchor_propagate_tracks for V videos in ONE launch, on the buffers of vdet_track_from_anchors_batch / vdet_video_batch:
+ * d_det_score is flat, video v's [C,T,F_v] block at element C*T*h_frame_off[v]; d_best [V,C,T]. */
+int vdet_anchor_propagate_tracks_batch(vdet_ctx *ctx, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                                       const float *d_boxes, const float *d_scores, const int64_t *h_frame_off, int64_t V,
+                                       int64_t B, int64_t C, int T, double *d_det_score, int32_t *d_best);
 
 #ifdef __cplusplus
 }

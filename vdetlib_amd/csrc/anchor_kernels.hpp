@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "track_kernels.hpp"     // link_iou, trunc4
+#include "batch_kernels.hpp"     // VidDesc
 #include "tubelet_kernels.hpp"   // argmax_better, iou_f64_pair
 
 namespace vdet {
@@ -38,7 +39,9 @@ constexpr int kAnchorWaves = kAnchorLT / 64;
 
 struct AnchorLinkArgs {
     const float4 *boxes;        // [F,B]
-    int F, B, C, T;
+    int F, B, C, T;             // (batch: C counts the V*C (video, class) groups, F all frames)
+    const VidDesc *vids;        // batch form only: the frame range of every video
+    int cls;                    // batch form only: classes per video
     const int32_t *aframes;     // [C,T] 1-based, 0: empty slot
     const float *aboxes;        // [C,T,4]
     const float *ascores;       // [C,T] or null
@@ -56,7 +59,10 @@ __device__ __forceinline__ void anchor_row(float *r, float4 b, float s)
 }
 
 // grid (C*T, 2): blockIdx.y = 0 links forward (and owns the slot's anchor row, its anchors entry and -- slot 0 of a class --
-// the class's ntracks), 1 backward
+// the class's ntracks), 1 backward.  BATCH: the slots of V videos side by side, [V,C,T]; a chain lives in its own video's
+// frames (VidDesc), its rows where video_batch keeps them (video v at element C*T*5*f0 of the flat buffer); frames are
+// local to the video.  The single-video instantiation is the kernel as it was.
+template <bool BATCH>
 __global__ __launch_bounds__(kAnchorLT) void anchor_link_kernel(const AnchorLinkArgs a)
 {
     __shared__ float sv[2][kAnchorWaves];
@@ -66,11 +72,22 @@ __global__ __launch_bounds__(kAnchorLT) void anchor_link_kernel(const AnchorLink
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int slot = blockIdx.x, c = slot / a.T, t = slot - c * a.T;
     const int dir = blockIdx.y == 0 ? 1 : -1;
-    const int F = a.F, B = a.B;
+    int F = a.F;
+    const int B = a.B;
+    const float4 *boxes = a.boxes;
+    float *trk;
+    if (BATCH) {
+        const int v = c / a.cls;
+        const VidDesc vd = a.vids[v];
+        F = vd.F;
+        boxes += (int64_t)vd.f0 * B;
+        trk = a.tracks + (int64_t)a.cls * a.T * 5 * vd.f0 + (int64_t)(slot - v * a.cls * a.T) * F * 5;
+    } else {
+        trk = a.tracks + (int64_t)slot * F * 5;
+    }
     const int fr = a.aframes[slot];
     const bool live = fr >= 1 && fr <= F;
     const int af = live ? fr - 1 : 0;
-    float *trk = a.tracks + (int64_t)slot * F * 5;
     const float qnan = __uint_as_float(0x7FC00000u);
 
     if (dir > 0) {
@@ -105,7 +122,7 @@ __global__ __launch_bounds__(kAnchorLT) void anchor_link_kernel(const AnchorLink
         if (f < 0 || f >= F) break;
         const int par = step & 1;
         const float carea = box_area(cur);
-        const float4 *fb = a.boxes + (int64_t)f * B;
+        const float4 *fb = boxes + (int64_t)f * B;
         float bv = -1.0f;
         int bi = -1;
         float4 bb = cur;
@@ -180,16 +197,30 @@ __device__ __forceinline__ int64_t anchor_best(const double *p, const TB *__rest
     return bi;
 }
 
-// grid C*T, one workgroup per slot
+// grid C*T, one workgroup per slot.  BATCH (vids != null in spirit): slots [V,C,T], C counts the V*C groups, `cls` the
+// classes per video; tracks / det_score in video_batch's flat layout, boxes / scores of the video's own frames.
+template <bool BATCH>
 __global__ __launch_bounds__(kAnchorLT) void anchor_propagate_kernel(const float *__restrict__ tracks, const int32_t *__restrict__ ntracks,
                                                                      const float *__restrict__ anchors, const float *__restrict__ boxes,
                                                                      const float *__restrict__ scores, int F, int B, int C, int T,
                                                                      double *__restrict__ det_score, int32_t *__restrict__ best,
-                                                                     int *__restrict__ status)
+                                                                     int *__restrict__ status, const VidDesc *__restrict__ vids, int cls)
 {
     const int tid = threadIdx.x;
     const int slot = blockIdx.x, c = slot / T, t = slot - c * T;
     const float *trk = tracks + (int64_t)slot * F * 5;
+    int cl = c, NC = C;             // the class inside its video, classes of a score row
+    if (BATCH) {
+        const int v = c / cls;
+        const VidDesc vd = vids[v];
+        F = vd.F;
+        cl = c - v * cls; NC = cls;
+        const int64_t sv = slot - (int64_t)v * cls * T;
+        trk = tracks + (int64_t)cls * T * 5 * vd.f0 + sv * F * 5;
+        det_score += (int64_t)cls * T * vd.f0 + sv * F - (int64_t)slot * F;
+        boxes += (int64_t)vd.f0 * B * 4;
+        scores += (int64_t)vd.f0 * B * cls;
+    }
     int nt = ntracks[c];
     nt = nt < 0 ? 0 : (nt > T ? T : nt);
     const float a0 = anchors[(int64_t)slot * 3];
@@ -208,7 +239,7 @@ __global__ __launch_bounds__(kAnchorLT) void anchor_propagate_kernel(const float
     int64_t bi = -1;
     if (ok) {                    // (block-uniform)
         bi = anchor_best<float>(p, boxes + (int64_t)(fa - 1) * B * 4, B);
-        sc = (double)scores[((int64_t)(fa - 1) * B + bi) * C + c];
+        sc = (double)scores[((int64_t)(fa - 1) * B + bi) * NC + cl];
     }
     for (int f = tid; f < F; f += kAnchorLT) {
         const float r0 = trk[(int64_t)f * 5];

@@ -32,6 +32,7 @@
 #include "tcn_kernels.hpp"
 #include "interp_kernels.hpp"
 #include "anchor_kernels.hpp"
+#include "topanchor_kernels.hpp"
 
 using namespace vdet;
 
@@ -211,6 +212,11 @@ struct vdet_ctx {
     bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
     bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
     StagedTab interp_tab;         // device interpolation (interp_kernels.hpp): frame offsets and the frame table of the last call
+    // device anchor selection (topanchor_kernels.hpp) and the batch forms of the anchor route: the per-video {first frame,
+    // frames} table, keyed by the frame offsets (anchor_tab.uploads: vdet_query 11), and the selection's scratch
+    StagedTab anchor_tab;
+    DevBuf topa_hist, topa_state, topa_cnt, topa_nrec, topa_rec;
+    bool topa_hist_clean = false; // the histogram holds zeros (every selection round clears what it read)
 };
 
 namespace {
@@ -1443,7 +1449,8 @@ int vdet_destroy(vdet_ctx *c)
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
-                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev};
+                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
+                      &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1497,6 +1504,7 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 3) return c->wave_transpose ? 1 : 0;
     if (what == 8) return (int)std::min<long long>(c->n_host_syncs, 0x7FFFFFFF);
     if (what == 10) return (int)std::min<long long>(c->tcn_params.uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
+    if (what == 11) return (int)std::min<long long>(c->anchor_tab.uploads, 0x7FFFFFFF);   // per-video tables of the anchor route's batch forms staged so far
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -3298,7 +3306,7 @@ int vdet_track_from_anchors(vdet_ctx *c, const float *d_boxes, int64_t F, int64_
     a.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_TLINK);
-        hipLaunchKernelGGL(anchor_link_kernel, dim3((unsigned)(C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
+        hipLaunchKernelGGL(anchor_link_kernel<false>, dim3((unsigned)(C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
@@ -3318,8 +3326,9 @@ int vdet_anchor_propagate_tracks(vdet_ctx *c, const float *d_tracks, const int32
     timing_reset(c);
     {
         StageTimer tm(c, ST_OTHER);
-        hipLaunchKernelGGL(anchor_propagate_kernel, dim3((unsigned)(C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks, d_anchors,
-                           d_boxes, d_scores, (int)F, (int)B, (int)C, T, d_det_score, d_best, &c->d_cnt->status);
+        hipLaunchKernelGGL(anchor_propagate_kernel<false>, dim3((unsigned)(C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks, d_anchors,
+                           d_boxes, d_scores, (int)F, (int)B, (int)C, T, d_det_score, d_best, &c->d_cnt->status,
+                           (const VidDesc *)nullptr, 0);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
@@ -3355,6 +3364,155 @@ int vdet_anchor_argmax_f64(vdet_ctx *c, const double *h_anchor_boxes, const int3
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_best, c->tmp[4].p, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, host_sync(c));
+    return VDET_OK;
+}
+
+// the {first frame, frames} table of the anchor route's batch forms: one owner (anchor_tab), keyed by the offsets
+static int anchor_vidtab(vdet_ctx *c, const int64_t *h_frame_off, int64_t V)
+{
+    return stage_keyed(c, c->anchor_tab, h_frame_off, (size_t)(V + 1) * 8, (size_t)V * sizeof(VidDesc), [&](char *dst) {
+        VidDesc *tab = reinterpret_cast<VidDesc *>(dst);
+        for (int64_t v = 0; v < V; ++v) tab[v] = VidDesc{(int32_t)h_frame_off[v], (int32_t)(h_frame_off[v + 1] - h_frame_off[v])};
+    });
+}
+
+int vdet_top_anchors(vdet_ctx *c, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int top_num,
+                     int mode, int use_score_thresh, double score_thresh, const int64_t *h_frame_off, int64_t V,
+                     int32_t *d_anchor_frames, float *d_anchor_boxes, float *d_anchor_scores, int32_t *d_anchor_index)
+{
+    if (!c) return VDET_EINVAL;
+    if (mode != 0 && mode != 1) return fail(c, VDET_EINVAL, "mode must be 0 (video) or 1 (frame)");
+    if (F <= 0 || B <= 0 || C <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (top_num < 1) return fail(c, VDET_EINVAL, "top_num must be at least 1");
+    if (mode == 0 && top_num > kTopaMaxT) return fail(c, VDET_EINVAL, "top_num = %d; the limit is %d per class", top_num, kTopaMaxT);
+    if (mode == 1 && top_num > kTopaMaxTFrame) return fail(c, VDET_EINVAL, "top_num = %d; the limit is %d per frame and class", top_num, kTopaMaxTFrame);
+    if (mode == 1 && h_frame_off) return fail(c, VDET_EINVAL, "frame mode has no batch form");
+    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
+    if (F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
+    if (!d_boxes || !d_scores || !d_anchor_frames || !d_anchor_boxes || !d_anchor_scores || !d_anchor_index) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_boxes & 15) != 0 || ((uintptr_t)d_anchor_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes and d_anchor_boxes must be 16-byte aligned");
+    int64_t Fmax = F, nv = 1;
+    if (h_frame_off) {
+        int64_t Ft = 0;
+        const int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
+        if (rc) return rc;
+        if (Ft != F) return fail(c, VDET_EINVAL, "frame_off must end at F");
+        nv = V;
+    } else if (mode == 1) {
+        if (F > 65535) return fail(c, VDET_EINVAL, "frame mode: at most 65535 frames");
+        nv = F; Fmax = 1;
+    }
+    const int T = top_num;
+    const int64_t nseg = (Fmax * B + kTopaRows - 1) / kTopaRows, ctiles = (C + 63) / 64;
+    if (nv * C * (int64_t)T > 0x7FFFFFF0ll || nv * nseg * C > 0x7FFFFFF0ll || ctiles > 65535) return fail(c, VDET_EINVAL, "too many slots");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (h_frame_off) {
+        const int rc = anchor_vidtab(c, h_frame_off, V);
+        if (rc) return rc;
+    }
+    const size_t hist_bytes = (size_t)(nv * C) * 256 * 4;
+    if (hist_bytes > c->topa_hist.cap) c->topa_hist_clean = false;
+    HIPCHK(c, c->topa_hist.reserve(hist_bytes));
+    HIPCHK(c, c->topa_state.reserve((size_t)(nv * C) * 8));
+    HIPCHK(c, c->topa_cnt.reserve((size_t)(nv * nseg * C) * 8));
+    HIPCHK(c, c->topa_nrec.reserve((size_t)(nv * C) * 4));
+    HIPCHK(c, c->topa_rec.reserve((size_t)(nv * C) * T * 8));
+    if (!c->topa_hist_clean) HIPCHK(c, hipMemsetAsync(c->topa_hist.p, 0, c->topa_hist.cap, c->stream));
+    c->topa_hist_clean = false;
+    TopaArgs a{};
+    a.scores = d_scores; a.boxes = reinterpret_cast<const float4 *>(d_boxes);
+    a.vids = h_frame_off ? c->anchor_tab.dev.as<VidDesc>() : nullptr;
+    a.Fu = mode == 1 ? 1 : (int)F;
+    a.V = (int)nv; a.B = (int)B; a.C = (int)C; a.T = T;
+    a.use_thr = use_score_thresh ? 1 : 0; a.thr = (float)score_thresh;
+    a.nseg = (int)nseg; a.frame_mode = mode;
+    a.hist = c->topa_hist.as<uint32_t>(); a.state = c->topa_state.as<uint2>(); a.cnt = c->topa_cnt.as<uint2>();
+    a.nrec = c->topa_nrec.as<uint32_t>(); a.rec = c->topa_rec.as<unsigned long long>();
+    a.ovs = mode == 1 ? T : C * (int64_t)T; a.ocs = mode == 1 ? F * (int64_t)T : T;
+    a.oframes = d_anchor_frames; a.oboxes = reinterpret_cast<float4 *>(d_anchor_boxes); a.oscores = d_anchor_scores;
+    a.oindex = d_anchor_index;
+    const dim3 ghist((unsigned)((nseg + kTopaHistLT / 64 - 1) / (kTopaHistLT / 64)), (unsigned)ctiles, (unsigned)nv);
+    const dim3 gseg((unsigned)((nseg + kTopaLT / 64 - 1) / (kTopaLT / 64)), (unsigned)ctiles, (unsigned)nv);
+    const dim3 gcls((unsigned)C, (unsigned)nv);
+    {
+        StageTimer tm(c, ST_TPICK);
+        for (int pass = 0; pass < 4; ++pass) {
+            hipLaunchKernelGGL(topa_hist_kernel, ghist, dim3(kTopaHistLT), 0, c->stream, a, pass);
+            hipLaunchKernelGGL(topa_select_kernel, gcls, dim3(256), 0, c->stream, a, pass);
+        }
+        hipLaunchKernelGGL(topa_count_kernel, gseg, dim3(kTopaLT), 0, c->stream, a);
+        hipLaunchKernelGGL(topa_prefix_kernel, dim3((unsigned)ctiles, (unsigned)nv), dim3(1024), 0, c->stream, a);
+        hipLaunchKernelGGL(topa_gather_kernel, gseg, dim3(kTopaLT), 0, c->stream, a);
+        hipLaunchKernelGGL(topa_emit_kernel, gcls, dim3(kTopaLT), 0, c->stream, a, (int)pow2ceil((uint32_t)T));
+    }
+    HIPCHK(c, hipGetLastError());
+    c->topa_hist_clean = true;
+    return VDET_OK;
+}
+
+int vdet_track_from_anchors_batch(vdet_ctx *c, const float *d_boxes, const int64_t *h_frame_off, int64_t V, int64_t B,
+                                  const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores,
+                                  int64_t C, int T, double link_thres, int max_frames, float *d_tracks, float *d_anchors,
+                                  int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll || V * C * std::max(T, 1) > 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (F*B, C*T*F and V*C*T must stay below 2^31)");
+    if (!d_boxes || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (T == 0) {
+        HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)(V * C) * 4, c->stream));
+        return VDET_OK;
+    }
+    if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+    AnchorLinkArgs a{};
+    a.boxes = reinterpret_cast<const float4 *>(d_boxes);
+    a.F = (int)F; a.B = (int)B; a.C = (int)(V * C); a.T = T;
+    a.vids = c->anchor_tab.dev.as<VidDesc>(); a.cls = (int)C;
+    a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
+    a.link_t32 = thresh_to_f32(link_thres);
+    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)Fmax;
+    a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
+    a.status = &c->d_cnt->status;
+    {
+        StageTimer tm(c, ST_TLINK);
+        hipLaunchKernelGGL(anchor_link_kernel<true>, dim3((unsigned)(V * C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_anchor_propagate_tracks_batch(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                                       const float *d_boxes, const float *d_scores, const int64_t *h_frame_off, int64_t V,
+                                       int64_t B, int64_t C, int T, double *d_det_score, int32_t *d_best)
+{
+    if (!c) return VDET_EINVAL;
+    if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll || V * C * std::max(T, 1) > 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (F*B, C*T*F and V*C*T must stay below 2^31)");
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_anchors || !d_boxes || !d_scores || !d_det_score || !d_best) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(anchor_propagate_kernel<true>, dim3((unsigned)(V * C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks,
+                           d_anchors, d_boxes, d_scores, (int)F, (int)B, (int)(V * C), T, d_det_score, d_best, &c->d_cnt->status,
+                           (const VidDesc *)c->anchor_tab.dev.as<VidDesc>(), (int)C);
+    }
+    HIPCHK(c, hipGetLastError());
     return VDET_OK;
 }
 

@@ -572,6 +572,152 @@ def anchor_propagate_tracks(tracks, ntracks, anchors, boxes, scores, sync=True, 
     return det, best
 
 
+def top_anchors(boxes, scores, top_num, mode='video', score_thresh=None, frame_off=None, sync=True, ctx=None):
+    """The array form of protocol.top_detections (mode='video', utils/protocol.py:330-339) and frame_top_detections
+    (mode='frame', :341-351) for EVERY class in one call: the anchors ``track_from_anchors`` takes.
+
+    boxes [F,B,4] f32, scores [F,B,C] f32 (class innermost), same GPU.  A candidate of class c is a detection whose score is
+    not NaN and -- with ``score_thresh`` -- is > score_thresh (float32 compare, as ``nms_volume``; ``-inf`` drops io.py's
+    padding; without a threshold ``-inf`` IS a candidate: it is what ``det_score`` returns for a missing class).  Candidates
+    are ordered by descending score, equal scores (-0.0 == +0.0) by ascending flat index f*B + b, like Python's stable
+    ``sorted(..., reverse=True)`` over a frame-major det_proto.  One point of the reference is NOT mirrored: it returns a
+    proto of fewer than ``top_num`` detections unsorted; this call always sorts.
+      mode='video': T = top_num (<= 1024); slot t of class c is the t-th candidate; slots behind the last one are empty.
+        With ``frame_off`` [V+1] the selection runs inside every video's frame range, the outputs are [V,C,T,...] and frames
+        are local to the video (``track_from_anchors_batch``'s inputs).
+      mode='frame': T = F*top_num (top_num <= 128); slot f*top_num + r is the r-th candidate of frame f (frames ascending).
+        No batch form (ValueError with ``frame_off``).
+    Returns anchor_frames [C,T] int32 (1-based, 0 = empty slot), anchor_boxes [C,T,4] f32 (the proposal's box, not
+    truncated), anchor_scores [C,T] f32, anchor_index [C,T] int32 (box index in its frame, -1 = empty); an empty slot's box
+    and score are 0."""
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if mode not in ('video', 'frame'):
+        raise ValueError("mode must be 'video' or 'frame'")
+    if mode == 'frame' and frame_off is not None:
+        raise ValueError("mode='frame' has no batch form (frame_off)")
+    top_num = int(top_num)
+    if top_num < 1:
+        raise ValueError("top_num must be at least 1")
+    if top_num > (1024 if mode == 'video' else 128):
+        raise ValueError("top_num is limited to 1024 (mode='video') / 128 (mode='frame')")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4]")
+    F, B = boxes.shape[0], boxes.shape[1]
+    if scores.dim() != 3 or scores.shape[0] != F or scores.shape[1] != B:
+        raise ValueError("scores must be [F,B,C]")
+    C = scores.shape[2]
+    if F < 1 or B < 1 or C < 1:
+        raise ValueError("at least one frame, one box per frame and one class")
+    if not scores.is_cuda or scores.device != boxes.device:
+        if boxes.is_cuda:
+            raise ValueError("boxes and scores must live on the same GPU")
+    off = None if frame_off is None else _frame_offsets(frame_off, F)
+    ctx = _ctx_for(boxes, ctx)
+    boxes, scores = boxes.contiguous(), scores.contiguous()
+    T = top_num if mode == 'video' else F * top_num
+    lead = (C, T) if off is None else (len(off) - 1, C, T)
+    dev = boxes.device
+    frames = torch.empty(lead, dtype=torch.int32, device=dev)
+    aboxes = torch.empty(lead + (4,), dtype=torch.float32, device=dev)
+    ascores = torch.empty(lead, dtype=torch.float32, device=dev)
+    index = torch.empty(lead, dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.vdet_top_anchors(
+        ctx.h, boxes.data_ptr(), scores.data_ptr(), F, B, C, top_num, 0 if mode == 'video' else 1,
+        0 if score_thresh is None else 1, 0.0 if score_thresh is None else float(score_thresh),
+        off.ctypes.data if off is not None else None, 0 if off is None else len(off) - 1,
+        frames.data_ptr(), aboxes.data_ptr(), ascores.data_ptr(), index.data_ptr()))
+    if sync:
+        ctx.sync()
+    return frames, aboxes, ascores, index
+
+
+def track_from_anchors_batch(boxes, frame_off, anchor_frames, anchor_boxes, anchor_scores=None, link_thres=0.5, max_frames=0,
+                             sync=True, ctx=None):
+    """``track_from_anchors`` for V videos in ONE launch.  boxes [F,B,4] f32 holds the videos' frames one after the other,
+    ``frame_off`` [V+1] their ranges; anchor_frames [V,C,T] int32 (1-based INSIDE the video, 0 = empty slot), anchor_boxes
+    [V,C,T,4] f32, anchor_scores [V,C,T] f32 or None (``top_anchors(frame_off=...)``'s outputs).  A chain stops at its own
+    video's first and last frame; per video the rows are bit for bit ``track_from_anchors``' on that video alone.
+    Returns a dict in ``video_batch``'s shape: tracks[v] views [C,T,F_v,5] of one flat buffer (video v at element
+    C*T*5*frame_off[v]), anchors [V,C,T,3], ntracks [V,C], frame_off.  ValueError for an anchor frame outside 0..F_v."""
+    if boxes.dtype != torch.float32 or anchor_boxes.dtype != torch.float32 or \
+            (anchor_scores is not None and anchor_scores.dtype != torch.float32):
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if anchor_frames.dtype != torch.int32:
+        raise ValueError("anchor_frames must be int32")
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4]")
+    F, B = boxes.shape[0], boxes.shape[1]
+    if F < 1 or B < 1:
+        raise ValueError("boxes must hold at least one frame and one box per frame")
+    off = _frame_offsets(frame_off, F)
+    V = len(off) - 1
+    if anchor_frames.dim() != 3 or anchor_frames.shape[0] != V or anchor_frames.shape[1] < 1:
+        raise ValueError("anchor_frames must be [V,C,T] with C >= 1")
+    C, T = anchor_frames.shape[1], anchor_frames.shape[2]
+    if tuple(anchor_boxes.shape) != (V, C, T, 4):
+        raise ValueError("anchor_boxes must be [V,C,T,4]")
+    if anchor_scores is not None and tuple(anchor_scores.shape) != (V, C, T):
+        raise ValueError("anchor_scores must be [V,C,T]")
+    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("boxes, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    boxes, anchor_frames, anchor_boxes = boxes.contiguous(), anchor_frames.contiguous(), anchor_boxes.contiguous()
+    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
+    dev = boxes.device
+    tracks = torch.empty((C * T * F * 5,), dtype=torch.float32, device=dev)
+    anchors = torch.empty((V, C, T, 3), dtype=torch.float32, device=dev)
+    ntracks = torch.empty((V, C), dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.vdet_track_from_anchors_batch(
+        ctx.h, boxes.data_ptr(), off.ctypes.data, V, B, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+        anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, float(link_thres), int(max_frames),
+        tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
+    if sync:
+        ctx.sync()
+    tv = [tracks[C * T * 5 * int(off[v]): C * T * 5 * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v]), 5) for v in range(V)]
+    return dict(tracks=tv, anchors=anchors, ntracks=ntracks, frame_off=off)
+
+
+def anchor_propagate_tracks_batch(batch_out, boxes, scores, sync=True, ctx=None):
+    """``anchor_propagate_tracks`` for every video of a ``track_from_anchors_batch`` (or ``video_batch``) result in ONE
+    launch; boxes [F,B,4] / scores [F,B,C] f32 are the batch's volume.  Returns (det, best): det[v] views [C,T,F_v] f64 of one
+    flat buffer -- also stored as ``batch_out['det']``, where ``tcn_tracks_batch(series='det')`` reads it -- and best
+    [V,C,T] int32.  Per video both equal the single-video call's."""
+    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
+    V = len(off) - 1
+    tv = batch_out['tracks']
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or tv[0].dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    F = int(off[-1])
+    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4] over all frames of the batch")
+    B = boxes.shape[1]
+    if tuple(scores.shape) != (F, B, C):
+        raise ValueError("scores must be [F,B,C]")
+    tracks = _batch_flat(tv, 5)
+    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
+    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or \
+            tuple(anchors.shape) != (V, C, T, 3) or tracks.numel() != C * T * F * 5:
+        raise ValueError("not a track_from_anchors_batch / video_batch result")
+    for t in (tracks, ntracks, anchors, scores):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("the batch result, boxes and scores must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    dev = boxes.device
+    det = torch.empty((C * T * F,), dtype=torch.float64, device=dev)
+    best = torch.empty((V, C, T), dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.vdet_anchor_propagate_tracks_batch(
+        ctx.h, tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), boxes.contiguous().data_ptr(),
+        scores.contiguous().data_ptr(), off.ctypes.data, V, B, C, T, det.data_ptr(), best.data_ptr()))
+    if sync:
+        ctx.sync()
+    dv = [det[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
+    batch_out['det'] = dv
+    return dv, best
+
+
 def _tcn_net_args(net):
     from .vdet.tcn import TCNNet
     if not isinstance(net, TCNNet):
