@@ -69,6 +69,8 @@
  *                                                                     top_num: selection by threshold, then a sort of <= top_num
  *   device anchor selection / batch forms  B <= 32767, F*B < 2^31 - 16, V <= 65535 (frame mode: F <= 65535), C*T*F < 2^31
  *                                                                     VDET_EINVAL
+ *   device merge: slots, series            C*T*F < 2^31 - 16 for Ta, Tb AND the output's T (Ta + Tb under 'combine'), V <= 65535,
+ *                                          1 .. 4 series              VDET_EINVAL; one path for every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -709,6 +711,56 @@ int vdet_track_from_anchors_batch(vdet_ctx *ctx, const float *d_boxes, const int
 int vdet_anchor_propagate_tracks_batch(vdet_ctx *ctx, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
                                        const float *d_boxes, const float *d_scores, const int64_t *h_frame_off, int64_t V,
                                        int64_t B, int64_t C, int T, double *d_det_score, int32_t *d_best);
+
+/* ---- device merge: two scored tubelet sets into one (merge_score_protos, utils/protocol.py:504-525) ------------------------
+ *
+ * A tubelet SET of one video: d_tracks [C,T,F,5] f32, d_ntracks [C] i32, d_anchors [C,T,3] f32, optionally d_tboxes [C,T,F,4]
+ * f32, and n_series (1..4) series [C,T,F] f64 whose DEVICE pointers sit in the host arrays h_series_a / h_series_b; series 0
+ * is det_score.  A box exists where d_tracks[c,t,f,0] is not NaN and t < d_ntracks[c] -- the rule of every other stage; counts
+ * outside 0..T are clamped.  Sets a and b share C, F, n_series and the presence of tboxes (d_tboxes_a, d_tboxes_b and
+ * d_tboxes_out: all given or all NULL); Ta and Tb may differ.  Inputs are never modified; a and b may be the same buffers.
+ *
+ * VDET_MERGE_COMBINE (:510-511, list extend: a's tubelets, then b's).  T_out = Ta + Tb.  For class c, out slot t < nta[c] is a's
+ *   slot t, out slot nta[c] + u (u < ntb[c]) is b's slot u, d_ntracks_out[c] = nta[c] + ntb[c].  Live slots are copied bit for
+ *   bit in every field (rows, tboxes, all series, anchors), empty slots below ntracks included.  Every slot at or behind
+ *   d_ntracks_out[c] is written as NaN rows, NaN tboxes, NaN series and a zero anchor, whatever the inputs hold there.
+ *   d_from_b is not written (NULL).
+ * VDET_MERGE_MAX (:512-524).  The output has a's shape: T_out = Ta, d_ntracks_out = nta.  Slots t >= min(nta[c], ntb[c]) are
+ *   copies of a (zip over the tubelet lists).  Inside a paired slot the reference zips the two box lists: with ca / cb boxes and
+ *   m = min(ca, cb), the i-th box of a meets the i-th box of b for i < m.  The two must lie on the same frame (assert
+ *   box1['frame'] == box2['frame']) and, when m >= 1, the integer anchor frames (int)d_anchors[c,t,0] of the two slots must be
+ *   equal (assert box1['anchor'] == box2['anchor']).  Where det_b > det_a (the f64 compare of box1['det_score'] <
+ *   box2['det_score']: a NaN on either side, equal scores and -0.0 against +0.0 keep a) b's values are taken for every field a's
+ *   box has: the row (box and track score), tboxes and all series.  Boxes of a with ordinal >= m are unchanged; anchors are a's.
+ *   d_from_b [C,Ta,F] u8: 1 where b's box was taken, 0 elsewhere.  A slot that violates an assertion latches VDET_EINVAL in the
+ *   context's status word (reported by vdet_sync, as vdet_track_from_anchors' bad anchor frame) and is written as a copy of a;
+ *   all other slots are unaffected.  The reference's `gt` and `class` assertions have no device counterpart: the sets carry no
+ *   gt flag, and the class of a slot is its index c on both sides.
+ * d_series_out [n_series][C*T_out*F] f64: series q starts at element q*C*T_out*F (batch: F = all frames of the call) and is laid
+ * out like every other [C,T,F] output.  Every output element is written by the ONE launch of the call (no fill pass).
+ * Asynchronous: no host wait, no host table, no scratch; reads and writes nothing of the context's cached graph, lists, index
+ * or link memo.
+ */
+#define VDET_MERGE_COMBINE 0
+#define VDET_MERGE_MAX 1
+
+int vdet_merge_tracks(vdet_ctx *ctx, int scheme, int64_t F, int64_t C, int Ta, int Tb,
+                      const float *d_tracks_a, const int32_t *d_ntracks_a, const float *d_anchors_a, const float *d_tboxes_a,
+                      const float *d_tracks_b, const int32_t *d_ntracks_b, const float *d_anchors_b, const float *d_tboxes_b,
+                      const double *const *h_series_a, const double *const *h_series_b, int n_series, float *d_tracks_out,
+                      int32_t *d_ntracks_out, float *d_anchors_out, float *d_tboxes_out, double *d_series_out, uint8_t *d_from_b);
+
+/* The same for V videos in vdet_video_batch's layout, ONE launch with the video as a grid dimension: set a's arrays of video v
+ * start at element C*Ta*h_frame_off[v] and are [C,Ta,F_v], set b's at C*Tb*h_frame_off[v], the outputs at C*T_out*h_frame_off[v];
+ * d_ntracks_* [V,C], d_anchors_* [V,C,T,3].  Per video the bits are vdet_merge_tracks' on that video alone.  More than one video
+ * reads the per-video table of the anchor route's batch forms, staged keyed by the offsets (vdet_query 11): the same offsets
+ * again neither wait nor copy. */
+int vdet_merge_tracks_batch(vdet_ctx *ctx, int scheme, const int64_t *h_frame_off, int64_t V, int64_t C, int Ta, int Tb,
+                            const float *d_tracks_a, const int32_t *d_ntracks_a, const float *d_anchors_a, const float *d_tboxes_a,
+                            const float *d_tracks_b, const int32_t *d_ntracks_b, const float *d_anchors_b, const float *d_tboxes_b,
+                            const double *const *h_series_a, const double *const *h_series_b, int n_series, float *d_tracks_out,
+                            int32_t *d_ntracks_out, float *d_anchors_out, float *d_tboxes_out, double *d_series_out,
+                            uint8_t *d_from_b);
 
 #ifdef __cplusplus
 }

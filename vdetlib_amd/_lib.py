@@ -81,6 +81,10 @@ SYMBOLS = {
     "vdet_top_anchors": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _ci, _f64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "vdet_track_from_anchors_batch": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _f64, _ci, _vp, _vp, _vp]),
     "vdet_anchor_propagate_tracks_batch": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp]),
+    "vdet_merge_tracks": (_ci, [_vp, _ci, _i64, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp,
+                                _vp, _vp, _vp]),
+    "vdet_merge_tracks_batch": (_ci, [_vp, _ci, _vp, _i64, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
 }
 
 

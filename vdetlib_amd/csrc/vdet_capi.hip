@@ -33,6 +33,7 @@
 #include "interp_kernels.hpp"
 #include "anchor_kernels.hpp"
 #include "topanchor_kernels.hpp"
+#include "merge_kernels.hpp"
 
 using namespace vdet;
 
@@ -339,6 +340,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStPoolAsync) return fail(c, VDET_EAGAIN, "adjacency pool overflow in an asynchronous graph build: run the calls again");
     if (st & kStBadOrder) return fail(c, VDET_EINVAL, "a caller-supplied candidate list holds a count or a box index out of range");
     if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
+    if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -3514,6 +3516,77 @@ int vdet_anchor_propagate_tracks_batch(vdet_ctx *c, const float *d_tracks, const
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device merge of two tubelet sets (merge_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_merge_tracks_batch(vdet_ctx *c, int scheme, const int64_t *h_frame_off, int64_t V, int64_t C, int Ta, int Tb,
+                            const float *d_tracks_a, const int32_t *d_ntracks_a, const float *d_anchors_a, const float *d_tboxes_a,
+                            const float *d_tracks_b, const int32_t *d_ntracks_b, const float *d_anchors_b, const float *d_tboxes_b,
+                            const double *const *h_series_a, const double *const *h_series_b, int n_series, float *d_tracks_out,
+                            int32_t *d_ntracks_out, float *d_anchors_out, float *d_tboxes_out, double *d_series_out,
+                            uint8_t *d_from_b)
+{
+    if (!c) return VDET_EINVAL;
+    if (scheme != VDET_MERGE_COMBINE && scheme != VDET_MERGE_MAX) return fail(c, VDET_EINVAL, "scheme must be VDET_MERGE_COMBINE or VDET_MERGE_MAX");
+    if (n_series < 1 || n_series > kMergeMaxSeries) return fail(c, VDET_EINVAL, "1 to %d series (series 0 is det_score)", kMergeMaxSeries);
+    if (C < 1 || Ta < 0 || Tb < 0) return fail(c, VDET_EINVAL, "bad shape");
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    const int64_t To = scheme == VDET_MERGE_COMBINE ? (int64_t)Ta + Tb : Ta, Tmax = std::max<int64_t>(std::max<int64_t>(To, Tb), 1);
+    if (C * Tmax >= 0x7FFFFFF0ll || C * Tmax * F >= 0x7FFFFFF0ll || V * C * Tmax >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16 for Ta, Tb and the output's T)");
+    if (!d_ntracks_a || !d_ntracks_b || !d_ntracks_out) return fail(c, VDET_EINVAL, "null buffer");
+    const bool tbx = d_tboxes_out != nullptr;
+    if ((Ta && (d_tboxes_a != nullptr) != tbx) || (Tb && (d_tboxes_b != nullptr) != tbx))
+        return fail(c, VDET_EINVAL, "tboxes: both sets and the output, or none of them");
+    if ((Ta && (!d_tracks_a || !d_anchors_a || !h_series_a)) || (Tb && (!d_tracks_b || !d_anchors_b || !h_series_b)) ||
+        (To && (!d_tracks_out || !d_anchors_out || !d_series_out)) || (scheme == VDET_MERGE_MAX && To && !d_from_b))
+        return fail(c, VDET_EINVAL, "null buffer");
+    MergeArgs g{};
+    for (int q = 0; q < n_series; ++q) {
+        if ((Ta && !h_series_a[q]) || (Tb && !h_series_b[q])) return fail(c, VDET_EINVAL, "null buffer");
+        g.a.series[q] = Ta ? h_series_a[q] : nullptr;
+        g.b.series[q] = Tb ? h_series_b[q] : nullptr;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (To == 0) {      // no slot to write: the counts alone ('combine': 0 + 0, 'max': a's, clamped to Ta = 0)
+        HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
+        return VDET_OK;
+    }
+    // one video travels in the kernel arguments alone; more share the anchor route's per-video table, keyed by the offsets
+    if (V > 1) {
+        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+        g.vids = c->anchor_tab.dev.as<VidDesc>();
+    }
+    g.a.tracks = d_tracks_a; g.a.ntracks = d_ntracks_a; g.a.anchors = d_anchors_a; g.a.tboxes = d_tboxes_a; g.a.T = Ta;
+    g.b.tracks = d_tracks_b; g.b.ntracks = d_ntracks_b; g.b.anchors = d_anchors_b; g.b.tboxes = d_tboxes_b; g.b.T = Tb;
+    g.F = (int)F; g.C = (int)C; g.nser = n_series; g.To = (int)To;
+    g.otracks = d_tracks_out; g.ontracks = d_ntracks_out; g.oanchors = d_anchors_out; g.otboxes = d_tboxes_out;
+    g.oseries = d_series_out; g.oN = C * To * F; g.from_b = d_from_b; g.status = &c->d_cnt->status;
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)((C * To + kMergeWaves - 1) / kMergeWaves), (unsigned)V);
+        if (scheme == VDET_MERGE_COMBINE) hipLaunchKernelGGL(merge_combine_kernel, grid, dim3(kMergeLT), 0, c->stream, g);
+        else hipLaunchKernelGGL(merge_max_kernel, grid, dim3(kMergeLT), 0, c->stream, g);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_merge_tracks(vdet_ctx *c, int scheme, int64_t F, int64_t C, int Ta, int Tb,
+                      const float *d_tracks_a, const int32_t *d_ntracks_a, const float *d_anchors_a, const float *d_tboxes_a,
+                      const float *d_tracks_b, const int32_t *d_ntracks_b, const float *d_anchors_b, const float *d_tboxes_b,
+                      const double *const *h_series_a, const double *const *h_series_b, int n_series, float *d_tracks_out,
+                      int32_t *d_ntracks_out, float *d_anchors_out, float *d_tboxes_out, double *d_series_out, uint8_t *d_from_b)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_merge_tracks_batch(c, scheme, off, 1, C, Ta, Tb, d_tracks_a, d_ntracks_a, d_anchors_a, d_tboxes_a, d_tracks_b,
+                                   d_ntracks_b, d_anchors_b, d_tboxes_b, h_series_a, h_series_b, n_series, d_tracks_out,
+                                   d_ntracks_out, d_anchors_out, d_tboxes_out, d_series_out, d_from_b);
 }
 
 }  // extern "C"

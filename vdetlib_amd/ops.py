@@ -980,6 +980,198 @@ def interpolate_tracks_batch(batch_out, frames, num_frames, sync=True, ctx=None)
     return out
 
 
+_MERGE_SCHEMES = {'combine': 0, 'max': 1}      # include/vdet_hip.h: VDET_MERGE_COMBINE / VDET_MERGE_MAX
+
+
+def _merge_series(series, shape, who):
+    if torch.is_tensor(series):
+        series = (series,)
+    series = tuple(series)
+    if not 1 <= len(series) <= 4:
+        raise ValueError("%s: 1 to 4 series (series 0 is det_score)" % who)
+    for x in series:
+        if not torch.is_tensor(x) or x.dtype != torch.float64 or tuple(x.shape) != shape:
+            raise ValueError("%s: every series must be a float64 tensor [C,T,F]" % who)
+    return series
+
+
+def _merge_set(s, who):
+    """One side of merge_tracks, checked: (tracks, ntracks, anchors, tboxes or None, series tuple)."""
+    if not isinstance(s, dict) or any(k not in s for k in ('tracks', 'ntracks', 'anchors', 'series')):
+        raise ValueError("%s must be a dict with tracks, ntracks, anchors and series (optionally tboxes)" % who)
+    tracks, ntracks, anchors, tboxes = s['tracks'], s['ntracks'], s['anchors'], s.get('tboxes')
+    if not torch.is_tensor(tracks) or tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("%s: tracks must be float32 [C,T,F,5]" % who)
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if C < 1 or F < 1:
+        raise ValueError("%s: at least one class and one frame" % who)
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("%s: ntracks must be int32 [C]" % who)
+    if not torch.is_tensor(anchors) or anchors.dtype != torch.float32 or tuple(anchors.shape) != (C, T, 3):
+        raise ValueError("%s: anchors must be float32 [C,T,3]" % who)
+    if tboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float32 or tuple(tboxes.shape) != (C, T, F, 4)):
+        raise ValueError("%s: tboxes must be float32 [C,T,F,4]" % who)
+    return tracks, ntracks, anchors, tboxes, _merge_series(s['series'], (C, T, F), who)
+
+
+def _merge_call(ctx, scheme, off, C, Ta, Tb, sa, sb, sync):
+    """Allocate the outputs (flat, batch layout) and enqueue the one launch.  sa / sb: (tracks, ntracks, anchors, tboxes or
+    None, series tuple), contiguous, one device.  Returns (tracks, ntracks, anchors, tboxes or None, series [n, N], from_b or
+    None, T_out), all flat."""
+    V, Ft = len(off) - 1, int(off[-1])
+    To = Ta + Tb if scheme == 'combine' else Ta
+    if max(C * To * Ft, C * Tb * Ft, V * C * max(To, Tb)) >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16, the output's T included)")
+    dev = sa[0].device
+    n, N = len(sa[4]), C * To * Ft
+    tracks = torch.empty((N * 5,), dtype=torch.float32, device=dev)
+    ntracks = torch.empty((V, C), dtype=torch.int32, device=dev)
+    anchors = torch.empty((V, C, To, 3), dtype=torch.float32, device=dev)
+    tboxes = torch.empty((N * 4,), dtype=torch.float32, device=dev) if sa[3] is not None else None
+    series = torch.empty((n, N), dtype=torch.float64, device=dev)
+    from_b = torch.empty((N,), dtype=torch.uint8, device=dev) if scheme == 'max' else None
+    pa = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in sa[4]])
+    pb = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in sb[4]])
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    tail = (C, Ta, Tb, sa[0].data_ptr(), sa[1].data_ptr(), sa[2].data_ptr(), ptr(sa[3]), sb[0].data_ptr(), sb[1].data_ptr(),
+            sb[2].data_ptr(), ptr(sb[3]), pa, pb, n, tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), ptr(tboxes),
+            series.data_ptr(), ptr(from_b))
+    if V == 1:
+        ctx.check(ctx.lib.vdet_merge_tracks(ctx.h, _MERGE_SCHEMES[scheme], Ft, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_merge_tracks_batch(ctx.h, _MERGE_SCHEMES[scheme], off.ctypes.data, V, *tail))
+    if sync:
+        ctx.sync()
+    return tracks, ntracks, anchors, tboxes, series, from_b, To
+
+
+def merge_tracks(a, b, scheme='combine', sync=True, ctx=None):
+    """``merge_score_protos`` (utils/protocol.py:504-525) on two device tubelet sets of one video, one launch, no host wait.
+
+    ``a`` / ``b``: dicts with ``tracks`` [C,T,F,5] f32, ``ntracks`` [C] int32, ``anchors`` [C,T,3] f32, ``series`` (a tuple of
+    1..4 f64 [C,T,F] tensors, or one tensor; series 0 is det_score) and optionally ``tboxes`` [C,T,F,4] f32 -- the keys
+    ``interpolate_tracks`` returns, whose result goes in unchanged.  The sets share C, F, the number of series and the presence
+    of tboxes; Ta and Tb may differ; ``a is b`` is fine; the inputs are never modified.
+      'combine': a's tubelets, then b's: T_out = Ta + Tb, out slot t < nta[c] is a's slot t, slot nta[c] + u is b's slot u,
+        ntracks = nta + ntb; the slots behind are NaN (zero anchors).  Copies are bit for bit.
+      'max': the output has a's shape; in slot t < min(nta[c], ntb[c]) the i-th box of a meets the i-th box of b and takes all
+        of b's values (row, tboxes, every series) where det_b > det_a (NaN, equal scores, -0.0 vs +0.0 keep a); everything
+        else is a's.  Paired boxes must lie on the same frames and the slots' anchor frames must be equal, else ValueError
+        when the call -- or with ``sync=False`` a later ``ctx.sync()`` -- waits (the slot is then a copy of a).
+    Semantics in full: include/vdet_hip.h (vdet_merge_tracks).  Returns a dict of the same form (``tracks``, ``ntracks``,
+    ``anchors``, ``series``, ``tboxes`` when the inputs have them), plus ``from_b`` [C,T,F] uint8 for 'max'."""
+    if scheme not in _MERGE_SCHEMES:
+        raise ValueError("scheme must be 'combine' or 'max'")
+    sa, sb = _merge_set(a, 'a'), _merge_set(b, 'b')
+    C, Ta, F = sa[0].shape[0], sa[0].shape[1], sa[0].shape[2]
+    Tb = sb[0].shape[1]
+    if sb[0].shape[0] != C or sb[0].shape[2] != F:
+        raise ValueError("a and b must share C and F (a: C=%d F=%d, b: C=%d F=%d)" % (C, F, sb[0].shape[0], sb[0].shape[2]))
+    if len(sa[4]) != len(sb[4]):
+        raise ValueError("a and b must have the same number of series")
+    if (sa[3] is None) != (sb[3] is None):
+        raise ValueError("tboxes: in both sets or in neither")
+    flat = lambda s: [x for x in s[:4] if x is not None] + list(s[4])
+    for x in flat(sa) + flat(sb):
+        if not x.is_cuda or x.device != sa[0].device:
+            raise ValueError("every tensor of a and b must live on the same GPU (vdetlib_amd has no CPU path)")
+    cont = lambda s: tuple(None if x is None else x.contiguous() for x in s[:4]) + (tuple(x.contiguous() for x in s[4]),)
+    sa, sb = cont(sa), cont(sb)
+    ctx = _ctx_for(sa[0], ctx)
+    tracks, ntracks, anchors, tboxes, series, from_b, To = _merge_call(ctx, scheme, np.array([0, F], dtype=np.int64), C, Ta, Tb, sa,
+                                                                       sb, sync)
+    out = dict(tracks=tracks.view(C, To, F, 5), ntracks=ntracks.view(C), anchors=anchors.view(C, To, 3),
+               series=tuple(series[q].view(C, To, F) for q in range(series.shape[0])))
+    if tboxes is not None:
+        out['tboxes'] = tboxes.view(C, To, F, 4)
+    if from_b is not None:
+        out['from_b'] = from_b.view(C, To, F)
+    return out
+
+
+def _merge_flat(views, per, who):
+    try:
+        return _batch_flat(views, per)
+    except RuntimeError:       # (as_strided past the end of the first view's storage)
+        raise ValueError("%s: the per-video views are not consecutive slices of one allocation" % who)
+
+
+def _merge_batch_set(bo, off, who):
+    """One side of merge_tracks_batch, checked: (flat tracks, ntracks, anchors, C, T)."""
+    if not isinstance(bo, dict) or any(k not in bo for k in ('tracks', 'ntracks', 'anchors', 'frame_off')) or not bo.get('det'):
+        raise ValueError("%s must be a dict in video_batch's layout with tracks, det, ntracks, anchors and frame_off" % who)
+    V, tv = len(off) - 1, bo['tracks']
+    if len(tv) != V or len(bo['det']) != V or tv[0].dtype != torch.float32 or tv[0].dim() != 4 or tv[0].shape[3] != 5:
+        raise ValueError("%s: not a video_batch result" % who)
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    for v in range(V):
+        if tuple(tv[v].shape) != (C, T, int(off[v + 1] - off[v]), 5):
+            raise ValueError("%s: tracks[%d] must be [C,T,F_v,5]" % (who, v))
+    ntracks, anchors = bo['ntracks'], bo['anchors']
+    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or \
+            tuple(anchors.shape) != (V, C, T, 3):
+        raise ValueError("%s: ntracks must be int32 [V,C], anchors float32 [V,C,T,3]" % who)
+    return _merge_flat(tv, 5, who), ntracks.contiguous(), anchors.contiguous(), C, T
+
+
+def merge_tracks_batch(batch_a, batch_b, scheme='combine', sync=True, ctx=None):
+    """``merge_tracks`` for every video of two results in ``video_batch``'s layout (``video_batch``, ``track_from_anchors_batch``
+    + ``anchor_propagate_tracks_batch``, ``interpolate_tracks_batch``) in ONE launch.  Both dicts need ``tracks``, ``det``
+    (series 0), ``ntracks``, ``anchors`` and the same ``frame_off``; ``pooled`` (a second series) and ``tboxes`` are taken when
+    BOTH have them.  Per video the bits are ``merge_tracks``' on that video alone.  Returns a dict in the same layout --
+    ``tracks`` / ``det`` / ``pooled`` / ``tboxes`` (and ``from_b`` for 'max') as consecutive per-video views of one allocation
+    each, ``anchors`` [V,C,T_out,3], ``ntracks`` [V,C], ``frame_off`` -- which ``tcn_tracks_batch``, ``tubelets_overlap_batch``
+    and ``DetEvaluator.add_batch`` take as they take ``video_batch``'s."""
+    if scheme not in _MERGE_SCHEMES:
+        raise ValueError("scheme must be 'combine' or 'max'")
+    for bo, who in ((batch_a, 'batch_a'), (batch_b, 'batch_b')):
+        if not isinstance(bo, dict) or 'frame_off' not in bo:
+            raise ValueError("%s must be a dict in video_batch's layout" % who)
+    off = np.ascontiguousarray(batch_a['frame_off'], dtype=np.int64).reshape(-1)
+    offb = np.ascontiguousarray(batch_b['frame_off'], dtype=np.int64).reshape(-1)
+    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0) or not np.array_equal(off, offb):
+        raise ValueError("batch_a and batch_b must have the same frame_off (0 = o[0] < o[1] < ... < o[V])")
+    V, Ft = len(off) - 1, int(off[-1])
+    ta, nta, ana, C, Ta = _merge_batch_set(batch_a, off, 'batch_a')
+    tb, ntb, anb, Cb, Tb = _merge_batch_set(batch_b, off, 'batch_b')
+    if Cb != C:
+        raise ValueError("batch_a and batch_b must share C")
+    names = ['det'] + (['pooled'] if batch_a.get('pooled') and batch_b.get('pooled') else [])
+    with_tb = bool(batch_a.get('tboxes')) and bool(batch_b.get('tboxes'))
+
+    def side(bo, T, who):
+        ser = []
+        for k in names:
+            if len(bo[k]) != V or any(x.dtype != torch.float64 for x in bo[k]) or sum(x.numel() for x in bo[k]) != C * T * Ft:
+                raise ValueError("%s: %s must be float64 [C,T,F_v] views" % (who, k))
+            ser.append(_merge_flat(bo[k], 1, who))
+        bx = None
+        if with_tb:
+            if len(bo['tboxes']) != V or any(x.dtype != torch.float32 for x in bo['tboxes']) or \
+                    sum(x.numel() for x in bo['tboxes']) != C * T * Ft * 4:
+                raise ValueError("%s: tboxes must be float32 [C,T,F_v,4] views" % who)
+            bx = _merge_flat(bo['tboxes'], 4, who)
+        return ser, bx
+    sera, bxa = side(batch_a, Ta, 'batch_a')
+    serb, bxb = side(batch_b, Tb, 'batch_b')
+    for x in [ta, nta, ana, tb, ntb, anb] + sera + serb + [y for y in (bxa, bxb) if y is not None]:
+        if not x.is_cuda or x.device != ta.device:
+            raise ValueError("every tensor of batch_a and batch_b must live on the same GPU (vdetlib_amd has no CPU path)")
+    ctx = _ctx_for(ta, ctx)
+    tracks, ntracks, anchors, tboxes, series, from_b, To = _merge_call(
+        ctx, scheme, off, C, Ta, Tb, (ta, nta, ana, bxa, tuple(sera)), (tb, ntb, anb, bxb, tuple(serb)), sync)
+
+    def views(flat, per):
+        shape = (lambda fv: (C, To, fv, per)) if per > 1 else (lambda fv: (C, To, fv))
+        return [flat[C * To * per * int(off[v]): C * To * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
+
+    out = dict(tracks=views(tracks, 5), det=views(series[0], 1), pooled=views(series[1], 1) if len(names) > 1 else [],
+               tboxes=views(tboxes, 4) if with_tb else [], anchors=anchors, ntracks=ntracks, frame_off=off)
+    if from_b is not None:
+        out['from_b'] = views(from_b, 1)
+    return out
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 
