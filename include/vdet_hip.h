@@ -71,6 +71,9 @@
  *                                                                     VDET_EINVAL
  *   device merge: slots, series            C*T*F < 2^31 - 16 for Ta, Tb AND the output's T (Ta + Tb under 'combine'), V <= 65535,
  *                                          1 .. 4 series              VDET_EINVAL; one path for every size
+ *   device tubelet NMS: rows per list      top_still + T <= 1024, 1 <= R <= 1024 (the evaluator's tracks-per-(frame, class) limit),
+ *                                          C*R*F and C*T*F < 2^31 - 16, B <= 32767, V <= 65535      VDET_EINVAL; one path for
+ *                                                                     every size: a wave's LDS follows the call's top_still + T
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -761,6 +764,54 @@ int vdet_merge_tracks_batch(vdet_ctx *ctx, int scheme, const int64_t *h_frame_of
                             const double *const *h_series_a, const double *const *h_series_b, int n_series, float *d_tracks_out,
                             int32_t *d_ntracks_out, float *d_anchors_out, float *d_tboxes_out, double *d_series_out,
                             uint8_t *d_from_b);
+
+/* ---- device NMS of tubelets with still-image detections, per frame and class (vid_nms, utils/nms.pyx:71-125) ---------------
+ *
+ * What apply_vid_nms (vdet/video_det.py:51-61) does to a detection proto: vid_nms never suppresses across frames, so it is one
+ * nms (utils/nms.pyx:17-68) per (class, frame) list.  For every class c and frame f the candidate ROWS are, in this order:
+ *   1. still-image rows (optional source: the four tensors vdet_eval_match_keep takes, layout [F,B,C] only).  For
+ *      k in 0 .. min(d_keep_cnt[f,c], top_still) - 1, with b = d_keep_idx[f,c,k], the row is (d_boxes[f,b,0:4], d_scores[f,b,c]).
+ *      Keep lists are in descending score order, so the prefix is the max_per_image cut of fast_rcnn_det_vid.  Entries behind
+ *      the count are never read.  Without the source (top_still = 0) the four pointers are not read and may be NULL.
+ *   2. tubelet rows.  For t in 0 .. d_ntracks[c] - 1 (clamped to 0..T) where d_tracks[c,t,f,0] is not NaN, the row is
+ *      (box, (float)score[c,t,f]): box is d_tboxes[c,t,f] when d_tboxes is given, else d_tracks[c,t,f,0:4]; d_score is a [C,T,F]
+ *      series of the caller's choice, f32 or f64 (score_f64), rounded to f32 to nearest.  Slots t >= d_ntracks[c] are never
+ *      read, whatever they hold.  T = 0: no tubelet source, the pointers may be NULL.
+ * A row whose f32 score is NaN is absent, from either source (the evaluator's "NaN = no box" rule).
+ * The result of the list is nms(rows, thresh) with the conventions at the top of this file: f32 arithmetic, +1 areas,
+ * suppression iff (double)ovr_f32 >= thresh; descending score, -0.0 == +0.0, equal scores by DESCENDING row index -- at equal
+ * score a tubelet row therefore precedes a still-image row, and a higher slot a lower one.  A zero union of an EVALUATED pair
+ * (a kept row against a still-alive one) latches VDET_EDIVZERO (vdet_sync); a pair the reference never evaluates raises
+ * nothing.  NaN / inf coordinates behave as in every other NMS entry point (comparisons with NaN are false).
+ *
+ * Outputs, in the tubelet layout with the RANK as the slot axis (R rows; top_still + T can never overflow), so every consumer
+ * of tubelets reads them unchanged (vdet_eval_match_tracks with box_stride 5 and the f64 score):
+ *   d_tracks_out [C,R,F,5] f32   row r of frame f is the r-th kept detection (x1,y1,x2,y2, f32 score); NaN behind the count
+ *   d_score_out  [C,R,F]   f64   the source's own score unrounded (f64 series as given, f32 widened); NaN behind the count
+ *   d_src_out    [C,R,F]   i32   b >= 0: still-image box b of that frame; -(t+1): tubelet slot t; INT32_MIN behind the count
+ *   d_cnt_out    [C,F]     i32   detections kept
+ *   d_ntracks_out [C]      i32   max over f of min(cnt[c,f], R) (an integer atomic max)
+ * More survivors than R latch VDET_ECAP: the count is still written, nothing is written past R.  A d_keep_cnt outside 0..cap
+ * (the list then has no still-image rows) or a read d_keep_idx outside 0..B-1 (that row is skipped) latches VDET_EINVAL.
+ * Inputs are never modified.  Every output element is written by the ONE launch of the call; asynchronous, no host wait, no
+ * scratch; reads and writes nothing of the context's cached graph, lists, index or link memo.  d_boxes and d_tboxes must be
+ * 16-byte aligned.  Limits: the table at the top of this file.
+ */
+int vdet_nms_tracks(vdet_ctx *ctx, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks, const void *d_score,
+                    int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores, int64_t B,
+                    const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R,
+                    float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out, int32_t *d_ntracks_out);
+
+/* The same for V videos in vdet_video_batch's layout, ONE launch with the video as a grid dimension.  The still-image tensors
+ * are frame-major over all videos ([Ftot,...]); the tubelet arrays of video v start at element C*T*h_frame_off[v] and are
+ * [C,T,F_v], the outputs at C*R*h_frame_off[v] ([C,R,F_v]); d_ntracks [V,C], d_cnt_out [C,Ftot], d_ntracks_out [V,C].  Per video
+ * the bits are vdet_nms_tracks' on that video alone.  More than one video reads the per-video table of the anchor route's batch
+ * forms, staged keyed by the offsets (vdet_query 11): the same offsets again neither wait nor copy. */
+int vdet_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
+                          const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
+                          int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                          int32_t *d_cnt_out, int32_t *d_ntracks_out);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@
 #include "anchor_kernels.hpp"
 #include "topanchor_kernels.hpp"
 #include "merge_kernels.hpp"
+#include "tracknms_kernels.hpp"
 
 using namespace vdet;
 
@@ -341,6 +342,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadOrder) return fail(c, VDET_EINVAL, "a caller-supplied candidate list holds a count or a box index out of range");
     if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
+    if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -3587,6 +3589,71 @@ int vdet_merge_tracks(vdet_ctx *c, int scheme, int64_t F, int64_t C, int Ta, int
     return vdet_merge_tracks_batch(c, scheme, off, 1, C, Ta, Tb, d_tracks_a, d_ntracks_a, d_anchors_a, d_tboxes_a, d_tracks_b,
                                    d_ntracks_b, d_anchors_b, d_tboxes_b, h_series_a, h_series_b, n_series, d_tracks_out,
                                    d_ntracks_out, d_anchors_out, d_tboxes_out, d_series_out, d_from_b);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-frame NMS of tubelets with still-image detections (tracknms_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
+                          const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
+                          int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                          int32_t *d_cnt_out, int32_t *d_ntracks_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (C < 1 || T < 0 || top_still < 0) return fail(c, VDET_EINVAL, "bad shape");
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    if ((int64_t)top_still + T > kTnMaxList)
+        return fail(c, VDET_EINVAL, "top_still + T = %lld candidates per (frame, class); the limit is %d", (long long)top_still + T, kTnMaxList);
+    if (R < 1 || R > kTnMaxList) return fail(c, VDET_EINVAL, "R = %d output rows per (frame, class); 1 .. %d", R, kTnMaxList);
+    if (C * (int64_t)R * F >= 0x7FFFFFF0ll || C * (int64_t)T * F >= 0x7FFFFFF0ll || V * C >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many tubelet boxes (C*R*F and C*T*F must stay below 2^31 - 16)");
+    if (top_still > 0) {
+        if (B < 1 || B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; 1 .. 32767", (long long)B);
+        if (cap < 1 || cap > 0x7FFFFFF0ll || F * C * cap >= (1ll << 40)) return fail(c, VDET_EINVAL, "bad keep-list capacity");
+        if (!d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt) return fail(c, VDET_EINVAL, "null buffer (top_still > 0 needs the still-image source)");
+        if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    }
+    if (T > 0 && (!d_tracks || !d_ntracks || !d_score)) return fail(c, VDET_EINVAL, "null buffer");
+    if (T > 0 && d_tboxes && ((uintptr_t)d_tboxes & 15) != 0) return fail(c, VDET_EINVAL, "d_tboxes must be 16-byte aligned");
+    if (!d_tracks_out || !d_score_out || !d_src_out || !d_cnt_out || !d_ntracks_out) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    TrackNmsArgs g{};
+    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_merge_tracks_batch)
+        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+        g.vids = c->anchor_tab.dev.as<VidDesc>();
+    }
+    g.tracks = d_tracks; g.ntracks = d_ntracks; g.score = d_score; g.tboxes = T > 0 ? reinterpret_cast<const float4 *>(d_tboxes) : nullptr;
+    g.boxes = reinterpret_cast<const float4 *>(d_boxes); g.scores = d_scores; g.keep_idx = d_keep_idx; g.keep_cnt = d_keep_cnt;
+    g.F = (int)F; g.Ftot = (int)F; g.C = (int)C; g.T = T; g.B = (int)B; g.cap = (int)cap; g.top_still = top_still; g.R = R;
+    g.nmax = top_still + T; g.score_f64 = score_f64 ? 1 : 0; g.t32 = thresh_to_f32(thresh);
+    g.otracks = d_tracks_out; g.oscore = d_score_out; g.osrc = d_src_out; g.ocnt = d_cnt_out; g.ontracks = d_ntracks_out;
+    g.status = &c->d_cnt->status;
+    // the LDS of a wave follows the call's own top_still + T; as many waves per workgroup (4, 2, 1) as 64 KiB hold
+    int waves = 4;
+    while (waves > 1 && (size_t)waves * g.nmax * kTnBytesPerCand > 65536) waves >>= 1;
+    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)((C * Fmax + waves - 1) / waves), (unsigned)V);
+        hipLaunchKernelGGL(tracknms_kernel, grid, dim3(64 * waves), (size_t)waves * g.nmax * kTnBytesPerCand, c->stream, g);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks, const void *d_score,
+                    int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores, int64_t B,
+                    const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R,
+                    float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out, int32_t *d_ntracks_out)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B, d_keep_idx,
+                                 d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
+                                 d_ntracks_out);
 }
 
 }  // extern "C"

@@ -1172,6 +1172,186 @@ def merge_tracks_batch(batch_a, batch_b, scheme='combine', sync=True, ctx=None):
     return out
 
 
+_TN_MAX = 1024         # include/vdet_hip.h: top_still + T and R per (frame, class) list; the evaluator's tracks-per-list limit
+
+
+def _tn_still(still, Ft, C, T, top_still):
+    """The still-image source of nms_tracks, checked: ((boxes, scores, keep_idx, keep_cnt) or None, B, keep capacity, top_still)."""
+    if still is None:
+        if top_still not in (None, 0):
+            raise ValueError("top_still needs the still-image source (still=(boxes, scores, keep_idx, keep_cnt))")
+        return None, 0, 0, 0
+    if not isinstance(still, (tuple, list)) or len(still) != 4 or not all(torch.is_tensor(x) for x in still):
+        raise ValueError("still must be (boxes, scores, keep_idx, keep_cnt)")
+    boxes, scores, keep_idx, keep_cnt = still
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if boxes.dim() != 3 or tuple(boxes.shape[::2]) != (Ft, 4) or boxes.shape[1] < 1:
+        raise ValueError("still: boxes must be float32 [F,B,4] over the frames of the tubelets (F = %d)" % Ft)
+    B = boxes.shape[1]
+    if B > 32767:
+        raise ValueError("B = %d boxes per frame; the limit is 32767" % B)
+    if tuple(scores.shape) != (Ft, B, C):
+        raise ValueError("still: scores must be float32 [F,B,C] (layout 'FBC' only)")
+    if keep_idx.dtype != torch.int32 or keep_idx.dim() != 3 or tuple(keep_idx.shape[:2]) != (Ft, C) or keep_idx.shape[2] < 1:
+        raise ValueError("still: keep_idx must be int32 [F,C,cap]")
+    if keep_cnt.dtype != torch.int32 or tuple(keep_cnt.shape) != (Ft, C):
+        raise ValueError("still: keep_cnt must be int32 [F,C]")
+    kcap = keep_idx.shape[2]
+    if top_still is None:
+        top_still = max(min(kcap, _TN_MAX - T), 0)
+    top_still = int(top_still)
+    if top_still < 0:
+        raise ValueError("top_still must not be negative")
+    return (boxes, scores, keep_idx, keep_cnt), B, kcap, top_still
+
+
+def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync):
+    """Allocate the outputs (flat, batch layout) and enqueue the one launch; every tensor contiguous and on one device."""
+    V, Ft = len(off) - 1, int(off[-1])
+    dev = ntracks.device
+    N = C * R * Ft
+    otracks = torch.empty((N * 5,), dtype=torch.float32, device=dev)
+    oscore = torch.empty((N,), dtype=torch.float64, device=dev)
+    osrc = torch.empty((N,), dtype=torch.int32, device=dev)
+    ocnt = torch.empty((C, Ft), dtype=torch.int32, device=dev)
+    ont = torch.empty((V, C), dtype=torch.int32, device=dev)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    sp = [ptr(x) for x in still] if still is not None and top_still > 0 else [None] * 4
+    tail = (C, T, ptr(tracks), ntracks.data_ptr(), ptr(score), int(score.dtype == torch.float64), ptr(tboxes), sp[0], sp[1], B, sp[2],
+            sp[3], kcap, top_still if still is not None else 0, float(thresh), R, otracks.data_ptr(), oscore.data_ptr(),
+            osrc.data_ptr(), ocnt.data_ptr(), ont.data_ptr())
+    if V == 1:
+        ctx.check(ctx.lib.vdet_nms_tracks(ctx.h, Ft, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_nms_tracks_batch(ctx.h, off.ctypes.data, V, *tail))
+    if sync:
+        ctx.sync()
+    return otracks, oscore, osrc, ocnt, ont
+
+
+def _tn_limits(C, T, Ft, top_still, cap):
+    if top_still + T > _TN_MAX:
+        raise ValueError("top_still + T = %d candidates per (frame, class); the limit is %d" % (top_still + T, _TN_MAX))
+    R = max(top_still + T, 1) if cap is None else int(cap)
+    if not 1 <= R <= _TN_MAX:
+        raise ValueError("cap = %d output rows per (frame, class); 1 .. %d" % (R, _TN_MAX))
+    if max(C * R * Ft, C * T * Ft) >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*cap*F and C*T*F must stay below 2^31 - 16)")
+    return R
+
+
+def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None, sync=True, ctx=None):
+    """Per-frame NMS of tubelet boxes together with still-image detections (``apply_vid_nms`` / ``vid_nms``, utils/nms.pyx:71-125,
+    as arrays): one list of detections per frame and class, one launch, no host wait.
+
+    tracks [C,T,F,5] f32, ntracks [C] int32, score [C,T,F] f32 / f64 (``pooled``, ``det``, a TCN output: the series that scores
+    the tubelet boxes), tboxes [C,T,F,4] f32 (the boxes to use instead of the track rows).  A ``merge_tracks`` /
+    ``interpolate_tracks`` dict goes in as ``tracks`` (then ``ntracks`` stays None, ``score`` is the index of the series,
+    default 0, or a tensor; the dict's tboxes are used unless ``tboxes`` is given).  ``still`` = (boxes [F,B,4] f32, scores
+    [F,B,C] f32, keep_idx [F,C,k] int32, keep_cnt [F,C] int32): NMS survivors as ``DetEvaluator.add_keep_lists`` takes them
+    ('FBC'); the first ``top_still`` of every list take part (default min(k, 1024 - T)).  T = 0 is the still-image source alone.
+    The rows of a list are the still-image rows, then the tubelet rows by slot; a NaN score is no row.  Result: nms of the
+    reference (f32, +1 areas, suppression iff ovr >= thresh, descending score, ties by descending row) -- semantics in full:
+    include/vdet_hip.h (vdet_nms_tracks).  ``cap``: output rows per list (default top_still + T, which cannot overflow; fewer
+    than a list keeps raises ValueError at the wait).  An evaluated zero-union pair raises ZeroDivisionError, a keep count or
+    index out of range ValueError, when the call -- or with ``sync=False`` a later ``ctx.sync()`` -- waits.
+
+    Returns a dict in the tubelet layout with the RANK as the slot axis: ``tracks`` [C,R,F,5] f32 (x1,y1,x2,y2,f32 score),
+    ``score`` [C,R,F] f64 (the source's own score), ``src`` [C,R,F] int32 (b >= 0: still-image box b; -(t+1): tubelet slot t;
+    INT32_MIN behind the count), ``cnt`` [C,F] int32, ``ntracks`` [C] int32 -- NaN behind the counts.  ``tracks`` / ``ntracks`` /
+    ``score`` feed every consumer of tubelets; ``DetEvaluator.add_detections`` takes the dict."""
+    if isinstance(tracks, dict):
+        d = tracks
+        if ntracks is not None or any(k not in d for k in ('tracks', 'ntracks')):
+            raise ValueError("a tubelet dict needs tracks and ntracks, and takes the place of both arguments")
+        if not torch.is_tensor(score):
+            ser = d.get('series')
+            ser = (ser,) if torch.is_tensor(ser) else tuple(ser or ())
+            q = 0 if score is None else score
+            if not isinstance(q, int) or not 0 <= q < len(ser):
+                raise ValueError("score must name one of the dict's %d series by index, or be a tensor" % len(ser))
+            score = ser[q]
+        tracks, ntracks, tboxes = d['tracks'], d['ntracks'], (d.get('tboxes') if tboxes is None else tboxes)
+    if not torch.is_tensor(tracks) or tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if C < 1 or F < 1:
+        raise ValueError("at least one class and one frame")
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if not torch.is_tensor(score) or score.dtype not in (torch.float32, torch.float64) or tuple(score.shape) != (C, T, F):
+        raise ValueError("score must be float32 / float64 [C,T,F]")
+    if tboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float32 or tuple(tboxes.shape) != (C, T, F, 4)):
+        raise ValueError("tboxes must be float32 [C,T,F,4]")
+    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
+    R = _tn_limits(C, T, F, top_still, cap)
+    every = [tracks, ntracks, score] + ([tboxes] if tboxes is not None else []) + list(still or ())
+    for x in every:
+        if not x.is_cuda or x.device != ntracks.device:
+            raise ValueError("every tensor must live on the same GPU (vdetlib_amd has no CPU path)")
+    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
+    tboxes = None if tboxes is None else tboxes.contiguous()
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still, B, kcap,
+                                        top_still, thresh, R, sync)
+    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt, ntracks=ont.view(C))
+
+
+def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_still=None, cap=None, use_tboxes=True, sync=True,
+                     ctx=None):
+    """``nms_tracks`` for every video of a result in ``video_batch``'s layout (``video_batch``, the anchor route's batch forms,
+    ``interpolate_tracks_batch``, ``merge_tracks_batch``) in ONE launch.  ``score`` names the per-video series of the dict that
+    scores the tubelet boxes ('pooled', 'det', ...: f32 or f64 [C,T,F_v] views); the dict's ``tboxes`` are the boxes when it has
+    them and ``use_tboxes`` holds.  ``still`` as in ``nms_tracks``, frame-major over all videos ([Ftot,...]: what ``video_batch``
+    takes and returns).  Per video the bits are ``nms_tracks``' on that video alone.  Returns ``tracks`` / ``score`` / ``src`` as
+    consecutive per-video views ([C,R,F_v,...]) of one allocation each, ``cnt`` [C,Ftot], ``ntracks`` [V,C] and ``frame_off``."""
+    if not isinstance(batch_out, dict) or any(k not in batch_out for k in ('tracks', 'ntracks', 'frame_off')):
+        raise ValueError("batch_out must be a dict in video_batch's layout with tracks, ntracks and frame_off")
+    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
+    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0):
+        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V]")
+    V, Ft = len(off) - 1, int(off[-1])
+    if V > 65535:
+        raise ValueError("at most 65535 videos in one call")
+    tv, sv = batch_out['tracks'], batch_out.get(score) if isinstance(score, str) else None
+    if not sv or len(sv) != V:
+        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
+    if len(tv) != V or tv[0].dtype != torch.float32 or tv[0].dim() != 4 or tv[0].shape[3] != 5:
+        raise ValueError("not a video_batch result")
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    bv = batch_out.get('tboxes') if use_tboxes else None
+    bv = bv if bv else None
+    for v in range(V):
+        fv = int(off[v + 1] - off[v])
+        if tuple(tv[v].shape) != (C, T, fv, 5):
+            raise ValueError("tracks[%d] must be [C,T,F_v,5]" % v)
+        if sv[v].dtype not in (torch.float32, torch.float64) or sv[v].dtype != sv[0].dtype or tuple(sv[v].shape) != (C, T, fv):
+            raise ValueError("%s[%d] must be float32 / float64 [C,T,F_v]" % (score, v))
+        if bv is not None and (len(bv) != V or bv[v].dtype != torch.float32 or tuple(bv[v].shape) != (C, T, fv, 4)):
+            raise ValueError("tboxes[%d] must be float32 [C,T,F_v,4]" % v)
+    ntracks = batch_out['ntracks']
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
+        raise ValueError("ntracks must be int32 [V,C]")
+    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
+    R = _tn_limits(C, T, Ft, top_still, cap)
+    tracks, sc = _merge_flat(tv, 5, 'batch_out'), _merge_flat(sv, 1, 'batch_out')
+    tboxes = _merge_flat(bv, 4, 'batch_out') if bv is not None else None
+    for x in [tracks, ntracks, sc] + ([tboxes] if tboxes is not None else []) + list(still or ()):
+        if not x.is_cuda or x.device != ntracks.device:
+            raise ValueError("every tensor must live on the same GPU (vdetlib_amd has no CPU path)")
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ntracks = ntracks.contiguous()
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
+
+    def views(flat, per):
+        shape = (lambda fv: (C, R, fv, per)) if per > 1 else (lambda fv: (C, R, fv))
+        return [flat[C * R * per * int(off[v]): C * R * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
+    return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 
@@ -1260,6 +1440,7 @@ class DetEvaluator(object):
       ev.add_tracks(video, tracks, ntracks, scores, boxes=None)      # track_volume / rescore_tracks outputs
       ev.add_keep_lists(video, boxes, scores, keep_idx, keep_cnt)    # nms_volume[_topk] / nms_track_volume survivors
       ev.add_batch(videos, video_batch(...))                         # all videos of a batch, one match launch
+      ev.add_detections(video, nms_tracks(...))                      # per-frame detections (or videos, nms_tracks_batch(...))
       aps, mAP = ev.compute()                                        # {class_index: AP}, float
 
     Every add appends its matched detections to a device stream of (class, score, tp); ``compute`` sorts it stably by
@@ -1425,6 +1606,43 @@ class DetEvaluator(object):
         return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks_batch(
             ctx.h, *self._gt_args(), vids.ctypes.data, off.ctypes.data, V, C, T, bx0.data_ptr(), 4, sc0.data_ptr(), 1,
             nt.data_ptr(), slots.ctypes.data, *st), C * T * Ft)
+
+    def add_detections(self, video_or_videos, out):
+        """The per-frame detections ``nms_tracks`` (``video_or_videos``: the video's name) or ``nms_tracks_batch`` (the names of
+        the batch's videos) returned: rows ``tracks[..., :4]`` scored by the f64 ``score``, rank as the slot axis.  Same stream
+        as ``add_tracks`` of those arrays video after video; returns the number of detections added."""
+        if not isinstance(out, dict) or any(k not in out for k in ('tracks', 'score', 'ntracks')):
+            raise ValueError("out must be the dict nms_tracks or nms_tracks_batch returned")
+        slots_of = lambda C: self._col_slots(C, 1)
+        if 'frame_off' not in out:
+            tr, sc, nt = out['tracks'], out['score'], out['ntracks']
+            if tr.dtype != torch.float32 or tr.dim() != 4 or tr.shape[3] != 5:
+                raise ValueError("tracks must be float32 [C,R,F,5]")
+            C, R, F = tr.shape[0], tr.shape[1], tr.shape[2]
+            if sc.dtype != torch.float64 or tuple(sc.shape) != (C, R, F) or nt.dtype != torch.int32 or tuple(nt.shape) != (C,):
+                raise ValueError("score must be float64 [C,R,F], ntracks int32 [C]")
+            self._check(tr, sc, nt)
+            tr, sc, nt = tr.contiguous(), sc.contiguous(), nt.contiguous()
+            slots, vid = slots_of(C), self._vidx.get(video_or_videos, -1)
+            return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks(
+                ctx.h, *self._gt_args(), vid, F, C, R, tr.data_ptr(), 5, sc.data_ptr(), 1, nt.data_ptr(), slots.ctypes.data, *st),
+                C * R * F)
+        off = np.ascontiguousarray(out['frame_off'], dtype=np.int64)
+        V, Ft = len(off) - 1, int(off[-1])
+        if isinstance(video_or_videos, str) or len(video_or_videos) != V:
+            raise ValueError("one name per video of the batch")
+        tr0, nt = out['tracks'][0], out['ntracks']
+        C, R = tr0.shape[0], tr0.shape[1]
+        if nt.dtype != torch.int32 or tuple(nt.shape) != (V, C) or out['score'][0].dtype != torch.float64:
+            raise ValueError("not an nms_tracks_batch result")
+        tr, sc = _batch_flat(out['tracks'], 5), _batch_flat(out['score'], 1)
+        self._check(tr, sc, nt)
+        nt = nt.contiguous()
+        vids = np.array([self._vidx.get(v, -1) for v in video_or_videos], dtype=np.int32)
+        slots = slots_of(C)
+        return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks_batch(
+            ctx.h, *self._gt_args(), vids.ctypes.data, off.ctypes.data, V, C, R, tr.data_ptr(), 5, sc.data_ptr(), 1,
+            nt.data_ptr(), slots.ctypes.data, *st), C * R * Ft)
 
     def stream(self, raw=False):
         """The stream so far: (class_index int64, score f64, tp bool) device tensors (raw: class slot int32, tp uint8)."""
