@@ -74,6 +74,9 @@
  *   device tubelet NMS: rows per list      top_still + T <= 1024, 1 <= R <= 1024 (the evaluator's tracks-per-(frame, class) limit),
  *                                          C*R*F and C*T*F < 2^31 - 16, B <= 32767, V <= 65535      VDET_EINVAL; one path for
  *                                                                     every size: a wave's LDS follows the call's top_still + T
+ *   device tubelet re-scoring              B <= 32767, F*B and C*T*F < 2^31 - 16, V <= 65535, window odd      VDET_EINVAL; videos
+ *                                                                     of more than 1536 frames re-score their series one thread
+ *                                                                     per series (slower, same results)
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -812,6 +815,56 @@ int vdet_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, 
                           const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
                           int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
                           int32_t *d_cnt_out, int32_t *d_ntracks_out);
+
+/* ---- device re-scoring of ANY tubelet set against the detections -----------------------------------------------------------
+ *
+ * raw_dets_spatial_max_pooling (vdet/tubelet_cls.py:493-535), then do_score_completion (:284-303), then
+ * score_proto_temporal_maxpool (:386-414) for tubelets of any origin -- caller-supplied, anchor-route, merged, interpolated --
+ * and, with a FLOOR, the part of rcnn_sampling_dets_scoring (:221-259) that follows the CNN.  vdet_rescore_tracks and
+ * vdet_video_batch keep their own kernels, which assume the greedy tracker's contiguous tubelets; this entry point treats a
+ * tubelet as the reference does, as the LIST of its boxes.
+ *
+ * Layout (vdet_video_batch's): video v's [C,T,F_v,5] tracks start at element C*T*5*h_frame_off[v] of one flat buffer;
+ * d_ntracks [V,C], d_boxes [F,B,4], d_scores [F,B,C] over all frames.  d_floor, d_det, d_pooled, d_src are [C,T,F_v] per video at
+ * C*T*h_frame_off[v], d_tboxes [C,T,F_v,4].  d_floor may be NULL; it is f64 when floor_f64, else f32.
+ *
+ * A tubelet box is PRESENT when t < d_ntracks[v,c] and the row's x1 is not NaN.  Everything else gets NaN in det, pooled and
+ * tboxes and -1 in src.
+ *
+ * Spatial step, per present box.  Candidates: the detections j of the same frame with f64 iou(row, box_j) > overlap_thres
+ * (strict; the f32 values widened to f64; utils/common.py:451-468).  best = numpy's argmax of their class scores: the first
+ * maximum, a NaN counts as the maximum.
+ *   no floor:  a hit gives det = score, tbox = the detection's box, src = j; a miss det = -1e5, tbox = the row's box, src = -1.
+ *   floor:     det = best, tbox = the detection's box, src = j only when there is a hit and best > floor in f64 (false for any
+ *              NaN); else det = floor, tbox = the row's box, src = -1.
+ *
+ * Series step, per tubelet, over its present boxes in frame order addressed by ORDINAL (position in that list), not by frame:
+ * a hole inside a tubelet is no list element.  With `complete`, runs of det <= -10 are filled -- from the first / last valid
+ * value at the ends, inside by l + (r-l)*(k-i+1)/(j-i+1) on ordinals; a NaN is neither missing nor filled.  A tubelet without
+ * any valid value latches VDET_EINDEX (reported by vdet_sync), its det keeps the sentinels and its pooled stays NaN.  Then the
+ * centred max-pool of `window` (odd; 1: a copy) over ordinals, -1e5 outside the list, writes d_pooled: starting from the
+ * centre, a neighbour replaces the running value when it compares greater, so a NaN centre stays and a NaN neighbour is
+ * skipped.  With complete, the filled values are also written to d_det.
+ *
+ * On tubelets without holes, no floor and complete = 1, det / pooled / tboxes are bit for bit vdet_rescore_tracks' and
+ * vdet_video_batch's.  Per video the bits of the batch are those of the single call on that video alone.
+ *
+ * Host side: the regular-frame flags and the x-sorted index over the concatenated volume are those of the graph build of the
+ * same boxes when the cache holds them, else rebuilt (the cached graph and lists are then dropped), exactly as
+ * vdet_rescore_tracks does; VDET_NO_INDEX / VDET_FORCE_GENERAL scan whole frames instead, same results.  More than one video
+ * reads the per-video table of the anchor route's batch forms, staged keyed by the offsets.  Three launches (two without a
+ * video of more than 1536 frames), no host wait in asynchronous mode, inputs never modified.  The series stage keeps 11 bytes of
+ * LDS per frame of the call's longest video up to 1536 frames; longer videos take a one-thread-per-series kernel.  d_boxes must
+ * be 16-byte aligned.  T = 0 writes nothing.  Limits: the table at the top of this file.
+ */
+int vdet_rescore_tubelets(vdet_ctx *ctx, int64_t F, int64_t B, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                          const float *d_boxes, const float *d_scores, const void *d_floor, int floor_f64, double overlap_thres,
+                          int complete, int window, double *d_det, double *d_pooled, float *d_tboxes, int32_t *d_src);
+
+int vdet_rescore_tubelets_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t B, int64_t C, int T,
+                                const float *d_tracks, const int32_t *d_ntracks, const float *d_boxes, const float *d_scores,
+                                const void *d_floor, int floor_f64, double overlap_thres, int complete, int window, double *d_det,
+                                double *d_pooled, float *d_tboxes, int32_t *d_src);
 
 #ifdef __cplusplus
 }

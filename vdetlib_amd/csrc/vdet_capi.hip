@@ -35,6 +35,7 @@
 #include "topanchor_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "tracknms_kernels.hpp"
+#include "rescore_kernels.hpp"
 
 using namespace vdet;
 
@@ -3654,6 +3655,85 @@ int vdet_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tra
     return vdet_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B, d_keep_idx,
                                  d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
                                  d_ntracks_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Re-scoring of any tubelet set against the detections (rescore_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_rescore_tubelets_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t B, int64_t C, int T, const float *d_tracks,
+                                const int32_t *d_ntracks, const float *d_boxes, const float *d_scores, const void *d_floor,
+                                int floor_f64, double overlap_thres, int complete, int window, double *d_det, double *d_pooled,
+                                float *d_tboxes, int32_t *d_src)
+{
+    if (!c) return VDET_EINVAL;
+    if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (window < 1 || window % 2 != 1) return fail(c, VDET_EINVAL, "Window size must be odd!");
+    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    if (F * B > 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || V * C >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31 - 16)");
+    if (T == 0) return VDET_OK;
+    if (!d_tracks || !d_ntracks || !d_boxes || !d_scores || !d_det || !d_pooled || !d_tboxes || !d_src) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    RescoreArgs g{};
+    if (!c->no_index && !c->force_general && (size_t)8 * B + 24 * 1024 <= c->max_lds) {   // (the x1 sort must fit the LDS)
+        // per-frame regular flags + x-sorted index over the concatenated volume: those of the graph build of the same boxes
+        // when the cache holds them, else rebuilt here (as vdet_rescore_tracks does)
+        if (!index_matches(c, d_boxes, F, B)) {
+            c->graph_valid = c->lists_valid = c->index_valid = false;       // gflags / the index are rewritten
+            if ((rc = volume_groups(c, F, B))) return rc;
+            HIPCHK(c, c->gflags.reserve((size_t)F * 4));
+            c->sym_built = false;
+            hipLaunchKernelGGL(frame_flags_kernel, dim3((unsigned)F), dim3(256), 0, c->stream,
+                               reinterpret_cast<const float4 *>(d_boxes), c->groups.as<GroupDesc>(), c->gflags.as<uint32_t>(),
+                               &c->d_cnt->irregular);
+            if ((rc = build_frame_index(c, reinterpret_cast<const float4 *>(d_boxes), F * B, F, (int)B))) return rc;
+        }
+        g.ix = frame_index_of(c);
+        g.group_flags = c->gflags.as<uint32_t>();
+    }
+    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_merge_tracks_batch)
+        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+        g.vids = c->anchor_tab.dev.as<VidDesc>();
+    }
+    g.tracks = d_tracks; g.ntracks = d_ntracks; g.boxes = reinterpret_cast<const float4 *>(d_boxes); g.scores = d_scores;
+    g.floor = d_floor; g.floor_f64 = floor_f64 ? 1 : 0;
+    g.F = (int)F; g.B = (int)B; g.C = (int)C; g.T = T;
+    g.thres = overlap_thres; g.complete = complete ? 1 : 0; g.window = window;
+    g.det = d_det; g.pooled = d_pooled; g.tboxes = d_tboxes; g.src = d_src;
+    g.err = &c->d_cnt->eindex;
+    {
+        StageTimer tm(c, ST_RSPATIAL);
+        hipLaunchKernelGGL(rescore_tubelets_spatial_kernel, dim3((unsigned)((Fmax * C * T + 3) / 4), (unsigned)V), dim3(256), 0, c->stream, g);
+    }
+    {
+        StageTimer tm(c, ST_RSERIES);
+        // one wave per series with its present boxes in LDS, sized from the call's longest video; as many waves per workgroup
+        // (4, 2, 1) as 64 KiB hold.  Videos too long for the stage take the one-thread-per-series kernel
+        const int cap = (int)std::min<int64_t>(Fmax, kRescoreWaveMaxF);
+        const int stride = (int)(((size_t)cap * kRescoreBytesPerFrame + 15) & ~(size_t)15);
+        int waves = 4;
+        while (waves > 1 && (size_t)waves * stride > 65536) waves >>= 1;
+        hipLaunchKernelGGL(rescore_tubelets_series_kernel, dim3((unsigned)((C * T + waves - 1) / waves), (unsigned)V), dim3(64 * waves),
+                           (size_t)waves * stride, c->stream, g, stride, cap);
+        if (Fmax > cap)
+            hipLaunchKernelGGL(rescore_tubelets_series_long_kernel, dim3((unsigned)((C * T + 63) / 64), (unsigned)V), dim3(64), 0, c->stream, g, cap);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_rescore_tubelets(vdet_ctx *c, int64_t F, int64_t B, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                          const float *d_boxes, const float *d_scores, const void *d_floor, int floor_f64, double overlap_thres,
+                          int complete, int window, double *d_det, double *d_pooled, float *d_tboxes, int32_t *d_src)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_rescore_tubelets_batch(c, off, 1, B, C, T, d_tracks, d_ntracks, d_boxes, d_scores, d_floor, floor_f64, overlap_thres,
+                                       complete, window, d_det, d_pooled, d_tboxes, d_src);
 }
 
 }  // extern "C"

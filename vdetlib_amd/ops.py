@@ -1352,6 +1352,150 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
 
 
+def _rt_call(ctx, off, B, C, T, tracks, ntracks, boxes, scores, floor, overlap_thres, complete, window, sync):
+    """The one call behind rescore_tubelets / rescore_tubelets_batch: flat tensors in, flat outputs back."""
+    V, Ft = len(off) - 1, int(off[-1])
+    if B > 32767:
+        raise ValueError("B = %d boxes per frame; the limit is 32767" % B)
+    if V > 65535:
+        raise ValueError("at most 65535 videos in one call")
+    if Ft * B > 0x7FFFFFF0 or C * max(T, 1) * Ft >= 0x7FFFFFF0:
+        raise ValueError("volume too large (F*B and C*T*F must stay below 2^31 - 16)")
+    dev = boxes.device
+    n = C * T * Ft
+    det = torch.empty((n,), dtype=torch.float64, device=dev)
+    pooled = torch.empty((n,), dtype=torch.float64, device=dev)
+    tboxes = torch.empty((n * 4,), dtype=torch.float32, device=dev)
+    src = torch.empty((n,), dtype=torch.int32, device=dev)
+    complete = floor is None if complete is None else bool(complete)
+    tail = (B, C, T, tracks.data_ptr(), ntracks.data_ptr(), boxes.data_ptr(), scores.data_ptr(),
+            floor.data_ptr() if floor is not None else None, int(floor is not None and floor.dtype == torch.float64),
+            float(overlap_thres), int(complete), int(window), det.data_ptr(), pooled.data_ptr(), tboxes.data_ptr(), src.data_ptr())
+    if V == 1:
+        ctx.check(ctx.lib.vdet_rescore_tubelets(ctx.h, Ft, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_rescore_tubelets_batch(ctx.h, off.ctypes.data, V, *tail))
+    if sync:
+        ctx.sync()
+    return det, pooled, tboxes, src
+
+
+def rescore_tubelets(tracks, ntracks, boxes, scores, floor=None, overlap_thres=0.7, window=3, complete=None, sync=True, ctx=None):
+    """Re-score ANY tubelet set against the detections (include/vdet_hip.h: vdet_rescore_tubelets): ``rescore_tracks``' three
+    steps -- spatial max-pooling (raw_dets_spatial_max_pooling, vdet/tubelet_cls.py:493-535), gap completion (:284-303),
+    temporal max-pooling (:386-414) -- with a tubelet taken as the LIST of its boxes, as the reference takes it: holes (NaN
+    rows) inside a tubelet are no list elements, so completion and the pool work on ordinals.  ``rescore_tracks`` is for
+    ``track_volume``'s own contiguous tubelets; on those the two agree bit for bit.
+
+    tracks [C,T,F,5] f32, ntracks [C] int32, boxes [F,B,4] / scores [F,B,C] f32.  ``floor`` [C,T,F] f32 or f64: a box's own
+    score, kept unless an overlapping detection scores strictly higher (the half of rcnn_sampling_dets_scoring, :221-259, that
+    follows the CNN); without it a miss scores -1e5.  ``complete``: run the gap completion (default: only without a floor).
+    Returns (det f64 [C,T,F], pooled f64 [C,T,F], tboxes f32 [C,T,F,4], src int32 [C,T,F]: the winning detection or -1);
+    NaN / -1 where there is no box.  IndexError for a tubelet whose every box misses under completion (at the call, or at a
+    later ``ctx.sync()`` with ``sync=False``)."""
+    if window % 2 != 1:
+        raise ValueError('Window size must be odd!')
+    if tracks.dtype != torch.float32 or boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if ntracks.dtype != torch.int32:
+        raise ValueError("ntracks must be int32")
+    if floor is not None and floor.dtype not in (torch.float32, torch.float64):
+        raise ValueError("floor must be float32 or float64")
+    if tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4]")
+    B = boxes.shape[1]
+    if F < 1 or B < 1 or C < 1:
+        raise ValueError("at least one frame, one box per frame and one class")
+    if tuple(scores.shape) != (F, B, C):
+        raise ValueError("scores must be [F,B,C]")
+    if tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be [C]")
+    if floor is not None and tuple(floor.shape) != (C, T, F):
+        raise ValueError("floor must be [C,T,F]")
+    for t in (tracks, ntracks, scores) + (() if floor is None else (floor,)):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("tracks, ntracks, boxes, scores and floor must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    off = np.array([0, F], dtype=np.int64)
+    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks.contiguous(), ntracks.contiguous(), boxes.contiguous(),
+                                        scores.contiguous(), None if floor is None else floor.contiguous(), overlap_thres,
+                                        complete, window, sync)
+    return det.view(C, T, F), pooled.view(C, T, F), tboxes.view(C, T, F, 4), src.view(C, T, F)
+
+
+def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0.7, window=3, complete=None, sync=True, ctx=None):
+    """``rescore_tubelets`` for every video of ANY dict in ``video_batch``'s layout (``video_batch``,
+    ``track_from_anchors_batch``, ``merge_tracks_batch``, ``interpolate_tracks_batch``) in one call; boxes [F,B,4] / scores
+    [F,B,C] f32 are the batch's volume.  ``floor``: a list of per-video [C,T,F_v] views or one flat tensor in the batch layout,
+    f32 or f64.  Per video the bits are ``rescore_tubelets``' on that video alone.  Returns a NEW dict in the same layout --
+    the input's ``tracks``, ``anchors``, ``ntracks`` and ``frame_off`` carried over, ``det`` / ``pooled`` / ``tboxes`` / ``src``
+    as consecutive per-video views of one allocation each -- which ``tcn_tracks_batch``, ``merge_tracks_batch``,
+    ``nms_tracks_batch``, ``tubelets_overlap_batch`` and ``DetEvaluator.add_batch`` take as they take ``video_batch``'s.  The
+    input dict is not modified."""
+    if window % 2 != 1:
+        raise ValueError('Window size must be odd!')
+    if not isinstance(batch_out, dict) or any(k not in batch_out for k in ('tracks', 'ntracks', 'frame_off')):
+        raise ValueError("not a video_batch result: batch_out must be a dict in video_batch's layout with tracks, ntracks and frame_off")
+    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
+    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0):
+        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V]")
+    V, Ft = len(off) - 1, int(off[-1])
+    tv = batch_out['tracks']
+    if not isinstance(tv, (list, tuple)) or len(tv) != V or not all(torch.is_tensor(x) for x in tv):
+        raise ValueError("not a video_batch result: tracks must be one view per video")
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or tv[0].dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if tv[0].dim() != 4 or tv[0].shape[3] != 5:
+        raise ValueError("not a video_batch result: tracks[v] must be [C,T,F_v,5]")
+    C, T = tv[0].shape[0], tv[0].shape[1]
+    for v in range(V):
+        if tuple(tv[v].shape) != (C, T, int(off[v + 1] - off[v]), 5):
+            raise ValueError("not a video_batch result: tracks[%d] must be [C,T,F_v,5]" % v)
+    if boxes.dim() != 3 or boxes.shape[0] != Ft or boxes.shape[2] != 4:
+        raise ValueError("boxes must be [F,B,4] over all frames of the batch")
+    B = boxes.shape[1]
+    if B < 1 or C < 1:
+        raise ValueError("at least one box per frame and one class")
+    if tuple(scores.shape) != (Ft, B, C):
+        raise ValueError("scores must be [F,B,C]")
+    ntracks = batch_out['ntracks']
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
+        raise ValueError("not a video_batch result: ntracks must be int32 [V,C]")
+    tracks = _merge_flat(tv, 5, 'batch_out')
+    if floor is not None:
+        if isinstance(floor, (list, tuple)):
+            if len(floor) != V or any(not torch.is_tensor(x) or tuple(x.shape) != (C, T, int(off[v + 1] - off[v])) or
+                                      x.dtype != floor[0].dtype for v, x in enumerate(floor)):
+                raise ValueError("floor must be one [C,T,F_v] view per video, all of one dtype")
+            try:
+                floor = _merge_flat(floor, 1, 'floor')
+            except ValueError:       # separate per-video tensors: gathered into the batch layout
+                floor = torch.cat([x.reshape(-1) for x in floor])
+        if not torch.is_tensor(floor) or floor.numel() != C * T * Ft:
+            raise ValueError("floor must hold C*T*F elements in the batch layout")
+        if floor.dtype not in (torch.float32, torch.float64):
+            raise ValueError("floor must be float32 or float64")
+        floor = floor.contiguous()
+    for t in (tracks, ntracks, scores) + (() if floor is None else (floor,)):
+        if not t.is_cuda or t.device != boxes.device:
+            raise ValueError("the batch result, boxes, scores and floor must live on the same GPU")
+    ctx = _ctx_for(boxes, ctx)
+    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks, ntracks.contiguous(), boxes.contiguous(), scores.contiguous(),
+                                        floor, overlap_thres, complete, window, sync)
+
+    def views(flat, per):
+        shape = (lambda fv: (C, T, fv, per)) if per > 1 else (lambda fv: (C, T, fv))
+        return [flat[C * T * per * int(off[v]): C * T * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
+    out = dict(tracks=list(tv), ntracks=ntracks, frame_off=off, det=views(det, 1), pooled=views(pooled, 1), tboxes=views(tboxes, 4),
+               src=views(src, 1))
+    if 'anchors' in batch_out:
+        out['anchors'] = batch_out['anchors']
+    return out
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 
