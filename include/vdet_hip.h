@@ -77,6 +77,10 @@
  *   device tubelet re-scoring              B <= 32767, F*B and C*T*F < 2^31 - 16, V <= 65535, window odd      VDET_EINVAL; videos
  *                                                                     of more than 1536 frames re-score their series one thread
  *                                                                     per series (slower, same results)
+ *   device R-CNN windows                   1 <= crop_size S <= 1024, S - 2*padding >= 1, H, W <= 32767, num <= 255 sampled boxes
+ *                                          per box, windows < 2^31 - 16, C*T*F < 2^31 - 16      VDET_EINVAL; more present tubelet
+ *                                                                     boxes than cap: VDET_ECAP latched (vdet_sync), the count
+ *                                                                     still written.  One path for every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -865,6 +869,72 @@ int vdet_rescore_tubelets_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64
                                 const float *d_tracks, const int32_t *d_ntracks, const float *d_boxes, const float *d_scores,
                                 const void *d_floor, int floor_f64, double overlap_thres, int complete, int window, double *d_det,
                                 double *d_pooled, float *d_tboxes, int32_t *d_src);
+
+/* ---- R-CNN windows on the device: the patches the CNN scorers read ----------------------------------------------------------
+ *
+ * rcnn_img_crop + im_transform (utils/common.py:208-280) for every box of a call in one launch: what googlenet_features
+ * (vdet/image_det.py:75-106) does one box at a time on the host in front of rcnn_scoring, rcnn_sampling_scoring and
+ * rcnn_sampling_dets_scoring (vdet/tubelet_cls.py:102-260).  The net itself is the caller's.  All pointers are DEVICE pointers.
+ *
+ * d_images [Fi,H,W,3] uint8, channel order as stored (cv2.imread gives BGR and the reference never swaps it).  A box is
+ * (x1,y1,x2,y2), 1-based inclusive, f64 when boxes_f64 else f32 (widened to f64 first).  Everything up to the final cast is
+ * f64, one operation per product and sum (no fused multiply-add).
+ *
+ * Geometry per window (S = crop_size), rcnn_img_crop line for line.  bbox = box - 1.  If padding > 0 or mode is
+ * VDET_PATCH_SQUARE: scale = S / (S - 2*padding); half sizes (x2-x1+1)/2, (y2-y1+1)/2; centre = corner + half size; 'square'
+ * sets both half sizes to the larger; the four corners centre -+ half*scale are rounded with Python 2's round (half AWAY from
+ * zero, C round()); unclipped_w/h = x2-x1+1 / y2-y1+1; pad_x1 = max(0,-x1), pad_y1 = max(0,-y1); the corners are clipped to
+ * [0, W-1] x [0, H-1]; clipped_w/h likewise; scale_x = S/unclipped_w, scale_y = S/unclipped_h; crop_w = int(round(clipped_w *
+ * scale_x)), crop_h alike, pad_w = int(round(pad_x1*scale_x)), pad_h alike; if pad_h + crop_h > S then crop_h = S - pad_h, the
+ * same for the width.  Otherwise (VDET_PATCH_WARP with padding 0) the corners are truncated towards zero, crop_w = crop_h = S
+ * and the pads are 0.
+ *
+ * Resize of the clipped window (src_w x src_h) to crop_w x crop_h, bilinear, OpenCV's generic INTER_LINEAR path for 64-bit
+ * input as this project fixes it: per destination column fx = (float)((dx + 0.5) * (src_w / (double)crop_w) - 0.5), sx =
+ * floor(fx), fx -= sx in f32; sx < 0 -> sx = 0, fx = 0; sx >= src_w - 1 -> sx = src_w - 1, fx = 0; weights a0 = 1.f - fx and
+ * a1 = fx in f32, widened; rows likewise (b0, b1).  value = (S[y0][sx]*a0 + S[y0][sx+1]*a1)*b0 + (S[y1][sx]*a0 + S[y1][sx+1]*a1)
+ * *b1.  Parity of this rule with cv2.resize is UNPINNED (no OpenCV where the goldens are made); the device is bit for bit the
+ * numpy statement of the rule in tests/patch_spec.py.
+ *
+ * Output: d_patches [M,3,S,S] in out_dtype; element [ch][pad_h + y][pad_w + x] = (float)(value - d_mean[ch]) (d_mean [3] f64
+ * or NULL: (float)value), every other element 0.  VDET_PATCH_F16 / VDET_PATCH_BF16 round that f32 once, to nearest even.
+ * d_patches must be 16-byte aligned.
+ *
+ * Status: d_ok [M] uint8, 1 for a patch the reference would have produced.  0 -- the patch is all zeros and no pixel is read --
+ * when a coordinate (or a padded corner) is NaN or infinite, unclipped_w/h < 1, clipped_w/h < 1, crop_w/h < 1, the image index
+ * is outside 0..Fi-1, or a VDET_PATCH_WARP window with padding 0 does not lie inside the image with x1 <= x2 and y1 <= y2 (the
+ * reference raises inside cv2.resize for these, or lets numpy slice a shorter / wrapped window).
+ *
+ * vdet_rcnn_patches: d_boxes [N,4]; d_image_idx [N] int32 or NULL (image 0).  d_offsets [N,num,4] f64 or NULL (num = 0) is
+ * sampling_boxes (vdet/tubelet_cls.py:136-142, return_orig) with the caller's draw: M = N*(num+1), window (n,0) is box n,
+ * window (n,1+j) is box + d_offsets[n,j]*[w,h,w,h] with w = x2-x1, h = y2-y1 (no +1), in f64; d_sboxes [N,num+1,4] f64 or NULL
+ * receives the boxes used.
+ *
+ * vdet_tubelet_patches: d_tracks [C,T,F,ld] (ld >= 4 elements per row: tracks, tboxes), d_ntracks [C]; frames f0 <= f < f1,
+ * d_images holds Fi = f1 - f0 frames, image f - f0 is frame f.  A slot is PRESENT when t < d_ntracks[c] and column 0 of its row
+ * is not NaN.  The present slots get their ordinal in the order ((f-f0)*C + c)*T + t -- frames outer, tubelets inner, the order
+ * of the reference's frame loop.  d_slot [cap,3] int32 rows (c,t,f), -1 behind the count; d_count [1] int32, the TRUE number of
+ * present slots even beyond cap, in which case VDET_ECAP is latched (vdet_sync) and the first cap windows are valid.  Window i
+ * of d_patches [cap,3,S,S] / d_ok [cap] is slot i's box; behind the count zeros / 0.
+ *
+ * One launch (two for the tubelet form), on the context's stream, no host wait, inputs never modified; timed under "other".
+ * ctx NULL: VDET_EINVAL, nothing touched.  Limits: 1 <= S <= 1024, S - 2*padding >= 1, H, W <= 32767, num <= 255 (the table at
+ * the top of this file).
+ */
+#define VDET_PATCH_WARP 0
+#define VDET_PATCH_SQUARE 1
+#define VDET_PATCH_F32 0
+#define VDET_PATCH_F16 1
+#define VDET_PATCH_BF16 2
+
+int vdet_rcnn_patches(vdet_ctx *ctx, const uint8_t *d_images, int64_t Fi, int64_t H, int64_t W, const void *d_boxes, int boxes_f64,
+                      int64_t N, const int32_t *d_image_idx, const double *d_offsets, int num, const double *d_mean, int S,
+                      int padding, int mode, int out_dtype, void *d_patches, uint8_t *d_ok, double *d_sboxes);
+
+int vdet_tubelet_patches(vdet_ctx *ctx, const uint8_t *d_images, int64_t Fi, int64_t H, int64_t W, const void *d_tracks,
+                         int tracks_f64, int64_t C, int T, int64_t F, int ld, const int32_t *d_ntracks, int64_t f0, int64_t f1,
+                         int64_t cap, const double *d_mean, int S, int padding, int mode, int out_dtype, void *d_patches,
+                         uint8_t *d_ok, int32_t *d_slot, int32_t *d_count);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,9 @@ SYMBOLS = {
     "vdet_rescore_tubelets": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp, _vp, _vp]),
     "vdet_rescore_tubelets_batch": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp, _vp,
                                           _vp]),
+    "vdet_rcnn_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "vdet_tubelet_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _ci, _i64, _ci, _vp, _i64, _i64, _i64, _vp, _ci, _ci,
+                                   _ci, _ci, _vp, _vp, _vp, _vp]),
 }
 
 

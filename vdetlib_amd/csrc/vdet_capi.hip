@@ -36,6 +36,7 @@
 #include "merge_kernels.hpp"
 #include "tracknms_kernels.hpp"
 #include "rescore_kernels.hpp"
+#include "patch_kernels.hpp"
 
 using namespace vdet;
 
@@ -344,6 +345,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
+    if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -3734,6 +3736,111 @@ int vdet_rescore_tubelets(vdet_ctx *c, int64_t F, int64_t B, int64_t C, int T, c
     const int64_t off[2] = {0, F};
     return vdet_rescore_tubelets_batch(c, off, 1, B, C, T, d_tracks, d_ntracks, d_boxes, d_scores, d_floor, floor_f64, overlap_thres,
                                        complete, window, d_det, d_pooled, d_tboxes, d_src);
+}
+
+// ---------------------------------------------------------------------------------------------
+// R-CNN windows for the CNN scorers (patch_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+int patch_check(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64_t H, int64_t W, int S, int padding, int mode, int out_dtype,
+                int64_t M, const void *d_patches)
+{
+    if (S < 1 || S > kPatchMaxS) return fail(c, VDET_EINVAL, "crop_size = %d; 1 .. %d", S, kPatchMaxS);
+    if (padding < 0 || S - 2 * padding < 1) return fail(c, VDET_EINVAL, "padding = %d; 0 <= padding and crop_size - 2*padding >= 1", padding);
+    if (mode != VDET_PATCH_WARP && mode != VDET_PATCH_SQUARE) return fail(c, VDET_EINVAL, "mode must be VDET_PATCH_WARP or VDET_PATCH_SQUARE");
+    if (out_dtype != VDET_PATCH_F32 && out_dtype != VDET_PATCH_F16 && out_dtype != VDET_PATCH_BF16)
+        return fail(c, VDET_EINVAL, "out_dtype must be VDET_PATCH_F32, VDET_PATCH_F16 or VDET_PATCH_BF16");
+    if (Fi < 1 || H < 1 || W < 1 || H > kPatchMaxHW || W > kPatchMaxHW || Fi > 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "images must be [Fi,H,W,3] with Fi >= 1 and 1 <= H, W <= %d", kPatchMaxHW);
+    if (M < 0 || M >= 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many windows (below 2^31 - 16)");
+    if (M && (!d_images || !d_patches)) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_patches & 15) != 0) return fail(c, VDET_EINVAL, "d_patches must be 16-byte aligned");
+    return VDET_OK;
+}
+
+template <typename OutT> void patch_launch_t(vdet_ctx *c, const PatchArgs &g, int vec, unsigned blocks)
+{
+    if (vec == 8) hipLaunchKernelGGL((rcnn_patches_kernel<OutT, 8>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else if (vec == 4) hipLaunchKernelGGL((rcnn_patches_kernel<OutT, 4>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else hipLaunchKernelGGL((rcnn_patches_kernel<OutT, 1>), dim3(blocks), dim3(256), 0, c->stream, g);
+}
+
+// one wave per (window, strip of kPatchRows rows), four per workgroup, on a 1-D grid
+int patch_launch(vdet_ctx *c, PatchArgs &g, int out_dtype)
+{
+    if (g.M == 0) return VDET_OK;
+    g.nstrips = (g.S + kPatchRows - 1) / kPatchRows;
+    const int64_t blocks = (g.M * g.nstrips + 3) / 4;
+    if (blocks > 0x7FFFFFFFll) return fail(c, VDET_EINVAL, "too many windows for one launch (windows * ceil(crop_size / %d) must stay below 2^33)", kPatchRows);
+    const int vec16 = g.S % 8 == 0 ? 8 : g.S % 4 == 0 ? 4 : 1, vec32 = g.S % 4 == 0 ? 4 : 1;
+    StageTimer tm(c, ST_OTHER);
+    if (out_dtype == VDET_PATCH_F32) patch_launch_t<float>(c, g, vec32, (unsigned)blocks);
+    else if (out_dtype == VDET_PATCH_F16) patch_launch_t<_Float16>(c, g, vec16, (unsigned)blocks);
+    else patch_launch_t<PatchBf16>(c, g, vec16, (unsigned)blocks);
+    return VDET_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int vdet_rcnn_patches(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64_t H, int64_t W, const void *d_boxes, int boxes_f64,
+                      int64_t N, const int32_t *d_image_idx, const double *d_offsets, int num, const double *d_mean, int S,
+                      int padding, int mode, int out_dtype, void *d_patches, uint8_t *d_ok, double *d_sboxes)
+{
+    if (!c) return VDET_EINVAL;
+    if (N < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (num < 0 || num > kPatchMaxNum) return fail(c, VDET_EINVAL, "num = %d sampled boxes per box; 0 .. %d", num, kPatchMaxNum);
+    if (!d_offsets) num = 0;
+    const int64_t M = N * (num + 1);
+    int rc = patch_check(c, d_images, Fi, H, W, S, padding, mode, out_dtype, M, d_patches);
+    if (rc) return rc;
+    if (M == 0) return VDET_OK;
+    if (!d_boxes || !d_ok) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    PatchArgs g{};
+    g.images = d_images; g.Fi = (int)Fi; g.H = (int)H; g.W = (int)W;
+    g.boxes = d_boxes; g.boxes_f64 = boxes_f64 ? 1 : 0; g.ld = 4;
+    g.image_idx = d_image_idx; g.offsets = d_offsets; g.num = num;
+    g.mean = d_mean; g.S = S; g.padding = padding; g.square = mode == VDET_PATCH_SQUARE ? 1 : 0;
+    g.M = M; g.patches = d_patches; g.ok = d_ok; g.sboxes = d_sboxes;
+    if ((rc = patch_launch(c, g, out_dtype))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_tubelet_patches(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64_t H, int64_t W, const void *d_tracks, int tracks_f64,
+                         int64_t C, int T, int64_t F, int ld, const int32_t *d_ntracks, int64_t f0, int64_t f1, int64_t cap,
+                         const double *d_mean, int S, int padding, int mode, int out_dtype, void *d_patches, uint8_t *d_ok,
+                         int32_t *d_slot, int32_t *d_count)
+{
+    if (!c) return VDET_EINVAL;
+    if (C < 1 || T < 0 || F < 1 || ld < 4) return fail(c, VDET_EINVAL, "bad shape (tracks must be [C,T,F,>=4])");
+    if (f0 < 0 || f1 <= f0 || f1 > F) return fail(c, VDET_EINVAL, "frames must be a range 0 <= f0 < f1 <= F");
+    if (Fi != f1 - f0) return fail(c, VDET_EINVAL, "images must hold the f1 - f0 = %lld frames of the range", (long long)(f1 - f0));
+    if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16)");
+    if (cap < 0) return fail(c, VDET_EINVAL, "cap must not be negative");
+    int rc = patch_check(c, d_images, Fi, H, W, S, padding, mode, out_dtype, cap, d_patches);
+    if (rc) return rc;
+    if (!d_ntracks || !d_count || (T && !d_tracks) || (cap && (!d_slot || !d_ok))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(tubelet_slots_kernel, dim3(1), dim3(1024), 0, c->stream, d_tracks, tracks_f64 ? 1 : 0, ld, d_ntracks, (int)C, T,
+                           F, f0, f1, cap, d_slot, d_count, &c->d_cnt->status);
+    }
+    PatchArgs g{};
+    g.images = d_images; g.Fi = (int)Fi; g.H = (int)H; g.W = (int)W;
+    g.boxes = d_tracks; g.boxes_f64 = tracks_f64 ? 1 : 0; g.ld = ld;
+    g.slot = d_slot; g.T = T; g.F = F; g.f0 = f0;
+    g.mean = d_mean; g.S = S; g.padding = padding; g.square = mode == VDET_PATCH_SQUARE ? 1 : 0;
+    g.M = cap; g.patches = d_patches; g.ok = d_ok;
+    if ((rc = patch_launch(c, g, out_dtype))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
 }
 
 }  // extern "C"

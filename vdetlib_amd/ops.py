@@ -1496,6 +1496,158 @@ def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0
     return out
 
 
+_PATCH_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}     # include/vdet_hip.h: VDET_PATCH_F32 / _F16 / _BF16
+_PATCH_MODES = {'warp': 0, 'square': 1}
+
+
+def _patch_common(images, crop_size, padding, mean, mode, dtype):
+    """The checks rcnn_patches and tubelet_patches share: (S, padding, mode code, dtype code, mean tensor or None)."""
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("images must be uint8 [Fi,H,W,3]")
+    if not images.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    Fi, H, W = images.shape[0], images.shape[1], images.shape[2]
+    if Fi < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767:
+        raise ValueError("images must hold at least one frame of 1 .. 32767 rows and columns")
+    S, padding = int(crop_size), int(padding)
+    if not 1 <= S <= 1024:
+        raise ValueError("crop_size = %d; 1 .. 1024" % S)
+    if padding < 0 or S - 2 * padding < 1:
+        raise ValueError("padding = %d; 0 <= padding and crop_size - 2*padding >= 1" % padding)
+    if mode not in _PATCH_MODES:
+        raise ValueError("mode must be 'warp' or 'square'")
+    if dtype not in _PATCH_DTYPES:
+        raise ValueError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    if mean is not None:
+        if torch.is_tensor(mean):
+            if mean.dtype != torch.float64 or tuple(mean.shape) != (3,) or mean.device != images.device:
+                raise ValueError("mean must be three values, or a float64 [3] tensor on the images' GPU")
+            mean = mean.contiguous()
+        else:
+            m = np.asarray(mean, dtype=np.float64).reshape(-1)
+            if m.size != 3:
+                raise ValueError("mean must be three values, or a float64 [3] tensor on the images' GPU")
+            mean = torch.from_numpy(m).to(images.device)
+    return S, padding, _PATCH_MODES[mode], _PATCH_DTYPES[dtype], mean
+
+
+def rcnn_patches(images, boxes, image_idx=None, offsets=None, crop_size=224, padding=16, mean=(103.939, 116.779, 123.68),
+                 mode='warp', dtype=torch.float32, sync=True, ctx=None):
+    """The CNN scorers' input windows on the device (include/vdet_hip.h: vdet_rcnn_patches): ``rcnn_img_crop`` +
+    ``im_transform`` (utils/common.py:208-280) for every box in one launch -- context padding, Python-2 rounding, clipping,
+    bilinear resize in f64, minus the mean, zero canvas, channel-major.
+
+    images uint8 [Fi,H,W,3] in the stored channel order (BGR from cv2.imread: never swapped); boxes [N,4] f32 / f64, 1-based
+    inclusive; image_idx int32 [N] (None: a single image).  ``offsets`` f64 [N,num,4] is ``sampling_boxes``
+    (vdet/tubelet_cls.py:136-142) with the caller's draw: window (n,0) is box n, window (n,1+j) is
+    box + offsets[n,j]*[w,h,w,h].  ``mean`` None: no subtraction.  ``mode`` 'warp' / 'square'.  ``dtype`` float32, or float16 /
+    bfloat16: the f32 value rounded once (== patches_f32.to(dtype)).
+
+    Returns a dict: ``patches`` [N,3,S,S] (with offsets [N,num+1,3,S,S]), ``ok`` uint8 [N] ([N,num+1]): 0 where the reference
+    would raise inside cv2.resize (or the input is not finite, or the image index is out of range) -- that patch is all zeros --
+    and with offsets ``sboxes`` f64 [N,num+1,4], the boxes used.  Parity of the resize rule with OpenCV is unpinned (DESIGN.md
+    10j); the bits are those of tests/patch_spec.py.  No CPU fallback."""
+    S, padding, mcode, dcode, mean = _patch_common(images, crop_size, padding, mean, mode, dtype)
+    if not torch.is_tensor(boxes) or boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be float32 / float64 [N,4]")
+    N = boxes.shape[0]
+    if image_idx is None:
+        if images.shape[0] != 1:
+            raise ValueError("image_idx=None needs a single image ([1,H,W,3])")
+    elif not torch.is_tensor(image_idx) or image_idx.dtype != torch.int32 or tuple(image_idx.shape) != (N,):
+        raise ValueError("image_idx must be int32 [N]")
+    num = 0
+    if offsets is not None:
+        if not torch.is_tensor(offsets) or offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != N or offsets.shape[2] != 4:
+            raise ValueError("offsets must be float64 [N,num,4]")
+        num = offsets.shape[1]
+        if not 1 <= num <= 255:
+            raise ValueError("num = %d sampled boxes per box; 1 .. 255" % num)
+    M = N * (num + 1)
+    if M >= 2 ** 31 - 16:
+        raise ValueError("too many windows (below 2^31 - 16)")
+    for x in (boxes, image_idx, offsets):
+        if x is not None and (not x.is_cuda or x.device != images.device):
+            raise ValueError("images, boxes, image_idx and offsets must live on the same GPU")
+        if x is not None and not x.is_contiguous():
+            raise ValueError("boxes, image_idx and offsets must be contiguous")
+    dev = images.device
+    patches = torch.empty((M, 3, S, S), dtype=dtype, device=dev)
+    ok = torch.empty((M,), dtype=torch.uint8, device=dev)
+    sboxes = torch.empty((N, num + 1, 4), dtype=torch.float64, device=dev) if offsets is not None else None
+    ctx = _ctx_for(images, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_rcnn_patches(ctx.h, images.data_ptr(), images.shape[0], images.shape[1], images.shape[2], ptr(boxes),
+                                        int(boxes.dtype == torch.float64), N, ptr(image_idx), ptr(offsets), num, ptr(mean), S, padding,
+                                        mcode, dcode, ptr(patches), ptr(ok), ptr(sboxes)))
+    if sync:
+        ctx.sync()
+    if offsets is None:
+        return dict(patches=patches, ok=ok)
+    return dict(patches=patches.view(N, num + 1, 3, S, S), ok=ok.view(N, num + 1), sboxes=sboxes)
+
+
+def tubelet_patches(images, tracks, ntracks, frames, cap, crop_size=224, padding=16, mean=(103.939, 116.779, 123.68), mode='warp',
+                    dtype=torch.float32, sync=True, ctx=None):
+    """``rcnn_patches`` for the tubelet boxes of the frames ``frames = (f0, f1)``, f0 <= f < f1, straight from device tubelets
+    (include/vdet_hip.h: vdet_tubelet_patches): the input of ``rcnn_scoring`` (vdet/tubelet_cls.py:102-134) for those frames.
+
+    tracks: any [C,T,F,>=4] f32 / f64 tensor whose first four columns are the box -- ``tracks``, ``tboxes``, one video of a
+    batch; ntracks int32 [C]; images uint8 [f1-f0,H,W,3], images[f - f0] is frame f.  The PRESENT boxes (t < ntracks[c], x1 not
+    NaN) are compacted in the order frames, classes, slots -- the order of the reference's frame loop.  Returns a dict:
+    ``patches`` [cap,3,S,S], ``slot`` int32 [cap,3] rows (c,t,f), -1 behind the count, ``count`` int32 [1]: the TRUE number of
+    present boxes, ``ok`` uint8 [cap].  ``count > cap`` raises ValueError when the call -- with ``sync=False`` a later
+    ``ctx.sync()`` -- waits; the first ``cap`` windows are valid then.  The other options are ``rcnn_patches``'.
+
+    The way back, with any torch ``net`` giving one score per patch::
+
+        n = int(out['count']); c, t, f = out['slot'][:n].long().unbind(1)
+        series = torch.full(tracks.shape[:3], float('nan'), dtype=torch.float64, device=tracks.device)
+        series[c, t, f] = net(out['patches'][:n]).double()
+        det, pooled, tboxes, src = rescore_tubelets(tracks, ntracks, boxes, scores, floor=series)"""
+    S, padding, mcode, dcode, mean = _patch_common(images, crop_size, padding, mean, mode, dtype)
+    if not torch.is_tensor(tracks) or tracks.dtype not in (torch.float32, torch.float64) or tracks.dim() != 4 or tracks.shape[3] < 4:
+        raise ValueError("tracks must be float32 / float64 [C,T,F,>=4]")
+    C, T, F, ld = tracks.shape
+    if C < 1 or F < 1:
+        raise ValueError("at least one class and one frame")
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if C * max(T, 1) * F >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16)")
+    try:
+        f0, f1 = (int(x) for x in frames)
+    except (TypeError, ValueError):
+        raise ValueError("frames must be (f0, f1)")
+    if not 0 <= f0 < f1 <= F:
+        raise ValueError("frames must be a range 0 <= f0 < f1 <= F (F = %d)" % F)
+    if images.shape[0] != f1 - f0:
+        raise ValueError("images must hold the f1 - f0 = %d frames of the range" % (f1 - f0))
+    cap = int(cap)
+    if not 0 <= cap < 2 ** 31 - 16:
+        raise ValueError("cap must be 0 .. 2^31 - 17 windows")
+    for x in (tracks, ntracks):
+        if not x.is_cuda or x.device != images.device:
+            raise ValueError("images, tracks and ntracks must live on the same GPU")
+        if not x.is_contiguous():
+            raise ValueError("tracks and ntracks must be contiguous")
+    dev = images.device
+    patches = torch.empty((cap, 3, S, S), dtype=dtype, device=dev)
+    ok = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    slot = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    ctx = _ctx_for(images, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_tubelet_patches(ctx.h, images.data_ptr(), images.shape[0], images.shape[1], images.shape[2], ptr(tracks),
+                                           int(tracks.dtype == torch.float64), C, T, F, ld, ntracks.data_ptr(), f0, f1, cap, ptr(mean),
+                                           S, padding, mcode, dcode, ptr(patches), ptr(ok), ptr(slot), count.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(patches=patches, slot=slot, count=count, ok=ok)
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 

@@ -1,8 +1,12 @@
 """Helpers of the reference's utils/common.py that the hot path and its callers use:
 ``iou`` (:451-468, computed on the GPU), ``options`` (:470-471), path/list helpers.
 
-Out of scope (external engines): image cropping / CNN preprocessing
-(:141-280), MATLAB and Caffe launchers (:302-396), window files (:48-121), SVM loader (:416-423).
+``rcnn_img_crop`` (:208-266) and ``im_transform`` (:268-280, the ``size <= 0`` branch) -- the window warp in front of the CNN
+scorers -- run on the GPU (``ops.rcnn_patches``).
+
+Out of scope (see DESIGN.md sections 7 and 10j): ``img_crop`` (:141-205, a uint8 imresize without a caller in the
+reference), ``im_transform``'s resizing branch, MATLAB and Caffe launchers (:302-396), window files (:48-121), SVM loader
+(:416-423).
 """
 import argparse
 import codecs
@@ -60,6 +64,39 @@ def iou(boxes1, boxes2):
     (vdet_iou_f64); bit-exact with the numpy expression of the reference."""
     from .. import ops
     return ops.iou(boxes1, boxes2)
+
+
+def rcnn_img_crop(img, in_bbox, crop_mode, crop_size, padding, image_mean=None):
+    """utils/common.py:208-266 for one window, on the GPU: img uint8 [H,W,3], in_bbox four 1-based inclusive coordinates ->
+    float32 [crop_size,crop_size,3], the warped window minus ``image_mean`` on a zero canvas.  ValueError where the reference
+    raises inside cv2.resize (an empty window).  Many boxes of one frame: ``ops.rcnn_patches`` / ``googlenet_features`` upload
+    the frame once.  RuntimeError without a GPU (no CPU fallback)."""
+    import numpy as np
+    import torch
+    from .. import _lib, ops
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("img must be uint8 [H,W,3]")
+    box = np.asarray(in_bbox, dtype=np.float64).reshape(1, 4)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    out = ops.rcnn_patches(torch.from_numpy(img).to(dev)[None], torch.from_numpy(box).to(dev), crop_size=crop_size, padding=padding,
+                           mean=None if image_mean is None else np.asarray(image_mean, dtype=np.float64).reshape(3),
+                           mode='square' if crop_mode == 'square' else 'warp')
+    if not int(out['ok'][0]):
+        raise ValueError("rcnn_img_crop: the window of box %s is empty (the reference raises inside cv2.resize)" % (box[0].tolist(),))
+    return out['patches'][0].permute(1, 2, 0).contiguous().cpu().numpy()
+
+
+def im_transform(image, size=-1, scale=1., mean_values=[0., 0., 0.]):
+    """utils/common.py:268-280 for ``size <= 0`` (the only branch RCNNProcesser uses): (image - mean_values) * scale,
+    [H,W,3] -> [3,H,W].  The resizing branch (cv2.resize of a uint8 crop, googlenet_det's) is out of scope."""
+    import numpy as np
+    assert len(mean_values) == 3
+    if size > 0:
+        raise NotImplementedError("im_transform: only size <= 0 (no resize) is provided; see DESIGN.md section 10j")
+    trans_img = (np.asarray(image) - np.asarray(mean_values)) * scale
+    return trans_img.swapaxes(1, 2).swapaxes(0, 1)
 
 
 def pickle(data, file_path):

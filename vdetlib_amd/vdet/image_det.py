@@ -1,6 +1,7 @@
-"""Still-image NMS wrapper of the reference's vdet/image_det.py (:117-123).  The CNN scorers of
-that file (:12-106: Fast R-CNN / GoogLeNet R-CNN forward passes) are external engines
-and out of scope."""
+"""Still-image NMS wrapper (:117-123), the SVM scorer (:109-114) and the R-CNN feature loop of the reference's
+vdet/image_det.py: ``googlenet_features`` / ``googlenet_rcnn`` (:56-106) warp their windows on the GPU (``ops.rcnn_patches``,
+DESIGN.md section 10j) and drive any pycaffe-like ``net`` through the reference's blob protocol; the nets themselves are the
+caller's.  Out of scope: ``simple_crop`` / ``googlenet_det`` (:12-53, a fixed-point uint8 resize) and ``fast_rcnn_det``."""
 import numpy as np
 
 from ..utils.cython_nms import nms
@@ -14,6 +15,53 @@ def apply_image_nms(boxes, scores, thres=0.3):
     keep = nms(box_score, thres)
     logging.info("{} / {} boxes kept.".format(len(keep), len(boxes)))
     return keep
+
+
+def googlenet_rcnn(img, boxes, net):
+    """:56-57."""
+    return googlenet_features(img, boxes, net, 'cls_score')
+
+
+def googlenet_features(img, boxes, net, blob_name):
+    """:75-106: the 224-pixel 'warp' windows of ``boxes`` (padding 16, minus the BGR mean, channel-major float32) through
+    ``net`` in slices of 128, ``net.blobs[blob_name].data`` of every slice concatenated.  img uint8 [H,W,3] is uploaded once;
+    every slice is one device call (``ops.rcnn_patches``).  ``net``: anything with pycaffe's blob protocol --
+    ``blobs['data'].reshape(*shape)``, ``blobs['data'].data[...] = patches``, ``forward()``, ``blobs[blob_name].data``.
+    ValueError for a box whose window is empty (the reference raises inside cv2.resize).  RuntimeError without a GPU."""
+    import torch
+    from .. import _lib, ops
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    size = 224
+    mean_values = np.asarray([103.939, 116.779, 123.68])
+    batch_size = 128
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("img must be uint8 [H,W,3]")
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    d_img = torch.from_numpy(img).to(dev)[None]
+    d_boxes = torch.from_numpy(np.ascontiguousarray(boxes)).to(dev)
+    features = None
+    for b0 in range(0, max(len(boxes), 1), batch_size):
+        out = ops.rcnn_patches(d_img, d_boxes[b0:b0 + batch_size], crop_size=size, padding=16, mean=mean_values, mode='warp')
+        bad = (out['ok'] == 0).nonzero()
+        if bad.numel():
+            raise ValueError("googlenet_features: the window of box %d is empty (the reference raises inside cv2.resize)"
+                             % (b0 + int(bad[0])))
+        patches = out['patches'].cpu().numpy()
+        net.blobs['data'].reshape(*(patches.shape))
+        net.blobs['data'].data[...] = patches
+        net.forward()
+        cur_feat = net.blobs[blob_name].data
+        if features is None:
+            features = np.copy(cur_feat)
+        else:
+            try:
+                features = np.r_[features, cur_feat]
+            except ValueError as e:
+                logging.error("Unable to concatenate features.")
+                raise e
+    return np.asarray(features)
 
 
 def svm_scores(features, svm_model):
