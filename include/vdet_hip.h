@@ -936,6 +936,60 @@ int vdet_tubelet_patches(vdet_ctx *ctx, const uint8_t *d_images, int64_t Fi, int
                          int64_t cap, const double *d_mean, int S, int padding, int mode, int out_dtype, void *d_patches,
                          uint8_t *d_ok, int32_t *d_slot, int32_t *d_count);
 
+/*
+ * The SVM head of the CNN scorers on the device: rcnn_scoring / rcnn_sampling_scoring (vdet/tubelet_cls.py:102-194) AFTER the
+ * net -- svm_scores (vdet/image_det.py:109-114) for the one class column a window needs, the max and argmax over the windows
+ * of a box (:166-189) and the scatter into the [C,T,F] layout the other stages read.
+ *
+ * d_feat [N*G, K]: the net's features, window m = g*G + j is window j of group (box) g, G = num + 1 windows per box;
+ * feat_dtype VDET_FEAT_F32 / _F16 / _BF16 / _F64.  d_W [K,M] and d_B [M] (or NULL: no bias) as the model stores them, f64
+ * when w_f64 / b_f64 else f32.  scale = 20 / feat_norm_mean, worked out by the caller.  The compute type is f64 when
+ * compute_f64, else f32 -- numpy's result type: f32 only when features, W and B are all at most f32 (VDET_EINVAL otherwise).
+ *
+ *     s[m] = sum_k (feat[m,k] * scale) * W[k, col] + B[col]
+ *
+ * feat is widened to the compute type exactly, feat*scale is rounded once (the reference's order, :112-113), then every
+ * product and every sum is one rounded operation (no fused multiply-add).  THE ORDER OF THE SUM: k is cut into units of 8;
+ * unit u = k/8 belongs to lane u % 64; a lane adds its products to one accumulator from +0 in ascending k; the 64 accumulators
+ * are combined by the butterfly acc[l] = acc[l] + acc[l ^ d] for d = 32, 16, 8, 4, 2, 1; B[col] is added last.  The order does
+ * not depend on N, G, the launch or feat_dtype; tests/svm_spec.py states it in numpy and the device equals it bit for bit.
+ *
+ * Column: with d_slot [N,3] int32 rows (c,t,f) (vdet_tubelet_patches' d_slot), col = d_cols[c] (d_cols [C] int32; NULL: col =
+ * c); without d_slot every group is class c = 0 (C must be 1, d_cols [1] or NULL).  d_count [1] int32 (vdet_tubelet_patches'
+ * d_count) or NULL: groups g >= min(count, N) are skipped and their slot rows are not read.
+ *
+ * Per group: score = max_j s[g*G + j], arg = the first j attaining it by np.argmax's rules (the first maximum wins; a NaN wins
+ * at its first occurrence and the score is NaN).  Windows with d_ok[m] == 0 (d_ok [N*G] uint8 or NULL) do not compete and
+ * their features are not read; a group with no window left scores NaN with arg -1 and is counted in d_nbad [1] int32.
+ *
+ * Outputs.  Compact: d_score [N] (compute type), d_arg_flat [N] int32 -- NaN / -1 for a skipped group.  With d_slot: d_det
+ * [C,T,F] (compute type) and d_arg [C,T,F] int32 receive score / arg at (c,t,f), and d_tboxes [C,T,F,4] f64 the winning row of
+ * d_sboxes [N,G,4] f64 (vdet_rcnn_patches' d_sboxes; NaN for a group without a window); ONLY the slots of the call's groups are
+ * written, so consecutive calls over the frame ranges of a video fill the same tensors.  Without d_slot d_det / d_arg are not
+ * used and d_tboxes is compact, [N,4].  d_det, d_arg, d_tboxes may be NULL; d_tboxes is written only with d_sboxes.
+ *
+ * A slot row outside (C,T,F) or a column outside 0..M-1 in front of the count: the group is skipped (compact NaN / -1, nothing
+ * else written) and VDET_EINVAL is latched for vdet_sync.  On the context's stream, no host wait: a W^T copy (a column becomes
+ * contiguous), the head itself in ONE launch, and the sum of the empty groups; timed under "other".  ctx NULL: VDET_EINVAL.
+ * d_feat rows are read with 16-byte loads when K % 8 == 0 and d_feat is 16-byte aligned; any K >= 1 works.
+ */
+#define VDET_FEAT_F32 0
+#define VDET_FEAT_F16 1
+#define VDET_FEAT_BF16 2
+#define VDET_FEAT_F64 3
+
+int vdet_svm_head(vdet_ctx *ctx, const void *d_feat, int feat_dtype, int64_t N, int G, int64_t K, const void *d_W, int w_f64,
+                  const void *d_B, int b_f64, int64_t M, double scale, int compute_f64, const int32_t *d_slot,
+                  const int32_t *d_count, int64_t C, int T, int64_t F, const int32_t *d_cols, const double *d_sboxes,
+                  const uint8_t *d_ok, void *d_det, int32_t *d_arg, double *d_tboxes, void *d_score, int32_t *d_arg_flat,
+                  int32_t *d_nbad);
+
+/* vdet_svm_scores_f64 / _f32 on DEVICE buffers: the same kernel, on the context's stream, no copies and no host wait. */
+int vdet_svm_scores_dev_f64(vdet_ctx *ctx, const double *d_feat, int64_t n, int64_t k, const double *d_W, const double *d_B,
+                            int64_t m, double *d_out);
+int vdet_svm_scores_dev_f32(vdet_ctx *ctx, const float *d_feat, int64_t n, int64_t k, const float *d_W, const float *d_B,
+                            int64_t m, float *d_out);
+
 #ifdef __cplusplus
 }
 #endif

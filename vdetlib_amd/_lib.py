@@ -95,6 +95,10 @@ SYMBOLS = {
     "vdet_rcnn_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "vdet_tubelet_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _ci, _i64, _ci, _vp, _i64, _i64, _i64, _vp, _ci, _ci,
                                    _ci, _ci, _vp, _vp, _vp, _vp]),
+    "vdet_svm_head": (_ci, [_vp, _vp, _ci, _i64, _ci, _i64, _vp, _ci, _vp, _ci, _i64, _f64, _ci, _vp, _vp, _i64, _ci, _i64, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vdet_svm_scores_dev_f64": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "vdet_svm_scores_dev_f32": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
 

@@ -37,6 +37,7 @@
 #include "tracknms_kernels.hpp"
 #include "rescore_kernels.hpp"
 #include "patch_kernels.hpp"
+#include "svmhead_kernels.hpp"
 
 using namespace vdet;
 
@@ -221,6 +222,7 @@ struct vdet_ctx {
     StagedTab anchor_tab;
     DevBuf topa_hist, topa_state, topa_cnt, topa_nrec, topa_rec;
     bool topa_hist_clean = false; // the histogram holds zeros (every selection round clears what it read)
+    DevBuf svm_wt, svm_wavebad;   // SVM head (svmhead_kernels.hpp): the W^T copy of the call and the per-wave counts of empty groups
 };
 
 namespace {
@@ -346,6 +348,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
     if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
+    if (st & kStSvmBad) return fail(c, VDET_EINVAL, "svm_head: a slot row outside shape or a class column outside W (the group is skipped, nothing is written for it)");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -1457,7 +1460,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
-                      &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec};
+                      &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -3839,6 +3842,114 @@ int vdet_tubelet_patches(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64
     g.mean = d_mean; g.S = S; g.padding = padding; g.square = mode == VDET_PATCH_SQUARE ? 1 : 0;
     g.M = cap; g.patches = d_patches; g.ok = d_ok;
     if ((rc = patch_launch(c, g, out_dtype))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The SVM head of the CNN scorers (svmhead_kernels.hpp) and svm_scores on device pointers
+// ---------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+template <typename FeatT, typename CT> void svm_head_launch_t(vdet_ctx *c, const SvmHeadArgs &g, bool vec, unsigned blocks)
+{
+    if (vec && g.K <= kSvmRound) hipLaunchKernelGGL((svm_head_kernel<FeatT, CT, 1, true>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else if (vec && g.K <= kSvmRegRounds * kSvmRound) hipLaunchKernelGGL((svm_head_kernel<FeatT, CT, 2, true>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else if (vec) hipLaunchKernelGGL((svm_head_kernel<FeatT, CT, 0, true>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else hipLaunchKernelGGL((svm_head_kernel<FeatT, CT, 0, false>), dim3(blocks), dim3(256), 0, c->stream, g);
+}
+
+template <typename CT> void svm_head_launch(vdet_ctx *c, const SvmHeadArgs &g, int feat_dtype, bool vec, unsigned blocks)
+{
+    if (feat_dtype == VDET_FEAT_F32) svm_head_launch_t<float, CT>(c, g, vec, blocks);
+    else if (feat_dtype == VDET_FEAT_F16) svm_head_launch_t<_Float16, CT>(c, g, vec, blocks);
+    else svm_head_launch_t<SvmBf16, CT>(c, g, vec, blocks);
+}
+
+template <typename T>
+int svm_scores_dev_impl(vdet_ctx *c, const T *d_feat, int64_t n, int64_t k, const T *d_W, const T *d_B, int64_t m, T *d_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (n < 0 || k < 0 || m < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (n == 0 || m == 0) return VDET_OK;
+    if ((k > 0 && (!d_feat || !d_W)) || !d_out) return fail(c, VDET_EINVAL, "null buffer");
+    if (n * k > ((int64_t)1 << 34) || k * m > ((int64_t)1 << 34) || n * m > ((int64_t)1 << 34)) return fail(c, VDET_EINVAL, "matrix too large");
+    if ((n + 63) / 64 > 65535) return fail(c, VDET_EINVAL, "at most 65535 * 64 rows in one call");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(svm_scores_kernel<T>, dim3((unsigned)((m + 63) / 64), (unsigned)((n + 63) / 64)), dim3(256), 0, c->stream, d_feat,
+                           d_W, d_B, n, k, m, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int vdet_svm_scores_dev_f64(vdet_ctx *c, const double *d_feat, int64_t n, int64_t k, const double *d_W, const double *d_B, int64_t m,
+                            double *d_out)
+{
+    return svm_scores_dev_impl<double>(c, d_feat, n, k, d_W, d_B, m, d_out);
+}
+
+int vdet_svm_scores_dev_f32(vdet_ctx *c, const float *d_feat, int64_t n, int64_t k, const float *d_W, const float *d_B, int64_t m,
+                            float *d_out)
+{
+    return svm_scores_dev_impl<float>(c, d_feat, n, k, d_W, d_B, m, d_out);
+}
+
+int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, int G, int64_t K, const void *d_W, int w_f64,
+                  const void *d_B, int b_f64, int64_t M, double scale, int compute_f64, const int32_t *d_slot, const int32_t *d_count,
+                  int64_t C, int T, int64_t F, const int32_t *d_cols, const double *d_sboxes, const uint8_t *d_ok, void *d_det,
+                  int32_t *d_arg, double *d_tboxes, void *d_score, int32_t *d_arg_flat, int32_t *d_nbad)
+{
+    if (!c) return VDET_EINVAL;
+    if (N < 0 || G < 1 || K < 1 || M < 1) return fail(c, VDET_EINVAL, "bad shape (N >= 0 groups of G >= 1 windows, K >= 1 features, M >= 1 columns)");
+    if (feat_dtype != VDET_FEAT_F32 && feat_dtype != VDET_FEAT_F16 && feat_dtype != VDET_FEAT_BF16 && feat_dtype != VDET_FEAT_F64)
+        return fail(c, VDET_EINVAL, "feat_dtype must be VDET_FEAT_F32, VDET_FEAT_F16, VDET_FEAT_BF16 or VDET_FEAT_F64");
+    if (!compute_f64 && (feat_dtype == VDET_FEAT_F64 || w_f64 || (d_B && b_f64)))
+        return fail(c, VDET_EINVAL, "the compute type is f32 only when features, W and B are at most f32");
+    if (!d_W || !d_nbad || (N && (!d_feat || !d_score || !d_arg_flat))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (N == 0) {
+        HIPCHK(c, hipMemsetAsync(d_nbad, 0, sizeof(int32_t), c->stream));
+        return VDET_OK;
+    }
+    if (d_slot ? (C < 1 || T < 1 || F < 1 || C * (int64_t)T * F >= 0x7FFFFFF0ll) : (C != 1))
+        return fail(c, VDET_EINVAL, "shape must be C, T, F >= 1 with C*T*F below 2^31 - 16 (without slot: C = 1)");
+    if (K > ((int64_t)1 << 40) / M || N > ((int64_t)1 << 46) / G / K) return fail(c, VDET_EINVAL, "matrix too large");
+    const size_t csz = compute_f64 ? 8 : 4;
+    const int gpw = G >= 32 ? 1 : (32 + G - 1) / G;
+    const int64_t nwaves = (N + gpw - 1) / gpw, blocks = (nwaves + 3) / 4;
+    if (blocks > 0x7FFFFFFFll) return fail(c, VDET_EINVAL, "too many groups for one launch");
+    HIPCHK(c, c->svm_wt.reserve((size_t)(M * K) * csz));
+    HIPCHK(c, c->svm_wavebad.reserve((size_t)nwaves * sizeof(int32_t)));
+    StageTimer tm(c, ST_OTHER);
+    {
+        const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((K + 31) / 32)), block(32, 8);
+        if (grid.y > 65535u || grid.x > 0x7FFFFFFFu) return fail(c, VDET_EINVAL, "matrix too large");
+        if (compute_f64 && w_f64) hipLaunchKernelGGL((svm_wt_kernel<double, double>), grid, block, 0, c->stream, static_cast<const double *>(d_W), K, M, c->svm_wt.as<double>());
+        else if (compute_f64) hipLaunchKernelGGL((svm_wt_kernel<float, double>), grid, block, 0, c->stream, static_cast<const float *>(d_W), K, M, c->svm_wt.as<double>());
+        else hipLaunchKernelGGL((svm_wt_kernel<float, float>), grid, block, 0, c->stream, static_cast<const float *>(d_W), K, M, c->svm_wt.as<float>());
+    }
+    SvmHeadArgs g{};
+    g.feat = d_feat; g.N = N; g.K = K; g.M = M; g.G = G;
+    g.wt = c->svm_wt.p; g.bias = d_B; g.bias_f64 = b_f64 ? 1 : 0; g.scale = scale;
+    g.slot = d_slot; g.count = d_count; g.cols = d_cols; g.C = C; g.F = F; g.T = T;
+    g.sboxes = d_sboxes; g.ok = d_ok;
+    g.det = d_slot ? d_det : nullptr; g.arg = d_slot ? d_arg : nullptr; g.tboxes = d_tboxes;
+    g.score = d_score; g.arg_flat = d_arg_flat; g.wavebad = c->svm_wavebad.as<int32_t>();
+    g.gpw = gpw; g.nwaves = nwaves; g.status = &c->d_cnt->status;
+    const bool vec = K % kSvmUnit == 0 && ((uintptr_t)d_feat & 15) == 0;
+    if (feat_dtype == VDET_FEAT_F64) svm_head_launch_t<double, double>(c, g, vec, (unsigned)blocks);
+    else if (compute_f64) svm_head_launch<double>(c, g, feat_dtype, vec, (unsigned)blocks);
+    else svm_head_launch<float>(c, g, feat_dtype, vec, (unsigned)blocks);
+    hipLaunchKernelGGL(svm_nbad_kernel, dim3(1), dim3(1024), 0, c->stream, c->svm_wavebad.as<int32_t>(), nwaves, d_nbad);
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
 }

@@ -1648,6 +1648,191 @@ def tubelet_patches(images, tracks, ntracks, frames, cap, crop_size=224, padding
     return dict(patches=patches, slot=slot, count=count, ok=ok)
 
 
+_FEAT_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}     # include/vdet_hip.h: VDET_FEAT_*
+
+
+def _svm_model(model, dev):
+    """W [K,M], B [M] or None as device tensors, the scale 20 / feat_norm_mean as numpy computes it, and whether that scale is
+    'at most float32' for numpy's result type (a python float is; a float64 scalar or array is not)."""
+    W, B, fnm = model['W'], model['B'], model['feat_norm_mean']
+    if not torch.is_tensor(W):
+        W = torch.from_numpy(np.ascontiguousarray(np.asarray(W))).to(dev)
+    if B is not None and not torch.is_tensor(B):
+        B = torch.from_numpy(np.ascontiguousarray(np.asarray(B))).to(dev)
+    if torch.is_tensor(fnm):
+        fnm = fnm.detach().cpu().numpy()
+    scale = 20. / fnm
+    if np.size(scale) != 1:
+        raise ValueError("feat_norm_mean must be a scalar")
+    small = isinstance(scale, float) and not isinstance(scale, np.floating) or np.asarray(scale).dtype in (np.float32, np.float16)
+    if W.dim() != 2 or W.dtype not in (torch.float32, torch.float64):
+        raise ValueError("W must be float32 / float64 [K,M]")
+    if B is not None:
+        if B.dtype not in (torch.float32, torch.float64) or B.numel() != W.shape[1] or (B.dim() > 1 and tuple(B.shape) != (1, W.shape[1])):
+            raise ValueError("B must be float32 / float64 [M] (or [1,M])")
+        B = B.reshape(-1)
+    for x in (W, B):
+        if x is not None and (not x.is_cuda or x.device != dev):
+            raise ValueError("features, W and B must live on the same GPU")
+        if x is not None and not x.is_contiguous():
+            raise ValueError("W and B must be contiguous")
+    return W, B, float(np.asarray(scale).reshape(())), bool(small)
+
+
+def svm_head(features, model, group=1, slot=None, count=None, shape=None, cols=None, sboxes=None, ok=None, out=None, sync=True,
+             ctx=None):
+    """The CNN scorers after the net, on the device (include/vdet_hip.h: vdet_svm_head): ``svm_scores`` (vdet/image_det.py:
+    109-114) for the ONE class column each window needs, the max / argmax over the ``group`` windows of a box
+    (rcnn_sampling_scoring, vdet/tubelet_cls.py:166-189) and the scatter into [C,T,F].
+
+    features [N*group, K] (or [N*group,K,1,1]) f64 / f32 / f16 / bf16: window n*group + j is window j of box n.  ``model``: the
+    ``svm_from_rcnn_model`` dict, ``W`` [K,M] and ``B`` [M] f64 / f32 as device tensors or numpy, ``feat_norm_mean`` a scalar.
+    The compute dtype is numpy's result type: float32 when features, W, B and the scale 20 / feat_norm_mean are all at most
+    float32 (a python-float feat_norm_mean counts as such, a float64 scalar does not), else float64.
+
+    ``slot`` int32 [N,3] rows (c,t,f) and ``count`` int32 [1] as ``tubelet_patches`` returns them (count None: all N; rows behind
+    it are not read); ``shape`` = (C,T,F), or taken from ``out``.  ``cols`` int32 [C]: the column of W of class c (default the
+    identity, C <= M; for VID classes ``index_vdet_to_det[c+1] - 1``).  Without ``slot`` (the ``rcnn_patches`` route) every box
+    is of the one class ``cols[0]`` and only the compact form is written.  ``sboxes`` f64 [N,group,4] and ``ok`` uint8
+    [N*group] (any shape of that size) are the patch calls': a window with ok == 0 does not compete; a box with no window left
+    scores NaN with arg -1 and is counted in ``nbad``.  ``out``: the dict of an earlier call -- its det / arg / tboxes are
+    written in place at this call's slots only (frame ranges of one video).  ``out=None`` allocates them, NaN / -1.
+
+    Returns a dict: ``det`` [C,T,F] (compute dtype), ``arg`` int32 [C,T,F], ``tboxes`` f64 [C,T,F,4] (None without sboxes) --
+    with slot=None det / arg are None and tboxes is [N,4] --, the compact ``score`` [N] and ``arg_flat`` int32 [N] (NaN / -1
+    behind count), ``nbad`` int32 [1].  The bits are those of tests/svm_spec.py.  A slot outside ``shape`` or a column outside W
+    raises ValueError when the call -- with ``sync=False`` a later ``ctx.sync()`` -- waits; that box is skipped.  No CPU
+    fallback."""
+    if not torch.is_tensor(features) or features.dtype not in _FEAT_DTYPES:
+        raise ValueError("features must be a float64 / float32 / float16 / bfloat16 tensor")
+    if not features.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if features.dim() == 4 and features.shape[2] == 1 and features.shape[3] == 1:
+        features = features[:, :, 0, 0]
+    if features.dim() != 2 or features.shape[1] < 1:
+        raise ValueError("features must be [N*group, K] with K >= 1")
+    if not features.is_contiguous():
+        raise ValueError("features must be contiguous")
+    dev = features.device
+    W, B, scale, small = _svm_model(model, dev)
+    Mw, K = features.shape
+    if W.shape[0] != K:
+        raise ValueError("shapes %s and %s not aligned" % (tuple(features.shape), tuple(W.shape)))
+    M = W.shape[1]
+    G = int(group)
+    if G < 1 or Mw % G:
+        raise ValueError("group = %d windows per box must divide the %d feature rows" % (G, Mw))
+    N = Mw // G
+    f32 = features.dtype != torch.float64 and W.dtype == torch.float32 and small and (B is None or B.dtype == torch.float32)
+    cdt = torch.float32 if f32 else torch.float64
+    if f32:
+        scale = float(np.float32(scale))
+    if out is not None and slot is None:
+        raise ValueError("out= needs slot")
+    if slot is not None:
+        if not torch.is_tensor(slot) or slot.dtype != torch.int32 or tuple(slot.shape) != (N, 3):
+            raise ValueError("slot must be int32 [N,3]")
+        if out is not None:
+            if not isinstance(out, dict) or not torch.is_tensor(out.get('det')) or not torch.is_tensor(out.get('arg')):
+                raise ValueError("out must be the dict of an earlier svm_head call")
+            if shape is not None and tuple(shape) != tuple(out['det'].shape):
+                raise ValueError("shape differs from out's")
+            shape = tuple(out['det'].shape)
+        try:
+            C, T, F = (int(x) for x in shape)
+        except (TypeError, ValueError):
+            raise ValueError("shape must be (C, T, F)")
+        if C < 1 or T < 1 or F < 1 or C * T * F >= 2 ** 31 - 16:
+            raise ValueError("shape must be C, T, F >= 1 with C*T*F below 2^31 - 16")
+    else:
+        if count is not None or shape is not None:
+            raise ValueError("count and shape need slot")
+        C, T, F = 1, 1, 1
+    if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("count must be int32 [1]")
+    if cols is None:
+        if C > M:
+            raise ValueError("the identity cols needs C <= M columns of W")
+    elif not torch.is_tensor(cols) or cols.dtype != torch.int32 or tuple(cols.shape) != (C,):
+        raise ValueError("cols must be int32 [C]")
+    if sboxes is not None and (not torch.is_tensor(sboxes) or sboxes.dtype != torch.float64 or tuple(sboxes.shape) != (N, G, 4)):
+        raise ValueError("sboxes must be float64 [N,group,4]")
+    if ok is not None and (not torch.is_tensor(ok) or ok.dtype != torch.uint8 or ok.numel() != N * G):
+        raise ValueError("ok must be uint8 with N*group elements")
+    for x in (slot, count, cols, sboxes, ok):
+        if x is not None and (not x.is_cuda or x.device != dev):
+            raise ValueError("features, slot, count, cols, sboxes and ok must live on the same GPU")
+        if x is not None and not x.is_contiguous():
+            raise ValueError("slot, count, cols, sboxes and ok must be contiguous")
+    det = arg = tboxes = None
+    if slot is not None:
+        if out is not None:
+            det, arg, tboxes = out['det'], out['arg'], out.get('tboxes')
+            if det.dtype != cdt or arg.dtype != torch.int32 or tuple(arg.shape) != (C, T, F):
+                raise ValueError("out's det / arg do not fit this call (compute dtype %s, shape %s)" % (cdt, (C, T, F)))
+            if sboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float64 or tuple(tboxes.shape) != (C, T, F, 4)):
+                raise ValueError("out's tboxes must be float64 [C,T,F,4] when sboxes are given")
+            for x in (det, arg, tboxes):
+                if x is not None and (x.device != dev or not x.is_contiguous()):
+                    raise ValueError("out's tensors must be contiguous on the features' GPU")
+        else:
+            det = torch.full((C, T, F), float('nan'), dtype=cdt, device=dev)
+            arg = torch.full((C, T, F), -1, dtype=torch.int32, device=dev)
+            tboxes = torch.full((C, T, F, 4), float('nan'), dtype=torch.float64, device=dev) if sboxes is not None else None
+    elif sboxes is not None:
+        tboxes = torch.empty((N, 4), dtype=torch.float64, device=dev)
+    score = torch.empty((N,), dtype=cdt, device=dev)
+    arg_flat = torch.empty((N,), dtype=torch.int32, device=dev)
+    nbad = torch.empty((1,), dtype=torch.int32, device=dev)
+    ctx = _ctx_for(features, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_svm_head(ctx.h, ptr(features), _FEAT_DTYPES[features.dtype], N, G, K, W.data_ptr(),
+                                    int(W.dtype == torch.float64), ptr(B), int(B is not None and B.dtype == torch.float64), M, scale,
+                                    int(not f32), ptr(slot), ptr(count), C, T, F, ptr(cols), ptr(sboxes), ptr(ok), ptr(det), ptr(arg),
+                                    ptr(tboxes) if sboxes is not None else None, ptr(score), ptr(arg_flat), nbad.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(det=det, arg=arg, tboxes=tboxes, score=score, arg_flat=arg_flat, nbad=nbad)
+
+
+def svm_scores(features, model, sync=True, ctx=None):
+    """``image_det.svm_scores`` (vdet/image_det.py:109-114) on DEVICE tensors, all M columns (include/vdet_hip.h:
+    vdet_svm_scores_dev_f64 / _f32, the MFMA kernel of the host form): for the ``all_score`` rows of the CNN scorers -- gather
+    the winners' feature rows by ``svm_head``'s ``arg`` and pass them in.  features [n,K] f64 / f32 on the GPU, ``model`` as for
+    ``svm_head``.  The scaling ``features * (20 / feat_norm_mean)`` and the dtype rules are the host form's (torch's
+    elementwise product stands in for numpy's, the same bits); B joins in the product's dtype.  Returns [n,M]."""
+    if not torch.is_tensor(features) or features.dtype not in (torch.float32, torch.float64):
+        raise ValueError("features must be a float64 / float32 tensor")
+    if not features.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if features.dim() == 4 and features.shape[2] == 1 and features.shape[3] == 1:
+        features = features[:, :, 0, 0]
+    if features.dim() != 2:
+        raise ValueError("features must be [n, K]")
+    dev = features.device
+    W, B, scale, small = _svm_model(model, dev)
+    if W.shape[0] != features.shape[1]:
+        raise ValueError("shapes %s and %s not aligned" % (tuple(features.shape), tuple(W.shape)))
+    f32 = features.dtype == torch.float32 and W.dtype == torch.float32 and small
+    cdt = torch.float32 if f32 else torch.float64
+    if B is not None and B.dtype == torch.float64 and f32:
+        raise ValueError("a float64 B on a float32 product: use image_det.svm_scores (numpy promotes the sum)")
+    a = (features if small else features.double()) * scale        # rounded in the features' dtype first, as numpy does (:112)
+    a = a.to(cdt).contiguous()
+    w = W.to(cdt).contiguous()
+    b = None if B is None else B.to(cdt).contiguous()
+    n, K = a.shape
+    M = w.shape[1]
+    out_t = torch.empty((n, M), dtype=cdt, device=dev)
+    ctx = _ctx_for(features, ctx)
+    fn = ctx.lib.vdet_svm_scores_dev_f32 if f32 else ctx.lib.vdet_svm_scores_dev_f64
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(fn(ctx.h, ptr(a), n, K, ptr(w), ptr(b), M, ptr(out_t)))
+    if sync:
+        ctx.sync()
+    return out_t
+
+
 def _evaluator_of(gt):
     return gt if isinstance(gt, DetEvaluator) else DetEvaluator(gt)
 

@@ -5,8 +5,7 @@
 scorers -- run on the GPU (``ops.rcnn_patches``).
 
 Out of scope (see DESIGN.md sections 7 and 10j): ``img_crop`` (:141-205, a uint8 imresize without a caller in the
-reference), ``im_transform``'s resizing branch, MATLAB and Caffe launchers (:302-396), window files (:48-121), SVM loader
-(:416-423).
+reference), ``im_transform``'s resizing branch, MATLAB and Caffe launchers (:302-396), window files (:48-121).
 """
 import argparse
 import codecs
@@ -183,3 +182,17 @@ def quick_args(arglist):
         else:
             parser.add_argument(arg)
     return parser.parse_args()
+
+
+def svm_from_rcnn_model(rcnn_model):
+    """utils/common.py:416-423: the SVM head of an R-CNN .mat model -- ``W`` [K,M] and ``B`` [1,M] of
+    ``rcnn_model.detectors`` and the scalar ``training_opts.feat_norm_mean`` -- as ``image_det.svm_scores`` and
+    ``ops.svm_head`` read it."""
+    import scipy.io as sio
+    rcnn_model = sio.loadmat(rcnn_model)['rcnn_model']
+    detectors = rcnn_model['detectors'][0, 0]
+    svm = {}
+    svm['W'] = detectors['W'][0, 0]
+    svm['B'] = detectors['B'][0, 0]
+    svm['feat_norm_mean'] = rcnn_model['training_opts'][0, 0]['feat_norm_mean'][0, 0][0, 0]
+    return svm

@@ -1,19 +1,28 @@
 """Tubelet re-scoring of the reference's vdet/tubelet_cls.py: spatial max-pooling of detection
-scores onto tubelet boxes, gap completion, temporal max-pooling, interpolation, and the channel
-assembly of the temporal-convolution scorer.  Dict plumbing in python, every numeric core on the
-GPU (vdetlib_amd.hot -> include/vdet_hip.h).
+scores onto tubelet boxes, gap completion, temporal max-pooling, interpolation, the channel
+assembly of the temporal-convolution scorer, and the CNN scorers ``rcnn_scoring`` /
+``rcnn_sampling_scoring`` with ``sampling_boxes`` (:102-194).  Dict plumbing in python, every numeric
+core on the GPU (vdetlib_amd.hot / vdetlib_amd.ops -> include/vdet_hip.h).
 
-Out of scope (external Caffe/SVM engines): fast_rcnn_cls, googlenet_cls,
-rcnn_scoring, rcnn_sampling_scoring, rcnn_sampling_dets_scoring, sampling_boxes (:53-260).
+The CNN scorers: the net is the caller's (any pycaffe-like object, ``image_det.googlenet_features``);
+its windows are warped on the GPU (``ops.rcnn_patches``) and everything after it -- the class column
+of the SVM, the max over a box's sampled windows, the winning box -- is ``ops.svm_head`` (DESIGN.md
+section 10k).
+
+Out of scope (external Caffe engines): fast_rcnn_cls, googlenet_cls (:53-100).
+``rcnn_sampling_dets_scoring`` (:196-260) has no dict-level form; its half after the CNN is
+``ops.rescore_tubelets(floor=...)`` on the scores ``ops.svm_head`` writes.
 """
 import copy
 from collections import defaultdict
 
 import numpy as np
 
-from ..utils.protocol import tubelets_overlap, tubelets_proto_from_tracks_proto
+from ..utils.protocol import frame_path_at, tubelet_box_at_frame, tubelets_overlap, tubelets_proto_from_tracks_proto
+from ..utils.common import imread, svm_from_rcnn_model
 from ..utils.log import logger as logging
-from .dataset import imagenet_vdet_classes
+from .dataset import imagenet_vdet_classes, index_vdet_to_det
+from .image_det import googlenet_features
 from .. import hot
 
 
@@ -85,6 +94,124 @@ def score_conv_cls_batched(score_proto, net):
         for box, p in zip(tubelet['boxes'], probs):
             box['conv_score'] = float(p)
     return out
+
+
+def sampling_boxes(orig_box, num, ratio=0.05, return_orig=True):
+    """:136-142, line for line: ``num`` boxes around ``orig_box``, every corner moved by a uniform draw of at most ``ratio``
+    of the box's width / height (x2-x1, y2-y1) from numpy's GLOBAL generator."""
+    h, w = orig_box[3] - orig_box[1], orig_box[2] - orig_box[0]
+    offsets = np.random.uniform(-ratio, ratio, [num, 4]) * [w, h, w, h]
+    if not return_orig:
+        return orig_box + offsets
+    else:
+        return np.vstack((orig_box, orig_box + offsets))
+
+
+def _frame_tubelet_boxes(tubelets_proto, frame_id):
+    """The boxes of a frame as the reference's frame loop collects them (:111-114): (boxes [n,4], tubelet index of each)."""
+    boxes = [tubelet_box_at_frame(tubelet, frame_id) for tubelet in tubelets_proto]
+    valid_boxes = np.asarray([box for box in boxes if box is not None])
+    valid_index = [i for i, box in enumerate(boxes) if box is not None]
+    return valid_boxes, valid_index
+
+
+def _svm_head_frame(features, svm_model, cache, class_idx, group, want_all):
+    """One upload of a frame's features, then ``ops.svm_head``: per box the class score and the winning window (f64 numpy),
+    the winners' feature rows, and their scores of ALL classes (``ops.svm_scores``) when asked for.  ``cache``: a dict of the
+    calling scorer that keeps the model's device copy from frame to frame."""
+    import torch
+    from .. import _lib, ops
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    features = np.asarray(features)
+    if features.ndim == 4:
+        features = np.squeeze(features, axis=(2, 3))
+    W = np.asarray(svm_model['W'])
+    if W.shape[1] != 200:
+        raise RuntimeError("the SVM model must score the 200 DET classes")        # the reference's bare `raise` (:122-123)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    model = cache.get('model')
+    if model is None or model['W'].device != dev:
+        model = {'W': torch.from_numpy(np.ascontiguousarray(W)).to(dev),
+                 'B': torch.from_numpy(np.ascontiguousarray(np.asarray(svm_model['B']).reshape(-1))).to(dev),
+                 'feat_norm_mean': svm_model['feat_norm_mean']}
+        cache['model'] = model
+    d_feat = torch.from_numpy(np.ascontiguousarray(features)).to(dev)
+    cols = torch.tensor([index_vdet_to_det[class_idx] - 1], dtype=torch.int32, device=dev)
+    out = ops.svm_head(d_feat, model, group=group, cols=cols)
+    if int(out['nbad']):
+        raise ValueError("a box without a window to score")
+    arg = out['arg_flat'].cpu().numpy().astype(np.int64)
+    rows = np.arange(len(arg)) * group + arg
+    all_scores = None
+    if want_all:
+        all_scores = ops.svm_scores(d_feat[torch.from_numpy(rows).to(dev)], model).cpu().numpy()
+    return out['score'].cpu().numpy(), arg, features[rows], all_scores
+
+
+def rcnn_scoring(vid_proto, track_proto, net, class_idx, rcnn_model, save_feat=False, save_all_sc=False):
+    """:102-134 -- every tubelet box of class ``class_idx`` gets ``det_score``: the R-CNN SVM score of its ``pool5`` features
+    for the class (column ``index_vdet_to_det[class_idx] - 1`` of the 200).  ``save_feat`` / ``save_all_sc`` add ``feat`` and
+    ``all_score`` (all 200 classes).  Per frame: ``googlenet_features`` (windows warped on the GPU, ``net`` the caller's), one
+    upload of the features, ``ops.svm_head``."""
+    svm_model = svm_from_rcnn_model(rcnn_model)
+    tubelets_proto = tubelets_proto_from_tracks_proto(track_proto['tracks'], class_idx)
+    cache = {}
+    logging.info("Scoring {} for {}...".format(vid_proto['video'], imagenet_vdet_classes[class_idx]))
+    for frame in vid_proto['frames']:
+        frame_id = frame['frame']
+        img = imread(frame_path_at(vid_proto, frame_id))
+        valid_boxes, valid_index = _frame_tubelet_boxes(tubelets_proto, frame_id)
+        logging.info("frame {}: {} boxes".format(frame_id, len(valid_index)))
+        if len(valid_index) == 0:
+            continue
+        features = googlenet_features(img, valid_boxes, net, 'pool5')
+        cls_scores, _, feats, all_scores = _svm_head_frame(features, svm_model, cache, class_idx, 1, save_all_sc)
+        for k, tubelet_id in enumerate(valid_index):
+            cur_box = [box for box in tubelets_proto[tubelet_id]['boxes'] if box['frame'] == frame_id]
+            assert len(cur_box) == 1
+            cur_box[0]['det_score'] = cls_scores[k]
+            if save_feat:
+                cur_box[0]['feat'] = feats[k].ravel().tolist()
+            if save_all_sc:
+                cur_box[0]['all_score'] = all_scores[k].ravel().tolist()
+    return tubelets_proto
+
+
+def rcnn_sampling_scoring(vid_proto, track_proto, net, class_idx, rcnn_model, samples_per_box=32, ratio=0.05,
+                          save_feat=False, save_all_sc=False):
+    """:144-194 -- ``rcnn_scoring`` over ``samples_per_box`` boxes sampled around every tubelet box (``sampling_boxes``, numpy's
+    global generator, drawn in the reference's order) and the box itself: ``det_score`` is the best class score of the
+    ``samples_per_box + 1`` windows and ``bbox`` becomes the winning window's box (the first one on ties, np.argmax);
+    ``feat`` / ``all_score`` are the winner's.  The max, the argmax and the class column are one ``ops.svm_head`` call per
+    frame."""
+    svm_model = svm_from_rcnn_model(rcnn_model)
+    tubelets_proto = tubelets_proto_from_tracks_proto(track_proto['tracks'], class_idx)
+    cache = {}
+    logging.info("Scoring {} for {}...".format(vid_proto['video'], imagenet_vdet_classes[class_idx]))
+    for frame in vid_proto['frames']:
+        frame_id = frame['frame']
+        img = imread(frame_path_at(vid_proto, frame_id))
+        valid_boxes, valid_index = _frame_tubelet_boxes(tubelets_proto, frame_id)
+        logging.info("frame {}: {} boxes".format(frame_id, len(valid_index)))
+        if len(valid_index) == 0:
+            continue
+        # sample nearby boxes to increase spatial robustness
+        sampled_boxes = np.vstack([sampling_boxes(box, samples_per_box, ratio) for box in valid_boxes])
+        features = googlenet_features(img, sampled_boxes, net, 'pool5')
+        max_scores, max_idx, feats, all_scores = _svm_head_frame(features, svm_model, cache, class_idx, samples_per_box + 1,
+                                                                 save_all_sc)
+        sampled_boxes = sampled_boxes.reshape((len(valid_index), samples_per_box + 1, -1))
+        boxes = sampled_boxes[range(len(valid_index)), max_idx, :]
+        for k, tubelet_id in enumerate(valid_index):
+            cur_box = [box for box in tubelets_proto[tubelet_id]['boxes'] if box['frame'] == frame_id]
+            assert len(cur_box) == 1
+            cur_box[0]['det_score'] = max_scores[k]
+            cur_box[0]['bbox'] = boxes[k].tolist()
+            if save_feat:
+                cur_box[0]['feat'] = feats[k].ravel().tolist()
+            if save_all_sc:
+                cur_box[0]['all_score'] = all_scores[k].ravel().tolist()
+    return tubelets_proto
 
 
 def scoring_tracks(vid_proto, track_proto, annot_proto, sc_method, net, class_idx):
