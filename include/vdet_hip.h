@@ -50,7 +50,8 @@
  *   evaluator: gt table cells              videos x frames x K < 2^31 VDET_EINVAL;  class slots 1 <= K <= 65536
  *   evaluator: stream entries              < 2^31 (per add: C*T*F or F*C*cap < 2^31)   VDET_EINVAL
  *   device TCN: layers of a net            1 .. 16                    VDET_EINVAL
- *   device TCN: channels of a layer        1 .. 4096 (inputs: 1 .. 16 assembled channels; any count up to 4096 for
+ *   device TCN: channels of a layer        1 .. 4096 (inputs: 1 .. 16 assembled channels; 1 .. 16 inputs of up to 4096
+ *                                          channels together for vdet_tcn_tracks_wide; any count up to 4096 for
  *                                          vdet_tcn_series_f32); the last layer has 2      VDET_EINVAL
  *   device TCN: kernel size                odd, <= 31                 VDET_EINVAL
  *   device TCN: series length, net width   none                       series whose activations exceed 48 KiB of LDS are tiled
@@ -568,6 +569,37 @@ int vdet_tcn_tracks_batch(vdet_ctx *ctx, const float *h_params, const int32_t *h
                           int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
                           const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
                           const double *d_gt_overlap, float *d_conv_score);
+
+/* The same scorer for nets whose inputs include WIDE blobs: per-box rows such as all_scores (the 200 SVM class scores of the
+ * box) or feats (its pool5 feature, 1024 values), the second kind of input of score_conv_cls (vdet/tubelet_cls.py:35-41).
+ * Input i of the n_inputs (1 .. 16, in the net's input order, one-channel and wide together) is
+ *   h_codes[i] = 0 .. 5   an assembled channel as above; h_widths[i] must be 1, h_rows[i] / h_dtypes[i] are ignored;
+ *   h_codes[i] = -1       a wide blob of h_widths[i] channels (1 .. 4096): h_rows[i] is a DEVICE pointer to contiguous rows
+ *                         [C,T,F,W] in the box order of d_tracks (batch: video v's rows start at box C*T*h_frame_off[v],
+ *                         i.e. one flat [C*T*Ftotal, W] array), h_dtypes[i] their storage: 0 f32 (taken as it is), 1 f16,
+ *                         2 bf16 (both widened exactly), 3 f64 (rounded once to f32, like np.asarray(.., dtype='float32')).
+ * Layer 0 sees Cin = the sum of the widths (<= 4096), concatenated in input order: channel q of a wide blob at series
+ * position j is entry q of the row of the tubelet's j-th box.  A row is read only where the tubelet has a box
+ * (t < d_ntracks[c] and column 0 of the track row is not NaN); rows of holes and of slots behind d_ntracks are never read,
+ * whatever they hold; NaN / Inf inside a row that is read propagates as the arithmetic dictates.  Row bases need only element
+ * alignment.  Arithmetic = vdet_conv1d_f32's, element for element, as above: bit-identical to the layer-by-layer path on
+ * the same [Cin, L] input.  Layer 0 runs in a kernel of its own that reads the rows where they lie (no transposed or
+ * compacted copy) and writes [Cout0, L] into a buffer of the context; the net kernel above runs the remaining layers (none
+ * for a one-layer net: the softmax only).  VDET_EINVAL: n_inputs outside 1 .. 16, an unknown code or dtype, a null row
+ * pointer, a width outside its range or unequal to layer 0's share (sum of widths != Cin of h_layers[0]), Cin > 4096.
+ * One assembly launch + two network launches; asynchronous, no host wait (a call whose row pointers, widths or order
+ * differ from the previous call's waits once for the copy of the previous input table, like a change of nets).
+ */
+int vdet_tcn_tracks_wide(vdet_ctx *ctx, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_codes,
+                         const int32_t *h_widths, const void *const *h_rows, const int32_t *h_dtypes, int n_inputs, int64_t F,
+                         int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                         const void *d_det_score, int det_f64, const double *d_gt_overlap, float *d_conv_score);
+
+int vdet_tcn_tracks_wide_batch(vdet_ctx *ctx, const float *h_params, const int32_t *h_layers, int n_layers,
+                               const int32_t *h_codes, const int32_t *h_widths, const void *const *h_rows,
+                               const int32_t *h_dtypes, int n_inputs, const int64_t *h_frame_off, int64_t V, int64_t C, int T,
+                               const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score,
+                               int det_f64, const double *d_gt_overlap, float *d_conv_score);
 
 /* The network kernel on T ragged host series: series t is h_x[cin*h_off[t] ...], channel-major [cin, L_t] with
  * L_t = h_off[t+1] - h_off[t]; h_out[h_off[t] + j] = probs[1] of position j.  Synchronous: one upload, one launch, one

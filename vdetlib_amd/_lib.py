@@ -69,7 +69,10 @@ SYMBOLS = {
     "vdet_eval_ap": (_ci, [_vp, _vp, _vp, _vp, _i64, _ci, _vp, _vp, _vp]),
     "vdet_tcn_tracks": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
     "vdet_tcn_tracks_batch": (_ci, [_vp, _vp, _vp, _ci, _vp, _ci, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
-    "vdet_tcn_series_f32": (_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp, _i64, _vp]),
+    "vdet_tcn_tracks_wide": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    "vdet_tcn_tracks_wide_batch": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci,
+                                         _vp, _vp]),
+    "vdet_tcn_series_f32":(_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp, _i64, _vp]),
     "vdet_tubelets_overlap": (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_tubelets_overlap_batch": (_ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_interp_tracks": (_ci, [_vp, _i64, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -187,8 +187,9 @@ __global__ __launch_bounds__(kTcnThreads) void tcn_net_kernel(TcnNet net, const 
                 __syncthreads();
                 float *sw = in; in = ob; ob = sw;
             }
-            // channel softmax of the last layer's output (softmax_channels_kernel), probs[1] to the box's frame
-            const int cl = net.l[net.n - 1].cout;
+            // channel softmax of the last layer's output (softmax_channels_kernel), probs[1] to the box's frame; a net of
+            // zero layers (the wide first layer was the only one) is this stage alone on its staged input
+            const int cl = net.n ? net.l[net.n - 1].cout : net.cin;
             for (int p = s + tid; p < e; p += kTcnThreads) {
                 const float *a = in + (p - org);
                 float m = a[0];
@@ -198,6 +199,179 @@ __global__ __launch_bounds__(kTcnThreads) void tcn_net_kernel(TcnNet net, const 
                 const float pr = expf(a[wt] - m) / sum;
                 const int64_t f = frames ? (int64_t)frames[base + p] : (int64_t)p;
                 out[base + f] = pr;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The wide first layer: layer 0 of a net whose input has per-box ROWS (all_scores [.., 200], feats [.., 1024]) beside, or
+// instead of, the assembled one-value-per-box channels.  The input is a table of segments in the net's `inputs` order; a wide
+// segment is read where the caller left it, rows [boxes, width] in the tracks' box order, gathered through the frame list:
+// a row is read only for a box of the series, so rows of holes and of slots behind ntracks are never touched.
+//
+// Grid (tubelets (grid-stride), position tiles (grid-stride)); a workgroup computes every output channel of one tile of
+// kTcnWideTile = 128 positions, two per lane (lane and lane + 64).  The concatenated channels pass through LDS in chunks of
+// kTcnWideChunk = 32:
+//   staging  a half wave takes a row (a position of tile + halo), its 32 lanes consecutive channels of it -- consecutive
+//            addresses of the caller's tensor, by ELEMENT loads, because row bases are only element-aligned (odd widths,
+//            16-bit storage, views); the call is bound by its multiply-adds (cout * K of them per element), not by these
+//            loads -- and writes tile[channel][position]; the pitch is ODD, so the 32 lanes, one pitch apart each, fall on
+//            32 different banks (bank = dword address % 32 for ds_write_b32, conflicts per 32-lane half);
+//   compute  a lane reads tile[ci][lane + k] and [lane + 64 + k]: consecutive dwords over the lanes, conflict-free at any pitch.
+// A wave owns A consecutive output channels, so a lane carries 2A accumulators: two LDS reads and A scalar weights feed A
+// packed multiplies and A packed adds (the two positions of a lane are the two halves; every product and every sum is
+// rounded on its own, nothing is fused or reassociated).  The four waves cover 4A channels; a layer with more takes further
+// passes over the tile, whose rows then come from L2 again.  The accumulators stay in registers across all chunks of a pass,
+// because every chain is sequential in ci.  W0[co] is contiguous in ci*K + k and comes through scalar loads; with K a template
+// parameter (3, 5) two channels' taps of one output channel are one run of 2K dwords, which the compiler loads in wide
+// pieces; any other K takes the generic instantiation (KT = 0), one scalar dword per weight.
+// Arithmetic = conv1d_kernel's: acc = b[co]; ci ascending over the concatenation, k inner; p = w * x rounded, acc = acc + p; a
+// position outside the series is staged as +0.0f and its product IS added.  h0 [cout, L] channel-major at tub_base * cout.
+// ------------------------------------------------------------------------------------------------
+constexpr int kTcnMaxSegs = 16;          // inputs of one call, one-channel and wide together
+constexpr int kTcnWideTile = 128;        // positions of one tile of the wide first layer: two per lane
+constexpr int kTcnWideChunk = 32;        // channels staged at a time: one per lane of a staging half wave
+constexpr int kTcnWidePitch = (kTcnWideTile + 2 * (kTcnMaxK / 2)) | 1;   // largest (odd) pitch: 159 floats
+
+enum { kTcnRowF32 = 0, kTcnRowF16 = 1, kTcnRowBF16 = 2, kTcnRowF64 = 3, kTcnRowTypes = 4 };   // storage of wide rows
+
+struct TcnSeg {
+    const void *rows;    // wide: the caller's rows [boxes, width]; null: channel `xq` of the assembled x
+    int32_t width;       // channels of the segment (1 for an assembled channel)
+    int32_t dtype;       // kTcnRow*
+    int32_t c0;          // first channel of the segment in the concatenation
+    int32_t xq;
+};
+
+typedef float tcn_f2 __attribute__((ext_vector_type(2)));
+
+// one element of a wide row as f32: f16 / bf16 widen exactly, f64 rounds once to nearest (np.asarray(.., dtype='float32'))
+__device__ __forceinline__ float tcn_row_elem(const void *rows, int dtype, int64_t i)
+{
+    switch (dtype) {
+    case kTcnRowF32: return static_cast<const float *>(rows)[i];
+    case kTcnRowF16: return (float)static_cast<const _Float16 *>(rows)[i];
+    case kTcnRowBF16: return __uint_as_float((uint32_t) static_cast<const uint16_t *>(rows)[i] << 16);
+    default: return (float)static_cast<const double *>(rows)[i];
+    }
+}
+
+// NT consecutive weights of each of the A output channels (t = ci*K + k onward) against the NT staged values xv, in order
+template <int A, int NT>
+__device__ __forceinline__ void tcn_wide_mac(tcn_f2 (&acc)[A], const float *const (&wr)[A], int t, const tcn_f2 (&xv)[NT])
+{
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const float *w = wr[a] + t;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const tcn_f2 pr = w[i] * xv[i];
+            acc[a] = acc[a] + pr;
+        }
+    }
+}
+
+template <int A, int KT>
+__global__ __launch_bounds__(kTcnThreads) void tcn_wide_layer_kernel(const TcnSeg *__restrict__ segs, int nseg, int cin, int cout, int krt,
+                                                                     int relu, const float *__restrict__ w0, const float *__restrict__ b0,
+                                                                     const float *__restrict__ x, int nx, const int32_t *__restrict__ frames,
+                                                                     const int64_t *__restrict__ tub_base, const int32_t *__restrict__ tub_len,
+                                                                     int64_t ntub, float *__restrict__ h0)
+{
+    __shared__ float tile[kTcnWideChunk * kTcnWidePitch];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int nwaves = kTcnThreads / 64;
+    const int K = KT ? KT : krt;
+    const int h = K / 2;
+    const int w0n = kTcnWideTile + 2 * h;       // staged positions: the tile and its halo
+    const int pitch = w0n | 1;
+    const int npass = (cout + A * nwaves - 1) / (A * nwaves);
+    for (int64_t tub = blockIdx.x; tub < ntub; tub += gridDim.x) {
+        const int L = tub_len[tub];
+        if (L <= 0) continue;
+        const int64_t base = tub_base[tub];
+        for (int64_t s64 = (int64_t)blockIdx.y * kTcnWideTile; s64 < L; s64 += (int64_t)gridDim.y * kTcnWideTile) {
+            const int s = (int)s64, org = s - h;           // series position of tile column 0
+            for (int pass = 0; pass < npass; ++pass) {
+                const int co0 = (pass * nwaves + wave) * A;
+                const bool live = co0 < cout;              // wave-uniform
+                tcn_f2 acc[A];
+                const float *wr[A];                        // rows of W0 [cout, cin*K]; channels past cout repeat the last one
+#pragma unroll
+                for (int a = 0; a < A; ++a) {
+                    const int co = min(co0 + a, cout - 1);
+                    wr[a] = w0 + (size_t)co * cin * K;
+                    acc[a] = b0[co];
+                }
+                for (int g0 = 0; g0 < cin; g0 += kTcnWideChunk) {
+                    const int cw = min(kTcnWideChunk, cin - g0);
+                    __syncthreads();                       // the previous chunk / pass / tile is read
+                    for (int sg = 0; sg < nseg; ++sg) {
+                        const TcnSeg S = segs[sg];
+                        const int qa = max(S.c0, g0), qb = min(S.c0 + S.width, g0 + cw);
+                        if (qa >= qb) continue;
+                        if (!S.rows) {
+                            const float *xc = x + base * nx + (int64_t)S.xq * L;
+                            float *tc = tile + (qa - g0) * pitch;
+                            for (int j = tid; j < w0n; j += kTcnThreads) {
+                                const int p = org + j;
+                                tc[j] = (p >= 0 && p < L) ? xc[p] : 0.0f;
+                            }
+                        } else {
+                            const int q = qa + (lane & 31);
+                            for (int j = 2 * wave + (lane >> 5); j < w0n; j += 2 * nwaves) {
+                                const int p = org + j;
+                                if (q < qb) {
+                                    float v = 0.0f;
+                                    if (p >= 0 && p < L)
+                                        v = tcn_row_elem(S.rows, S.dtype, (base + (int64_t)frames[base + p]) * S.width + (q - S.c0));
+                                    tile[(q - g0) * pitch + j] = v;
+                                }
+                            }
+                        }
+                    }
+                    __syncthreads();
+                    if (live) {
+                        const float *tp = tile + lane;
+                        int t = g0 * K, ci = 0;
+                        if (KT) {
+                            constexpr int KK = KT ? KT : 1;
+                            for (; ci + 2 <= cw; ci += 2, tp += 2 * pitch, t += 2 * KK) {
+                                tcn_f2 xv[2 * KK];
+#pragma unroll
+                                for (int k = 0; k < KK; ++k) {
+                                    xv[k] = tcn_f2{tp[k], tp[k + 64]};
+                                    xv[KK + k] = tcn_f2{tp[pitch + k], tp[pitch + k + 64]};
+                                }
+                                tcn_wide_mac<A, 2 * KK>(acc, wr, t, xv);
+                            }
+                            for (; ci < cw; ++ci, tp += pitch, t += KK) {
+                                tcn_f2 xv[KK];
+#pragma unroll
+                                for (int k = 0; k < KK; ++k) xv[k] = tcn_f2{tp[k], tp[k + 64]};
+                                tcn_wide_mac<A, KK>(acc, wr, t, xv);
+                            }
+                        } else {
+                            for (; ci < cw; ++ci, tp += pitch)
+                                for (int k = 0; k < K; ++k, ++t) {
+                                    const tcn_f2 xv[1] = {tcn_f2{tp[k], tp[k + 64]}};
+                                    tcn_wide_mac<A, 1>(acc, wr, t, xv);
+                                }
+                        }
+                    }
+                }
+                if (live) {
+#pragma unroll
+                    for (int a = 0; a < A; ++a) {
+                        if (co0 + a >= cout) break;
+                        float *ho = h0 + base * cout + (int64_t)(co0 + a) * L;
+                        const int p0 = s + lane, p1 = p0 + 64;
+                        if (p0 < L) ho[p0] = (relu && !(acc[a].x > 0.0f)) ? 0.0f : acc[a].x;
+                        if (p1 < L) ho[p1] = (relu && !(acc[a].y > 0.0f)) ? 0.0f : acc[a].y;
+                    }
+                }
             }
         }
     }

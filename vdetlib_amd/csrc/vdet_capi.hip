@@ -212,8 +212,8 @@ struct vdet_ctx {
     DevBuf ev_tab, ev_dtp, ev_dsc, ev_dslot, ev_bcnt, ev_boff, ev_key[2], ev_val[2], ev_hist;
     // device TCN (tcn_kernels.hpp): assembled channels, frame lists, tubelet descriptors, the global-path activations, and the
     // host tables its asynchronous calls read on the device (net parameters, frame offsets, the overlap call's tables)
-    DevBuf tcn_x, tcn_frames, tcn_base, tcn_len, tcn_scratch;
-    StagedTab tcn_params, tcn_foff, tcn_ovtab;      // (tcn_params.uploads: vdet_query 10)
+    DevBuf tcn_x, tcn_frames, tcn_base, tcn_len, tcn_scratch, tcn_h0;      // (tcn_h0: the wide first layer's output)
+    StagedTab tcn_params, tcn_foff, tcn_ovtab, tcn_segs;      // (tcn_params.uploads: vdet_query 10)
     bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
     bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
     StagedTab interp_tab;         // device interpolation (interp_kernels.hpp): frame offsets and the frame table of the last call
@@ -1459,7 +1459,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
-                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
+                      &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
                       &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
@@ -3051,45 +3051,68 @@ static int tcn_launch_net(vdet_ctx *c, const TcnNet &net, const float *d_x, cons
     return VDET_OK;
 }
 
-int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
-                          int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
-                          const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
-                          const double *d_gt_overlap, float *d_conv_score)
+// The wide first layer (tcn_wide_layer_kernel) over the assembled tubelets: h0 = layer 0 of `net` on the segment table.
+static void tcn_launch_wide(vdet_ctx *c, dim3 grid, const TcnLayer &l0, int relu, int nseg, int nx, int64_t ntub)
 {
-    if (!c) return VDET_EINVAL;
+    const TcnSeg *segs = c->tcn_segs.dev.as<TcnSeg>();
+    const float *params = c->tcn_params.dev.as<float>();
+#define VDET_TCN_WIDE(A, KT)                                                                                                       \
+    hipLaunchKernelGGL((tcn_wide_layer_kernel<A, KT>), grid, dim3(kTcnThreads), 0, c->stream, segs, nseg, l0.cin, l0.cout, l0.k, relu,  \
+                       params + l0.woff, params + l0.boff, c->tcn_x.as<float>(), nx, c->tcn_frames.as<int32_t>(),                 \
+                       c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(), ntub, c->tcn_h0.as<float>())
+    // accumulator blocking by width (8 channels per wave; 2 for layers of at most 8), taps unrolled for K = 3 and 5
+    if (l0.cout <= 8) {
+        if (l0.k == 3) VDET_TCN_WIDE(2, 3);
+        else if (l0.k == 5) VDET_TCN_WIDE(2, 5);
+        else VDET_TCN_WIDE(2, 0);
+    } else {
+        if (l0.k == 3) VDET_TCN_WIDE(8, 3);
+        else if (l0.k == 5) VDET_TCN_WIDE(8, 5);
+        else VDET_TCN_WIDE(8, 0);
+    }
+#undef VDET_TCN_WIDE
+}
+
+// THE device TCN over tracks.  segs == nullptr: the narrow call, every input an assembled channel and the whole net in
+// tcn_net_kernel.  Otherwise layer 0 reads the nseg segments (TcnSeg.c0 / xq filled here) and tcn_net_kernel runs the rest.
+static int tcn_tracks_impl(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const TcnChannels &ch,
+                           TcnSeg *segs, int nseg, int cin, const int64_t *h_frame_off, int64_t V, int64_t C, int T,
+                           const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score,
+                           int det_f64, const double *d_gt_overlap, float *d_conv_score)
+{
     int64_t Ft = 0, Fmax = 0;
     int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
     if (rc) return rc;
     if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
-    if (!h_channels || n_channels < 1 || n_channels > 16) return fail(c, VDET_EINVAL, "1 to 16 input channels");
-    TcnChannels ch{};
-    ch.n = n_channels;
     bool need_gt = false, need_det = false;
-    for (int q = 0; q < n_channels; ++q) {
-        if (h_channels[q] < 0 || h_channels[q] >= kChCount) return fail(c, VDET_EINVAL, "unknown input channel code %d", h_channels[q]);
-        ch.code[q] = h_channels[q];
-        need_gt = need_gt || h_channels[q] == kChGtOverlap || h_channels[q] == kChLabel;
-        need_det = need_det || h_channels[q] == kChDet;
+    for (int q = 0; q < ch.n; ++q) {
+        need_gt = need_gt || ch.code[q] == kChGtOverlap || ch.code[q] == kChLabel;
+        need_det = need_det || ch.code[q] == kChDet;
     }
     if (need_gt && !d_gt_overlap) return fail(c, VDET_EINVAL, "the net reads gt_overlaps / labels: a gt_overlap buffer is needed");
     const int64_t N = C * T * Ft;
-    if (N > 0x7FFFFFF0ll || N * n_channels > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
+    if (N > 0x7FFFFFF0ll || N * std::max(ch.n, 1) > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     if (T == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_anchors || (need_det && !d_det_score) || !d_conv_score) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     TcnNet net;
-    if ((rc = tcn_net_args(c, h_params, h_layers, n_layers, n_channels, net))) return rc;
+    if ((rc = tcn_net_args(c, h_params, h_layers, n_layers, cin, net))) return rc;
+    if (segs) {
+        if (N * net.l[0].cout > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
+        if ((rc = stage_table(c, c->tcn_segs, segs, (size_t)nseg * sizeof(TcnSeg)))) return rc;
+    }
     const int64_t *d_foff = nullptr;
     if (V > 1) {
         if ((rc = stage_table(c, c->tcn_foff, h_frame_off, (size_t)(V + 1) * 8))) return rc;
         d_foff = c->tcn_foff.dev.as<int64_t>();
     }
     const int64_t ntub = V * C * T;
-    HIPCHK(c, c->tcn_x.reserve((size_t)N * n_channels * 4));
+    HIPCHK(c, c->tcn_x.reserve((size_t)N * ch.n * 4));
     HIPCHK(c, c->tcn_frames.reserve((size_t)N * 4));
     HIPCHK(c, c->tcn_base.reserve((size_t)ntub * 8));
     HIPCHK(c, c->tcn_len.reserve((size_t)ntub * 4));
+    if (segs) HIPCHK(c, c->tcn_h0.reserve((size_t)N * net.l[0].cout * 4));
     {
         StageTimer tm(c, ST_OTHER);
         hipLaunchKernelGGL(tcn_assemble_kernel, dim3((unsigned)(C * T), (unsigned)V), dim3(64), 0, c->stream, d_tracks, d_ntracks, d_anchors,
@@ -3099,8 +3122,46 @@ int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_l
                            d_conv_score);
     }
     HIPCHK(c, hipGetLastError());
-    return tcn_launch_net(c, net, c->tcn_x.as<float>(), c->tcn_frames.as<int32_t>(), c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(),
+    if (!segs)
+        return tcn_launch_net(c, net, c->tcn_x.as<float>(), c->tcn_frames.as<int32_t>(), c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(),
+                              ntub, Fmax, d_conv_score);
+    {
+        StageTimer tm(c, ST_OTHER);
+        const TcnLayer &l0 = net.l[0];
+        const int64_t tiles = (Fmax + kTcnWideTile - 1) / kTcnWideTile;
+        const dim3 grid((unsigned)std::min<int64_t>(ntub, (int64_t)64 * c->n_cu), (unsigned)std::min<int64_t>(tiles, 1024));
+        const int relu = n_layers > 1;
+        tcn_launch_wide(c, grid, l0, relu, nseg, ch.n, ntub);
+    }
+    HIPCHK(c, hipGetLastError());
+    // layers 1 .. n-1 on h0 [cout0, L]; a one-layer net leaves the softmax alone (a net of zero layers)
+    TcnNet tail{};
+    tail.n = net.n - 1;
+    tail.cin = tail.maxc = net.l[0].cout;
+    for (int i = 0; i < tail.n; ++i) {
+        tail.l[i] = net.l[i + 1];
+        tail.maxc = std::max(tail.maxc, tail.l[i].cout);
+        tail.halo += tail.l[i].k / 2;
+    }
+    return tcn_launch_net(c, tail, c->tcn_h0.as<float>(), c->tcn_frames.as<int32_t>(), c->tcn_base.as<int64_t>(), c->tcn_len.as<int32_t>(),
                           ntub, Fmax, d_conv_score);
+}
+
+int vdet_tcn_tracks_batch(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
+                          int n_channels, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
+                          const double *d_gt_overlap, float *d_conv_score)
+{
+    if (!c) return VDET_EINVAL;
+    if (!h_channels || n_channels < 1 || n_channels > 16) return fail(c, VDET_EINVAL, "1 to 16 input channels");
+    TcnChannels ch{};
+    ch.n = n_channels;
+    for (int q = 0; q < n_channels; ++q) {
+        if (h_channels[q] < 0 || h_channels[q] >= kChCount) return fail(c, VDET_EINVAL, "unknown input channel code %d", h_channels[q]);
+        ch.code[q] = h_channels[q];
+    }
+    return tcn_tracks_impl(c, h_params, h_layers, n_layers, ch, nullptr, 0, n_channels, h_frame_off, V, C, T, d_tracks, d_ntracks,
+                           d_anchors, d_det_score, det_f64, d_gt_overlap, d_conv_score);
 }
 
 int vdet_tcn_tracks(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_channels,
@@ -3110,6 +3171,49 @@ int vdet_tcn_tracks(vdet_ctx *c, const float *h_params, const int32_t *h_layers,
     const int64_t foff[2] = {0, F};
     return vdet_tcn_tracks_batch(c, h_params, h_layers, n_layers, h_channels, n_channels, foff, 1, C, T, d_tracks, d_ntracks, d_anchors,
                                  d_det_score, det_f64, d_gt_overlap, d_conv_score);
+}
+
+int vdet_tcn_tracks_wide_batch(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_codes,
+                               const int32_t *h_widths, const void *const *h_rows, const int32_t *h_dtypes, int n_inputs,
+                               const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                               const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score, int det_f64,
+                               const double *d_gt_overlap, float *d_conv_score)
+{
+    if (!c) return VDET_EINVAL;
+    if (!h_codes || !h_widths || !h_rows || !h_dtypes) return fail(c, VDET_EINVAL, "null buffer");
+    if (n_inputs < 1 || n_inputs > kTcnMaxSegs) return fail(c, VDET_EINVAL, "1 to %d inputs", kTcnMaxSegs);
+    TcnChannels ch{};
+    TcnSeg segs[kTcnMaxSegs] = {};
+    int64_t cin = 0;
+    for (int i = 0; i < n_inputs; ++i) {
+        TcnSeg &sg = segs[i];
+        sg.c0 = (int32_t)cin;
+        if (h_codes[i] == -1) {
+            if (h_widths[i] < 1 || h_widths[i] > kTcnMaxChannels) return fail(c, VDET_EINVAL, "input %d: a wide blob has 1 to %d channels", i, kTcnMaxChannels);
+            if (h_dtypes[i] < 0 || h_dtypes[i] >= kTcnRowTypes) return fail(c, VDET_EINVAL, "input %d: unknown row dtype %d", i, h_dtypes[i]);
+            if (!h_rows[i]) return fail(c, VDET_EINVAL, "input %d: null rows", i);
+            sg.rows = h_rows[i]; sg.width = h_widths[i]; sg.dtype = h_dtypes[i];
+        } else {
+            if (h_codes[i] < 0 || h_codes[i] >= kChCount) return fail(c, VDET_EINVAL, "unknown input channel code %d", h_codes[i]);
+            if (h_widths[i] != 1) return fail(c, VDET_EINVAL, "input %d: an assembled channel has width 1", i);
+            sg.width = 1; sg.xq = ch.n;
+            ch.code[ch.n++] = h_codes[i];
+        }
+        cin += sg.width;
+    }
+    if (cin > kTcnMaxChannels) return fail(c, VDET_EINVAL, "a net has 1 to %d input channels", kTcnMaxChannels);
+    return tcn_tracks_impl(c, h_params, h_layers, n_layers, ch, segs, n_inputs, (int)cin, h_frame_off, V, C, T, d_tracks, d_ntracks,
+                           d_anchors, d_det_score, det_f64, d_gt_overlap, d_conv_score);
+}
+
+int vdet_tcn_tracks_wide(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, const int32_t *h_codes,
+                         const int32_t *h_widths, const void *const *h_rows, const int32_t *h_dtypes, int n_inputs, int64_t F, int64_t C,
+                         int T, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score,
+                         int det_f64, const double *d_gt_overlap, float *d_conv_score)
+{
+    const int64_t foff[2] = {0, F};
+    return vdet_tcn_tracks_wide_batch(c, h_params, h_layers, n_layers, h_codes, h_widths, h_rows, h_dtypes, n_inputs, foff, 1, C, T,
+                                      d_tracks, d_ntracks, d_anchors, d_det_score, det_f64, d_gt_overlap, d_conv_score);
 }
 
 int vdet_tcn_series_f32(vdet_ctx *c, const float *h_params, const int32_t *h_layers, int n_layers, int cin, const float *h_x,

@@ -748,7 +748,39 @@ def _tcn_check(tracks, ntracks, anchors, det_score, gt_overlap, V, C, T, n, code
             raise ValueError("tensors must be contiguous")
 
 
-def tcn_tracks(net, tracks, ntracks, anchors, det_score, gt_overlap=None, sync=True, ctx=None):
+_TCN_ROW_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}      # include/vdet_hip.h
+
+
+def _tcn_wide_args(net, wide, rows_of, device):
+    """The per-input host tables of vdet_tcn_tracks_wide[_batch] for ``net`` and the ``wide`` dict (blob name -> rows):
+    (params, shapes, codes of the one-channel inputs, (codes, widths, row pointers, dtypes) int32 / uint64 arrays, the row
+    tensors to keep alive).  ``rows_of(name, rows, ch)`` returns the checked flat tensor of one blob."""
+    from .vdet.tcn import TCNNet
+    if not isinstance(net, TCNNet):
+        raise ValueError("net must be a vdetlib_amd.vdet.tcn.TCNNet")
+    params, shapes = net.packed()
+    inputs = net.device_inputs(wide)
+    n = len(inputs)
+    codes, widths = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ptrs, dtypes = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+    keep = []
+    for i, ((name, _), (code, ch)) in enumerate(zip(net.inputs, inputs)):
+        codes[i], widths[i] = code, ch
+        if code != -1:
+            continue
+        rows = rows_of(name, wide[name], ch)
+        if rows.dtype not in _TCN_ROW_DTYPES:
+            raise ValueError("wide rows must be float32 / float16 / bfloat16 / float64; %r is %s" % (name, rows.dtype))
+        if not rows.is_cuda or rows.device != device:
+            raise ValueError("wide rows must live on the tracks' GPU; %r does not" % name)
+        if not rows.is_contiguous():
+            raise ValueError("wide rows must be contiguous; %r is not" % name)
+        ptrs[i], dtypes[i] = rows.data_ptr(), _TCN_ROW_DTYPES[rows.dtype]
+        keep.append(rows)
+    return params, shapes, codes[codes >= 0].copy(), (codes, widths, ptrs, dtypes), keep
+
+
+def tcn_tracks(net, tracks, ntracks, anchors, det_score, gt_overlap=None, sync=True, ctx=None, wide=None):
     """The tubelet temporal-convolution scorer (score_conv_cls, vdet/tubelet_cls.py:15-51) on device tubelets: channel
     assembly and every layer of ``net`` (a ``vdet.tcn.TCNNet`` whose inputs are one-channel blobs among det_scores,
     track_scores, anchors, abs_anchors, gt_overlaps, labels) in two launches for ALL tubelets of the video.
@@ -756,7 +788,15 @@ def tcn_tracks(net, tracks, ntracks, anchors, det_score, gt_overlap=None, sync=T
     tracks [C,T,F,5] f32 / ntracks [C] int32 / anchors [C,T,3] f32 (track_volume, nms_track_volume), det_score [C,T,F] f64
     or f32 (rescore_tracks' det_score or pooled), gt_overlap [C,T,F] f64 (tubelets_overlap) when the net reads it.
     Returns conv_score [C,T,F] f32: probs[1] per box, NaN where there is none -- bit for bit what ``score_conv_cls`` writes
-    on the protocol dicts of the same tensors; feeds ``DetEvaluator.add_tracks(..., scores=conv_score)`` as is."""
+    on the protocol dicts of the same tensors; feeds ``DetEvaluator.add_tracks(..., scores=conv_score)`` as is.
+
+    ``wide``: dict blob name -> rows [C,T,F,W] (f32 / f16 / bf16 / f64, contiguous, on the tracks' GPU) for the net's WIDE
+    blobs, e.g. ``{'all_scores': ..., 'feats': ...}``: channel q of the blob at series position j is entry q of the row of
+    the tubelet's j-th box; W must equal the blob's channel count.  Rows of holes and of slots behind ntracks are never
+    read.  The first layer then runs in a kernel of its own that reads the rows where they lie (three launches in all);
+    results stay bit-equal to ``TCNNet.forward`` on the same [Cin, L] input.  Without ``wide`` the call is the narrow one."""
+    if wide:
+        return _tcn_tracks_wide(net, tracks, ntracks, anchors, det_score, gt_overlap, sync, ctx, wide)
     params, shapes, codes = _tcn_net_args(net)
     if tracks.dim() != 4 or tracks.shape[3] != 5:
         raise ValueError("tracks must be float32 [C,T,F,5]")
@@ -780,6 +820,39 @@ def tcn_tracks(net, tracks, ntracks, anchors, det_score, gt_overlap=None, sync=T
     return out
 
 
+def _tcn_tracks_wide(net, tracks, ntracks, anchors, det_score, gt_overlap, sync, ctx, wide):
+    """``tcn_tracks`` with wide blobs (vdet_tcn_tracks_wide)."""
+    if not isinstance(wide, dict):
+        raise ValueError("wide must be a dict: blob name -> rows [C,T,F,W]")
+    if tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+
+    def rows_of(name, rows, ch):
+        if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (C, T, F, ch):
+            raise ValueError("wide[%r] must be a tensor [C,T,F,%d]: the blob's channel count is the rows' width" % (name, ch))
+        return rows
+
+    params, shapes, codes, (wcodes, widths, ptrs, dtypes), keep = _tcn_wide_args(net, wide, rows_of, tracks.device)
+    if tuple(ntracks.shape) != (C,) or tuple(anchors.shape) != (C, T, 3) or tuple(det_score.shape) != (C, T, F) or \
+            (gt_overlap is not None and tuple(gt_overlap.shape) != (C, T, F)):
+        raise ValueError("ntracks [C], anchors [C,T,3], det_score / gt_overlap [C,T,F]")
+    if F < 1:
+        raise ValueError("a video needs at least one frame")
+    tracks, ntracks, anchors, det_score = tracks.contiguous(), ntracks.contiguous(), anchors.contiguous(), det_score.contiguous()
+    gt_overlap = None if gt_overlap is None else gt_overlap.contiguous()
+    _tcn_check(tracks, ntracks, anchors, det_score, gt_overlap, 1, C, T, C * T * F, codes)
+    ctx = _ctx_for(tracks, ctx)
+    out = torch.empty((C, T, F), dtype=torch.float32, device=tracks.device)
+    ctx.check(ctx.lib.vdet_tcn_tracks_wide(
+        ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), wcodes.ctypes.data, widths.ctypes.data, ptrs.ctypes.data,
+        dtypes.ctypes.data, len(wcodes), F, C, T, tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), det_score.data_ptr(),
+        int(det_score.dtype == torch.float64), gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
+    if sync:
+        ctx.sync()
+    return out
+
+
 def _batch_flat(views, per):
     """The flat buffer behind video_batch's per-video views (they are consecutive slices of one allocation)."""
     total = sum(v.numel() for v in views)
@@ -789,11 +862,12 @@ def _batch_flat(views, per):
     return flat
 
 
-def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, ctx=None):
+def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, ctx=None, wide=None):
     """``tcn_tracks`` for every video of a ``video_batch`` result in ONE assembly launch and ONE network launch.
     ``series``: which re-scored series feeds det_scores ('det' or 'pooled'); gt_overlap: the flat f64 buffer
-    ``tubelets_overlap_batch`` returns.  Returns the list of per-video conv_score [C,T,F_v] f32 views."""
-    params, shapes, codes = _tcn_net_args(net)
+    ``tubelets_overlap_batch`` returns.  Returns the list of per-video conv_score [C,T,F_v] f32 views.
+    ``wide``: as in ``tcn_tracks``, in the batch layout: per blob one flat tensor [C*T*F_total, W] (video v's rows start at
+    box C*T*frame_off[v]) or the list of its consecutive per-video views [C,T,F_v,W]."""
     off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
     V = len(off) - 1
     if series not in ('det', 'pooled') or not batch_out.get(series):
@@ -801,6 +875,32 @@ def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, c
     tv, sv = batch_out['tracks'], batch_out[series]
     C, T = tv[0].shape[0], tv[0].shape[1]
     Ft = int(off[-1])
+    if wide:
+        if not isinstance(wide, dict):
+            raise ValueError("wide must be a dict: blob name -> rows")
+
+        def rows_of(name, rows, ch):
+            if isinstance(rows, (list, tuple)):
+                if len(rows) != V or any(not isinstance(r, torch.Tensor) or tuple(r.shape) != (C, T, int(off[v + 1] - off[v]), ch)
+                                         for v, r in enumerate(rows)):
+                    raise ValueError("wide[%r] must be one view [C,T,F_v,%d] per video" % (name, ch))
+                if any(not r.is_contiguous() or r.dtype != rows[0].dtype or r.device != rows[0].device for r in rows):
+                    raise ValueError("the views of wide[%r] must be contiguous, of one dtype and on one GPU" % name)
+                if any(b.data_ptr() != a.data_ptr() + a.numel() * a.element_size() for a, b in zip(rows, rows[1:])):
+                    raise ValueError("the views of wide[%r] are not consecutive slices of one buffer" % name)
+                try:
+                    return _batch_flat(rows, ch).view(C * T * Ft, ch)
+                except RuntimeError:           # neighbours by address, but not one allocation
+                    raise ValueError("the views of wide[%r] are not consecutive slices of one buffer" % name)
+            if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (C * T * Ft, ch):
+                raise ValueError("wide[%r] must be a tensor [C*T*F_total,%d] or its per-video views: the blob's channel count is "
+                                 "the rows' width" % (name, ch))
+            return rows
+
+        params, shapes, codes, wargs, _keep = _tcn_wide_args(net, wide, rows_of, tv[0].device)
+    else:
+        params, shapes, codes = _tcn_net_args(net)
+        wargs = None
     tracks, det = _batch_flat(tv, 5), _batch_flat(sv, 1)
     ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
     if tuple(ntracks.shape) != (V, C) or tuple(anchors.shape) != (V, C, T, 3):
@@ -808,10 +908,18 @@ def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, c
     _tcn_check(tracks, ntracks, anchors, det, gt_overlap, V, C, T, C * T * Ft, codes)
     ctx = _ctx_for(tracks, ctx)
     out = torch.empty((C * T * Ft,), dtype=torch.float32, device=tracks.device)
-    ctx.check(ctx.lib.vdet_tcn_tracks_batch(
-        ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), codes.ctypes.data, len(codes), off.ctypes.data, V, C, T,
-        tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), det.data_ptr(), int(det.dtype == torch.float64),
-        gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
+    if wargs is not None:
+        wcodes, widths, ptrs, dtypes = wargs
+        ctx.check(ctx.lib.vdet_tcn_tracks_wide_batch(
+            ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), wcodes.ctypes.data, widths.ctypes.data,
+            ptrs.ctypes.data, dtypes.ctypes.data, len(wcodes), off.ctypes.data, V, C, T, tracks.data_ptr(), ntracks.data_ptr(),
+            anchors.data_ptr(), det.data_ptr(), int(det.dtype == torch.float64),
+            gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
+    else:
+        ctx.check(ctx.lib.vdet_tcn_tracks_batch(
+            ctx.h, params.ctypes.data, shapes.ctypes.data, len(net.layers), codes.ctypes.data, len(codes), off.ctypes.data, V, C, T,
+            tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), det.data_ptr(), int(det.dtype == torch.float64),
+            gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
     if sync:
         ctx.sync()
     return [out[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]

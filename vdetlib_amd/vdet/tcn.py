@@ -87,7 +87,7 @@ class TCNNet(object):
 
     def device_channels(self):
         """The input list as channel codes of the device assembly; ValueError for blobs it cannot assemble
-        (``all_scores`` / ``feats``, multi-channel blobs, unknown names)."""
+        (``all_scores`` / ``feats``, multi-channel blobs, unknown names: those travel as rows, ``device_inputs``)."""
         codes = []
         for name, ch in self.inputs:
             if name not in self.DEVICE_CHANNELS or ch != 1:
@@ -95,6 +95,35 @@ class TCNNet(object):
                                  % (sorted(self.DEVICE_CHANNELS), name, ch))
             codes.append(self.DEVICE_CHANNELS[name])
         return np.array(codes, dtype=np.int32)
+
+    def device_inputs(self, wide):
+        """The input list for the wide entry points (vdet_tcn_tracks_wide): per input ``(code, channels)``, code -1 for
+        a blob whose name is in ``wide`` (per-box rows, e.g. ``all_scores`` / ``feats``), else its ``DEVICE_CHANNELS``
+        code.  ValueError: a device-channel name in ``wide``, a one-channel name with more than one channel, a blob
+        that is neither, more than 16 inputs, more than 4096 channels together."""
+        clash = sorted(set(wide) & set(self.DEVICE_CHANNELS))
+        if clash:
+            raise ValueError("%r is assembled on the device and cannot be a wide blob" % clash)
+        unused = sorted(set(wide) - set(n for n, _ in self.inputs))
+        if unused:
+            raise ValueError("the net has no blob named %r" % unused)
+        if len(self.inputs) > 16:
+            raise ValueError("the device TCN takes at most 16 inputs; the net has %d" % len(self.inputs))
+        out = []
+        for name, ch in self.inputs:
+            if name in wide:
+                if not 1 <= ch <= 4096:
+                    raise ValueError("a wide blob has 1 to 4096 channels; %r has %d" % (name, ch))
+                out.append((-1, ch))
+            elif name in self.DEVICE_CHANNELS and ch == 1:
+                out.append((self.DEVICE_CHANNELS[name], 1))
+            else:
+                raise ValueError("the device TCN assembles one-channel blobs named %s and reads wide blobs from the rows "
+                                 "passed as wide={name: rows}; got %r with %d channel(s) and no rows"
+                                 % (sorted(self.DEVICE_CHANNELS), name, ch))
+        if sum(ch for _, ch in out) > 4096:
+            raise ValueError("the device TCN takes at most 4096 input channels")
+        return out
 
     def forward_series(self, series, ctx=None):
         """The net on many series in ONE launch (vdet_tcn_series_f32): ``series`` is a list of float32 arrays

@@ -55,7 +55,10 @@ def score_conv_cls(score_proto, net):
     reshaped to (1, its channel count, 1, L) and filled with the float32 sequence; ``net.forward()['probs'][:, 1, :]``
     becomes ``box['conv_score']`` (python float) of the tubelet's boxes, in place; the returned proto is a shallow copy.
     ``net`` is any object with ``.blobs`` (name -> object with ``.shape``, ``.reshape(*dims)``, ``.data``) and
-    ``.forward()`` -- pycaffe's interface; ``vdetlib_amd.vdet.tcn.TCNNet`` is a gfx950 implementation of it."""
+    ``.forward()`` -- pycaffe's interface; ``vdetlib_amd.vdet.tcn.TCNNet`` is a gfx950 implementation of it.
+    A net with a wide blob (``all_scores`` / ``feats``, per-box lists) raises ValueError here exactly as in the reference:
+    the [L, ch] array of the boxes' rows does not broadcast into the (1, ch, 1, L) blob.  ``score_conv_cls_batched`` and
+    ``ops.tcn_tracks(wide=...)`` give such nets their intended input."""
     out = copy.copy(score_proto)
     print("{}: {} tubelet(s).".format(score_proto['video'], len(out['tubelets'])))
     blob_names = set(net.blobs.keys())
@@ -74,7 +77,11 @@ def score_conv_cls(score_proto, net):
 def score_conv_cls_batched(score_proto, net):
     """``score_conv_cls`` for a ``vdetlib_amd.vdet.tcn.TCNNet`` with ALL tubelets of the proto in one launch
     (``TCNNet.forward_series``): same channel assembly, same ``conv_score`` values bit for bit, same return value.  The
-    net's blobs are not touched (``score_conv_cls`` itself keeps the per-tubelet pycaffe contract)."""
+    net's blobs are not touched (``score_conv_cls`` itself keeps the per-tubelet pycaffe contract).
+
+    Wide blobs (``all_scores``, ``feats``: per-box lists, :35-41) are laid out [ch, L] by TRANSPOSING the [L, ch] array of
+    the boxes' rows: channel q at position j is entry q of box j.  ``score_conv_cls`` keeps the reference's behaviour for
+    them, which is to raise: it assigns the [L, ch] array to the (1, ch, 1, L) blob, and numpy cannot broadcast that."""
     from .tcn import TCNNet
     if not isinstance(net, TCNNet):
         raise TypeError("score_conv_cls_batched needs a vdetlib_amd.vdet.tcn.TCNNet (any pycaffe-like net: score_conv_cls)")
@@ -88,7 +95,12 @@ def score_conv_cls_batched(score_proto, net):
         for name, ch in net.inputs:
             if name not in channels:
                 raise ValueError("the net reads a blob %r that score_conv_cls does not assemble" % name)
-            rows.append(np.asarray(channels[name], dtype='float32').reshape(ch, length))
+            arr = np.asarray(channels[name], dtype='float32')
+            if arr.ndim == 2:       # a per-box field whose entries are lists ([L, ch]): channel q at position j = entry q of box j
+                if arr.shape != (length, ch):
+                    raise ValueError("blob %r has %d channels; its boxes carry rows of %d" % (name, ch, arr.shape[1]))
+                arr = arr.T
+            rows.append(np.ascontiguousarray(arr).reshape(ch, length))
         series.append(np.concatenate(rows, 0))
     for tubelet, probs in zip(out['tubelets'], net.forward_series(series)):
         for box, p in zip(tubelet['boxes'], probs):
