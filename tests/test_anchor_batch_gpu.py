@@ -252,3 +252,85 @@ def test_same_offsets_stage_the_table_once():
         assert tuple(sel[0].shape) == (3, 2, 3)
     finally:
         cx.close()
+
+
+# ---- video_batch's layout: one reader for every consumer (ops._batch_read / _batch_field / _batch_views) -----------------------
+def small_batch():
+    """videos of 1, 2 and 3 frames, B = 8, C = 2, T = 2: (offsets, boxes, scores, video_batch's dict, names, gt table)"""
+    from vdetlib_amd import eval as vev, ops
+    off, B, C, T = [0, 1, 3, 6], 8, 2, 2
+    boxes, scores = coherent_video(8500, off[-1], B, C)
+    tb, ts = g(boxes), g(scores)
+    vb = ops.video_batch(tb, ts, off, max_tracks=T)
+    names = ['v%d' % v for v in range(3)]
+    annots = [{'video': names[v], 'annotations': [{'id': '0', 'track': [
+        {'frame': f + 1, 'bbox': [int(x) for x in n_(vb['tracks'][v])[0, 0, f, :4]], 'class_index': 1, 'class': 'c1'}
+        for f in range(off[v + 1] - off[v]) if not np.isnan(n_(vb['tracks'][v])[0, 0, f, 0])]}]} for v in range(3)]
+    return off, tb, ts, vb, names, vev.gt_table_from_annots(annots)
+
+
+def one_allocation(d, keys):
+    from vdetlib_amd import ops
+    for k in keys:
+        assert ops._batch_flat(d[k], 1).data_ptr() == d[k][0].data_ptr(), k
+        assert len({x.untyped_storage().data_ptr() for x in d[k]}) == 1, k
+
+
+def test_per_video_clones_are_refused_on_the_host():
+    """per-video tensors of their own allocations are not the layout: the kernels would index past the first of them"""
+    from vdetlib_amd import ops
+    off, tb, ts, vb, names, gt = small_batch()
+    apart = lambda d, k: dict(d, **{k: [x.clone() for x in d[k]]})
+    ev = ops.DetEvaluator(gt, classes=[1, 2])
+    assert ev.add_batch(names, vb) > 0
+    dets = ops.nms_tracks_batch(vb, 'pooled')
+    assert ev.add_detections(names, dets) > 0
+    n = ev.stream()[0].numel()
+    calls = [lambda: ev.add_batch(names, apart(vb, 'pooled')), lambda: ev.add_batch(names, apart(vb, 'tboxes')),
+             lambda: ev.add_batch(names, apart(vb, 'tracks')),
+             lambda: ev.add_detections(names, apart(dets, 'score')), lambda: ev.add_detections(names, apart(dets, 'tracks')),
+             lambda: ops.tubelets_overlap_batch(ev, names, apart(vb, 'tracks')),
+             lambda: ops.tubelets_overlap_batch(ev, names, apart(vb, 'tboxes'), use_tboxes=True),
+             lambda: ops.anchor_propagate_tracks_batch(apart(vb, 'tracks'), tb, ts)]
+    for i, call in enumerate(calls):
+        with pytest.raises(ValueError, match="consecutive"):
+            call()
+        assert ev.stream()[0].numel() == n, i
+    assert ev.add_batch(names, vb) > 0 and ev.stream()[0].numel() > n           # the evaluator still works
+
+
+def test_chain_of_batch_stages_equals_the_single_video_calls():
+    """video_batch -> rescore_tubelets_batch -> merge_tracks_batch -> nms_tracks_batch -> add_detections: every stage hands on
+    a dict the reader accepts, every field one allocation, per video the bits of the single-video calls"""
+    import torch
+    from vdetlib_amd import ops
+    off, tb, ts, vb, names, gt = small_batch()
+    rs = ops.rescore_tubelets_batch(vb, tb, ts)
+    mg = ops.merge_tracks_batch(rs, rs, 'combine')
+    dets = ops.nms_tracks_batch(mg, 'pooled')
+    for d, keys in ((vb, ('tracks', 'det', 'pooled', 'tboxes')), (rs, ('tracks', 'det', 'pooled', 'tboxes', 'src')),
+                    (mg, ('tracks', 'det', 'pooled', 'tboxes')), (dets, ('tracks', 'score', 'src'))):
+        b = ops._batch_read(d, need=('anchors',) if d is not dets else ())
+        assert b.V == 3 and b.Ft == 6 and b.tracks.data_ptr() == d['tracks'][0].data_ptr()
+        one_allocation(d, keys)
+    assert 'src' not in vb and rs['tracks'][0] is vb['tracks'][0]                # a new dict; the input is left alone
+    eb, e1 = ops.DetEvaluator(gt, classes=[1, 2]), ops.DetEvaluator(gt, classes=[1, 2])
+    for v in range(3):
+        sl = slice(off[v], off[v + 1])
+        tr, nt, an = vb['tracks'][v], vb['ntracks'][v], vb['anchors'][v]
+        single = ops.rescore_tubelets(tr, nt, tb[sl], ts[sl])
+        for k, x in zip(('det', 'pooled', 'tboxes', 'src'), single):
+            assert same(n_(rs[k][v]), n_(x)), (v, k)
+        a = dict(tracks=tr, ntracks=nt, anchors=an, series=single[:2], tboxes=single[2])
+        m1 = ops.merge_tracks(a, a, 'combine')
+        for k, x in (('tracks', m1['tracks']), ('det', m1['series'][0]), ('pooled', m1['series'][1]), ('tboxes', m1['tboxes']),
+                     ('anchors', m1['anchors']), ('ntracks', m1['ntracks'])):
+            assert same(n_(mg[k][v]), n_(x)), (v, k)
+        d1 = ops.nms_tracks(m1, score=1)
+        for k in ('tracks', 'score', 'src', 'ntracks'):
+            assert same(n_(dets[k][v]), n_(d1[k])), (v, k)
+        assert same(n_(dets['cnt'][:, sl]), n_(d1['cnt'])), v
+        e1.add_detections(names[v], d1)
+    assert eb.add_detections(names, dets) == e1.stream()[0].numel() > 0
+    for x, y in zip(eb.stream(raw=True), e1.stream(raw=True)):
+        assert torch.equal(x, y)

@@ -6,6 +6,7 @@ A c2-size video (300 frames x 10k boxes x 200 classes) cannot travel as protocol
 ``vdetlib_amd.vdet`` is built on.
 """
 import ctypes
+import itertools
 
 import numpy as np
 import torch
@@ -286,20 +287,154 @@ def volume_pass(scores, window=3, taps=None, pad_max=-1e5, bias=0.0, pad_conv=0.
     return out_m, out_c
 
 
-def _frame_offsets(frame_off, F):
+def _frame_offsets(frame_off, F=None):
     off = np.ascontiguousarray(frame_off, dtype=np.int64).reshape(-1)
-    if off.size < 2 or off[0] != 0 or off[-1] != F or np.any(np.diff(off) <= 0):
-        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V] = F")
+    o = off.tolist()
+    if len(o) < 2 or o[0] != 0 or (F is not None and o[-1] != F) or any(a >= e for a, e in zip(o, o[1:])):
+        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V]" + ("" if F is None else " = F"))
     return off
+
+
+class _Batch(object):
+    """The parsed form of a dict in ``video_batch``'s layout: what ``_batch_read`` returns."""
+    __slots__ = ('off', 'o', 'V', 'Ft', 'C', 'T', 'tracks', 'ntracks', 'anchors', 'device')
+
+
+_F32, _F64 = (torch.float32,), (torch.float64,)
+_F32_F64 = _F32 + _F64
+
+
+def _same_gpu(tensors, who, device=None):
+    """ValueError unless every tensor lives on one GPU (``device``, or the first tensor's).  Called AFTER every layout check, so
+    that a wrong layout fails as a layout whatever memory it is in."""
+    device = tensors[0].device if device is None else device
+    for t in tensors:
+        if not t.is_cuda or t.device != device:
+            raise ValueError("%s must live on the same GPU (vdetlib_amd has no CPU path)" % who)
+
+
+def _batch_views(flat, off, C, T, per):
+    """The per-video views of one flat buffer in ``video_batch``'s layout (``_batch_read``): [C,T,F_v] for ``per`` == 1, else
+    [C,T,F_v,per]; video v starts at element C*T*per*off[v].  Each view is made by ONE as_strided call with the strides of a
+    contiguous tensor of its shape (torch counts an empty axis as 1: max(T, 1)) -- the same tensor as
+    ``flat[n*off[v]:n*off[v+1]].view(C, T, F_v, per)`` at half the host time, which the batches of many videos need."""
+    o, base = off.tolist(), flat.storage_offset()
+    shape, strides = ((per,), (per, 1)) if per > 1 else ((), (1,))
+    return [flat.as_strided((C, T, e - a) + shape, (max(T, 1) * (e - a) * per, (e - a) * per) + strides, base + C * T * per * a)
+            for a, e in zip(o, o[1:])]
+
+
+def _batch_field(b, views, per, dtypes, name, who, T=None, gather=False, axis=False, shapes=True):
+    """One field of a dict in ``video_batch``'s layout, checked against the batch ``b`` (``_batch_read``) and returned as its
+    flat buffer, with no copy: ``views`` must be b.V tensors of ONE of ``dtypes``, view v [C,T,F_v] for ``per`` == 1 (with
+    ``axis``: [C,T,F_v,1], the rows of a wide blob), else [C,T,F_v,per], with ``T`` slots (default b.T); every view contiguous
+    and exactly at element C*T*per*off[v] behind the first, all in one allocation (so on one device).  ``gather``: views of the
+    right shapes and dtype that are not such slices are copied into one buffer instead of refused.  One pass over the views;
+    the text of an error is made only when there is one."""
+    if T is None:
+        T = b.T
+    C, o = b.C, b.o
+    four = axis or per > 1
+    ok = isinstance(views, (list, tuple)) and len(views) == b.V and isinstance(views[0], torch.Tensor) and views[0].dtype in dtypes
+    if ok:
+        first = views[0]
+        dtype, p0, step, near = first.dtype, first.data_ptr(), C * T * per * first.element_size(), True
+        for x, a, e in zip(views, o, o[1:]):
+            if not isinstance(x, torch.Tensor) or x.dtype != dtype or \
+                    (shapes and x.shape != ((C, T, e - a, per) if four else (C, T, e - a))):
+                ok = False
+                break
+            near = near and x.is_contiguous() and x.data_ptr() == p0 + step * a
+    if not ok:
+        raise ValueError(_batch_field_error(b, views, per, dtypes, name, who, T, four, shapes))
+    if near:
+        try:
+            return torch.as_strided(first, (C * T * per * b.Ft,), (1,))
+        except RuntimeError:       # neighbours by address, but past the end of the first view's storage
+            pass
+    if not gather:
+        raise ValueError("%s: the views of %s are not contiguous, consecutive slices of one allocation" % (who, name))
+    return torch.cat([x.reshape(-1) for x in views])
+
+
+def _batch_field_error(b, views, per, dtypes, name, who, T, four, shapes):
+    what = "%s: %s must be %s [C,T,F_v%s] views in video_batch's layout, one per video" % (
+        who, name, ' / '.join(str(d).replace('torch.', '') for d in dtypes), ',%d' % per if four else '')
+    if isinstance(views, (list, tuple)) and len(views) == b.V:
+        for v, x in enumerate(views):
+            want = (b.C, T, b.o[v + 1] - b.o[v]) + ((per,) if four else ())
+            if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.dtype != views[0].dtype or (shapes and x.shape != want):
+                return "%s; %s[%d] must be %s of the one dtype, not %s" % (
+                    what, name, v, list(want), "%s %s" % (x.dtype, list(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__)
+    return what
+
+
+def _batch_flat(views, per=None):
+    """The flat buffer behind per-video views in ``video_batch``'s layout when there is no batch to check their shapes
+    against (``per`` is not used): ``_batch_field``'s checks with every view beginning where its predecessor ends."""
+    if not isinstance(views, (list, tuple)) or not views or not all(isinstance(x, torch.Tensor) for x in views):
+        raise ValueError("not a video_batch result: the per-video views must be a list of tensors")
+    b = _Batch()
+    b.o = [0] + list(itertools.accumulate(x.numel() for x in views))
+    b.V, b.Ft, b.C, b.T = len(views), b.o[-1], 1, 1
+    return _batch_field(b, views, 1, (views[0].dtype,), 'the per-video list', 'not a video_batch result', shapes=False)
+
+
+def _batch_read(bo, who='batch_out', need=()):
+    """The one reader of "a dict in ``video_batch``'s layout", the form in which ``video_batch``, ``track_from_anchors_batch``,
+    ``anchor_propagate_tracks_batch``, ``tcn_tracks_batch``, ``interpolate_tracks_batch``, ``merge_tracks_batch``,
+    ``nms_tracks_batch``, ``rescore_tubelets_batch``, ``tubelets_overlap_batch`` and ``DetEvaluator.add_batch`` /
+    ``add_detections`` hand V videos' tubelets to each other.  The layout:
+      frame_off   [V+1] offsets, 0 = o[0] < o[1] < ... < o[V] = F_total: video v owns the frames o[v] .. o[v+1] (F_v of them);
+      tracks      a list of V views [C,T,F_v,5] f32;  det / pooled / score / ... [C,T,F_v] and tboxes [C,T,F_v,4] likewise.
+                  The views of one field are CONSECUTIVE slices of ONE flat allocation: video v starts at element
+                  C*T*per*o[v] (per = 5, 1, 4: the width of a box's entry), which is how the kernels index the field from one
+                  pointer.  ``_batch_views`` builds such lists, ``_batch_field`` checks one and returns the flat buffer;
+      ntracks     [V,C] int32;  anchors [V,C,T,3] f32.
+    It is a plain dict: callers may build one by hand.  Everything is CHECKED BEFORE ANY LAUNCH, on the host and in this order:
+    the dict has ``tracks``, ``ntracks``, ``frame_off`` and the keys of ``need`` (an empty list is a missing field); frame_off;
+    V <= 65535; tracks (shapes, dtype, consecutive views); ntracks; anchors when needed.  ValueError otherwise -- a view that is
+    not where the layout puts it would be read from the wrong memory, or past the end of it.  Returns a ``_Batch``: off
+    (contiguous int64), o (off as a list of ints), V, Ft, C, T, the flat tracks, ntracks (contiguous), anchors (contiguous, None
+    unless needed) and the device."""
+    keys = ('tracks', 'ntracks', 'frame_off') + need
+    missing = not isinstance(bo, dict)
+    for k in () if missing else keys:
+        x = bo.get(k)
+        missing = missing or x is None or (isinstance(x, (list, tuple)) and not x)
+    if missing:
+        raise ValueError("%s is not a video_batch result: it must be a dict in video_batch's layout with %s" % (who, ', '.join(keys)))
+    b = _Batch()
+    b.off = _frame_offsets(bo['frame_off'])
+    b.o = b.off.tolist()
+    V, tv = len(b.o) - 1, bo['tracks']
+    if V > 65535:
+        raise ValueError("at most 65535 videos in one call")
+    bad = "%s is not a video_batch result" % who
+    if not isinstance(tv, (list, tuple)) or not isinstance(tv[0], torch.Tensor) or tv[0].dim() != 4:
+        raise ValueError("%s: tracks must be a list of float32 [C,T,F_v,5] views" % bad)
+    shape = tv[0].shape
+    b.V, b.Ft, b.C, b.T, b.device = V, b.o[-1], shape[0], shape[1], tv[0].device
+    b.tracks = _batch_field(b, tv, 5, _F32, 'tracks', bad)
+    ntracks = bo['ntracks']
+    if not isinstance(ntracks, torch.Tensor) or ntracks.dtype != torch.int32 or ntracks.shape != (V, b.C):
+        raise ValueError("%s: ntracks must be int32 [V,C]" % bad)
+    b.ntracks, b.anchors = ntracks.contiguous(), None
+    if 'anchors' in need:
+        anchors = bo['anchors']
+        if not isinstance(anchors, torch.Tensor) or anchors.dtype != torch.float32 or anchors.shape != (V, b.C, b.T, 3):
+            raise ValueError("%s: anchors float32 [V,C,T,3] are needed" % bad)
+        b.anchors = anchors.contiguous()
+    return b
 
 
 def video_batch(boxes, scores, frame_off, nms_thres=0.3, thres=0.0, max_tracks=10, link_thres=0.5, max_frames=0, cap=None,
                 nms=True, rescore=True, overlap_thres=0.7, window=3, sync=True, ctx=None, pad=True):
     """V small videos in ONE call (include/vdet_hip.h: vdet_video_batch): boxes [F,B,4] / scores [F,B,C] hold the frames
     of all videos one after the other, ``frame_off`` [V+1] their frame ranges.  Per video the results are what
-    ``nms_track_volume`` + ``rescore_tracks`` return for it alone.  Returns a dict:
-      keep_idx [F,C,cap] / keep_cnt [F,C] (nms), anchors [V,C,T,3], ntracks [V,C], and per-video VIEWS
-      tracks[v] [C,T,F_v,5], det[v] / pooled[v] [C,T,F_v] f64, tboxes[v] [C,T,F_v,4] (rescore)."""
+    ``nms_track_volume`` + ``rescore_tracks`` return for it alone.  Returns a dict in the batch layout (``_batch_read``):
+    tracks, det / pooled f64 and tboxes (rescore; else empty lists), anchors, ntracks, frame_off -- plus keep_idx [F,C,cap] /
+    keep_cnt [F,C] (nms)."""
     if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
         raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
     boxes, scores = boxes.contiguous(), scores.contiguous()
@@ -334,15 +469,8 @@ def video_batch(boxes, scores, frame_off, nms_thres=0.3, thres=0.0, max_tracks=1
 
     _finish(ctx, launch, sync, reset=reset)
     out = dict(keep_idx=keep_idx, keep_cnt=keep_cnt, anchors=anchors[:, :, :T], ntracks=ntracks, frame_off=off)
-    tv, dv, pv, bv = [], [], [], []
-    for v in range(V):
-        f0, fv = int(off[v]), int(off[v + 1] - off[v])
-        tv.append(tracks[C * T * 5 * f0: C * T * 5 * (f0 + fv)].view(C, T, fv, 5))
-        if rescore:
-            dv.append(det[C * T * f0: C * T * (f0 + fv)].view(C, T, fv))
-            pv.append(pooled[C * T * f0: C * T * (f0 + fv)].view(C, T, fv))
-            bv.append(tboxes[C * T * 4 * f0: C * T * 4 * (f0 + fv)].view(C, T, fv, 4))
-    out.update(tracks=tv, det=dv, pooled=pv, tboxes=bv)
+    views = lambda flat, per: _batch_views(flat, off, C, T, per) if flat is not None else []
+    out.update(tracks=views(tracks, 5), det=views(det, 1), pooled=views(pooled, 1), tboxes=views(tboxes, 4))
     return out
 
 
@@ -638,8 +766,8 @@ def track_from_anchors_batch(boxes, frame_off, anchor_frames, anchor_boxes, anch
     ``frame_off`` [V+1] their ranges; anchor_frames [V,C,T] int32 (1-based INSIDE the video, 0 = empty slot), anchor_boxes
     [V,C,T,4] f32, anchor_scores [V,C,T] f32 or None (``top_anchors(frame_off=...)``'s outputs).  A chain stops at its own
     video's first and last frame; per video the rows are bit for bit ``track_from_anchors``' on that video alone.
-    Returns a dict in ``video_batch``'s shape: tracks[v] views [C,T,F_v,5] of one flat buffer (video v at element
-    C*T*5*frame_off[v]), anchors [V,C,T,3], ntracks [V,C], frame_off.  ValueError for an anchor frame outside 0..F_v."""
+    Returns a dict in ``video_batch``'s layout (``_batch_read``): tracks, anchors, ntracks, frame_off.  ValueError for an anchor
+    frame outside 0..F_v."""
     if boxes.dtype != torch.float32 or anchor_boxes.dtype != torch.float32 or \
             (anchor_scores is not None and anchor_scores.dtype != torch.float32):
         raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
@@ -675,35 +803,24 @@ def track_from_anchors_batch(boxes, frame_off, anchor_frames, anchor_boxes, anch
         tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
     if sync:
         ctx.sync()
-    tv = [tracks[C * T * 5 * int(off[v]): C * T * 5 * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v]), 5) for v in range(V)]
-    return dict(tracks=tv, anchors=anchors, ntracks=ntracks, frame_off=off)
+    return dict(tracks=_batch_views(tracks, off, C, T, 5), anchors=anchors, ntracks=ntracks, frame_off=off)
 
 
 def anchor_propagate_tracks_batch(batch_out, boxes, scores, sync=True, ctx=None):
     """``anchor_propagate_tracks`` for every video of a ``track_from_anchors_batch`` (or ``video_batch``) result in ONE
-    launch; boxes [F,B,4] / scores [F,B,C] f32 are the batch's volume.  Returns (det, best): det[v] views [C,T,F_v] f64 of one
-    flat buffer -- also stored as ``batch_out['det']``, where ``tcn_tracks_batch(series='det')`` reads it -- and best
-    [V,C,T] int32.  Per video both equal the single-video call's."""
-    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
-    V = len(off) - 1
-    tv = batch_out['tracks']
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or tv[0].dtype != torch.float32:
+    launch; boxes [F,B,4] / scores [F,B,C] f32 are the batch's volume.  Returns (det, best): det, the [C,T,F_v] f64 views of
+    the batch layout (``_batch_read``) -- also stored as ``batch_out['det']``, where ``tcn_tracks_batch(series='det')`` reads
+    it -- and best [V,C,T] int32.  Per video both equal the single-video call's."""
+    b = _batch_read(batch_out, need=('anchors',))
+    off, V, F, C, T, tracks, ntracks, anchors = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks, b.anchors
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
         raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    F = int(off[-1])
     if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
         raise ValueError("boxes must be [F,B,4] over all frames of the batch")
     B = boxes.shape[1]
     if tuple(scores.shape) != (F, B, C):
         raise ValueError("scores must be [F,B,C]")
-    tracks = _batch_flat(tv, 5)
-    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
-    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or \
-            tuple(anchors.shape) != (V, C, T, 3) or tracks.numel() != C * T * F * 5:
-        raise ValueError("not a track_from_anchors_batch / video_batch result")
-    for t in (tracks, ntracks, anchors, scores):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("the batch result, boxes and scores must live on the same GPU")
+    _same_gpu((boxes, scores, tracks, ntracks, anchors), "the batch result, boxes and scores")
     ctx = _ctx_for(boxes, ctx)
     dev = boxes.device
     det = torch.empty((C * T * F,), dtype=torch.float64, device=dev)
@@ -713,7 +830,7 @@ def anchor_propagate_tracks_batch(batch_out, boxes, scores, sync=True, ctx=None)
         scores.contiguous().data_ptr(), off.ctypes.data, V, B, C, T, det.data_ptr(), best.data_ptr()))
     if sync:
         ctx.sync()
-    dv = [det[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
+    dv = _batch_views(det, off, C, T, 1)
     batch_out['det'] = dv
     return dv, best
 
@@ -853,58 +970,34 @@ def _tcn_tracks_wide(net, tracks, ntracks, anchors, det_score, gt_overlap, sync,
     return out
 
 
-def _batch_flat(views, per):
-    """The flat buffer behind video_batch's per-video views (they are consecutive slices of one allocation)."""
-    total = sum(v.numel() for v in views)
-    flat = torch.as_strided(views[0], (total,), (1,))
-    if views[-1].data_ptr() != views[0].data_ptr() + (total - views[-1].numel()) * views[0].element_size():
-        raise ValueError("not a video_batch result: the per-video views are not consecutive")
-    return flat
-
-
 def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, ctx=None, wide=None):
-    """``tcn_tracks`` for every video of a ``video_batch`` result in ONE assembly launch and ONE network launch.
-    ``series``: which re-scored series feeds det_scores ('det' or 'pooled'); gt_overlap: the flat f64 buffer
+    """``tcn_tracks`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in ONE assembly launch and ONE
+    network launch.  ``series``: which re-scored series feeds det_scores ('det' or 'pooled'); gt_overlap: the flat f64 buffer
     ``tubelets_overlap_batch`` returns.  Returns the list of per-video conv_score [C,T,F_v] f32 views.
-    ``wide``: as in ``tcn_tracks``, in the batch layout: per blob one flat tensor [C*T*F_total, W] (video v's rows start at
-    box C*T*frame_off[v]) or the list of its consecutive per-video views [C,T,F_v,W]."""
-    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
-    V = len(off) - 1
+    ``wide``: as in ``tcn_tracks``, in the batch layout: per blob one flat tensor [C*T*F_total, W], or the list of its
+    per-video views [C,T,F_v,W], checked like every field of the layout."""
+    b = _batch_read(batch_out, need=('anchors',))
+    off, V, Ft, C, T, tracks, ntracks, anchors = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks, b.anchors
     if series not in ('det', 'pooled') or not batch_out.get(series):
         raise ValueError("series must be 'det' or 'pooled' of a video_batch result that ran the re-scoring")
-    tv, sv = batch_out['tracks'], batch_out[series]
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    Ft = int(off[-1])
+    det = _batch_field(b, batch_out[series], 1, _F32_F64, series, 'batch_out')
     if wide:
         if not isinstance(wide, dict):
             raise ValueError("wide must be a dict: blob name -> rows")
 
         def rows_of(name, rows, ch):
             if isinstance(rows, (list, tuple)):
-                if len(rows) != V or any(not isinstance(r, torch.Tensor) or tuple(r.shape) != (C, T, int(off[v + 1] - off[v]), ch)
-                                         for v, r in enumerate(rows)):
-                    raise ValueError("wide[%r] must be one view [C,T,F_v,%d] per video" % (name, ch))
-                if any(not r.is_contiguous() or r.dtype != rows[0].dtype or r.device != rows[0].device for r in rows):
-                    raise ValueError("the views of wide[%r] must be contiguous, of one dtype and on one GPU" % name)
-                if any(b.data_ptr() != a.data_ptr() + a.numel() * a.element_size() for a, b in zip(rows, rows[1:])):
-                    raise ValueError("the views of wide[%r] are not consecutive slices of one buffer" % name)
-                try:
-                    return _batch_flat(rows, ch).view(C * T * Ft, ch)
-                except RuntimeError:           # neighbours by address, but not one allocation
-                    raise ValueError("the views of wide[%r] are not consecutive slices of one buffer" % name)
+                return _batch_field(b, rows, ch, tuple(_TCN_ROW_DTYPES), "wide[%r]" % name, 'tcn_tracks_batch',
+                                    axis=True).view(C * T * Ft, ch)
             if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != (C * T * Ft, ch):
                 raise ValueError("wide[%r] must be a tensor [C*T*F_total,%d] or its per-video views: the blob's channel count is "
                                  "the rows' width" % (name, ch))
             return rows
 
-        params, shapes, codes, wargs, _keep = _tcn_wide_args(net, wide, rows_of, tv[0].device)
+        params, shapes, codes, wargs, _keep = _tcn_wide_args(net, wide, rows_of, b.device)
     else:
         params, shapes, codes = _tcn_net_args(net)
         wargs = None
-    tracks, det = _batch_flat(tv, 5), _batch_flat(sv, 1)
-    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
-    if tuple(ntracks.shape) != (V, C) or tuple(anchors.shape) != (V, C, T, 3):
-        raise ValueError("not a video_batch result")
     _tcn_check(tracks, ntracks, anchors, det, gt_overlap, V, C, T, C * T * Ft, codes)
     ctx = _ctx_for(tracks, ctx)
     out = torch.empty((C * T * Ft,), dtype=torch.float32, device=tracks.device)
@@ -922,7 +1015,7 @@ def tcn_tracks_batch(net, batch_out, series='det', gt_overlap=None, sync=True, c
             gt_overlap.data_ptr() if gt_overlap is not None else None, out.data_ptr()))
     if sync:
         ctx.sync()
-    return [out[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
+    return _batch_views(out, off, C, T, 1)
 
 
 def _interp_frames(frames, off, num_frames):
@@ -1050,37 +1143,22 @@ def interpolate_tracks_batch(batch_out, frames, num_frames, sync=True, ctx=None)
     """``interpolate_tracks`` for every video of a ``video_batch`` result that was computed on SAMPLED frames, in one
     launch: ``frames`` flat [Fs_total] ints (the dense 1-based frame of every row, ascending inside each video; None:
     identity), ``num_frames`` [V] the dense frame counts.  The re-scored ``det`` / ``pooled`` series and ``tboxes`` are
-    interpolated when the batch has them (else the track boxes, no series).  Returns a dict in ``video_batch``'s layout on
-    the DENSE axis -- ``tracks`` / ``det`` / ``pooled`` / ``tboxes`` as consecutive per-video views of one allocation,
-    ``anchors`` [V,C,T,3], ``ntracks`` [V,C], the dense ``frame_off`` -- plus ``boxes64`` and ``anchor`` views, so that
-    ``tcn_tracks_batch``, ``tubelets_overlap_batch(use_tboxes=True)`` and ``DetEvaluator.add_batch`` take it unchanged."""
-    soff = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
-    V = len(soff) - 1
-    tv = batch_out['tracks']
-    if V < 1 or len(tv) != V or soff[0] != 0 or np.any(np.diff(soff) <= 0):
-        raise ValueError("not a video_batch result")
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    tracks = _batch_flat(tv, 5)
-    ntracks, anchors = batch_out['ntracks'].contiguous(), batch_out['anchors'].contiguous()
-    if tracks.dtype != torch.float32 or tracks.numel() != C * T * int(soff[-1]) * 5 or ntracks.dtype != torch.int32 or \
-            tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or tuple(anchors.shape) != (V, C, T, 3):
-        raise ValueError("not a video_batch result")
+    interpolated when the batch has them (else the track boxes, no series).  Returns a dict in the same layout
+    (``_batch_read``) on the DENSE axis -- ``tracks``, ``det`` / ``pooled`` / ``tboxes`` (empty lists without re-scoring),
+    ``anchors``, ``ntracks``, the dense ``frame_off`` -- plus ``boxes64`` and ``anchor`` views."""
+    b = _batch_read(batch_out, need=('anchors',))
+    soff, V, Fs, C, T, tracks, ntracks, anchors = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks, b.anchors
     rescored = bool(batch_out.get('pooled'))
-    series = _interp_series((_batch_flat(batch_out['det'], 1), _batch_flat(batch_out['pooled'], 1)) if rescored else (),
-                            C * T * int(soff[-1]), tracks.device)
-    boxes = _batch_flat(batch_out['tboxes'], 4) if rescored else None
-    for x in (ntracks, anchors) + (() if boxes is None else (boxes,)):
-        if not x.is_cuda or x.device != tracks.device:
-            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    field = lambda k, per, dtypes: _batch_field(b, batch_out.get(k), per, dtypes, k, 'batch_out')
+    series = (field('det', 1, _F32_F64), field('pooled', 1, _F32_F64)) if rescored else ()
+    boxes = field('tboxes', 4, _F32) if rescored else None
+    series = _interp_series(series, C * T * Fs, b.device)
+    _same_gpu((tracks, ntracks, anchors) + (() if boxes is None else (boxes,)), "tracks, ntracks, anchors, boxes and the series")
     fr, nf = _interp_frames(frames, soff, num_frames)
     doff = np.concatenate([[0], np.cumsum(nf)]).astype(np.int64)
     ctx = _ctx_for(tracks, ctx)
     out_tr, b64, tb, ser, anchor, oan = _interp_call(ctx, False, soff, doff, fr, C, T, tracks, boxes, ntracks, anchors, series, sync)
-
-    def views(flat, per):
-        shape = (lambda fv: (C, T, fv, per)) if per > 1 else (lambda fv: (C, T, fv))
-        return [flat[C * T * per * int(doff[v]): C * T * per * int(doff[v + 1])].view(*shape(int(doff[v + 1] - doff[v]))) for v in range(V)]
-
+    views = lambda flat, per: _batch_views(flat, doff, C, T, per)
     out = dict(tracks=views(out_tr, 5), tboxes=views(tb, 4), boxes64=views(b64, 4), anchor=views(anchor, 1), anchors=oan,
                ntracks=ntracks, frame_off=doff, det=[], pooled=[])
     if rescored:
@@ -1197,82 +1275,31 @@ def merge_tracks(a, b, scheme='combine', sync=True, ctx=None):
     return out
 
 
-def _merge_flat(views, per, who):
-    try:
-        return _batch_flat(views, per)
-    except RuntimeError:       # (as_strided past the end of the first view's storage)
-        raise ValueError("%s: the per-video views are not consecutive slices of one allocation" % who)
-
-
-def _merge_batch_set(bo, off, who):
-    """One side of merge_tracks_batch, checked: (flat tracks, ntracks, anchors, C, T)."""
-    if not isinstance(bo, dict) or any(k not in bo for k in ('tracks', 'ntracks', 'anchors', 'frame_off')) or not bo.get('det'):
-        raise ValueError("%s must be a dict in video_batch's layout with tracks, det, ntracks, anchors and frame_off" % who)
-    V, tv = len(off) - 1, bo['tracks']
-    if len(tv) != V or len(bo['det']) != V or tv[0].dtype != torch.float32 or tv[0].dim() != 4 or tv[0].shape[3] != 5:
-        raise ValueError("%s: not a video_batch result" % who)
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    for v in range(V):
-        if tuple(tv[v].shape) != (C, T, int(off[v + 1] - off[v]), 5):
-            raise ValueError("%s: tracks[%d] must be [C,T,F_v,5]" % (who, v))
-    ntracks, anchors = bo['ntracks'], bo['anchors']
-    if ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C) or anchors.dtype != torch.float32 or \
-            tuple(anchors.shape) != (V, C, T, 3):
-        raise ValueError("%s: ntracks must be int32 [V,C], anchors float32 [V,C,T,3]" % who)
-    return _merge_flat(tv, 5, who), ntracks.contiguous(), anchors.contiguous(), C, T
-
-
 def merge_tracks_batch(batch_a, batch_b, scheme='combine', sync=True, ctx=None):
-    """``merge_tracks`` for every video of two results in ``video_batch``'s layout (``video_batch``, ``track_from_anchors_batch``
-    + ``anchor_propagate_tracks_batch``, ``interpolate_tracks_batch``) in ONE launch.  Both dicts need ``tracks``, ``det``
-    (series 0), ``ntracks``, ``anchors`` and the same ``frame_off``; ``pooled`` (a second series) and ``tboxes`` are taken when
-    BOTH have them.  Per video the bits are ``merge_tracks``' on that video alone.  Returns a dict in the same layout --
-    ``tracks`` / ``det`` / ``pooled`` / ``tboxes`` (and ``from_b`` for 'max') as consecutive per-video views of one allocation
-    each, ``anchors`` [V,C,T_out,3], ``ntracks`` [V,C], ``frame_off`` -- which ``tcn_tracks_batch``, ``tubelets_overlap_batch``
-    and ``DetEvaluator.add_batch`` take as they take ``video_batch``'s."""
+    """``merge_tracks`` for every video of two dicts in ``video_batch``'s layout (``_batch_read``) in ONE launch.  Both dicts need
+    ``tracks``, ``det`` (series 0), ``ntracks``, ``anchors`` and the same ``frame_off``; ``pooled`` (a second series) and
+    ``tboxes`` are taken when BOTH have them.  Per video the bits are ``merge_tracks``' on that video alone.  Returns a dict in
+    the same layout: ``tracks`` / ``det`` / ``pooled`` / ``tboxes`` (and ``from_b`` for 'max') with T_out slots, ``anchors``
+    [V,C,T_out,3], ``ntracks``, ``frame_off``."""
     if scheme not in _MERGE_SCHEMES:
         raise ValueError("scheme must be 'combine' or 'max'")
-    for bo, who in ((batch_a, 'batch_a'), (batch_b, 'batch_b')):
-        if not isinstance(bo, dict) or 'frame_off' not in bo:
-            raise ValueError("%s must be a dict in video_batch's layout" % who)
-    off = np.ascontiguousarray(batch_a['frame_off'], dtype=np.int64).reshape(-1)
-    offb = np.ascontiguousarray(batch_b['frame_off'], dtype=np.int64).reshape(-1)
-    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0) or not np.array_equal(off, offb):
-        raise ValueError("batch_a and batch_b must have the same frame_off (0 = o[0] < o[1] < ... < o[V])")
-    V, Ft = len(off) - 1, int(off[-1])
-    ta, nta, ana, C, Ta = _merge_batch_set(batch_a, off, 'batch_a')
-    tb, ntb, anb, Cb, Tb = _merge_batch_set(batch_b, off, 'batch_b')
-    if Cb != C:
+    a, b = _batch_read(batch_a, 'batch_a', ('anchors', 'det')), _batch_read(batch_b, 'batch_b', ('anchors', 'det'))
+    if a.o != b.o:
+        raise ValueError("batch_a and batch_b must have the same frame_off")
+    if a.C != b.C:
         raise ValueError("batch_a and batch_b must share C")
+    off, C = a.off, a.C
     names = ['det'] + (['pooled'] if batch_a.get('pooled') and batch_b.get('pooled') else [])
     with_tb = bool(batch_a.get('tboxes')) and bool(batch_b.get('tboxes'))
 
-    def side(bo, T, who):
-        ser = []
-        for k in names:
-            if len(bo[k]) != V or any(x.dtype != torch.float64 for x in bo[k]) or sum(x.numel() for x in bo[k]) != C * T * Ft:
-                raise ValueError("%s: %s must be float64 [C,T,F_v] views" % (who, k))
-            ser.append(_merge_flat(bo[k], 1, who))
-        bx = None
-        if with_tb:
-            if len(bo['tboxes']) != V or any(x.dtype != torch.float32 for x in bo['tboxes']) or \
-                    sum(x.numel() for x in bo['tboxes']) != C * T * Ft * 4:
-                raise ValueError("%s: tboxes must be float32 [C,T,F_v,4] views" % who)
-            bx = _merge_flat(bo['tboxes'], 4, who)
-        return ser, bx
-    sera, bxa = side(batch_a, Ta, 'batch_a')
-    serb, bxb = side(batch_b, Tb, 'batch_b')
-    for x in [ta, nta, ana, tb, ntb, anb] + sera + serb + [y for y in (bxa, bxb) if y is not None]:
-        if not x.is_cuda or x.device != ta.device:
-            raise ValueError("every tensor of batch_a and batch_b must live on the same GPU (vdetlib_amd has no CPU path)")
-    ctx = _ctx_for(ta, ctx)
-    tracks, ntracks, anchors, tboxes, series, from_b, To = _merge_call(
-        ctx, scheme, off, C, Ta, Tb, (ta, nta, ana, bxa, tuple(sera)), (tb, ntb, anb, bxb, tuple(serb)), sync)
-
-    def views(flat, per):
-        shape = (lambda fv: (C, To, fv, per)) if per > 1 else (lambda fv: (C, To, fv))
-        return [flat[C * To * per * int(off[v]): C * To * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
-
+    def side(bo, x, who):
+        ser = tuple(_batch_field(x, bo[k], 1, _F64, k, who) for k in names)
+        return x.tracks, x.ntracks, x.anchors, _batch_field(x, bo['tboxes'], 4, _F32, 'tboxes', who) if with_tb else None, ser
+    sa, sb = side(batch_a, a, 'batch_a'), side(batch_b, b, 'batch_b')
+    _same_gpu([x for s in (sa, sb) for x in s[:4] + s[4] if x is not None], "every tensor of batch_a and batch_b")
+    ctx = _ctx_for(a.tracks, ctx)
+    tracks, ntracks, anchors, tboxes, series, from_b, To = _merge_call(ctx, scheme, off, C, a.T, b.T, sa, sb, sync)
+    views = lambda flat, per: _batch_views(flat, off, C, To, per)
     out = dict(tracks=views(tracks, 5), det=views(series[0], 1), pooled=views(series[1], 1) if len(names) > 1 else [],
                tboxes=views(tboxes, 4) if with_tb else [], anchors=anchors, ntracks=ntracks, frame_off=off)
     if from_b is not None:
@@ -1409,54 +1436,27 @@ def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh
 
 def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_still=None, cap=None, use_tboxes=True, sync=True,
                      ctx=None):
-    """``nms_tracks`` for every video of a result in ``video_batch``'s layout (``video_batch``, the anchor route's batch forms,
-    ``interpolate_tracks_batch``, ``merge_tracks_batch``) in ONE launch.  ``score`` names the per-video series of the dict that
-    scores the tubelet boxes ('pooled', 'det', ...: f32 or f64 [C,T,F_v] views); the dict's ``tboxes`` are the boxes when it has
-    them and ``use_tboxes`` holds.  ``still`` as in ``nms_tracks``, frame-major over all videos ([Ftot,...]: what ``video_batch``
-    takes and returns).  Per video the bits are ``nms_tracks``' on that video alone.  Returns ``tracks`` / ``score`` / ``src`` as
-    consecutive per-video views ([C,R,F_v,...]) of one allocation each, ``cnt`` [C,Ftot], ``ntracks`` [V,C] and ``frame_off``."""
-    if not isinstance(batch_out, dict) or any(k not in batch_out for k in ('tracks', 'ntracks', 'frame_off')):
-        raise ValueError("batch_out must be a dict in video_batch's layout with tracks, ntracks and frame_off")
-    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
-    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0):
-        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V]")
-    V, Ft = len(off) - 1, int(off[-1])
-    if V > 65535:
-        raise ValueError("at most 65535 videos in one call")
-    tv, sv = batch_out['tracks'], batch_out.get(score) if isinstance(score, str) else None
-    if not sv or len(sv) != V:
+    """``nms_tracks`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in ONE launch.  ``score`` names the
+    field of the dict that scores the tubelet boxes ('pooled', 'det', ...: f32 or f64); the dict's ``tboxes`` are the boxes when
+    it has them and ``use_tboxes`` holds.  ``still`` as in ``nms_tracks``, frame-major over all videos ([Ftot,...]: what
+    ``video_batch`` takes and returns).  Per video the bits are ``nms_tracks``' on that video alone.  Returns ``tracks`` /
+    ``score`` / ``src`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot], ``ntracks`` [V,C]
+    and ``frame_off``."""
+    b = _batch_read(batch_out)
+    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
+    sv = batch_out.get(score) if isinstance(score, str) else None
+    if not sv:
         raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
-    if len(tv) != V or tv[0].dtype != torch.float32 or tv[0].dim() != 4 or tv[0].shape[3] != 5:
-        raise ValueError("not a video_batch result")
-    C, T = tv[0].shape[0], tv[0].shape[1]
+    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
     bv = batch_out.get('tboxes') if use_tboxes else None
-    bv = bv if bv else None
-    for v in range(V):
-        fv = int(off[v + 1] - off[v])
-        if tuple(tv[v].shape) != (C, T, fv, 5):
-            raise ValueError("tracks[%d] must be [C,T,F_v,5]" % v)
-        if sv[v].dtype not in (torch.float32, torch.float64) or sv[v].dtype != sv[0].dtype or tuple(sv[v].shape) != (C, T, fv):
-            raise ValueError("%s[%d] must be float32 / float64 [C,T,F_v]" % (score, v))
-        if bv is not None and (len(bv) != V or bv[v].dtype != torch.float32 or tuple(bv[v].shape) != (C, T, fv, 4)):
-            raise ValueError("tboxes[%d] must be float32 [C,T,F_v,4]" % v)
-    ntracks = batch_out['ntracks']
-    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
-        raise ValueError("ntracks must be int32 [V,C]")
+    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
     still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
     R = _tn_limits(C, T, Ft, top_still, cap)
-    tracks, sc = _merge_flat(tv, 5, 'batch_out'), _merge_flat(sv, 1, 'batch_out')
-    tboxes = _merge_flat(bv, 4, 'batch_out') if bv is not None else None
-    for x in [tracks, ntracks, sc] + ([tboxes] if tboxes is not None else []) + list(still or ()):
-        if not x.is_cuda or x.device != ntracks.device:
-            raise ValueError("every tensor must live on the same GPU (vdetlib_amd has no CPU path)")
+    _same_gpu([ntracks, tracks, sc] + ([tboxes] if tboxes is not None else []) + list(still or ()), "every tensor")
     still = None if still is None else tuple(x.contiguous() for x in still)
-    ntracks = ntracks.contiguous()
     ctx = _ctx_for(ntracks, ctx)
     ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
-
-    def views(flat, per):
-        shape = (lambda fv: (C, R, fv, per)) if per > 1 else (lambda fv: (C, R, fv))
-        return [flat[C * R * per * int(off[v]): C * R * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
+    views = lambda flat, per: _batch_views(flat, off, C, R, per)
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
 
 
@@ -1535,33 +1535,18 @@ def rescore_tubelets(tracks, ntracks, boxes, scores, floor=None, overlap_thres=0
 
 
 def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0.7, window=3, complete=None, sync=True, ctx=None):
-    """``rescore_tubelets`` for every video of ANY dict in ``video_batch``'s layout (``video_batch``,
-    ``track_from_anchors_batch``, ``merge_tracks_batch``, ``interpolate_tracks_batch``) in one call; boxes [F,B,4] / scores
-    [F,B,C] f32 are the batch's volume.  ``floor``: a list of per-video [C,T,F_v] views or one flat tensor in the batch layout,
-    f32 or f64.  Per video the bits are ``rescore_tubelets``' on that video alone.  Returns a NEW dict in the same layout --
-    the input's ``tracks``, ``anchors``, ``ntracks`` and ``frame_off`` carried over, ``det`` / ``pooled`` / ``tboxes`` / ``src``
-    as consecutive per-video views of one allocation each -- which ``tcn_tracks_batch``, ``merge_tracks_batch``,
-    ``nms_tracks_batch``, ``tubelets_overlap_batch`` and ``DetEvaluator.add_batch`` take as they take ``video_batch``'s.  The
-    input dict is not modified."""
+    """``rescore_tubelets`` for every video of ANY dict in ``video_batch``'s layout (``_batch_read``) in one call; boxes [F,B,4] /
+    scores [F,B,C] f32 are the batch's volume.  ``floor``, f32 or f64: one flat tensor in the batch layout, or a list of
+    per-video [C,T,F_v] tensors -- used in place when they are the layout's consecutive views, gathered into one buffer when
+    not.  Per video the bits are ``rescore_tubelets``' on that video alone.  Returns a NEW dict in the same layout -- the
+    input's ``tracks``, ``anchors``, ``ntracks`` and ``frame_off`` carried over, new ``det`` / ``pooled`` / ``tboxes`` / ``src``.
+    The input dict is not modified."""
     if window % 2 != 1:
         raise ValueError('Window size must be odd!')
-    if not isinstance(batch_out, dict) or any(k not in batch_out for k in ('tracks', 'ntracks', 'frame_off')):
-        raise ValueError("not a video_batch result: batch_out must be a dict in video_batch's layout with tracks, ntracks and frame_off")
-    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64).reshape(-1)
-    if off.size < 2 or off[0] != 0 or np.any(np.diff(off) <= 0):
-        raise ValueError("frame_off must run 0 = o[0] < o[1] < ... < o[V]")
-    V, Ft = len(off) - 1, int(off[-1])
-    tv = batch_out['tracks']
-    if not isinstance(tv, (list, tuple)) or len(tv) != V or not all(torch.is_tensor(x) for x in tv):
-        raise ValueError("not a video_batch result: tracks must be one view per video")
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or tv[0].dtype != torch.float32:
+    b = _batch_read(batch_out)
+    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
         raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if tv[0].dim() != 4 or tv[0].shape[3] != 5:
-        raise ValueError("not a video_batch result: tracks[v] must be [C,T,F_v,5]")
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    for v in range(V):
-        if tuple(tv[v].shape) != (C, T, int(off[v + 1] - off[v]), 5):
-            raise ValueError("not a video_batch result: tracks[%d] must be [C,T,F_v,5]" % v)
     if boxes.dim() != 3 or boxes.shape[0] != Ft or boxes.shape[2] != 4:
         raise ValueError("boxes must be [F,B,4] over all frames of the batch")
     B = boxes.shape[1]
@@ -1569,36 +1554,21 @@ def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0
         raise ValueError("at least one box per frame and one class")
     if tuple(scores.shape) != (Ft, B, C):
         raise ValueError("scores must be [F,B,C]")
-    ntracks = batch_out['ntracks']
-    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
-        raise ValueError("not a video_batch result: ntracks must be int32 [V,C]")
-    tracks = _merge_flat(tv, 5, 'batch_out')
     if floor is not None:
         if isinstance(floor, (list, tuple)):
-            if len(floor) != V or any(not torch.is_tensor(x) or tuple(x.shape) != (C, T, int(off[v + 1] - off[v])) or
-                                      x.dtype != floor[0].dtype for v, x in enumerate(floor)):
-                raise ValueError("floor must be one [C,T,F_v] view per video, all of one dtype")
-            try:
-                floor = _merge_flat(floor, 1, 'floor')
-            except ValueError:       # separate per-video tensors: gathered into the batch layout
-                floor = torch.cat([x.reshape(-1) for x in floor])
+            floor = _batch_field(b, floor, 1, _F32_F64, 'floor', 'rescore_tubelets_batch', gather=True)
         if not torch.is_tensor(floor) or floor.numel() != C * T * Ft:
             raise ValueError("floor must hold C*T*F elements in the batch layout")
-        if floor.dtype not in (torch.float32, torch.float64):
+        if floor.dtype not in _F32_F64:
             raise ValueError("floor must be float32 or float64")
         floor = floor.contiguous()
-    for t in (tracks, ntracks, scores) + (() if floor is None else (floor,)):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("the batch result, boxes, scores and floor must live on the same GPU")
+    _same_gpu((boxes, scores, tracks, ntracks) + (() if floor is None else (floor,)), "the batch result, boxes, scores and floor")
     ctx = _ctx_for(boxes, ctx)
-    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks, ntracks.contiguous(), boxes.contiguous(), scores.contiguous(),
-                                        floor, overlap_thres, complete, window, sync)
-
-    def views(flat, per):
-        shape = (lambda fv: (C, T, fv, per)) if per > 1 else (lambda fv: (C, T, fv))
-        return [flat[C * T * per * int(off[v]): C * T * per * int(off[v + 1])].view(*shape(int(off[v + 1] - off[v]))) for v in range(V)]
-    out = dict(tracks=list(tv), ntracks=ntracks, frame_off=off, det=views(det, 1), pooled=views(pooled, 1), tboxes=views(tboxes, 4),
-               src=views(src, 1))
+    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks, ntracks, boxes.contiguous(), scores.contiguous(), floor,
+                                        overlap_thres, complete, window, sync)
+    views = lambda flat, per: _batch_views(flat, off, C, T, per)
+    out = dict(tracks=list(batch_out['tracks']), ntracks=batch_out['ntracks'], frame_off=off, det=views(det, 1),
+               pooled=views(pooled, 1), tboxes=views(tboxes, 4), src=views(src, 1))
     if 'anchors' in batch_out:
         out['anchors'] = batch_out['anchors']
     return out
@@ -1982,27 +1952,20 @@ def tubelets_overlap(gt, video, tracks, ntracks, boxes=None, sync=True, ctx=None
 
 
 def tubelets_overlap_batch(gt, videos, batch_out, use_tboxes=False, sync=True, ctx=None):
-    """``tubelets_overlap`` for every video of a ``video_batch`` result in one launch.  Returns (gt_overlap: flat f64
-    buffer in the batch layout -- what ``tcn_tracks_batch`` takes --, its per-video [C,T,F_v] views, mean_iou [V,C,T],
-    gt [V,C,T])."""
+    """``tubelets_overlap`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in one launch.  Returns
+    (gt_overlap: flat f64 buffer in the batch layout -- what ``tcn_tracks_batch`` takes --, its per-video [C,T,F_v] views,
+    mean_iou [V,C,T], gt [V,C,T])."""
     ev = _evaluator_of(gt)
-    off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
-    V = len(off) - 1
+    b = _batch_read(batch_out)
+    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
     if len(videos) != V:
         raise ValueError("one name per video of the batch")
-    tv = batch_out['tracks']
-    C, T = tv[0].shape[0], tv[0].shape[1]
-    Ft = int(off[-1])
-    tracks = _batch_flat(tv, 5)
     boxes = None
     if use_tboxes:
         if not batch_out.get('tboxes'):
             raise ValueError("video_batch ran without re-scoring (rescore=False): no tboxes")
-        boxes = _batch_flat(batch_out['tboxes'], 4)
-    ntracks = batch_out['ntracks'].contiguous()
-    if tracks.dtype != torch.float32 or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (V, C):
-        raise ValueError("not a video_batch result")
-    ev._check(tracks, ntracks)
+        boxes = _batch_field(b, batch_out['tboxes'], 4, _F32, 'tboxes', 'batch_out')
+    ev._check(tracks, ntracks, *([boxes] if boxes is not None else []))
     dev = tracks.device
     ov = torch.empty((C * T * Ft,), dtype=torch.float64, device=dev)
     mean = torch.empty((V, C, T), dtype=torch.float64, device=dev)
@@ -2017,8 +1980,7 @@ def tubelets_overlap_batch(gt, videos, batch_out, use_tboxes=False, sync=True, c
         flag.data_ptr()))
     if sync:
         ctx.sync()
-    views = [ov[C * T * int(off[v]): C * T * int(off[v + 1])].view(C, T, int(off[v + 1] - off[v])) for v in range(V)]
-    return ov, views, mean, flag
+    return ov, _batch_views(ov, off, C, T, 1), mean, flag
 
 
 class DetEvaluator(object):
@@ -2174,35 +2136,33 @@ class DetEvaluator(object):
             keep_cnt.data_ptr(), cap, slots.ctypes.data, *st), F * C * cap)
 
     def add_batch(self, videos, batch_out):
-        """The re-scored tubelets (``pooled`` scores, ``tboxes`` boxes) of every video of a ``video_batch`` result, in ONE
-        match launch; videos[v] names video v.  Same stream as add_tracks video after video."""
-        off = np.ascontiguousarray(batch_out['frame_off'], dtype=np.int64)
-        V = len(off) - 1
-        if len(videos) != V:
+        """The re-scored tubelets (``pooled`` scores, ``tboxes`` boxes) of every video of a dict in ``video_batch``'s layout
+        (``_batch_read``), in ONE match launch; videos[v] names video v.  Same stream as add_tracks video after video."""
+        b = _batch_read(batch_out)
+        if len(videos) != b.V:
             raise ValueError("one name per video of the batch")
         if not batch_out.get('pooled'):
             raise ValueError("video_batch ran without re-scoring (rescore=False): no tubelet scores")
-        nt = batch_out['ntracks']
-        tr0, sc0, bx0 = batch_out['tracks'][0], batch_out['pooled'][0], batch_out['tboxes'][0]
-        C, T = tr0.shape[0], tr0.shape[1]
-        if nt.dtype != torch.int32 or tuple(nt.shape) != (V, C) or sc0.dtype != torch.float64:
-            raise ValueError("not a video_batch result")
-        self._check(nt, sc0, bx0)
-        nt = nt.contiguous()
+        sc = _batch_field(b, batch_out['pooled'], 1, _F64, 'pooled', 'batch_out')
+        bx = _batch_field(b, batch_out.get('tboxes'), 4, _F32, 'tboxes', 'batch_out')
+        return self._append_batch(videos, b, bx, 4, sc)
+
+    def _append_batch(self, videos, b, bx, stride, sc):
+        """One match launch over the flat boxes ``bx`` (``stride`` floats per box) and f64 scores ``sc`` of the batch ``b``."""
+        self._check(b.ntracks, sc, bx)
         vids = np.array([self._vidx.get(v, -1) for v in videos], dtype=np.int32)
-        slots = self._col_slots(C, 1)
-        Ft = int(off[-1])
+        slots = self._col_slots(b.C, 1)
         return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks_batch(
-            ctx.h, *self._gt_args(), vids.ctypes.data, off.ctypes.data, V, C, T, bx0.data_ptr(), 4, sc0.data_ptr(), 1,
-            nt.data_ptr(), slots.ctypes.data, *st), C * T * Ft)
+            ctx.h, *self._gt_args(), vids.ctypes.data, b.off.ctypes.data, b.V, b.C, b.T, bx.data_ptr(), stride, sc.data_ptr(), 1,
+            b.ntracks.data_ptr(), slots.ctypes.data, *st), b.C * b.T * b.Ft)
 
     def add_detections(self, video_or_videos, out):
         """The per-frame detections ``nms_tracks`` (``video_or_videos``: the video's name) or ``nms_tracks_batch`` (the names of
-        the batch's videos) returned: rows ``tracks[..., :4]`` scored by the f64 ``score``, rank as the slot axis.  Same stream
-        as ``add_tracks`` of those arrays video after video; returns the number of detections added."""
+        the batch's videos; a dict in ``video_batch``'s layout, ``_batch_read``, checked like every other) returned: rows
+        ``tracks[..., :4]`` scored by the f64 ``score``, rank as the slot axis.  Same stream as ``add_tracks`` of those arrays
+        video after video; returns the number of detections added."""
         if not isinstance(out, dict) or any(k not in out for k in ('tracks', 'score', 'ntracks')):
             raise ValueError("out must be the dict nms_tracks or nms_tracks_batch returned")
-        slots_of = lambda C: self._col_slots(C, 1)
         if 'frame_off' not in out:
             tr, sc, nt = out['tracks'], out['score'], out['ntracks']
             if tr.dtype != torch.float32 or tr.dim() != 4 or tr.shape[3] != 5:
@@ -2212,26 +2172,14 @@ class DetEvaluator(object):
                 raise ValueError("score must be float64 [C,R,F], ntracks int32 [C]")
             self._check(tr, sc, nt)
             tr, sc, nt = tr.contiguous(), sc.contiguous(), nt.contiguous()
-            slots, vid = slots_of(C), self._vidx.get(video_or_videos, -1)
+            slots, vid = self._col_slots(C, 1), self._vidx.get(video_or_videos, -1)
             return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks(
                 ctx.h, *self._gt_args(), vid, F, C, R, tr.data_ptr(), 5, sc.data_ptr(), 1, nt.data_ptr(), slots.ctypes.data, *st),
                 C * R * F)
-        off = np.ascontiguousarray(out['frame_off'], dtype=np.int64)
-        V, Ft = len(off) - 1, int(off[-1])
-        if isinstance(video_or_videos, str) or len(video_or_videos) != V:
+        b = _batch_read(out, 'out')
+        if isinstance(video_or_videos, str) or len(video_or_videos) != b.V:
             raise ValueError("one name per video of the batch")
-        tr0, nt = out['tracks'][0], out['ntracks']
-        C, R = tr0.shape[0], tr0.shape[1]
-        if nt.dtype != torch.int32 or tuple(nt.shape) != (V, C) or out['score'][0].dtype != torch.float64:
-            raise ValueError("not an nms_tracks_batch result")
-        tr, sc = _batch_flat(out['tracks'], 5), _batch_flat(out['score'], 1)
-        self._check(tr, sc, nt)
-        nt = nt.contiguous()
-        vids = np.array([self._vidx.get(v, -1) for v in video_or_videos], dtype=np.int32)
-        slots = slots_of(C)
-        return self._append(lambda ctx, st: ctx.lib.vdet_eval_match_tracks_batch(
-            ctx.h, *self._gt_args(), vids.ctypes.data, off.ctypes.data, V, C, R, tr.data_ptr(), 5, sc.data_ptr(), 1,
-            nt.data_ptr(), slots.ctypes.data, *st), C * R * Ft)
+        return self._append_batch(video_or_videos, b, b.tracks, 5, _batch_field(b, out['score'], 1, _F64, 'score', 'out'))
 
     def stream(self, raw=False):
         """The stream so far: (class_index int64, score f64, tp bool) device tensors (raw: class slot int32, tp uint8)."""
