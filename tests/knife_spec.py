@@ -491,3 +491,297 @@ def reach_model(boxes, t, pairs, mode, lists):
                 last += 1
             lost += bool(c > last)
     return lost
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the x-bucket windows: frames whose pinned pairs sit on the window's edge and on a 64-rank word boundary, and a model of
+# the three dialects of the window (csrc/nms_kernels.hpp adj_build_kernel and xwindow, csrc/track_kernels.hpp link scans)
+# ---------------------------------------------------------------------------------------------------------------------
+WINDOW_FAMILIES = ('unit', 'top', 'wmaxcap', 'coarse', 'frac', 'flat')
+WINDOW_THRESHOLDS = (0.3, 0.5, 0.7)
+WINDOW_SITES = ('adj', 'xwindow', 'link')
+WINDOW_B = (322, 642, 1026, 2114)      # B - 2 a multiple of 64: the two partners in bucket 255 of 'top' are the whole last word
+# (322 / 642: the two adj_build_kernel instantiations; 1026: beyond the link table's 1024; 2114: a list of more than 2048)
+WINDOW_SEED = 7                 # the seed of the frames the suites share
+WINDOW_W = 100                  # the outer boxes' width: t * W is an integer for every searched threshold
+# mutant -> the sites it applies to.  'nomargin' is reported only (whether it loses a pair hangs on one float32 rounding).
+WINDOW_MUTANTS = dict(own_width_left=WINDOW_SITES, in1=WINDOW_SITES, cum_b1=WINDOW_SITES, floor_w1=('adj',), ceil_w0=('adj',),
+                      clamp254=WINDOW_SITES, wmax_no_plus1=WINDOW_SITES, no_trunc_slack=('link',))
+# Mutants no frame can kill, with the reason (tests/test_knife_edge_cpu.py asserts that they lose nothing here either):
+#   wmax_no_plus1   a left partner j satisfies x1_c - x1_j <= (1 - t) w_j <= (1 - t) (wmax' + 1) < (1 - t) wmax' + 1 with
+#                   wmax' = max(x2 - x1): the missing + 1 pulls the bound in by (1 - t) < 1 px, less than the smallest margin
+#                   (1 px at xwindow, 2 px at the other two sites)
+#   no_trunc_slack  the link scans take window AND IoU from the truncated current box, so truncation opens no gap between
+#                   the two; the bound is exact in real arithmetic and the 0.2 % of omt covers the float32 rounding
+WINDOW_UNKILLABLE = ('wmax_no_plus1', 'no_trunc_slack')
+WINDOW_MODES = ('kernel', 'nomargin') + tuple(WINDOW_MUTANTS)
+
+
+def iou64(a, b):
+    """The re-scoring IoU: float64 arithmetic on float32 coordinates, + 1 convention (oracle.iou on one pair)."""
+    a, b = np.asarray(a, F32).astype(np.float64), np.asarray(b, F32).astype(np.float64)
+    w = min(a[2], b[2]) - max(a[0], b[0]) + 1.0
+    h = min(a[3], b[3]) - max(a[1], b[1]) + 1.0
+    inter = max(w, 0.0) * max(h, 0.0)
+    return inter / ((a[2] - a[0] + 1.0) * (a[3] - a[1] + 1.0) + (b[2] - b[0] + 1.0) * (b[3] - b[1] + 1.0) - inter)
+
+
+def window_partner(query, partner, t, site):
+    """Is `partner` a true partner of `query` by the referee of the site: the reference's float32 quotient for the
+    suppression graph ('adj'), the oracle's link rule on the TRUNCATED current box ('link'), float64 IoU > t for
+    re-scoring ('xwindow')."""
+    query, partner = np.asarray(query, F32), np.asarray(partner, F32)
+    if site == 'xwindow':
+        return bool(iou64(query, partner) > t)
+    if site == 'link':
+        query = np.trunc(query)
+    return bool(classify(query[None], partner[None], t)['sup'][0])
+
+
+def _fill_x(ra, xa, rb, xb, g):
+    """x1 of the rb - ra - 1 filler ranks strictly between two anchored ranks: on the grid g, strictly inside (xa, xb), in
+    ascending order (fillers may share an x1; an anchored box keeps its x1 to itself)."""
+    n = rb - ra - 1
+    if n <= 0:
+        return []
+    inner = int(round((xb - xa) / g)) - 1
+    assert inner >= 1, (ra, xa, rb, xb)
+    return [xa + g * (1 + (i * inner) // n) for i in range(n)]
+
+
+def window_band(B):
+    """The height of a y band: every box has a band of its own below 65536."""
+    return 64 if B <= 1000 else 16
+
+
+def window_frame(t, B, family, seed, strict=False, band=None):
+    """A regular frame [B, 4] built RANK BY RANK in the x1 order whose pinned pairs sit on the edge of the x-bucket window
+    and on a 64-rank word boundary.  A pair is an outer box O of width W = 100 and an inner box I, flush right, full height,
+    t * W wide: I starts exactly (1 - t) * W right of O, the bound of the window on both sides.  Where the exact-t pair does
+    not count -- classify() says "keep" because thresh_to_f32 rounds the threshold up, or strict=True, the float64
+    IoU > t of re-scoring, where it never counts -- I is one grid step wider.  Every pinned box has an x1 of its own;
+    everything else is narrow fillers (at most 30 wide) in y bands of their own, which may share an x1 with each other.
+
+    unit     x1 range exactly 256 (scale == 1.0, one pixel per bucket).  O is the LAST rank of a word, I the FIRST rank of a
+             later word (64 or more filler ranks between them): one pair pins the right side from O (hi, cum[b1 + 1],
+             (r1 + 63) >> 6) and the left side from I (lo, r0 >> 6).  One filler is 3 W wide, so w_c / t decides on the left.
+    wmaxcap  the same without the wide filler: the outer boxes are the frame's widest and min(wmax, .) decides on the left.
+    frac     unit on a grid of quarter pixels (not a kFlagU16 frame): O on whole pixels, I a quarter wider where the exact
+             pair does not count, xmin on .75 so that I starts exactly on a bucket's edge.
+    top      unit scale; partners I with x1 == xmax and x1 == xmax - 1 (both in bucket 255, the whole last word, hi beyond
+             xmax) and the mirror image: partners O with x1 == xmin and xmin + 1, lo left of xmin.
+    coarse   x1 range 4096 (16 px per bucket, wider than any margin).  Right pins: I alone in its bucket, on the bucket's
+             first pixel, first rank of a word.  Left pins: O alone in its bucket, on its last pixel, last rank of a word.
+    flat     every x1 equal (scale == 0, one bucket): I flush LEFT.  Nothing can be culled; the frame checks the path.
+    Returns (boxes, pair rows [m, 2] = (row of O, row of I)): pair k is rows 2k, 2k + 1 (O first for even k), then fillers."""
+    assert family in WINDOW_FAMILIES and B >= 322 and (B - 2) % 64 == 0
+    band = window_band(B) if band is None else band
+    rng = np.random.RandomState(seed)
+    tf = Fraction(str(t))
+    W = WINDOW_W
+    g = 0.25 if family == 'frac' else 1.0
+    assert (tf * W).denominator == 1
+    span = 4096.0 if family == 'coarse' else 256.0
+    xmin = 1000.0 - (0.25 if family == 'frac' else 0.0)
+    xmax = xmin + span
+    heights = {}
+
+    def pair_at(k, xo=None, xi=None, left=False):
+        """(O, I) as (x1, x2) from the x1 of one of them; the smallest I that counts."""
+        H = heights.setdefault(k, int(rng.randint(8, min(41, band))))
+        w = float(tf * W)
+        while True:
+            o = xo if xo is not None else (xi if left else xi - (W - w))
+            O = np.array([o, 0, o + W - 1, H - 1], F32)
+            I = np.array([o, 0, o + w - 1, H - 1] if left else [o + W - w, 0, o + W - 1, H - 1], F32)
+            if (iou64(O, I) > t) if strict else bool(classify(O[None], I[None], t)['sup'][0]):
+                return (float(O[0]), float(O[2])), (float(I[0]), float(I[2]))
+            w += g
+
+    pins = {}           # rank -> (x1, x2, pair, is_outer)
+    anchors = {}        # rank -> x1 of a filler that must stand exactly there
+    wide = None         # rank of the 3 W wide filler
+
+    def pin(k, ro, ri, O, I):
+        assert ro not in pins and ri not in pins and ro not in anchors and ri not in anchors
+        pins[ro] = (O[0], O[1], k, True)
+        pins[ri] = (I[0], I[1], k, False)
+
+    if family == 'flat':
+        x1 = np.full(B, xmin)
+        for k in range(3):
+            O, I = pair_at(k, xo=xmin, left=True)
+            pin(k, 2 * k, 2 * k + 1, O, I)
+    elif family in ('unit', 'wmaxcap', 'frac'):
+        xo = float(np.ceil(xmin + 8))                                # (frac: O on whole pixels)
+        for k in range(min(3, (B - 3) // 128)):
+            O, I = pair_at(k, xo=xo)
+            pin(k, 64 * (2 * k + 1) - 1, 64 * (2 * k + 2), O, I)
+            xo = float(np.ceil(I[0] + 6))
+        assert xo < xmax - 4
+        wide = None if family == 'wmaxcap' else 5
+    elif family == 'top':
+        m = (B - 2) // 64 - 1
+        Oa, Ia = pair_at(0, xi=xmax)
+        Ob, Ib = pair_at(1, xi=xmax - 1)
+        pin(0, 64 * m - 1, B - 1, Oa, Ia)
+        pin(1, 64 * m - 2, B - 2, Ob, Ib)
+        assert Ob[0] < Oa[0]
+        Oc, Ic = pair_at(2, xo=xmin)
+        Od, Id = pair_at(3, xo=xmin + 1)
+        pin(2, 0, 64, Oc, Ic)
+        pin(3, 1, 65, Od, Id)
+        assert Ic[0] < Id[0] < Ob[0] - 2
+    else:       # coarse: (is a right pin, rank of O, rank of I, bucket of the pinned partner)
+        plan = [(True, 40, 64, 20), (False, 127, 158, 40), (False, 191, 215, 60), (True, 236, 256, 100)]
+        if B >= 642:
+            plan += [(True, 500, 512, 180), (False, 575, 600, 200)]
+        for k, (right, ro, ri, bucket) in enumerate(plan):
+            if right:
+                O, I = pair_at(k, xi=xmin + 16 * bucket)
+                anchors[ri + 1] = xmin + 16 * (bucket + 1)          # the next box starts in the next bucket
+            else:
+                O, I = pair_at(k, xo=xmin + 16 * bucket + 15)
+                anchors[ro - 1] = xmin + 16 * bucket - 1            # the box before starts in the bucket before
+            pin(k, ro, ri, O, I)
+        wide = 5
+    if family != 'flat':
+        fixed = dict(anchors)
+        fixed.update({r: p[0] for r, p in pins.items()})
+        fixed.setdefault(0, xmin)
+        fixed.setdefault(B - 1, xmax)
+        rs = sorted(fixed)
+        x1 = np.zeros(B)
+        for ra, rb in zip(rs[:-1], rs[1:]):
+            assert fixed[ra] < fixed[rb], (ra, rb)
+            x1[ra] = fixed[ra]
+            x1[ra + 1:rb] = _fill_x(ra, fixed[ra], rb, fixed[rb], g)
+        x1[rs[-1]] = fixed[rs[-1]]
+        assert np.all(np.diff(x1) >= 0) and x1[0] == xmin and x1[-1] == xmax
+    m = len(pins) // 2
+    fw = rng.randint(1, 31, B).astype(np.float64)
+    if family == 'frac':
+        fw = fw + rng.randint(0, 4, B) * 0.25
+    if wide is not None:
+        assert wide not in pins and wide not in anchors
+        fw[wide] = 3 * W
+    x2 = x1 + fw - 1
+    y1 = np.zeros(B)
+    hh = rng.randint(1, band, B).astype(np.float64)
+    fillers = [r for r in range(B) if r not in pins]
+    y1[fillers] = (m + rng.permutation(len(fillers))) * band
+    rows_of = np.zeros((m, 2), np.int64)        # ranks of (O, I) per pair
+    for r, (a, b, k, outer) in pins.items():
+        assert a == x1[r] or family == 'flat'
+        x1[r], x2[r], y1[r], hh[r] = a, b, k * band, heights[k]
+        rows_of[k, 0 if outer else 1] = r
+    if family != 'flat':        # a pinned box has its x1 to itself
+        for r in pins:
+            assert np.sum(x1 == x1[r]) == 1, (family, r)
+    assert y1.max() + band <= 65536 and x2.max() <= 65535
+    by_rank = np.stack([x1, y1, x2, y1 + hh - 1], 1).astype(F32)
+    assert np.array_equal(by_rank.astype(np.float64), np.stack([x1, y1, x2, y1 + hh - 1], 1))
+    pr = rows_of.copy()
+    pr[1::2] = pr[1::2, ::-1]
+    ranks = np.concatenate([pr.ravel(), rng.permutation(np.asarray(fillers))])
+    pairs = np.arange(2 * m).reshape(m, 2)
+    pairs[1::2] = pairs[1::2, ::-1]
+    return by_rank[ranks], pairs
+
+
+def xbucket(x, xmin, scale, top=255):
+    """xbucket of csrc/nms_kernels.hpp in float32 (top: the clamp)."""
+    t = (F32(x) - xmin) * scale
+    return 0 if t <= 0 else (top if t >= top else int(t))
+
+
+def window_index(boxes, mode='kernel'):
+    """frame_index_kernel in numpy: (rank of every row in the x1 order, cum [257], xmin, scale, wmax), all float32."""
+    boxes = np.asarray(boxes, F32)
+    order = np.argsort(boxes[:, 0], kind='stable')
+    rank = np.empty(boxes.shape[0], np.int64)
+    rank[order] = np.arange(boxes.shape[0])
+    xmin, xmax = boxes[:, 0].min(), boxes[:, 0].max()
+    scale = F32(256.0) / (xmax - xmin) if xmax > xmin else F32(0)
+    wd = boxes[:, 2] - boxes[:, 0]
+    wmax = (wd if mode == 'wmax_no_plus1' else wd + F32(1)).max()
+    bk = np.array([xbucket(x, xmin, scale) for x in boxes[:, 0]])
+    cum = np.concatenate([[0], np.cumsum(np.bincount(bk, minlength=256))])
+    return rank, cum, xmin, scale, wmax
+
+
+def window_model(boxes, query, t, site, mode='kernel', index=None):
+    """The rank range [r0, r1) of the frame's x1 order that a site reads for the box `query` (a row of the frame or a free
+    box [4]), as the code is written -- 'adj': adj_build_kernel (float32, 1.001 relative + 2 px; also returns the range of
+    64-rank words [w0, w1), the granularity it reads at), 'xwindow': xwindow() (float64, 1.001 + 1 px), 'link': the link
+    scans (float32, omt = (1 - t) * 1.002 + 1e-6, inv_t = 1.002 / t, + 2 px, the current box truncated) -- or as one of the
+    single-token mistakes of WINDOW_MUTANTS would write it.  Returns (r0, r1), for 'adj' (r0, r1, w0, w1)."""
+    assert site in WINDOW_SITES and mode in WINDOW_MODES
+    boxes = np.asarray(boxes, F32)
+    rank, cum, xmin, scale, wmax = index if index is not None else window_index(boxes, mode)
+    q = boxes[int(query)] if np.ndim(query) == 0 else np.asarray(query, F32)
+    bare = mode in ('in1', 'nomargin')                      # no relative and no pixel margin
+    shift = 1.0 if mode == 'in1' else 0.0                   # ... and both bounds one pixel inward
+    own = mode == 'own_width_left'
+    top = 254 if mode == 'clamp254' else 255
+    if site == 'adj':
+        omt = F32(max(0.0, 1.0 - float(t)))
+        rel = F32(1.0) if bare else F32(1.001)
+        px = F32(0.0 if bare else 2.0)
+        wrow = (q[2] - q[0]) + F32(1)
+        wleft = wrow if own else min(wmax, wrow / max(F32(1) - omt, F32(1e-6)) * rel)
+        lo = F32(F32(q[0] - omt * wleft * rel) - px) + F32(shift)
+        hi = F32(F32(q[0] + omt * wrow * rel) + px) - F32(shift)
+    elif site == 'xwindow':
+        t = float(t)
+        rel = 1.0 if bare else 1.001
+        px = 0.0 if bare else 1.0
+        x1c, wc = float(q[0]), float((q[2] - q[0]) + F32(1))
+        wj = wc if own else min(float(wmax), wc / t * rel)
+        lo = F32(max(x1c - (1.0 - t) * wj * rel - px + shift, -3.0e38))
+        hi = F32(min(x1c + (1.0 - t) * wc * rel + px - shift, 3.0e38))
+    else:
+        cur = np.trunc(q)
+        omt = F32(1.0 - float(t)) if bare else F32(1.0 - float(t)) * F32(1.002) + F32(1.0e-6)
+        inv_t = F32((1.0 if bare else 1.002) / max(float(t), 1.0e-6))
+        px = F32(0.0 if bare or mode == 'no_trunc_slack' else 2.0)
+        wc = (cur[2] - cur[0]) + F32(1)
+        lo = F32(F32(cur[0] - omt * (wc if own else min(wmax, wc * inv_t))) - px) + F32(shift)
+        hi = F32(F32(cur[0] + omt * wc) + px) - F32(shift)
+    b0, b1 = xbucket(lo, xmin, scale, top), xbucket(hi, xmin, scale, top)
+    r0, r1 = int(cum[b0]), int(cum[b1] if mode == 'cum_b1' else cum[b1 + 1])
+    if site != 'adj':
+        return r0, r1
+    nw = (boxes.shape[0] + 63) >> 6
+    w0 = (r0 + 63) >> 6 if mode == 'ceil_w0' else r0 >> 6
+    w1 = min(nw, r1 >> 6 if mode == 'floor_w1' else (r1 + 63) >> 6)
+    return r0, r1, w0, w1
+
+
+def link_query(box):
+    """The box of the frame before whose truncation is `box`: x1 and x2 moved right by 0.75 px where they are whole pixels
+    (the link scans truncate the current box, so the window is taken 0.75 px to the left of where the box stands)."""
+    q = np.array(box, F32)
+    if q[0] == np.trunc(q[0]) and q[2] == np.trunc(q[2]):
+        q[0] += F32(0.75); q[2] += F32(0.75)
+    return q
+
+
+def window_lost(boxes, pairs, t, site, mode, frac=False):
+    """(directed pinned pairs that are true partners by the site's referee, how many of them the window of `mode` does not
+    read).  Both directions of every pair: the window of O has to hold I (right side) and the window of I has to hold O
+    (left side).  frac: at the link site the queries are link_query() of the pinned boxes."""
+    boxes = np.asarray(boxes, F32)
+    index = window_index(boxes, mode)
+    rank = index[0]
+    true = lost = 0
+    for o, i in np.asarray(pairs):
+        for qrow, prow in ((o, i), (i, o)):
+            q = link_query(boxes[qrow]) if (site == 'link' and frac) else boxes[qrow]
+            if not window_partner(q, boxes[prow], t, site):
+                continue
+            true += 1
+            r = window_model(boxes, q, t, site, mode, index)
+            p = int(rank[prow])
+            lost += not (r[2] <= p >> 6 < r[3] if site == 'adj' else r[0] <= p < r[1])
+    return true, lost

@@ -183,3 +183,96 @@ def test_reach_frames_bite(t, B):
         assert lost[('tight1', False)] == (m if exact else 0)
         if B > 384:
             assert lost[('tight2', True)] >= 2 and lost[('tight1', True)] >= (2 if exact else 0)
+
+
+# ---- the x-bucket windows -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", K.WINDOW_B)
+@pytest.mark.parametrize("t", K.WINDOW_THRESHOLDS)
+def test_window_frames_hold_what_they_are_built_for(oracle, t, B):
+    """Every window frame of the GPU suite (tests/test_xwindow_gpu.py takes its B, band heights, thresholds, families and seed
+    from K.WINDOW_B, K.window_band, K.WINDOW_THRESHOLDS, K.WINDOW_FAMILIES and K.WINDOW_SEED, as this test does): the family's
+    geometry is what its name says, every pinned pair is a true partner by the referee of its site -- classify()['sup'] for the
+    suppression graph, the oracle's link rule (its float32 IoU of the TRUNCATED current box >= the threshold) for the link
+    scans, the oracle's float64 IoU > t on the strict frames of re-scoring -- and the windows as the kernels write them
+    (window_model, mode 'kernel') hold every pinned pair at every site."""
+    for family in K.WINDOW_FAMILIES:
+        for strict in (False, True):
+            boxes, pairs = K.window_frame(t, B, family, K.WINDOW_SEED, strict)
+            assert boxes.shape == (B, 4) and boxes.dtype == F32 and pairs.shape[0] >= 2
+            w, h = boxes[:, 2] - boxes[:, 0] + 1, boxes[:, 3] - boxes[:, 1] + 1
+            assert np.isfinite(boxes).all() and w.min() > 0 and h.min() > 0 and boxes.min() >= 0 and boxes.max() <= 65535  # regular
+            whole = bool(np.array_equal(boxes, np.rint(boxes)))
+            assert whole == (family != 'frac')                                                       # kFlagU16 or not
+            rank, cum, xmin, scale, wmax = K.window_index(boxes)
+            O, I = boxes[pairs[:, 0]], boxes[pairs[:, 1]]
+            assert np.array_equal(O[:, 2], I[:, 2]) or family == 'flat'                              # flush right, full height
+            assert np.array_equal(O[:, [1, 3]], I[:, [1, 3]])
+            if family == 'flat':
+                assert scale == 0 and cum[1] == B
+            elif family == 'coarse':
+                assert scale == F32(1.0 / 16)
+            else:
+                assert scale == 1.0
+            if family in ('unit', 'wmaxcap', 'frac'):          # O the last rank of a word, I the first of a later one
+                assert np.all(rank[pairs[:, 0]] % 64 == 63) and np.all(rank[pairs[:, 1]] % 64 == 0)
+                assert np.all(rank[pairs[:, 1]] - rank[pairs[:, 0]] >= 65)
+                assert (wmax == K.WINDOW_W) == (family == 'wmaxcap')
+                assert np.all((I[:, 2] - I[:, 0] + 1) / F32(t) * F32(1.001) > K.WINDOW_W)            # ... so min(wmax, .) decides
+            if family == 'top':
+                xmax = boxes[:, 0].max()
+                assert sorted(I[:2, 0]) == [xmax - 1, xmax] and sorted(O[2:, 0]) == [xmin, xmin + 1]
+                assert cum[256] - cum[255] == 2 and cum[255] % 64 == 0
+            if family == 'coarse':                             # the pinned partner is alone in its bucket
+                bk = [K.xbucket(x, xmin, scale) for x in boxes[:, 0]]
+                alone = [bk.count(bk[r]) == 1 for r in pairs.ravel()]
+                assert sum(alone) >= pairs.shape[0]
+            for o, i in pairs:
+                for q, p in ((o, i), (i, o)):
+                    if strict:
+                        with np.errstate(all='ignore'):
+                            assert oracle.iou([boxes[q]], boxes[p:p + 1]).ravel()[0] > t
+                        assert K.window_partner(boxes[q], boxes[p], t, 'xwindow')
+                    else:
+                        assert K.classify(boxes[q][None], boxes[p][None], t)['sup'][0]
+                        cur = np.trunc(K.link_query(boxes[q]) if family == 'frac' else boxes[q])
+                        assert float(oracle._iou_f32_row(cur, boxes[p:p + 1])[0]) >= t
+                        assert K.window_partner(K.link_query(boxes[q]) if family == 'frac' else boxes[q], boxes[p], t, 'link')
+            for site in K.WINDOW_SITES:
+                if strict == (site == 'xwindow'):
+                    true, lost = K.window_lost(boxes, pairs, t, site, 'kernel', family == 'frac')
+                    assert true == 2 * pairs.shape[0] and lost == 0, (family, site)
+
+
+@pytest.mark.parametrize("B", K.WINDOW_B)
+@pytest.mark.parametrize("t", K.WINDOW_THRESHOLDS)
+def test_window_frames_bite(t, B):
+    """The condition that keeps the GPU tests from passing by accident: every single-token mistake of K.WINDOW_MUTANTS loses
+    at least one pinned pair at every site it applies to, taken over the families -- per threshold and per frame size.
+
+    Two mutants lose nothing on any frame, and cannot (K.WINDOW_UNKILLABLE says why): wmax_no_plus1 pulls the left bound in by
+    (1 - t) px, less than the smallest margin of 1 px; no_trunc_slack removes a margin that nothing needs, because the link
+    scans take the window and the IoU from the same truncated box.  They are asserted to lose NOTHING, so that a change of
+    the model or the frames that makes them bite is noticed.  'nomargin' (margins removed, nothing moved inward) is printed
+    only: whether it loses a pair hangs on one float32 rounding."""
+    lost = {}
+    for family in K.WINDOW_FAMILIES:
+        for site in K.WINDOW_SITES:
+            boxes, pairs = K.window_frame(t, B, family, K.WINDOW_SEED, site == 'xwindow')
+            for mode in K.WINDOW_MODES:
+                if mode in ('kernel', 'nomargin') or site in K.WINDOW_MUTANTS[mode]:
+                    n = K.window_lost(boxes, pairs, t, site, mode, family == 'frac')[1]
+                    lost.setdefault((site, mode), {})[family] = n
+    for (site, mode), by in sorted(lost.items()):
+        print('t = %g B = %d %-8s %-15s lost: %s' % (t, B, site, mode, ' '.join('%s=%d' % kv for kv in by.items())))
+        total = sum(by.values())
+        if mode == 'kernel' or mode in K.WINDOW_UNKILLABLE:
+            assert total == 0, (site, mode, by)
+        elif mode != 'nomargin':
+            assert total >= 1, (site, mode, by)
+    # which family pins what: the clamp at bucket 255 only 'top', cum[b1 + 1] 'top' and 'coarse' (unit buckets hide it behind
+    # the 2 px margin), the word rounding every family with a word boundary, one pixel inward at re-scoring only 'frac'
+    assert lost[('adj', 'clamp254')]['top'] >= 1 and lost[('adj', 'cum_b1')]['coarse'] >= 1 and lost[('adj', 'cum_b1')]['unit'] == 0
+    for family in ('unit', 'wmaxcap', 'coarse', 'frac', 'top'):
+        assert lost[('adj', 'floor_w1')][family] >= 1 and lost[('adj', 'ceil_w0')][family] >= 1
+        assert all(lost[(site, 'own_width_left')][family] >= 1 for site in K.WINDOW_SITES)
+    assert lost[('xwindow', 'in1')]['frac'] >= 1 and lost[('link', 'in1')]['frac'] >= 1 and lost[('adj', 'in1')]['frac'] >= 1
