@@ -82,6 +82,12 @@
  *                                          per box, windows < 2^31 - 16, C*T*F < 2^31 - 16      VDET_EINVAL; more present tubelet
  *                                                                     boxes than cap: VDET_ECAP latched (vdet_sync), the count
  *                                                                     still written.  One path for every size
+ *   device pixel tracker                   grid S a multiple of 4 in 4 .. 64, 1 <= radius R <= 16, step >= 1, max_frames >= 0,
+ *                                          min_conf finite, H, W <= 32767, C*T*F < 2^31 - 16      VDET_EINVAL; an anchor frame
+ *                                                                     outside 0..F, or an anchor box that is not finite, beyond
+ *                                                                     2^20, empty or wholly outside the image: VDET_EINVAL latched
+ *                                                                     (vdet_sync), the slot written as an empty one.  One path
+ *                                                                     for every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1021,6 +1027,37 @@ int vdet_svm_scores_dev_f64(vdet_ctx *ctx, const double *d_feat, int64_t n, int6
                             int64_t m, double *d_out);
 int vdet_svm_scores_dev_f32(vdet_ctx *ctx, const float *d_feat, int64_t n, int64_t k, const float *d_W, const float *d_B,
                             int64_t m, float *d_out);
+
+/* ---- device pixel tracker: tubelets that follow the PIXELS of an anchor box (the role of fcn_tracker, vdet/track.py:52-106;
+ *      its MATLAB arithmetic is external, parity with it is unpinned by nature).  The rule is tests/pixtrack_spec.py --------
+ *
+ * d_images uint8 [F,H,W,3] in the stored channel order (BGR from cv2.imread, never swapped).  Slots as in
+ * vdet_track_from_anchors: d_anchor_frames [C,T] int32 (1-based, 0 = empty slot), d_anchor_boxes [C,T,4] f32 (1-based
+ * inclusive), d_anchor_scores [C,T] f32 or NULL.  All arithmetic is integer on the pixels except the confidence:
+ *   luma      L = (29*c0 + 150*c1 + 77*c2 + 128) >> 8
+ *   box       the anchor box truncated toward zero, minus 1: 0-based (x1,y1,x2,y2), w = x2-x1+1, h = y2-y1+1; the size never
+ *             changes
+ *   grid      cell k of side S samples column clamp(x1 + floor((2k+1)*w / (2S)), 0, W-1), rows likewise: point sampling, edge
+ *             replication
+ *   template  the S x S grid k = 0..S-1 of the anchor box on the anchor frame; fixed for both directions, never updated
+ *   step      f -> g = f +- step: the region is the grid k = -R..S+R-1 of the current box on frame g; every (dy,dx) in
+ *             [-R,R]^2 gets SAD = sum |Tm[i,j] - Rg[i+R+dy, j+R+dx]|; the smallest (SAD, dy*dy+dx*dx, dy, dx) wins;
+ *             conf = 1.0f - (float)SAD / (float)(255*S*S); conf < (float)min_conf ends the chain; the box moves by
+ *             floor((2*dx*w + S) / (2S)), floor((2*dy*h + S) / (2S)); a moved box wholly outside the image ends the chain; else
+ *             the row (x1+1, y1+1, x2+1, y2+1, conf) is written
+ *   chain     forward and backward from the anchor row (truncated box, 1.0); also ends at the video's end and after
+ *             ceil((max_frames+1)/2) - 1 steps when max_frames > 0.  Rows not written -- beyond a chain's end, on the frames a
+ *             step > 1 skips, every row of an empty slot -- are NaN
+ * d_tracks [C,T,F,5] f32, d_anchors [C,T,3] f32 (frame, -1, score or 0), d_ntracks [C] int32 (1 + the last live slot of the
+ * class): the bits and layout of vdet_track_from_anchors' outputs, written by the ONE launch of the call (no fill pass, no host
+ * table, no host wait); timed under "other".  An anchor frame outside 0..F, or on a live slot a box that is not finite, has
+ * |coordinate| > 2^20, w < 1 or h < 1 after truncation or lies wholly outside the image, is latched (VDET_EINVAL at vdet_sync);
+ * its slot is written as an empty one.  Reads and writes nothing of the context's cached graph, lists, index or link memo.
+ * ctx NULL: VDET_EINVAL, nothing touched.  Limits: the table at the top of this file.
+ */
+int vdet_track_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                      const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                      int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,7 @@ SYMBOLS = {
                             _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_svm_scores_dev_f64": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "vdet_svm_scores_dev_f32": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "vdet_track_pixels": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _vp, _vp, _vp]),
 }
 
 

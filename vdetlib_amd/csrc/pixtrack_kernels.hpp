@@ -1,0 +1,255 @@
+// Device pixel tracker: tubelets that follow the PIXELS of an anchor box through the frames (the role of the reference's
+// fcn_tracker, vdet/track.py:52-106; not its arithmetic: that is external MATLAB), in the [C,T,F,5] layout of the anchor route.
+// The rule is tests/pixtrack_spec.py, integers on uint8 pixels; the device matches it bit for bit.
+//
+//   luma      L = (29*c0 + 150*c1 + 77*c2 + 128) >> 8 on the stored channel order
+//   grid      box (x1,y1,x2,y2) 0-based, w = x2-x1+1, side S: cell k samples column clamp(x1 + floor((2k+1)*w / 2S), 0, W-1),
+//             rows likewise (point sampling, edge replication)
+//   template  the grid k = 0..S-1 of the (truncated, minus one) anchor box on the anchor frame, fixed for both directions
+//   step      f -> g = f +- step: the region is the grid k = -R..S+R-1 of the current box on frame g; every (dy,dx) in
+//             [-R,R]^2 gets SAD = sum |Tm[i,j] - Rg[i+R+dy, j+R+dx]|; the smallest key (SAD, dy^2+dx^2, dy, dx) wins;
+//             conf = 1.0f - float(SAD) / float(255*S*S); conf < (float)min_conf ends the chain; the box moves by
+//             floor((2*dx*w + S) / 2S), floor((2*dy*h + S) / 2S); a box wholly outside the image ends the chain; else the row
+//             (x1+1, y1+1, x2+1, y2+1, conf) is written
+//   bad data  an anchor frame outside 0..F; on a live slot a box that is not finite, has |coordinate| > 2^20, w < 1 or h < 1
+//             after truncation, or lies wholly outside the image: kStBadPixAnchor, the slot is written as an empty one
+//
+// Shape: anchor_link_kernel's.  ONE launch, grid (C*T, 2), a workgroup per chain (slot x direction); the forward block
+// writes the anchor row, the anchors entry, a dead slot's NaN rows and -- slot 0 of a class -- ntracks; every output element
+// is written exactly once by this launch (a chain's own rows by thread 0, the rows it does not reach -- beyond its end and on
+// the frames step > 1 skips -- by the whole block afterwards).  A chain is a dependent walk; the parallelism is across the
+// chains and inside a step:
+//   1. the first 2*(S+2R) threads make the step's column / row tables (one floor division each);
+//   2. the block gathers the (S+2R)^2 region, luma from the three bytes in flight, four pixels to a dword of LDS;
+//   3. the (2R+1)^2 candidates are spread over the lanes; a candidate is S*S/4 v_sad_u8 on dwords that v_alignbyte_b32 cuts
+//      from two neighbouring region dwords (the template dword is the same address in every lane: an LDS broadcast);
+//   4. the key packed in 64 bits (SAD | dy^2+dx^2 | dy+R | dx+R) is min-reduced by wave shuffles, then over the waves through
+//      an LDS slot per wave, double-buffered by step parity.  Keys are unique, so the order of the reduction cannot matter;
+//      every lane derives the new box from the winning key.
+// LDS: region 96 x 25 dwords (one spare dword per row for the pair read at shift 0) + template 64 x 16 dwords + tables:
+// 14.2 KiB, static.  Nothing of the context's cached graph, lists, index or link memo is read or written.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace vdet {
+
+constexpr int kStBadPixAnchor = 4096;    // vdet_track_pixels: an anchor frame outside 0..F or an anchor box that cannot be tracked
+constexpr int kPixLT = 256;              // threads per chain
+constexpr int kPixWaves = kPixLT / 64;
+constexpr int kPixMaxS = 64, kPixMaxR = 16;
+constexpr int kPixMaxP = kPixMaxS + 2 * kPixMaxR;       // region side
+constexpr int kPixMaxPitch = kPixMaxP / 4 + 1;          // region row pitch in dwords (one spare: see the pair read)
+constexpr int kPixCoordMax = 1 << 20;
+
+struct PixTrackArgs {
+    const uint8_t *images;      // [F,H,W,3]
+    int F, H, W, C, T;
+    const int32_t *aframes;     // [C,T] 1-based, 0: empty slot
+    const float *aboxes;        // [C,T,4]
+    const float *ascores;       // [C,T] or null
+    int S, R;
+    float min_conf;
+    int reach, step;
+    float *tracks;              // [C,T,F,5]
+    float *anchors;             // [C,T,3]
+    int32_t *ntracks;           // [C]
+    int *status;
+};
+
+__device__ __forceinline__ int pix_floordiv(int a, int b)      // b > 0
+{
+    int q = a / b;
+    if (a - q * b < 0) --q;
+    return q;
+}
+
+__device__ __forceinline__ bool pix_outside(int x1, int y1, int x2, int y2, int H, int W)
+{
+    return x2 < 0 || y2 < 0 || x1 > W - 1 || y1 > H - 1;
+}
+
+// 0: empty slot, -1: bad data, 1: live and b = the 0-based integer box
+__device__ __forceinline__ int pix_anchor_state(const PixTrackArgs &a, int64_t slot, int4 &b)
+{
+    const int fr = a.aframes[slot];
+    if (fr < 0 || fr > a.F) return -1;
+    if (fr == 0) return 0;
+    const float *p = a.aboxes + slot * 4;
+    const float lim = (float)kPixCoordMax;
+    const float v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
+    // (a NaN fails every comparison, an infinity the bound)
+    if (!(fabsf(v0) <= lim && fabsf(v1) <= lim && fabsf(v2) <= lim && fabsf(v3) <= lim)) return -1;
+    b = make_int4((int)v0 - 1, (int)v1 - 1, (int)v2 - 1, (int)v3 - 1);
+    if (b.z - b.x + 1 < 1 || b.w - b.y + 1 < 1 || pix_outside(b.x, b.y, b.z, b.w, a.H, a.W)) return -1;
+    return 1;
+}
+
+__device__ __forceinline__ uint32_t pix_luma(const uint8_t *p)
+{
+    return (29u * p[0] + 150u * p[1] + 77u * p[2] + 128u) >> 8;
+}
+
+// the tables of the grid k = k0 .. k0+n-1 of the box: tcol[i] = 3 * column, trow[i] = row.  n <= kPixMaxP, 2n <= kPixLT.
+__device__ __forceinline__ void pix_tables(int *tcol, int *trow, int x1, int y1, int w, int h, int S, int k0, int n, int H, int W)
+{
+    const int tid = threadIdx.x;
+    if (tid < 2 * n) {
+        const bool isrow = tid >= n;
+        const int i = isrow ? tid - n : tid;
+        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W;
+        int v = o + pix_floordiv((2 * (k0 + i) + 1) * e, 2 * S);
+        v = v < 0 ? 0 : (v > lim - 1 ? lim - 1 : v);
+        if (isrow) trow[i] = v;
+        else tcol[i] = 3 * v;
+    }
+}
+
+// n x n lumas of one frame into dst (row pitch `pitch` dwords, all of them written; bytes beyond n are 0)
+__device__ __forceinline__ void pix_gather(uint32_t *dst, int pitch, const int *tcol, const int *trow, int n,
+                                           const uint8_t *frame, int W)
+{
+    const int total = n * pitch;
+    for (int d = threadIdx.x; d < total; d += kPixLT) {
+        const int i = d / pitch, q = d - i * pitch;
+        const uint8_t *rp = frame + (int64_t)trow[i] * W * 3;
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int j = 4 * q + b;
+            if (j < n) v |= pix_luma(rp + tcol[j]) << (8 * b);
+        }
+        dst[d] = v;
+    }
+}
+
+// grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
+// slot 0 of a class -- the class's ntracks), 1 backward.
+__global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
+{
+    __shared__ uint32_t sreg[kPixMaxP * kPixMaxPitch];
+    __shared__ uint32_t stm[kPixMaxS * (kPixMaxS / 4)];
+    __shared__ int tcol[kPixMaxP], trow[kPixMaxP];
+    __shared__ unsigned long long skey[2][kPixWaves];
+    __shared__ int snt;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t slot = blockIdx.x;
+    const int c = (int)(slot / a.T), t = (int)(slot - (int64_t)c * a.T);
+    const int dir = blockIdx.y == 0 ? 1 : -1;
+    const int F = a.F, H = a.H, W = a.W, S = a.S, R = a.R;
+    float *trk = a.tracks + slot * F * 5;
+    const float qnan = __uint_as_float(0x7FC00000u);
+
+    int4 ab = make_int4(0, 0, 0, 0);
+    const int state = pix_anchor_state(a, slot, ab);
+    const bool live = state == 1;
+    const int af = live ? a.aframes[slot] - 1 : 0;
+
+    if (dir > 0) {
+        if (tid == 0) {
+            if (state < 0) atomicOr(a.status, kStBadPixAnchor);
+            a.anchors[slot * 3] = (float)a.aframes[slot];
+            a.anchors[slot * 3 + 1] = -1.0f;
+            a.anchors[slot * 3 + 2] = a.ascores ? a.ascores[slot] : 0.0f;
+        }
+        if (t == 0) {            // (block-uniform) the class's count: 1 + its last live slot
+            if (tid == 0) snt = 0;
+            __syncthreads();
+            for (int k = tid; k < a.T; k += kPixLT) {
+                int4 bk;
+                if (pix_anchor_state(a, (int64_t)c * a.T + k, bk) == 1) atomicMax(&snt, k + 1);
+            }
+            __syncthreads();
+            if (tid == 0) a.ntracks[c] = snt;
+        }
+    }
+    if (!live) {                 // every row of a dead slot is the forward block's
+        if (dir > 0)
+            for (int64_t i = tid; i < (int64_t)F * 5; i += kPixLT) trk[i] = qnan;
+        return;
+    }
+    // the box state is the same in every lane: keep it in scalar registers
+    int x1 = __builtin_amdgcn_readfirstlane(ab.x), y1 = __builtin_amdgcn_readfirstlane(ab.y);
+    const int w = __builtin_amdgcn_readfirstlane(ab.z - ab.x + 1), h = __builtin_amdgcn_readfirstlane(ab.w - ab.y + 1);
+    if (dir > 0 && tid == 0) {
+        float *r = trk + (int64_t)af * 5;
+        r[0] = (float)(x1 + 1); r[1] = (float)(y1 + 1); r[2] = (float)(x1 + w); r[3] = (float)(y1 + h); r[4] = 1.0f;
+    }
+    const int64_t frame_bytes = (int64_t)H * W * 3;
+    const int P = S + 2 * R, pitch = P / 4 + 1, tq = S / 4, side = 2 * R + 1, ncand = side * side;
+    // the template
+    pix_tables(tcol, trow, x1, y1, w, h, S, 0, S, H, W);
+    __syncthreads();
+    pix_gather(stm, tq, tcol, trow, S, a.images + (int64_t)af * frame_bytes, W);
+    __syncthreads();
+    const float denom = (float)(255 * S * S);
+
+    int n = 0;                   // steps taken so far (block-uniform)
+    for (int s = 1; s <= a.reach; ++s) {
+        const int64_t g64 = (int64_t)af + (int64_t)dir * s * a.step;
+        if (g64 < 0 || g64 >= F) break;
+        const int g = (int)g64, par = s & 1;
+        // (the readers of the tables and of the region are behind a barrier: the template's below, the step's last one)
+        pix_tables(tcol, trow, x1, y1, w, h, S, -R, P, H, W);
+        __syncthreads();
+        pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
+        __syncthreads();
+        unsigned long long key = ~0ull;
+        for (int cand = tid; cand < ncand; cand += kPixLT) {
+            const int cy = cand / side, cx = cand - cy * side;      // dy + R, dx + R
+            const int sh = cx & 3;
+            const uint32_t *rrow = sreg + cy * pitch + (cx >> 2);
+            const uint32_t *tp = stm;
+            uint32_t sad = 0;
+            for (int i = 0; i < S; ++i) {
+                uint32_t lo = rrow[0];
+                for (int q = 0; q < tq; ++q) {
+                    const uint32_t hi = rrow[q + 1];
+                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(hi, lo, sh), tp[q], sad);
+                    lo = hi;
+                }
+                rrow += pitch;
+                tp += tq;
+            }
+            const int dy = cy - R, dx = cx - R;
+            const unsigned long long k = ((unsigned long long)sad << 32) | ((unsigned long long)(dy * dy + dx * dx) << 16) |
+                                         ((unsigned long long)cy << 8) | (unsigned long long)cx;
+            key = k < key ? k : key;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long k2 = __shfl_xor(key, d, 64);
+            key = k2 < key ? k2 : key;
+        }
+        if (lane == 0) skey[par][wv] = key;
+        __syncthreads();
+        key = skey[par][0];
+#pragma unroll
+        for (int k = 1; k < kPixWaves; ++k) {
+            const unsigned long long k2 = skey[par][k];
+            key = k2 < key ? k2 : key;
+        }
+        const uint32_t sad = (uint32_t)(key >> 32);
+        const int dy = (int)((key >> 8) & 0xFF) - R, dx = (int)(key & 0xFF) - R;
+        const float conf = 1.0f - (float)sad / denom;
+        if (conf < a.min_conf) break;
+        x1 = __builtin_amdgcn_readfirstlane(x1 + pix_floordiv(2 * dx * w + S, 2 * S));
+        y1 = __builtin_amdgcn_readfirstlane(y1 + pix_floordiv(2 * dy * h + S, 2 * S));
+        if (pix_outside(x1, y1, x1 + w - 1, y1 + h - 1, H, W)) break;
+        if (tid == 0) {
+            float *r = trk + (int64_t)g * 5;
+            r[0] = (float)(x1 + 1); r[1] = (float)(y1 + 1); r[2] = (float)(x1 + w); r[3] = (float)(y1 + h); r[4] = conf;
+        }
+        n = s;
+    }
+    // the rows of this half the chain did not write: beyond its end, and the frames a step > 1 skips
+    const int nf = dir > 0 ? F - 1 - af : af;         // frames of the half, at distance 1 .. nf from the anchor
+    for (int64_t i = tid; i < (int64_t)nf * 5; i += kPixLT) {
+        const int d = (int)(i / 5) + 1, e = (int)(i - (int64_t)(d - 1) * 5);
+        if (d % a.step == 0 && d / a.step <= n) continue;
+        trk[(int64_t)(af + dir * d) * 5 + e] = qnan;
+    }
+}
+
+}  // namespace vdet

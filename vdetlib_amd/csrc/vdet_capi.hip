@@ -38,6 +38,7 @@
 #include "rescore_kernels.hpp"
 #include "patch_kernels.hpp"
 #include "svmhead_kernels.hpp"
+#include "pixtrack_kernels.hpp"
 
 using namespace vdet;
 
@@ -345,6 +346,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStPoolAsync) return fail(c, VDET_EAGAIN, "adjacency pool overflow in an asynchronous graph build: run the calls again");
     if (st & kStBadOrder) return fail(c, VDET_EINVAL, "a caller-supplied candidate list holds a count or a box index out of range");
     if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
+    if (st & kStBadPixAnchor) return fail(c, VDET_EINVAL, "track_pixels: an anchor frame outside the video, or an anchor box that is not finite, beyond 2^20, empty or wholly outside the image (the slot is written as an empty one)");
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
     if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
@@ -4054,6 +4056,47 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
     else if (compute_f64) svm_head_launch<double>(c, g, feat_dtype, vec, (unsigned)blocks);
     else svm_head_launch<float>(c, g, feat_dtype, vec, (unsigned)blocks);
     hipLaunchKernelGGL(svm_nbad_kernel, dim3(1), dim3(1024), 0, c->stream, c->svm_wavebad.as<int32_t>(), nwaves, d_nbad);
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device pixel tracker (pixtrack_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                      const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                      int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (S < 4 || S > kPixMaxS || S % 4) return fail(c, VDET_EINVAL, "grid = %d; a multiple of 4 in 4 .. %d", S, kPixMaxS);
+    if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
+    if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
+    if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
+    if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
+    if (!d_images || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (T == 0) {
+        HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
+        return VDET_OK;
+    }
+    PixTrackArgs a{};
+    a.images = d_images;
+    a.F = (int)F; a.H = (int)H; a.W = (int)W; a.C = (int)C; a.T = T;
+    a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
+    a.S = S; a.R = R;
+    a.min_conf = (float)min_conf;
+    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)F;
+    a.step = step;
+    a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
+    a.status = &c->d_cnt->status;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
+    }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
 }

@@ -7,6 +7,7 @@ A c2-size video (300 frames x 10k boxes x 200 classes) cannot travel as protocol
 """
 import ctypes
 import itertools
+import math
 
 import numpy as np
 import torch
@@ -655,6 +656,73 @@ def track_from_anchors(boxes, anchor_frames, anchor_boxes, anchor_scores=None, l
     ctx.check(ctx.lib.vdet_track_from_anchors(
         ctx.h, boxes.data_ptr(), F, B, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
         anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, float(link_thres), int(max_frames),
+        tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
+    if sync:
+        ctx.sync()
+    return tracks, anchors, ntracks
+
+
+def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
+                 sync=True, ctx=None):
+    """Tubelets that follow the PIXELS of the anchor boxes (include/vdet_hip.h: vdet_track_pixels; the rule is
+    tests/pixtrack_spec.py): the array form of track_from_det with an appearance tracker as ``track_method`` -- the role of the
+    reference's fcn_tracker (vdet/track.py:52-106), not its MATLAB arithmetic.  All chains of the video in one launch.
+
+    images uint8 [F,H,W,3], contiguous, in the stored channel order (BGR from cv2.imread: never swapped); anchor_frames [C,T]
+    int32 (1-based, 0 = empty slot), anchor_boxes [C,T,4] f32 (1-based inclusive), anchor_scores [C,T] f32 or None, all on the
+    images' GPU: ``top_anchors``' outputs go in unchanged.  A ``grid`` x ``grid`` point-sampled luma template of the
+    (int-truncated) anchor box is matched by SAD within ``radius`` grid cells on every ``step``-th frame, forward and backward;
+    a chain ends when the confidence 1 - SAD / (255 * grid^2) falls below ``min_conf``, when the box leaves the image, at the
+    video's end or after ceil((max_frames+1)/2) - 1 steps (max_frames = 0: no limit).  The box never changes size.
+    Returns, in ``track_from_anchors``' layout,
+      tracks  [C,T,F,5] f32 rows (x1,y1,x2,y2,confidence), NaN where a tubelet has no box (the frames ``step`` skips included),
+      anchors [C,T,3] f32 (frame, -1, score or 0),  ntracks [C] int32 = 1 + the last live slot of the class.
+    ValueError for grid not a multiple of 4 in 4..64, radius outside 1..16, step < 1, max_frames < 0 or a min_conf that is not
+    finite (before any launch); and for an anchor frame outside 0..F or an anchor box that is not finite, beyond 2^20, empty or
+    wholly outside the image (reported when the call, or a later ``ctx.sync()``, waits; the slot is written as an empty one)."""
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("images must be uint8 [F,H,W,3]")
+    if not images.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    F, H, W = images.shape[0], images.shape[1], images.shape[2]
+    if F < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767:
+        raise ValueError("images must hold at least one frame of 1 .. 32767 rows and columns")
+    if anchor_boxes.dtype != torch.float32 or (anchor_scores is not None and anchor_scores.dtype != torch.float32):
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if anchor_frames.dtype != torch.int32:
+        raise ValueError("anchor_frames must be int32")
+    if anchor_frames.dim() != 2:
+        raise ValueError("anchor_frames must be [C,T]")
+    C, T = anchor_frames.shape
+    if C < 1:
+        raise ValueError("anchor_frames must be [C,T] with C >= 1")
+    if tuple(anchor_boxes.shape) != (C, T, 4):
+        raise ValueError("anchor_boxes must be [C,T,4]")
+    if anchor_scores is not None and tuple(anchor_scores.shape) != (C, T):
+        raise ValueError("anchor_scores must be [C,T]")
+    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
+        if not t.is_cuda or t.device != images.device:
+            raise ValueError("images, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
+    grid, radius, max_frames, step, min_conf = int(grid), int(radius), int(max_frames), int(step), float(min_conf)
+    if grid % 4 or not 4 <= grid <= 64:
+        raise ValueError("grid = %d; a multiple of 4 in 4 .. 64" % grid)
+    if not 1 <= radius <= 16:
+        raise ValueError("radius = %d; 1 .. 16" % radius)
+    if step < 1 or max_frames < 0:
+        raise ValueError("step must be >= 1 and max_frames >= 0")
+    if not math.isfinite(min_conf):
+        raise ValueError("min_conf must be finite")
+    ctx = _ctx_for(images, ctx)
+    anchor_frames, anchor_boxes = anchor_frames.contiguous(), anchor_boxes.contiguous()
+    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
+    tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=images.device)
+    anchors = torch.empty((C, T, 3), dtype=torch.float32, device=images.device)
+    ntracks = torch.empty((C,), dtype=torch.int32, device=images.device)
+    ctx.check(ctx.lib.vdet_track_pixels(
+        ctx.h, images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+        anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, grid, radius, min_conf, max_frames, step,
         tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
     if sync:
         ctx.sync()

@@ -5,14 +5,19 @@ anchor -> run the tracker plug-in -> suppress the detections the new track expla
 The reference's trackers (fcn_tracker :52-106, tld_tracker :18-49) are wrappers around external
 MATLAB code and are out of scope; ``track_method(vid_proto, anchor_frame_id, anchor_bbox, opts)
 -> [tracklet, ...]`` stays the plug-in boundary (tracklet = list of
-{'frame','bbox','hash','score','anchor'}, utils/protocol.py:403-411).
+{'frame','bbox','hash','score','anchor'}, utils/protocol.py:403-411).  ``pixel_tracker`` is a
+track_method of this package's own: it follows the pixels of the anchor box on the GPU
+(ops.track_pixels); it plays fcn_tracker's role, it does not reproduce its arithmetic.
 """
+import os
 from collections import defaultdict
 
 import numpy as np
 
+from ..utils.common import imread
 from ..utils.cython_nms import track_det_nms, track_det_nms_batch     # noqa: F401 (track_det_nms: the reference's import)
 from ..utils.log import logger as logging
+from ..utils.protocol import tracks_proto_from_boxes
 
 
 def _external(name):
@@ -25,6 +30,51 @@ def _external(name):
 
 fcn_tracker = _external('fcn_tracker')
 tld_tracker = _external('tld_tracker')
+
+
+_pixel_video = {}          # (video name, frame count) -> uint8 [F,H,W,3] on the GPU; ONE video at a time
+
+
+def _pixel_frames(vid_proto):
+    """The video's frames on the device, read through the module attribute ``imread`` once per video."""
+    key = (vid_proto['video'], len(vid_proto['frames']))
+    images = _pixel_video.get(key)
+    if images is None:
+        import torch
+        frames = [imread(str(os.path.join(vid_proto['root_path'], frame['path']))) for frame in vid_proto['frames']]
+        images = torch.from_numpy(np.ascontiguousarray(np.stack(frames, 0), dtype=np.uint8)).cuda()
+        _pixel_video.clear()
+        _pixel_video[key] = images
+    return images
+
+
+def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
+    """A ``track_method`` that follows the pixels of ``bbox`` forward and backward from ``anchor_frame_id`` on the GPU
+    (ops.track_pixels, one call with C = T = 1).  Reads ``opts.step`` and ``opts.max_frames`` as fcn_tracker does (:64-71),
+    and the optional ``opts.grid`` / ``opts.radius`` / ``opts.min_conf``.  The frames are uploaded once per video (a module
+    cache keyed by the video's name and frame count).  Returns ``tracks_proto_from_boxes`` over the visited frames only, with
+    fcn_tracker's ``start_frame`` and ``step`` (:100-102)."""
+    import torch
+    from .. import ops
+    images = _pixel_frames(vid_proto)
+    ids = [frame['frame'] for frame in vid_proto['frames']]
+    pos = ids.index(anchor_frame_id)
+    max_frames = opts.max_frames if getattr(opts, 'max_frames', None) is not None else 0
+    step = int(getattr(opts, 'step', 1))
+    dev = images.device
+    tracks, _, _ = ops.track_pixels(
+        images, torch.tensor([[pos + 1]], dtype=torch.int32, device=dev),
+        torch.tensor([[[float(v) for v in bbox]]], dtype=torch.float32, device=dev), None,
+        grid=getattr(opts, 'grid', 32), radius=getattr(opts, 'radius', 8), min_conf=getattr(opts, 'min_conf', 0.5),
+        max_frames=max_frames, step=step)
+    rows = tracks[0, 0].cpu().numpy()
+    lo = hi = pos
+    while lo - step >= 0 and not np.isnan(rows[lo - step, 0]):
+        lo -= step
+    while hi + step < len(ids) and not np.isnan(rows[hi + step, 0]):
+        hi += step
+    start_frame = anchor_frame_id - (pos - lo)
+    return tracks_proto_from_boxes(rows[lo:hi + 1:step], vid_proto['video'], anchor_frame_id, start_frame, step)
 
 
 def track_from_det(vid_proto, det_proto, track_method):
