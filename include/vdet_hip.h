@@ -88,6 +88,10 @@
  *                                                                     2^20, empty or wholly outside the image: VDET_EINVAL latched
  *                                                                     (vdet_sync), the slot written as an empty one.  One path
  *                                                                     for every size
+ *   greedy loop with the pixel tracker     the pixel tracker's row with T = max_tracks, and B <= 32767, F*C and F*B < 2^31 - 16
+ *                                                                     VDET_EINVAL; an anchor box that cannot be tracked:
+ *                                                                     VDET_EINVAL latched (vdet_sync), the slot taken with NaN
+ *                                                                     rows, the loop goes on
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1058,6 +1062,30 @@ int vdet_svm_scores_dev_f32(vdet_ctx *ctx, const float *d_feat, int64_t n, int64
 int vdet_track_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
                       const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
                       int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+/* ---- greedy tubelet generation with the pixel tracker: greedily_track_from_raw_dets (vdet/track.py:189-252) for every class of
+ *      a video with vdet_track_pixels' chain as track_method.  The rule is tests/greedy_pixel_spec.py -----------------------
+ *
+ * d_images uint8 [F,H,W,3]; d_boxes [F,B,4] f32 (16-byte aligned), d_scores [F,B,C] f32 as vdet_track_volume.  Per class, up to
+ * max_tracks times: the best remaining detection after the monotone cursor is the anchor (stable descending order of the
+ * scores; a score < thres ends the class); its box, truncated toward zero, is followed through the pixels by vdet_track_pixels'
+ * rule (S, R, min_conf, max_frames, step); every detection list of a frame the new tubelet has a row on goes through
+ * track_det_nms (utils/nms.pyx:128-189) against that row at nms_thres.  Frames step skips have no row: their detections stay.
+ * d_tracks [C,max_tracks,F,5] f32 rows (x1,y1,x2,y2,confidence; 1.0 on the anchor row), d_anchors [C,max_tracks,3] f32 (1-based
+ * frame, box index, score: vdet_track_volume's), d_ntracks [C] int32.  The slots up to ntracks are written whole (NaN where a
+ * tubelet has no box); those behind it are NOT written: the caller pre-fills d_tracks with NaN and d_anchors with zeros.
+ * An anchor whose box cannot be tracked (not finite, |coordinate| > 2^20, empty after truncation, wholly outside the image)
+ * takes its slot with NaN rows, suppresses nothing, and is latched (VDET_EINVAL at vdet_sync); the loop goes on.
+ * Three launches per track (pick; chains, grid (C,2); eager track_det_nms of irregular frames + commit), enqueued back to back:
+ * no host wait.  Timed under "track_loop".  The suppression graph and the sorted lists are the context's, reused under
+ * vdet_nms_track_volume's conditions and consumed likewise; no tubelet nodes are recorded (vdet_rescore_tracks takes its
+ * general path on the result).  Argument checks: vdet_nms_track_volume's and vdet_track_pixels', before any launch.
+ * ctx NULL: VDET_EINVAL, nothing touched.
+ */
+int vdet_track_volume_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes,
+                             const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                             int max_tracks, int S, int R, double min_conf, int max_frames, int step, float *d_tracks,
+                             float *d_anchors, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

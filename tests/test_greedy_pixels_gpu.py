@@ -1,0 +1,292 @@
+"""-m gpu: greedy tubelet generation with the pixel tracker on the device (ops.track_volume_pixels; csrc/pixtrack_kernels.hpp,
+track_kernels.hpp) against tests/greedy_pixel_spec.py ON BITS: equal NaN masks, every other element the same bit pattern.
+  a. the main case;  b. the dict-level host loop with vdet.track.pixel_tracker on the same inputs;  c. step and max_frames;
+  d. min_conf with a vanishing object;  e. against the anchor route (top_anchors + track_pixels): no duplicates;
+  f. lazy and eager list maintenance;  g. an irregular frame (the eager pass under the default switches);
+  h. an untrackable anchor;  i. a class that stops early;  j. argument errors;  k. the context's state;  l. downstream."""
+import numpy as np
+import pytest
+
+import greedy_pixel_cases as gc
+import greedy_pixel_spec as gs
+import pixtrack_cases as pc
+
+pytestmark = pytest.mark.gpu
+
+
+def g(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def bits_equal(got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return False
+    if got.dtype.kind != 'f':
+        return np.array_equal(got, want)
+    nan = np.isnan(want)
+    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(u)[~nan], want.view(u)[~nan])
+
+
+def device(images, boxes, scores, **kw):
+    from vdetlib_amd import ops
+    return tuple(x.cpu().numpy() for x in ops.track_volume_pixels(g(images), g(boxes), g(scores), **kw))
+
+
+def assert_same(got, want):
+    for k, name in enumerate(('tracks', 'anchors', 'ntracks')):
+        assert bits_equal(got[k], want[k]), name
+
+
+def assert_spec(images, boxes, scores, ctx=None, **kw):
+    """device == spec on bits; returns the spec's outputs"""
+    want = gs.track_volume_pixels(images, boxes, scores, **kw)
+    assert not want[3]
+    assert_same(device(images, boxes, scores, ctx=ctx, **kw), want)
+    return want
+
+
+# a. -------------------------------------------------------------------------------------------------------------------
+def test_main_case():
+    (images, boxes, scores, posa, posb), want = gc.main_case()
+    got = device(images, boxes, scores, **gc.MAIN)
+    assert_same(got, want)
+    assert got[2].tolist() == [3, 1]          # (what the case is: test_greedy_pixels_cpu.py)
+
+
+# b. -------------------------------------------------------------------------------------------------------------------
+class Opts(object):
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def test_dict_level_loop_gives_the_same_tubelets():
+    from vdetlib_amd import ops
+    from vdetlib_amd.vdet import track
+    (images, boxes, scores, _, _), _ = gc.main_case()
+    tracks, anchors, ntracks = device(images, boxes, scores, **gc.MAIN)
+    vid = {'video': 'pixvid', 'root_path': '/nowhere', 'frames': [{'frame': f + 1, 'path': '%04d.JPEG' % f} for f in range(gc.F)]}
+    det_info = np.hstack([np.repeat(np.arange(1, gc.F + 1), gc.B)[:, None].astype(np.float64), boxes.reshape(-1, 4).astype(np.float64),
+                          scores.reshape(-1, gc.C).astype(np.float64)])
+    opts = Opts(step=1, max_frames=None, max_tracks=gc.MAIN['max_tracks'], thres=gc.MAIN['thres'], nms_thres=gc.MAIN['nms_thres'],
+                grid=gc.S, radius=gc.R, min_conf=gc.MAIN['min_conf'])
+    view = lambda proto: [[(b['frame'], b['bbox'], b['score'], b['anchor']) for b in t] for t in proto['tracks']]
+    saved = track.imread
+    track._pixel_video.clear()
+    try:
+        track.imread = lambda path: images[int(path.split('/')[-1].split('.')[0])]
+        for c in range(gc.C):
+            host = track.greedily_track_from_raw_dets(vid, det_info, track.pixel_tracker, c + 1, opts)
+            mine = ops.tracks_to_proto('pixvid', tracks[c], anchors[c], ntracks[c], method='pixel_tracker')
+            assert host['method'] == mine['method'] == 'pixel_tracker'
+            assert len(host['tracks']) == int(ntracks[c]) and view(host) == view(mine), c
+    finally:
+        track.imread = saved
+        track._pixel_video.clear()
+
+
+# c. -------------------------------------------------------------------------------------------------------------------
+def test_step_and_max_frames_leave_the_skipped_frames_alone():
+    (images, boxes, scores, _, _), _ = gc.main_case()
+    kw = dict(gc.MAIN, step=2, max_frames=5)
+    tracks, anchors, nt, _ = assert_spec(images, boxes, scores, **kw)
+    # track 0: the anchor frame and two steps of two frames each way
+    assert np.flatnonzero(np.isfinite(tracks[0, 0, :, 0])).tolist() == [gc.FA - 4, gc.FA - 2, gc.FA, gc.FA + 2, gc.FA + 4]
+    # the duplicate on the next frame was not crossed: it is alive, and second in the order -> the next anchor
+    assert anchors[0, 1, :2].tolist() == [gc.FA + 2, gc.IJA[0]]
+    assert np.flatnonzero(np.isfinite(tracks[0, 1, :, 0])).tolist() == [gc.FA - 3, gc.FA - 1, gc.FA + 1, gc.FA + 3, gc.FA + 5]
+
+
+# d. -------------------------------------------------------------------------------------------------------------------
+def test_min_conf_ends_the_chain_and_the_detections_beyond_stay():
+    images, boxes, scores, posa, posb = gc.two_objects(4200, vanish_a_from=7)
+    kw = dict(gc.MAIN, min_conf=0.9, max_tracks=4)
+    tracks, anchors, nt, _ = assert_spec(images, boxes, scores, **kw)
+    assert np.array_equal(tracks[0, 0], pc.rows_from_positions(posa, gc.WA, gc.HA, range(7)), equal_nan=True)
+    assert np.array_equal(tracks[0, 1], pc.rows_from_positions(posb, gc.WB, gc.HB, range(gc.F)))
+    # A's proposals on the frames after it vanished were not crossed: the best of them is the third anchor
+    assert anchors[0, 2, 0] >= 8 and int(anchors[0, 2, 1]) in (gc.IA,) + gc.IJA and nt[0] == 4
+
+
+# e. -------------------------------------------------------------------------------------------------------------------
+def test_no_duplicates_where_the_anchor_route_has_them():
+    from vdetlib_amd import ops
+    (images, boxes, scores, posa, posb), want = gc.main_case()
+    ti, tb, ts = g(images), g(boxes), g(scores)
+    fr, ab, asc, _ = ops.top_anchors(tb, ts, 3)
+    route = ops.track_pixels(ti, fr, ab, asc, grid=gc.S, radius=gc.R, min_conf=0.0)[0].cpu().numpy()
+    greedy = device(images, boxes, scores, **gc.MAIN)[0]
+    assert not bits_equal(route, greedy)
+    # the anchor route's slot 1 is the second detection in the order, A's jittered copy: the same object as slot 0 ...
+    assert fr.cpu().numpy()[0].tolist()[:2] == [gc.FA + 1, gc.FA + 2]
+    assert bits_equal(route[0, 0], greedy[0, 0])
+    overlap = [gc.iou(route[0, 0, f, :4], route[0, 1, f, :4]) for f in range(gc.F)]
+    assert overlap[gc.FA + 1] >= 0.3
+    # ... the greedy loop's slot 1 is the other object
+    assert max(gc.iou(greedy[0, 0, f, :4], greedy[0, 1, f, :4]) for f in range(gc.F)) == 0.0
+    assert np.array_equal(greedy[0, 1], pc.rows_from_positions(posb, gc.WB, gc.HB, range(gc.F)))
+
+
+# f. -------------------------------------------------------------------------------------------------------------------
+def test_eager_and_lazy_list_maintenance_agree(monkeypatch):
+    import torch
+    from vdetlib_amd import _lib
+    (images, boxes, scores, _, _), want = gc.main_case()
+    monkeypatch.setenv('VDET_NO_LAZY', '1')
+    cx = _lib.Context(torch.cuda.current_device())
+    try:
+        got = device(images, boxes, scores, ctx=cx, **gc.MAIN)
+        kw = dict(gc.MAIN, step=2, max_frames=5)
+        got2 = device(images, boxes, scores, ctx=cx, **kw)
+    finally:
+        cx.close()
+    monkeypatch.delenv('VDET_NO_LAZY')
+    assert_same(got, want)
+    assert_same(got2, device(images, boxes, scores, **kw))
+
+
+# g. -------------------------------------------------------------------------------------------------------------------
+def irregular_case():
+    (images, boxes, scores, _, _), _ = gc.main_case()
+    boxes, scores = boxes.copy(), scores.copy()
+    boxes[3, gc.IDIS[4]] = [50, 50, 49, 60]            # zero area
+    boxes[3, gc.IDIS[5]] = np.nan
+    scores[3, gc.IDIS[4]] = 0.01                       # (below thres: neither is ever an anchor)
+    scores[3, gc.IDIS[5]] = 0.02
+    return images, boxes, scores
+
+
+def test_irregular_frame_takes_the_eager_pass():
+    import torch
+    from vdetlib_amd import _lib
+    images, boxes, scores = irregular_case()
+    cx = _lib.Context(torch.cuda.current_device())
+    try:
+        tracks, anchors, nt, _ = assert_spec(images, boxes, scores, ctx=cx, **gc.MAIN)
+        assert cx.query(2) == 0                        # not every frame is regular: the eager pass ran under the default switches
+    finally:
+        cx.close()
+    assert np.isfinite(tracks[0, :, 3, 0]).all() and nt.tolist() == [3, 1]       # every tubelet of class 0 crosses the frame
+
+
+# h. -------------------------------------------------------------------------------------------------------------------
+def test_untrackable_anchor_takes_its_slot_and_is_latched():
+    import torch
+    from vdetlib_amd import _lib, ops
+    (images, boxes, scores, _, _), main = gc.main_case()
+    boxes, scores = boxes.copy(), scores.copy()
+    boxes[7, gc.IDIS[0]] = [10, 10, 9.5, 30]           # empty after truncation
+    scores[7, gc.IDIS[0], 0] = 2.0                     # the best of class 0
+    want = gs.track_volume_pixels(images, boxes, scores, **gc.MAIN)
+    assert want[3] and np.isnan(want[0][0, 0]).all() and want[1][0, 0].tolist() == [8, gc.IDIS[0], 2.0]
+    assert np.array_equal(want[0][0, 1:], main[0][0, :2])          # it suppressed nothing
+    ti, tb, ts = g(images), g(boxes), g(scores)
+    cx = _lib.Context(torch.cuda.current_device())
+    try:
+        with pytest.raises(ValueError):
+            ops.track_volume_pixels(ti, tb, ts, ctx=cx, **gc.MAIN)
+        out = ops.track_volume_pixels(ti, tb, ts, sync=False, ctx=cx, **gc.MAIN)
+        with pytest.raises(ValueError):
+            cx.sync()
+        assert_same(tuple(x.cpu().numpy() for x in out), want)
+        cx.sync()                                      # the latch is cleared
+    finally:
+        cx.close()
+
+
+# i. -------------------------------------------------------------------------------------------------------------------
+def test_early_stop_leaves_the_slots_behind_the_count_empty():
+    (images, boxes, scores, _, _), _ = gc.main_case()
+    tracks, anchors, nt = device(images, boxes, scores, **dict(gc.MAIN, max_tracks=5))
+    assert nt[1] == 1 and np.isnan(tracks[1, 1:]).all() and (anchors[1, 1:] == 0).all()
+    assert np.isfinite(tracks[1, 0, :, 0]).all() and anchors[1, 0, 0] == 3
+
+
+# j. -------------------------------------------------------------------------------------------------------------------
+def test_argument_errors_before_any_launch():
+    import torch
+    from vdetlib_amd import _lib, ops
+    (images, boxes, scores, _, _), want = gc.main_case()
+    ti, tb, ts = g(images), g(boxes), g(scores)
+    cx = _lib.Context(torch.cuda.current_device())
+    try:
+        cx.set_timing(2)
+        run = lambda i=ti, b=tb, s=ts, **kw: ops.track_volume_pixels(i, b, s, ctx=cx, **dict(gc.MAIN, **kw))
+        bad = [lambda: run(i=ti[1:]),                                   # images F mismatch
+               lambda: run(i=ti[:, :, ::2]),                            # not contiguous
+               lambda: run(i=ti.float()),
+               lambda: run(i=ti[0]),
+               lambda: run(i=ti.cpu()),
+               lambda: run(b=tb.cpu()),
+               lambda: run(s=ts.cpu()),
+               lambda: run(b=tb.double()),
+               lambda: run(s=ts.double()),
+               lambda: run(b=tb[:, :5]),
+               lambda: run(grid=6), lambda: run(grid=68), lambda: run(grid=0),
+               lambda: run(radius=0), lambda: run(radius=17),
+               lambda: run(step=0), lambda: run(max_frames=-1),
+               lambda: run(min_conf=float('nan')),
+               lambda: run(max_tracks=-1)]
+        for k, fn in enumerate(bad):
+            with pytest.raises(ValueError):
+                fn()
+                pytest.fail("case %d raised nothing" % k)
+        # the C-ABI refuses on its own: vdet_track_pixels' settings and vdet_nms_track_volume's B limit
+        L = cx.lib
+        o = tuple(x.data_ptr() for x in (ti, ti, ti))       # (never written: every call below is refused)
+        call = lambda B=gc.B, S=gc.S, R=gc.R, mc=0.0, mf=0, st=1, H=gc.H: L.vdet_track_volume_pixels(
+            cx.h, ti.data_ptr(), H, gc.W, tb.data_ptr(), ts.data_ptr(), gc.F, B, gc.C, 0.3, 0.3, 3, S, R, mc, mf, st, *o)
+        for kw in (dict(B=32768), dict(S=6), dict(S=68), dict(R=0), dict(R=17), dict(st=0), dict(mf=-1), dict(mc=float('nan')),
+                   dict(H=32768)):
+            assert call(**kw) == _lib.VDET_EINVAL, kw
+        assert sum(n for _, n in cx.last_timing().values()) == 0, "an argument error launched a kernel"
+        assert_same(tuple(x.cpu().numpy() for x in run()), want)       # the context still works
+    finally:
+        cx.close()
+
+
+# k. -------------------------------------------------------------------------------------------------------------------
+def test_context_state_around_the_call():
+    import synth
+    import torch
+    from vdetlib_amd import _lib, ops
+    other_boxes, other_scores = synth.coherent_video(7433, 12, 120, 3, frac=True)
+    ob, os_ = g(other_boxes), g(other_scores)
+    (images, boxes, scores, _, _), want = gc.main_case()
+    ti, tb, ts = g(images), g(boxes), g(scores)
+    cx = _lib.Context(torch.cuda.current_device())
+    try:
+        cx.set_cache(True)
+        run = lambda: tuple(x.cpu().numpy() for x in ops.nms_track_volume(ob, os_, max_tracks=4, ctx=cx))
+        first = run()
+        tracks, anchors, nt = ops.track_volume_pixels(ti, tb, ts, ctx=cx, **gc.MAIN)
+        # the tubelet boxes are no proposals: rescore_tracks must take its general path (hole-free at step = 1: rescore_tubelets')
+        det0, pooled0, box0 = ops.rescore_tracks(tracks, nt, tb, ts, ctx=cx)
+        second = run()
+        det, pooled, tboxes, _ = ops.rescore_tubelets(tracks, nt, tb, ts, ctx=cx)
+    finally:
+        cx.close()
+    for a, b in zip(first, second):
+        assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
+    assert_same(tuple(x.cpu().numpy() for x in (tracks, anchors, nt)), want)
+    for a, b in ((det0, det), (pooled0, pooled), (box0, tboxes)):
+        assert bits_equal(a.cpu().numpy(), b.cpu().numpy())
+    assert np.isfinite(det.cpu().numpy()).any()
+
+
+# l. -------------------------------------------------------------------------------------------------------------------
+def test_downstream_to_rescore_tubelets_and_nms_tracks():
+    import rescore_spec
+    from vdetlib_amd import ops
+    (images, boxes, scores, _, _), want = gc.main_case()
+    tb, ts = g(boxes), g(scores)
+    tracks, anchors, nt = ops.track_volume_pixels(g(images), tb, ts, **gc.MAIN)
+    det, pooled, tboxes, src = ops.rescore_tubelets(tracks, nt, tb, ts, complete=False)
+    wd, wp, wb, ws, _ = rescore_spec.spec(want[0], want[2], boxes, scores, complete=False)
+    for a, b in ((det, wd), (pooled, wp), (tboxes, wb), (src, ws)):
+        assert bits_equal(a.cpu().numpy(), b)
+    assert np.isin(ws[0, 0], (gc.IA,) + gc.IJA).all()                  # every box of A's tubelet hits one of A's proposals
+    out = ops.nms_tracks(tracks, nt, pooled, tboxes)
+    assert tuple(out['tracks'].shape) == (gc.C, 3, gc.F, 5) and int(out['cnt'].min()) >= 1

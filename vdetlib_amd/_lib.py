@@ -103,6 +103,8 @@ SYMBOLS = {
     "vdet_svm_scores_dev_f64": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "vdet_svm_scores_dev_f32": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "vdet_track_pixels": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _vp, _vp, _vp]),
+    "vdet_track_volume_pixels": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci, _ci,
+                                       _vp, _vp, _vp]),
 }
 
 

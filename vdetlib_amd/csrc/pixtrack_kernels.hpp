@@ -28,10 +28,15 @@
 //      every lane derives the new box from the winning key.
 // LDS: region 96 x 25 dwords (one spare dword per row for the pair read at shift 0) + template 64 x 16 dwords + tables:
 // 14.2 KiB, static.  Nothing of the context's cached graph, lists, index or link memo is read or written.
+//
+// The chain is pix_chain, a device function: track_pixels_kernel runs it from a slot table, track_pixel_chain_kernel -- the
+// tracker of the greedy loop vdet_track_volume_pixels (tests/greedy_pixel_spec.py) -- from the anchor the pick left in TrackState.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "track_kernels.hpp"
 
 namespace vdet {
 
@@ -70,20 +75,25 @@ __device__ __forceinline__ bool pix_outside(int x1, int y1, int x2, int y2, int 
     return x2 < 0 || y2 < 0 || x1 > W - 1 || y1 > H - 1;
 }
 
+// the box a chain starts from: -1: cannot be tracked, 1: b = the 0-based integer box (truncated toward zero, minus one)
+__device__ __forceinline__ int pix_box_state(const float *p, int H, int W, int4 &b)
+{
+    const float lim = (float)kPixCoordMax;
+    const float v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
+    // (a NaN fails every comparison, an infinity the bound)
+    if (!(fabsf(v0) <= lim && fabsf(v1) <= lim && fabsf(v2) <= lim && fabsf(v3) <= lim)) return -1;
+    b = make_int4((int)v0 - 1, (int)v1 - 1, (int)v2 - 1, (int)v3 - 1);
+    if (b.z - b.x + 1 < 1 || b.w - b.y + 1 < 1 || pix_outside(b.x, b.y, b.z, b.w, H, W)) return -1;
+    return 1;
+}
+
 // 0: empty slot, -1: bad data, 1: live and b = the 0-based integer box
 __device__ __forceinline__ int pix_anchor_state(const PixTrackArgs &a, int64_t slot, int4 &b)
 {
     const int fr = a.aframes[slot];
     if (fr < 0 || fr > a.F) return -1;
     if (fr == 0) return 0;
-    const float *p = a.aboxes + slot * 4;
-    const float lim = (float)kPixCoordMax;
-    const float v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
-    // (a NaN fails every comparison, an infinity the bound)
-    if (!(fabsf(v0) <= lim && fabsf(v1) <= lim && fabsf(v2) <= lim && fabsf(v3) <= lim)) return -1;
-    b = make_int4((int)v0 - 1, (int)v1 - 1, (int)v2 - 1, (int)v3 - 1);
-    if (b.z - b.x + 1 < 1 || b.w - b.y + 1 < 1 || pix_outside(b.x, b.y, b.z, b.w, a.H, a.W)) return -1;
-    return 1;
+    return pix_box_state(a.aboxes + slot * 4, a.H, a.W, b);
 }
 
 __device__ __forceinline__ uint32_t pix_luma(const uint8_t *p)
@@ -124,51 +134,26 @@ __device__ __forceinline__ void pix_gather(uint32_t *dst, int pitch, const int *
     }
 }
 
-// grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
-// slot 0 of a class -- the class's ntracks), 1 backward.
-__global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
+// every row of a slot without a tubelet
+__device__ __forceinline__ void pix_no_rows(float *trk, int F)
+{
+    const float qnan = __uint_as_float(0x7FC00000u);
+    for (int64_t i = threadIdx.x; i < (int64_t)F * 5; i += kPixLT) trk[i] = qnan;
+}
+
+// One half of a live slot's tubelet, by the whole block: the chain from frame af (0-based) and box ab in direction dir, into the
+// slot's rows trk [F,5].  The forward half (dir > 0) also writes the anchor row.  Every row of the half is written exactly once:
+// the chain's own by thread 0, those it does not reach -- beyond its end and on the frames step > 1 skips -- by the whole block
+// afterwards.  Reads of a: images, F, H, W, S, R, min_conf, reach, step.  Block-uniform control flow.
+__device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, const int af, const int4 ab, const int dir)
 {
     __shared__ uint32_t sreg[kPixMaxP * kPixMaxPitch];
     __shared__ uint32_t stm[kPixMaxS * (kPixMaxS / 4)];
     __shared__ int tcol[kPixMaxP], trow[kPixMaxP];
     __shared__ unsigned long long skey[2][kPixWaves];
-    __shared__ int snt;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t slot = blockIdx.x;
-    const int c = (int)(slot / a.T), t = (int)(slot - (int64_t)c * a.T);
-    const int dir = blockIdx.y == 0 ? 1 : -1;
     const int F = a.F, H = a.H, W = a.W, S = a.S, R = a.R;
-    float *trk = a.tracks + slot * F * 5;
     const float qnan = __uint_as_float(0x7FC00000u);
-
-    int4 ab = make_int4(0, 0, 0, 0);
-    const int state = pix_anchor_state(a, slot, ab);
-    const bool live = state == 1;
-    const int af = live ? a.aframes[slot] - 1 : 0;
-
-    if (dir > 0) {
-        if (tid == 0) {
-            if (state < 0) atomicOr(a.status, kStBadPixAnchor);
-            a.anchors[slot * 3] = (float)a.aframes[slot];
-            a.anchors[slot * 3 + 1] = -1.0f;
-            a.anchors[slot * 3 + 2] = a.ascores ? a.ascores[slot] : 0.0f;
-        }
-        if (t == 0) {            // (block-uniform) the class's count: 1 + its last live slot
-            if (tid == 0) snt = 0;
-            __syncthreads();
-            for (int k = tid; k < a.T; k += kPixLT) {
-                int4 bk;
-                if (pix_anchor_state(a, (int64_t)c * a.T + k, bk) == 1) atomicMax(&snt, k + 1);
-            }
-            __syncthreads();
-            if (tid == 0) a.ntracks[c] = snt;
-        }
-    }
-    if (!live) {                 // every row of a dead slot is the forward block's
-        if (dir > 0)
-            for (int64_t i = tid; i < (int64_t)F * 5; i += kPixLT) trk[i] = qnan;
-        return;
-    }
     // the box state is the same in every lane: keep it in scalar registers
     int x1 = __builtin_amdgcn_readfirstlane(ab.x), y1 = __builtin_amdgcn_readfirstlane(ab.y);
     const int w = __builtin_amdgcn_readfirstlane(ab.z - ab.x + 1), h = __builtin_amdgcn_readfirstlane(ab.w - ab.y + 1);
@@ -250,6 +235,74 @@ __global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs
         if (d % a.step == 0 && d / a.step <= n) continue;
         trk[(int64_t)(af + dir * d) * 5 + e] = qnan;
     }
+}
+
+// grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
+// slot 0 of a class -- the class's ntracks), 1 backward.
+__global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
+{
+    __shared__ int snt;
+    const int tid = threadIdx.x;
+    const int64_t slot = blockIdx.x;
+    const int c = (int)(slot / a.T), t = (int)(slot - (int64_t)c * a.T);
+    const int dir = blockIdx.y == 0 ? 1 : -1;
+    const int F = a.F;
+    float *trk = a.tracks + slot * F * 5;
+
+    int4 ab = make_int4(0, 0, 0, 0);
+    const int state = pix_anchor_state(a, slot, ab);
+    const bool live = state == 1;
+    const int af = live ? a.aframes[slot] - 1 : 0;
+
+    if (dir > 0) {
+        if (tid == 0) {
+            if (state < 0) atomicOr(a.status, kStBadPixAnchor);
+            a.anchors[slot * 3] = (float)a.aframes[slot];
+            a.anchors[slot * 3 + 1] = -1.0f;
+            a.anchors[slot * 3 + 2] = a.ascores ? a.ascores[slot] : 0.0f;
+        }
+        if (t == 0) {            // (block-uniform) the class's count: 1 + its last live slot
+            if (tid == 0) snt = 0;
+            __syncthreads();
+            for (int k = tid; k < a.T; k += kPixLT) {
+                int4 bk;
+                if (pix_anchor_state(a, (int64_t)c * a.T + k, bk) == 1) atomicMax(&snt, k + 1);
+            }
+            __syncthreads();
+            if (tid == 0) a.ntracks[c] = snt;
+        }
+    }
+    if (!live) {                 // every row of a dead slot is the forward block's
+        if (dir > 0) pix_no_rows(trk, F);
+        return;
+    }
+    pix_chain(a, trk, af, ab, dir);
+}
+
+// The tracker launch of the greedy loop (vdet_track_volume_pixels): grid (C, 2), one block per class and direction.  The anchor
+// is the one track_pick_kernel left in the class's TrackState -- frame anchor_frame, box boxes[anchor_frame, anchor_box]
+// truncated toward zero (vdet/track.py:224, map(int, bbox)) --, the tubelet goes into slot ntracks of the class, every row of
+// which this launch writes exactly once.  A class that is not active returns at once.  An anchor that cannot be tracked
+// (pix_box_state) latches kStBadPixAnchor and leaves a slot of NaN rows: the loop goes on and nothing is suppressed by it.
+// Reads of a: what pix_chain reads.
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrackArgs a, const TrackState *__restrict__ st,
+                                                                   const float *__restrict__ boxes, int B, int max_tracks,
+                                                                   float *__restrict__ tracks, int *status)
+{
+    const int c = blockIdx.x;
+    const int dir = blockIdx.y == 0 ? 1 : -1;
+    const TrackState s = st[c];
+    if (!s.active) return;
+    float *trk = tracks + ((int64_t)c * max_tracks + s.ntracks) * a.F * 5;
+    int4 ab = make_int4(0, 0, 0, 0);
+    if (pix_box_state(boxes + ((int64_t)s.anchor_frame * B + s.anchor_box) * 4, a.H, a.W, ab) < 0) {
+        if (dir > 0) {
+            if (threadIdx.x == 0) atomicOr(status, kStBadPixAnchor);
+            pix_no_rows(trk, a.F);
+        }
+        return;
+    }
+    pix_chain(a, trk, s.anchor_frame, ab, dir);
 }
 
 }  // namespace vdet

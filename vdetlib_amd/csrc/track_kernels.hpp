@@ -16,6 +16,9 @@
 //                          frame, the proposal with the highest IoU with the current box (>= link_thres).
 //   track_suppress_kernel  eager track_det_nms, one wave per (frame, class) crossed by the new track:
 //                          irregular frames only (and everywhere under VDET_NO_LAZY=1).
+//   track_loop_kernel      pick -> link -> suppress -> commit for all tracks of a class in one persistent block; with a tracker
+//                          that is a launch of its own (the pixel chains, pixtrack_kernels.hpp) the same iteration is
+//                          track_pick_kernel -> tracker -> track_suppress_commit_kernel.
 //   rescore_*_kernel       spatial max-pool / completion / temporal max-pool of the finished tubelets.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1203,6 +1206,40 @@ __global__ __launch_bounds__(256) void track_loop_kernel(const LoopArgs a, const
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     track_loop_body(blockIdx.x, a, lz, rv, sp, smem);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same loop with a tracker that is a launch of its own (vdet_track_volume_pixels: the pixel chains of
+// pixtrack_kernels.hpp need a block per direction and 14 KiB of LDS): per track
+//   track_pick_kernel -> the tracker's launch -> track_suppress_commit_kernel,
+// one block per class each, enqueued back to back.  No warm chains (rv is empty: resolved stays 0), no link memo.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void track_pick_kernel(const LoopArgs a, const LazyLists lz, const SuppressParams sp)
+{
+    track_pick_body(blockIdx.x, a.keys, a.lists, a.cnt, sp.F, sp.B, sp.C, a.scores, a.thres, sp.max_tracks,
+                    const_cast<TrackState *>(sp.st), a.anchors, lz, ResolveArgs{});
+}
+
+// the tail of track_loop_body's iteration: eager track_det_nms of the class's lists the pick does not maintain, against the
+// tubelet in slot ntracks, then the commit; ntracks_out follows the count.  dynamic LDS as track_loop_kernel's.
+__global__ __launch_bounds__(256) void track_suppress_commit_kernel(const LoopArgs a, const SuppressParams sp)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    TrackState *st = const_cast<TrackState *>(sp.st);
+    const TrackState s = st[c];
+    if (s.active) {      // (block-uniform)
+        if (a.need_suppress && !(sp.lazy && sp.group_flags && *sp.n_irregular == 0)) {
+            lds_mask_t mask = lds_mask_ptr(smem, w * sp.mask_words);
+            for (int f = w; f < sp.F; f += 4) {
+                track_suppress_list(sp, mask, lane, f * sp.C + c);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+        }
+        __syncthreads();     // every wave has read st[c].ntracks (track_suppress_list) before the commit
+        if (tid == 0) st[c].ntracks = s.ntracks + 1;
+    }
+    if (tid == 0) a.ntracks_out[c] = s.ntracks + (s.active ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -567,6 +567,19 @@ int track_scratch(vdet_ctx *c, int64_t Ftot, int64_t B, int64_t C, int T, int wm
     return VDET_OK;
 }
 
+// ... and what vdet_track_volume_pixels needs of it: the states, the visited marks and the pick's lazy-list state.  No
+// recorded nodes, no link memo and no warm chains: its tubelet boxes are no proposals and its tracker links nothing
+int pixel_track_scratch(vdet_ctx *c, int64_t F, int64_t C)
+{
+    c->nodes_valid = false;
+    HIPCHK(c, c->tstate.reserve((size_t)C * sizeof(TrackState)));
+    HIPCHK(c, c->visited.reserve((size_t)(F * C)));
+    HIPCHK(c, hipMemsetAsync(c->visited.p, 0, (size_t)(F * C), c->stream));
+    HIPCHK(c, c->heads.reserve((size_t)(F * C) * 16));
+    HIPCHK(c, hipMemsetAsync(c->heads.p, 0, (size_t)(F * C) * 16, c->stream));
+    return VDET_OK;
+}
+
 // host-buffer entry points: their group table dies with the call
 struct HostGroupsGuard {
     vdet_ctx *c;
@@ -4096,6 +4109,94 @@ int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H
     {
         StageTimer tm(c, ST_OTHER);
         hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Greedy tubelet generation with the pixel tracker (tests/greedy_pixel_spec.py): vdet_nms_track_volume's front half and
+// pick / lazy lists / eager pass, with pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
+// ---------------------------------------------------------------------------------------------
+int vdet_track_volume_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
+                             int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
+                             double min_conf, int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (!d_images || !d_boxes || !d_scores || !d_ntracks || (max_tracks > 0 && (!d_tracks || !d_anchors)))
+        return fail(c, VDET_EINVAL, "null buffer");
+    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
+    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (S < 4 || S > kPixMaxS || S % 4) return fail(c, VDET_EINVAL, "grid = %d; a multiple of 4 in 4 .. %d", S, kPixMaxS);
+    if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
+    if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
+    if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
+    if (C * (int64_t)std::max(max_tracks, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(max_tracks, 1) >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (C*max_tracks*F must stay below 2^31 - 16)");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    const float t32 = thresh_to_f32(nms_thres);
+    bool same_geo = false;
+    int rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, true, &same_geo);
+    if (rc) return rc;
+    if (!(same_geo && lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, 0, 0.f, 0}, F, B))) {
+        rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B);
+        if (rc) return rc;
+    }
+    const TrackWork w = track_work(c, B, 0.5, max_frames, (int)F);      // (no link: link_thres is not used)
+    if ((rc = pixel_track_scratch(c, F, C))) return rc;
+    c->lists_valid = false;          // the lists are consumed (compacted in place) below
+    TrackState *st = c->tstate.as<TrackState>();
+    hipLaunchKernelGGL(track_init_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->stream, st, (int)C);
+    HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
+    if (max_tracks == 0) {
+        HIPCHK(c, hipGetLastError());
+        return VDET_OK;
+    }
+    SuppressParams sp{};
+    sp.boxes = reinterpret_cast<const float4 *>(d_boxes);
+    sp.F = (int)F; sp.B = (int)B; sp.C = (int)C; sp.max_tracks = max_tracks;
+    sp.groups = c->groups.as<GroupDesc>();
+    sp.row_meta = c->rowmeta.as<uint2>();
+    sp.adj = c->adj.as<uint16_t>();
+    sp.group_z = c->groupz.as<uint32_t>();
+    sp.group_flags = w.flags; sp.ix = w.ix;
+    sp.thres = nms_thres;
+    sp.lists = c->order.as<uint16_t>();
+    sp.cnt = c->ncand.as<int32_t>();
+    sp.visited = c->visited.as<uint8_t>();
+    sp.st = st;
+    sp.tracks = d_tracks;
+    sp.t32 = t32;
+    sp.status = &c->d_cnt->status;
+    sp.mask_words = w.mask_words; sp.lazy = w.lazy;
+    sp.n_irregular = &c->d_cnt->irregular;
+    LazyLists lz{};
+    lz.boxes = sp.boxes; lz.tracks = d_tracks; lz.t32 = t32;
+    lz.t1 = c->heads.as<int32_t>(); lz.head = lz.t1 + F * C; lz.nkp = lz.head + F * C; lz.pos = lz.nkp + F * C;
+    lz.group_flags = sp.lazy ? sp.group_flags : nullptr;
+    LoopArgs la{};
+    la.keys = c->tkeys.as<uint32_t>(); la.lists = c->order.as<uint16_t>(); la.cnt = c->ncand.as<int32_t>();
+    la.scores = d_scores; la.thres = thres; la.anchors = d_anchors;
+    la.ntracks_out = d_ntracks;
+    la.need_suppress = w.need_suppress ? 1 : 0;
+    PixTrackArgs pa{};
+    pa.images = d_images;
+    pa.F = (int)F; pa.H = (int)H; pa.W = (int)W;
+    pa.S = S; pa.R = R;
+    pa.min_conf = (float)min_conf;
+    pa.reach = w.reach; pa.step = step;
+    {
+        StageTimer tm(c, ST_TLOOP);
+        for (int t = 0; t < max_tracks; ++t) {
+            hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, la, lz, sp);
+            hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, (const TrackState *)st,
+                               d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            hipLaunchKernelGGL(track_suppress_commit_kernel, dim3((unsigned)C), dim3(256), (size_t)sp.mask_words * 16, c->stream, la, sp);
+        }
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;

@@ -729,6 +729,71 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
     return tracks, anchors, ntracks
 
 
+def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
+                        max_frames=0, step=1, sync=True, ctx=None):
+    """Greedy tubelet generation for EVERY class of a video with the pixel tracker as ``track_method``: the array form of
+    greedily_track_from_raw_dets (vdet/track.py:189-252) as ``track_volume`` is, but each anchor is followed through the PIXELS
+    (``track_pixels``' rule) instead of being linked through the proposals.  Per class: the best remaining detection is the
+    anchor, its tubelet is tracked, every detection the tubelet explains is removed (track_det_nms at ``nms_thres`` on the frames
+    the tubelet has a box on), up to ``max_tracks`` times or until an anchor scores below ``thres``.  The rule is
+    tests/greedy_pixel_spec.py; include/vdet_hip.h: vdet_track_volume_pixels.  Three launches per track, no host wait.
+
+    images uint8 [F,H,W,3] contiguous, boxes [F,B,4] f32, scores [F,B,C] f32, all on one GPU.  Returns, in ``track_volume``'s
+    layout,
+      tracks  [C, max_tracks, F, 5] f32 rows (x1,y1,x2,y2,confidence; 1.0 on the anchor row), NaN where a track has no box,
+      anchors [C, max_tracks, 3] f32 (1-based frame, box index, score),  ntracks [C] int32.
+    ``tracks_to_proto(..., method='pixel_tracker')`` turns one class of the result into a .track dict.
+    ValueError for the arguments ``track_volume`` and ``track_pixels`` refuse (before any launch); and for an anchor whose box
+    is not finite, beyond 2^20, empty after truncation or wholly outside the image (reported when the call, or a later
+    ``ctx.sync()``, waits): its slot is taken with NaN rows, it suppresses nothing, and the loop goes on."""
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError("images must be uint8 [F,H,W,3]")
+    if not images.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if not images.is_contiguous():
+        raise ValueError("images must be contiguous")
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if scores.dim() != 3:
+        raise ValueError("scores must be [F,B,C]")
+    F, B, C = scores.shape
+    if tuple(boxes.shape) != (F, B, 4):
+        raise ValueError("boxes must be [F,B,4]")
+    if F < 1 or B < 1 or C < 1:
+        raise ValueError("scores must hold at least one frame, one box per frame and one class")
+    if images.shape[0] != F:
+        raise ValueError("images hold %d frames, boxes and scores %d" % (images.shape[0], F))
+    H, W = images.shape[1], images.shape[2]
+    if not 1 <= H <= 32767 or not 1 <= W <= 32767:
+        raise ValueError("images must hold frames of 1 .. 32767 rows and columns")
+    for t in (boxes, scores):
+        if not t.is_cuda or t.device != images.device:
+            raise ValueError("images, boxes and scores must live on the same GPU")
+    grid, radius, max_frames, step, min_conf = int(grid), int(radius), int(max_frames), int(step), float(min_conf)
+    max_tracks = int(max_tracks)
+    if max_tracks < 0:
+        raise ValueError("max_tracks must be >= 0")
+    if grid % 4 or not 4 <= grid <= 64:
+        raise ValueError("grid = %d; a multiple of 4 in 4 .. 64" % grid)
+    if not 1 <= radius <= 16:
+        raise ValueError("radius = %d; 1 .. 16" % radius)
+    if step < 1 or max_frames < 0:
+        raise ValueError("step must be >= 1 and max_frames >= 0")
+    if not math.isfinite(min_conf):
+        raise ValueError("min_conf must be finite")
+    boxes = boxes.contiguous()
+    scores = scores.contiguous()
+    ctx = _ctx_for(images, ctx)
+    tracks = torch.full((C, max_tracks, F, 5), float('nan'), dtype=torch.float32, device=images.device)
+    anchors = torch.zeros((C, max_tracks, 3), dtype=torch.float32, device=images.device)
+    ntracks = torch.zeros((C,), dtype=torch.int32, device=images.device)
+    _finish(ctx, lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(
+        ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), max_tracks,
+        grid, radius, min_conf, max_frames, step, tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())), sync,
+        reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
+    return tracks, anchors, ntracks
+
+
 def anchor_propagate_tracks(tracks, ntracks, anchors, boxes, scores, sync=True, ctx=None):
     """anchor_propagate (vdet/tubelet_cls.py:353-383) on device tubelets: per slot, the detection of the anchor frame that
     overlaps the anchor box most (f64 ``iou``, ``np.argmax``: first maximum, a NaN overlap counts as the maximum) lends its
