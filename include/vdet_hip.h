@@ -92,6 +92,11 @@
  *                                                                     VDET_EINVAL; an anchor box that cannot be tracked:
  *                                                                     VDET_EINVAL latched (vdet_sync), the slot taken with NaN
  *                                                                     rows, the loop goes on
+ *   pixel tracker with scale search        (vdet_track_pixels_scaled, vdet_track_volume_pixels_scaled) the row of the call without
+ *                                          the search, and 0 <= scales <= 3, 1 <= scale_step <= 25,
+ *                                          0 <= scale_penalty <= 65535                            VDET_EINVAL; bad anchor data as in
+ *                                                                     the call without the search.  A level whose box has a side
+ *                                                                     below 1 or above 2^21 is skipped, never an error
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1086,6 +1091,35 @@ int vdet_track_volume_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t H, 
                              const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
                              int max_tracks, int S, int R, double min_conf, int max_frames, int step, float *d_tracks,
                              float *d_anchors, int32_t *d_ntracks);
+
+/* ---- the pixel tracker with a scale search: tubelet boxes that grow and shrink with the object.  The rule is
+ *      tests/pixtrack_scale_spec.py; everything it does not restate is vdet_track_pixels' (vdet_track_volume_pixels') --------
+ *
+ * scales = ns levels each side (0 .. 3), scale_step = p percent per level (1 .. 25), scale_penalty = q SAD units per level
+ * (0 .. 65535).  Per step f -> g with the current box b = (x1,y1,x2,y2), w = x2-x1+1, h = y2-y1+1:
+ *   levels    for l in -ns .. ns: ex = sgn(l) * floor((|l|*p*w + 100) / 200), ey likewise with h; b_l = (x1-ex, y1-ey, x2+ex,
+ *             y2+ey), w_l = w + 2*ex, h_l = h + 2*ey: the centre is kept exactly.  Level 0 is always admissible; l != 0 is skipped
+ *             when w_l < 1, h_l < 1, w_l > 2^21 or h_l > 2^21.  Levels that give the same box are all searched
+ *   search    per admissible level the region is the grid k = -R..S+R-1 of b_l on frame g, and every (dy,dx) in [-R,R]^2 gets
+ *             the SAD against the anchor's S x S template (taken once, the same for every level, never updated)
+ *   winner    the smallest (SAD + |l|*q, |l|, dy*dy+dx*dx, dy, dx, l) over all admissible levels and shifts
+ *   conf      1.0f - (float)SAD / (float)(255*S*S) from the winner's raw SAD; conf < (float)min_conf ends the chain
+ *   move      b_l moved by floor((2*dx*w_l + S) / (2S)), floor((2*dy*h_l + S) / (2S)); the box is now w_l x h_l; a moved box
+ *             wholly outside the image ends the chain; else the row (x1+1, y1+1, x2+1, y2+1, conf) is written
+ * scales = 0 gives the bits of the call without the search.  Outputs, layouts, the chain ends, NaN rows, the anchor row, bad
+ * anchor data (latched), timing buckets ("other"; "track_loop") and launch sequences (ONE launch; three per track, no host wait,
+ * no tubelet nodes recorded) are those of vdet_track_pixels and vdet_track_volume_pixels.  Argument checks: theirs and the
+ * three ranges above, before any launch.  ctx NULL: VDET_EINVAL, nothing touched.  Limits: the table at the top of this file.
+ */
+int vdet_track_pixels_scaled(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t H, int64_t W,
+                             const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C,
+                             int T, int S, int R, double min_conf, int max_frames, int step, int scales, int scale_step,
+                             int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+int vdet_track_volume_pixels_scaled(vdet_ctx *ctx, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes,
+                                    const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                    int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
+                                    int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

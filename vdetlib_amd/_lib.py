@@ -105,6 +105,10 @@ SYMBOLS = {
     "vdet_track_pixels": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _vp, _vp, _vp]),
     "vdet_track_volume_pixels": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci, _ci,
                                        _vp, _vp, _vp]),
+    "vdet_track_pixels_scaled": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _ci, _ci, _ci,
+                                       _vp, _vp, _vp]),
+    "vdet_track_volume_pixels_scaled": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci,
+                                              _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
 }
 
 

@@ -31,6 +31,14 @@
 //
 // The chain is pix_chain, a device function: track_pixels_kernel runs it from a slot table, track_pixel_chain_kernel -- the
 // tracker of the greedy loop vdet_track_volume_pixels (tests/greedy_pixel_spec.py) -- from the anchor the pick left in TrackState.
+//
+// Scale search (tests/pixtrack_scale_spec.py; track_pixels_scaled_kernel, track_pixel_chain_scaled_kernel): pix_chain<true>.
+// Per step, for every level l in -ns..ns the box is grown about its centre by ex = sgn(l) * floor((|l|*p*w + 100) / 200) columns
+// and ey rows a side (l != 0 is skipped when a side falls below 1 or exceeds 2^21: block-uniform); each admissible level gets
+// its own tables, gather and SAD pass over the SAME S x S template, a lane keeps its smallest key across the levels in
+// registers, and the ONE reduction of the step follows the last level.  The key is (SAD + |l|*q | |l| | dy^2+dx^2 | dy+R | dx+R
+// | l+3): the raw SAD of the winner is key_hi - |l|*q.  The box state (x1, y1, w, h) stays scalar; the winner's level box,
+// moved, is the new box.  pix_chain<false> is the fixed-scale chain, the code it was before the template.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,6 +55,8 @@ constexpr int kPixMaxS = 64, kPixMaxR = 16;
 constexpr int kPixMaxP = kPixMaxS + 2 * kPixMaxR;       // region side
 constexpr int kPixMaxPitch = kPixMaxP / 4 + 1;          // region row pitch in dwords (one spare: see the pair read)
 constexpr int kPixCoordMax = 1 << 20;
+constexpr int kPixSideMax = 1 << 21;     // scale search: a level whose box is wider or higher is skipped (products stay in int32)
+constexpr int kPixMaxScales = 3, kPixMaxScaleStep = 25, kPixMaxScalePenalty = 65535;
 
 struct PixTrackArgs {
     const uint8_t *images;      // [F,H,W,3]
@@ -63,11 +73,25 @@ struct PixTrackArgs {
     int *status;
 };
 
+// the scale search of pix_chain<true>: ns levels each side (0 .. 3), p percent per level (1 .. 25), q SAD units per level
+struct PixScaleArgs {
+    int ns, p, q;
+};
+
 __device__ __forceinline__ int pix_floordiv(int a, int b)      // b > 0
 {
     int q = a / b;
     if (a - q * b < 0) --q;
     return q;
+}
+
+// the columns (rows) level l != 0 adds on each side of a box e wide (high): sgn(l) * floor((|l|*p*e + 100) / 200).
+// e <= 2^21 + 1, |l|*p <= 75: the product stays below 2^28
+__device__ __forceinline__ int pix_level_margin(int l, int p, int e)
+{
+    const int al = l < 0 ? -l : l;
+    const int m = (al * p * e + 100) / 200;
+    return l < 0 ? -m : m;
 }
 
 __device__ __forceinline__ bool pix_outside(int x1, int y1, int x2, int y2, int H, int W)
@@ -145,7 +169,10 @@ __device__ __forceinline__ void pix_no_rows(float *trk, int F)
 // slot's rows trk [F,5].  The forward half (dir > 0) also writes the anchor row.  Every row of the half is written exactly once:
 // the chain's own by thread 0, those it does not reach -- beyond its end and on the frames step > 1 skips -- by the whole block
 // afterwards.  Reads of a: images, F, H, W, S, R, min_conf, reach, step.  Block-uniform control flow.
-__device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, const int af, const int4 ab, const int dir)
+// SCALED: the scale search over the levels -sc.ns .. sc.ns (see the top of this file); otherwise sc is not read.
+template <bool SCALED>
+__device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, const int af, const int4 ab, const int dir,
+                                          const PixScaleArgs sc)
 {
     __shared__ uint32_t sreg[kPixMaxP * kPixMaxPitch];
     __shared__ uint32_t stm[kPixMaxS * (kPixMaxS / 4)];
@@ -156,7 +183,7 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
     const float qnan = __uint_as_float(0x7FC00000u);
     // the box state is the same in every lane: keep it in scalar registers
     int x1 = __builtin_amdgcn_readfirstlane(ab.x), y1 = __builtin_amdgcn_readfirstlane(ab.y);
-    const int w = __builtin_amdgcn_readfirstlane(ab.z - ab.x + 1), h = __builtin_amdgcn_readfirstlane(ab.w - ab.y + 1);
+    int w = __builtin_amdgcn_readfirstlane(ab.z - ab.x + 1), h = __builtin_amdgcn_readfirstlane(ab.w - ab.y + 1);     // (fixed unless SCALED)
     if (dir > 0 && tid == 0) {
         float *r = trk + (int64_t)af * 5;
         r[0] = (float)(x1 + 1); r[1] = (float)(y1 + 1); r[2] = (float)(x1 + w); r[3] = (float)(y1 + h); r[4] = 1.0f;
@@ -175,32 +202,58 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
         const int64_t g64 = (int64_t)af + (int64_t)dir * s * a.step;
         if (g64 < 0 || g64 >= F) break;
         const int g = (int)g64, par = s & 1;
-        // (the readers of the tables and of the region are behind a barrier: the template's below, the step's last one)
-        pix_tables(tcol, trow, x1, y1, w, h, S, -R, P, H, W);
-        __syncthreads();
-        pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
-        __syncthreads();
-        unsigned long long key = ~0ull;
-        for (int cand = tid; cand < ncand; cand += kPixLT) {
-            const int cy = cand / side, cx = cand - cy * side;      // dy + R, dx + R
-            const int sh = cx & 3;
-            const uint32_t *rrow = sreg + cy * pitch + (cx >> 2);
-            const uint32_t *tp = stm;
-            uint32_t sad = 0;
-            for (int i = 0; i < S; ++i) {
-                uint32_t lo = rrow[0];
-                for (int q = 0; q < tq; ++q) {
-                    const uint32_t hi = rrow[q + 1];
-                    sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(hi, lo, sh), tp[q], sad);
-                    lo = hi;
+        unsigned long long key = ~0ull;          // the lane's smallest key, across the levels
+        const int ns = SCALED ? sc.ns : 0;
+        for (int l = -ns; l <= ns; ++l) {        // (block-uniform; one trip at level 0 unless SCALED)
+            int lx1 = x1, ly1 = y1, lw = w, lh = h;
+            if constexpr (SCALED) {
+                if (l != 0) {
+                    const int ex = pix_level_margin(l, sc.p, w), ey = pix_level_margin(l, sc.p, h);
+                    lw = w + 2 * ex;
+                    lh = h + 2 * ey;
+                    if (lw < 1 || lh < 1 || lw > kPixSideMax || lh > kPixSideMax) continue;
+                    lx1 = x1 - ex;
+                    ly1 = y1 - ey;
                 }
-                rrow += pitch;
-                tp += tq;
             }
-            const int dy = cy - R, dx = cx - R;
-            const unsigned long long k = ((unsigned long long)sad << 32) | ((unsigned long long)(dy * dy + dx * dx) << 16) |
-                                         ((unsigned long long)cy << 8) | (unsigned long long)cx;
-            key = k < key ? k : key;
+            // (the readers of the tables and of the region are behind a barrier: the template's below, the step's last one.
+            // Between two levels of a step no barrier is added: the tables are read by the gather only, which every thread has
+            // left at the barrier behind it, and the barrier behind these tables stands between the previous level's SAD reads
+            // of the region and this level's gather, which overwrites it)
+            pix_tables(tcol, trow, lx1, ly1, lw, lh, S, -R, P, H, W);
+            __syncthreads();
+            pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
+            __syncthreads();
+            for (int cand = tid; cand < ncand; cand += kPixLT) {
+                const int cy = cand / side, cx = cand - cy * side;      // dy + R, dx + R
+                const int sh = cx & 3;
+                const uint32_t *rrow = sreg + cy * pitch + (cx >> 2);
+                const uint32_t *tp = stm;
+                uint32_t sad = 0;
+                for (int i = 0; i < S; ++i) {
+                    uint32_t lo = rrow[0];
+                    for (int q = 0; q < tq; ++q) {
+                        const uint32_t hi = rrow[q + 1];
+                        sad = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(hi, lo, sh), tp[q], sad);
+                        lo = hi;
+                    }
+                    rrow += pitch;
+                    tp += tq;
+                }
+                const int dy = cy - R, dx = cx - R;
+                unsigned long long k;
+                if constexpr (SCALED) {
+                    // SAD + |l|*q <= 255*64*64 + 3*65535; dy^2+dx^2 <= 512: 10 bits; cy, cx <= 32; l + 3 in 0 .. 6
+                    const uint32_t al = (uint32_t)(l < 0 ? -l : l);
+                    const uint32_t low = (al << 28) | ((uint32_t)(dy * dy + dx * dx) << 18) | ((uint32_t)cy << 11) | ((uint32_t)cx << 3) |
+                                         (uint32_t)(l + kPixMaxScales);
+                    k = ((unsigned long long)(sad + al * (uint32_t)sc.q) << 32) | (unsigned long long)low;
+                } else {
+                    k = ((unsigned long long)sad << 32) | ((unsigned long long)(dy * dy + dx * dx) << 16) |
+                        ((unsigned long long)cy << 8) | (unsigned long long)cx;
+                }
+                key = k < key ? k : key;
+            }
         }
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
@@ -215,8 +268,25 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
             const unsigned long long k2 = skey[par][k];
             key = k2 < key ? k2 : key;
         }
-        const uint32_t sad = (uint32_t)(key >> 32);
-        const int dy = (int)((key >> 8) & 0xFF) - R, dx = (int)(key & 0xFF) - R;
+        uint32_t sad = (uint32_t)(key >> 32);
+        int dy, dx;
+        if constexpr (SCALED) {
+            const uint32_t low = (uint32_t)key, al = low >> 28;
+            sad -= al * (uint32_t)sc.q;          // the confidence is the raw SAD's
+            dy = (int)((low >> 11) & 0x7F) - R;
+            dx = (int)((low >> 3) & 0xFF) - R;
+            const int l = __builtin_amdgcn_readfirstlane((int)(low & 7u) - kPixMaxScales);
+            if (l != 0) {                        // the winner's level box is the box that moves
+                const int ex = pix_level_margin(l, sc.p, w), ey = pix_level_margin(l, sc.p, h);
+                x1 -= ex;
+                y1 -= ey;
+                w += 2 * ex;
+                h += 2 * ey;
+            }
+        } else {
+            dy = (int)((key >> 8) & 0xFF) - R;
+            dx = (int)(key & 0xFF) - R;
+        }
         const float conf = 1.0f - (float)sad / denom;
         if (conf < a.min_conf) break;
         x1 = __builtin_amdgcn_readfirstlane(x1 + pix_floordiv(2 * dx * w + S, 2 * S));
@@ -238,8 +308,9 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
 }
 
 // grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
-// slot 0 of a class -- the class's ntracks), 1 backward.
-__global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
+// slot 0 of a class -- the class's ntracks), 1 backward.  The body of track_pixels_kernel and track_pixels_scaled_kernel.
+template <bool SCALED>
+__device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixScaleArgs sc)
 {
     __shared__ int snt;
     const int tid = threadIdx.x;
@@ -276,7 +347,18 @@ __global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs
         if (dir > 0) pix_no_rows(trk, F);
         return;
     }
-    pix_chain(a, trk, af, ab, dir);
+    pix_chain<SCALED>(a, trk, af, ab, dir, sc);
+}
+
+__global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
+{
+    pix_slots_body<false>(a, PixScaleArgs{0, 1, 0});
+}
+
+// vdet_track_pixels_scaled: the same launch with the scale search in every chain
+__global__ __launch_bounds__(kPixLT) void track_pixels_scaled_kernel(const PixTrackArgs a, const PixScaleArgs sc)
+{
+    pix_slots_body<true>(a, sc);
 }
 
 // The tracker launch of the greedy loop (vdet_track_volume_pixels): grid (C, 2), one block per class and direction.  The anchor
@@ -284,10 +366,11 @@ __global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs
 // truncated toward zero (vdet/track.py:224, map(int, bbox)) --, the tubelet goes into slot ntracks of the class, every row of
 // which this launch writes exactly once.  A class that is not active returns at once.  An anchor that cannot be tracked
 // (pix_box_state) latches kStBadPixAnchor and leaves a slot of NaN rows: the loop goes on and nothing is suppressed by it.
-// Reads of a: what pix_chain reads.
-__global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrackArgs a, const TrackState *__restrict__ st,
-                                                                   const float *__restrict__ boxes, int B, int max_tracks,
-                                                                   float *__restrict__ tracks, int *status)
+// Reads of a: what pix_chain reads.  The body of track_pixel_chain_kernel and track_pixel_chain_scaled_kernel.
+template <bool SCALED>
+__device__ __forceinline__ void pix_greedy_body(const PixTrackArgs &a, const PixScaleArgs sc, const TrackState *__restrict__ st,
+                                                const float *__restrict__ boxes, int B, int max_tracks, float *__restrict__ tracks,
+                                                int *status)
 {
     const int c = blockIdx.x;
     const int dir = blockIdx.y == 0 ? 1 : -1;
@@ -302,7 +385,23 @@ __global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrac
         }
         return;
     }
-    pix_chain(a, trk, s.anchor_frame, ab, dir);
+    pix_chain<SCALED>(a, trk, s.anchor_frame, ab, dir, sc);
+}
+
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrackArgs a, const TrackState *__restrict__ st,
+                                                                   const float *__restrict__ boxes, int B, int max_tracks,
+                                                                   float *__restrict__ tracks, int *status)
+{
+    pix_greedy_body<false>(a, PixScaleArgs{0, 1, 0}, st, boxes, B, max_tracks, tracks, status);
+}
+
+// vdet_track_volume_pixels_scaled: the same launch with the scale search in the chain
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_scaled_kernel(const PixTrackArgs a, const PixScaleArgs sc,
+                                                                          const TrackState *__restrict__ st,
+                                                                          const float *__restrict__ boxes, int B, int max_tracks,
+                                                                          float *__restrict__ tracks, int *status)
+{
+    pix_greedy_body<true>(a, sc, st, boxes, B, max_tracks, tracks, status);
 }
 
 }  // namespace vdet

@@ -4073,12 +4073,25 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
     return VDET_OK;
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------
-// Device pixel tracker (pixtrack_kernels.hpp)
+// Device pixel tracker (pixtrack_kernels.hpp), fixed scale and with the scale search (tests/pixtrack_scale_spec.py)
 // ---------------------------------------------------------------------------------------------
-int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
-                      const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
-                      int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+// the checks of the three scale-search settings, shared by the two scaled calls; 0 or the failure's code
+static int pix_scale_check(vdet_ctx *c, int scales, int scale_step, int scale_penalty)
+{
+    if (scales < 0 || scales > kPixMaxScales) return fail(c, VDET_EINVAL, "scales = %d; 0 .. %d", scales, kPixMaxScales);
+    if (scale_step < 1 || scale_step > kPixMaxScaleStep) return fail(c, VDET_EINVAL, "scale_step = %d; 1 .. %d", scale_step, kPixMaxScaleStep);
+    if (scale_penalty < 0 || scale_penalty > kPixMaxScalePenalty)
+        return fail(c, VDET_EINVAL, "scale_penalty = %d; 0 .. %d", scale_penalty, kPixMaxScalePenalty);
+    return VDET_OK;
+}
+
+// vdet_track_pixels (sc null) and vdet_track_pixels_scaled
+static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                             const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                             int max_frames, int step, const PixScaleArgs *sc, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -4087,6 +4100,7 @@ int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H
     if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
     if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
     if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
+    if (sc && pix_scale_check(c, sc->ns, sc->p, sc->q)) return VDET_EINVAL;
     if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
     if (!d_images || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
@@ -4108,19 +4122,44 @@ int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H
     a.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_OTHER);
-        hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
+        if (sc) hipLaunchKernelGGL(track_pixels_scaled_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
+        else hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
 }
 
+extern "C" {
+
+int vdet_track_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                      const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                      int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    return track_pixels_impl(c, d_images, F, H, W, d_anchor_frames, d_anchor_boxes, d_anchor_scores, C, T, S, R, min_conf, max_frames,
+                             step, nullptr, d_tracks, d_anchors, d_ntracks);
+}
+
+int vdet_track_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                             const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                             int max_frames, int step, int scales, int scale_step, int scale_penalty, float *d_tracks,
+                             float *d_anchors, int32_t *d_ntracks)
+{
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    return track_pixels_impl(c, d_images, F, H, W, d_anchor_frames, d_anchor_boxes, d_anchor_scores, C, T, S, R, min_conf, max_frames,
+                             step, &sc, d_tracks, d_anchors, d_ntracks);
+}
+
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------
 // Greedy tubelet generation with the pixel tracker (tests/greedy_pixel_spec.py): vdet_nms_track_volume's front half and
 // pick / lazy lists / eager pass, with pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
 // ---------------------------------------------------------------------------------------------
-int vdet_track_volume_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
-                             int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
-                             double min_conf, int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+// vdet_track_volume_pixels (sc null) and vdet_track_volume_pixels_scaled
+static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
+                                    int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
+                                    double min_conf, int max_frames, int step, const PixScaleArgs *sc, float *d_tracks,
+                                    float *d_anchors, int32_t *d_ntracks)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -4134,6 +4173,7 @@ int vdet_track_volume_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t H, in
     if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
     if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
     if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
+    if (sc && pix_scale_check(c, sc->ns, sc->p, sc->q)) return VDET_EINVAL;
     if (C * (int64_t)std::max(max_tracks, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(max_tracks, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*max_tracks*F must stay below 2^31 - 16)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4193,13 +4233,35 @@ int vdet_track_volume_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t H, in
         StageTimer tm(c, ST_TLOOP);
         for (int t = 0; t < max_tracks; ++t) {
             hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, la, lz, sp);
-            hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, (const TrackState *)st,
-                               d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            if (sc) hipLaunchKernelGGL(track_pixel_chain_scaled_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
+                                       (const TrackState *)st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            else hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, (const TrackState *)st,
+                                    d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
             hipLaunchKernelGGL(track_suppress_commit_kernel, dim3((unsigned)C), dim3(256), (size_t)sp.mask_words * 16, c->stream, la, sp);
         }
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
+}
+
+extern "C" {
+
+int vdet_track_volume_pixels(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
+                             int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
+                             double min_conf, int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    return track_volume_pixels_impl(c, d_images, H, W, d_boxes, d_scores, F, B, C, nms_thres, thres, max_tracks, S, R, min_conf,
+                                    max_frames, step, nullptr, d_tracks, d_anchors, d_ntracks);
+}
+
+int vdet_track_volume_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes,
+                                    const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                    int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
+                                    int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    return track_volume_pixels_impl(c, d_images, H, W, d_boxes, d_scores, F, B, C, nms_thres, thres, max_tracks, S, R, min_conf,
+                                    max_frames, step, &sc, d_tracks, d_anchors, d_ntracks);
 }
 
 }  // extern "C"

@@ -680,6 +680,23 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
     ValueError for grid not a multiple of 4 in 4..64, radius outside 1..16, step < 1, max_frames < 0 or a min_conf that is not
     finite (before any launch); and for an anchor frame outside 0..F or an anchor box that is not finite, beyond 2^20, empty or
     wholly outside the image (reported when the call, or a later ``ctx.sync()``, waits; the slot is written as an empty one)."""
+    return _track_pixels(None, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx)
+
+
+def _scale_settings(scales, scale_step, scale_penalty):
+    """the three checked settings of the scale search"""
+    scales, scale_step, scale_penalty = int(scales), int(scale_step), int(scale_penalty)
+    if not 0 <= scales <= 3:
+        raise ValueError("scales = %d; 0 .. 3" % scales)
+    if not 1 <= scale_step <= 25:
+        raise ValueError("scale_step = %d; 1 .. 25" % scale_step)
+    if not 0 <= scale_penalty <= 65535:
+        raise ValueError("scale_penalty = %d; 0 .. 65535" % scale_penalty)
+    return scales, scale_step, scale_penalty
+
+
+def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx):
+    """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
     if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
         raise ValueError("images must be uint8 [F,H,W,3]")
     if not images.is_cuda:
@@ -714,19 +731,38 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
         raise ValueError("step must be >= 1 and max_frames >= 0")
     if not math.isfinite(min_conf):
         raise ValueError("min_conf must be finite")
+    if scale is not None:
+        scale = _scale_settings(*scale)
     ctx = _ctx_for(images, ctx)
     anchor_frames, anchor_boxes = anchor_frames.contiguous(), anchor_boxes.contiguous()
     anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
     tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=images.device)
     anchors = torch.empty((C, T, 3), dtype=torch.float32, device=images.device)
     ntracks = torch.empty((C,), dtype=torch.int32, device=images.device)
-    ctx.check(ctx.lib.vdet_track_pixels(
-        ctx.h, images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
-        anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, grid, radius, min_conf, max_frames, step,
-        tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr()))
+    head = (ctx.h, images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+            anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, grid, radius, min_conf, max_frames, step)
+    out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
+    if scale is None:
+        ctx.check(ctx.lib.vdet_track_pixels(*(head + out)))
+    else:
+        ctx.check(ctx.lib.vdet_track_pixels_scaled(*(head + scale + out)))
     if sync:
         ctx.sync()
     return tracks, anchors, ntracks
+
+
+def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
+                        scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
+    """``track_pixels`` with a scale search: the tubelet's box grows and shrinks with the object (include/vdet_hip.h:
+    vdet_track_pixels_scaled; the rule is tests/pixtrack_scale_spec.py).  On every step the current box is also tried grown and
+    shrunk about its centre by ``scale_step`` percent per level, ``scales`` levels each side (0 .. 3; a side changes by
+    2 * ((level * scale_step * side + 100) // 200) pixels), each level sampled on the same ``grid`` x ``grid`` cells against the
+    anchor's fixed template; the smallest (SAD + level * ``scale_penalty``, level, shift) wins, the confidence is the winner's
+    raw SAD's, and the winner's box, moved, is the next box.  A level whose box would have a side below 1 or above 2^21 is
+    skipped.  ``scales = 0`` gives ``track_pixels``' bits.  Arguments, layouts and errors are ``track_pixels``'; in addition
+    ValueError for scales outside 0..3, scale_step outside 1..25 or scale_penalty outside 0..65535 (before any launch)."""
+    return _track_pixels((scales, scale_step, scale_penalty), images, anchor_frames, anchor_boxes, anchor_scores, grid, radius,
+                         min_conf, max_frames, step, sync, ctx)
 
 
 def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
@@ -746,6 +782,13 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
     ValueError for the arguments ``track_volume`` and ``track_pixels`` refuse (before any launch); and for an anchor whose box
     is not finite, beyond 2^20, empty after truncation or wholly outside the image (reported when the call, or a later
     ``ctx.sync()``, waits): its slot is taken with NaN rows, it suppresses nothing, and the loop goes on."""
+    return _track_volume_pixels(None, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step,
+                                sync, ctx)
+
+
+def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step, sync,
+                         ctx):
+    """track_volume_pixels (scale None) and track_volume_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
     if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
         raise ValueError("images must be uint8 [F,H,W,3]")
     if not images.is_cuda:
@@ -781,17 +824,34 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
         raise ValueError("step must be >= 1 and max_frames >= 0")
     if not math.isfinite(min_conf):
         raise ValueError("min_conf must be finite")
+    if scale is not None:
+        scale = _scale_settings(*scale)
     boxes = boxes.contiguous()
     scores = scores.contiguous()
     ctx = _ctx_for(images, ctx)
     tracks = torch.full((C, max_tracks, F, 5), float('nan'), dtype=torch.float32, device=images.device)
     anchors = torch.zeros((C, max_tracks, 3), dtype=torch.float32, device=images.device)
     ntracks = torch.zeros((C,), dtype=torch.int32, device=images.device)
-    _finish(ctx, lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(
-        ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), max_tracks,
-        grid, radius, min_conf, max_frames, step, tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())), sync,
-        reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
+    head = (ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), max_tracks,
+            grid, radius, min_conf, max_frames, step)
+    out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
+    if scale is None:
+        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(*(head + out)))
+    else:
+        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels_scaled(*(head + scale + out)))
+    _finish(ctx, call, sync, reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
     return tracks, anchors, ntracks
+
+
+def track_volume_pixels_scaled(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
+                               max_frames=0, step=1, scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
+    """``track_volume_pixels`` with ``track_pixels_scaled``'s chain as the tracker: the tubelet that suppresses the detections it
+    explains has a box that follows the object's size (include/vdet_hip.h: vdet_track_volume_pixels_scaled; the rule is the
+    greedy loop of tests/pixtrack_scale_spec.py).  ``scales = 0`` gives ``track_volume_pixels``' bits.  Arguments, layouts,
+    launches and errors are ``track_volume_pixels``'; in addition ValueError for scales outside 0..3, scale_step outside 1..25
+    or scale_penalty outside 0..65535 (before any launch)."""
+    return _track_volume_pixels((scales, scale_step, scale_penalty), images, boxes, scores, nms_thres, thres, max_tracks, grid,
+                                radius, min_conf, max_frames, step, sync, ctx)
 
 
 def anchor_propagate_tracks(tracks, ntracks, anchors, boxes, scores, sync=True, ctx=None):

@@ -51,7 +51,9 @@ def _pixel_frames(vid_proto):
 def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     """A ``track_method`` that follows the pixels of ``bbox`` forward and backward from ``anchor_frame_id`` on the GPU
     (ops.track_pixels, one call with C = T = 1).  Reads ``opts.step`` and ``opts.max_frames`` as fcn_tracker does (:64-71),
-    and the optional ``opts.grid`` / ``opts.radius`` / ``opts.min_conf``.  The frames are uploaded once per video (a module
+    and the optional ``opts.grid`` / ``opts.radius`` / ``opts.min_conf``.  With ``opts.scales`` > 0 the box follows the object's
+    size (ops.track_pixels_scaled, with the optional ``opts.scale_step`` / ``opts.scale_penalty``); absent or 0: the fixed-scale
+    call, unchanged.  The frames are uploaded once per video (a module
     cache keyed by the video's name and frame count).  Returns ``tracks_proto_from_boxes`` over the visited frames only, with
     fcn_tracker's ``start_frame`` and ``step`` (:100-102)."""
     import torch
@@ -62,11 +64,17 @@ def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     max_frames = opts.max_frames if getattr(opts, 'max_frames', None) is not None else 0
     step = int(getattr(opts, 'step', 1))
     dev = images.device
-    tracks, _, _ = ops.track_pixels(
+    scales = getattr(opts, 'scales', None)
+    if not scales:
+        track, scale = ops.track_pixels, {}
+    else:
+        track = ops.track_pixels_scaled
+        scale = dict(scales=scales, scale_step=getattr(opts, 'scale_step', 5), scale_penalty=getattr(opts, 'scale_penalty', 0))
+    tracks, _, _ = track(
         images, torch.tensor([[pos + 1]], dtype=torch.int32, device=dev),
         torch.tensor([[[float(v) for v in bbox]]], dtype=torch.float32, device=dev), None,
         grid=getattr(opts, 'grid', 32), radius=getattr(opts, 'radius', 8), min_conf=getattr(opts, 'min_conf', 0.5),
-        max_frames=max_frames, step=step)
+        max_frames=max_frames, step=step, **scale)
     rows = tracks[0, 0].cpu().numpy()
     lo = hi = pos
     while lo - step >= 0 and not np.isnan(rows[lo - step, 0]):
