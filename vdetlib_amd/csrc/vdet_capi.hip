@@ -518,7 +518,8 @@ bool rescore_from_graph(const uint32_t *group_flags, double nms_thres, double ov
     return group_flags && overlap_thres - nms_thres > 0.05 && nms_thres > 0.0 && overlap_thres < 1.0;
 }
 
-// ---- the tracking workspace of vdet_nms_track_volume (n_states = C) and vdet_video_batch (n_states = V * C)
+// ---- the tracking workspace of the greedy volume trackers: vdet_nms_track_volume and vdet_track_volume_pixels (n_states = C),
+// vdet_video_batch (n_states = V * C)
 struct TrackWork {
     const uint32_t *flags;        // regular-frame flags, or null: only when the graph in place ran K0 + the frame index
     FrameIndex ix;                // ... and the x-index for the link windows, when there is one
@@ -528,6 +529,9 @@ struct TrackWork {
     bool need_suppress;           // the eager track_det_nms pass, for the lists the pick does not maintain
 };
 
+// how many steps a chain may take either way from its anchor (vdet/track.py: max_frames boxes in all; 0 = no limit)
+int chain_reach(int max_frames, int unbounded) { return max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : unbounded; }
+
 // (the scalars first: how many warm chains a call wants depends on them.  reach_unbounded: the caller's kernels' "no max_frames")
 TrackWork track_work(vdet_ctx *c, int64_t B, double link_thres, int max_frames, int reach_unbounded)
 {
@@ -536,7 +540,7 @@ TrackWork track_work(vdet_ctx *c, int64_t B, double link_thres, int max_frames, 
     if (w.flags && c->index_valid && !c->no_index) w.ix = frame_index_of(c);
     w.filled = B <= kLinkFillMax && w.ix.xbox != nullptr;
     w.link_t32 = thresh_to_f32(link_thres);
-    w.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : reach_unbounded;
+    w.reach = chain_reach(max_frames, reach_unbounded);
     w.mask_words = (int)((((size_t)4 * ((B + 31) / 32) + 15) & ~(size_t)15) / 4);
     w.lazy = c->no_lazy ? 0 : 1;
     // (when the host does not know whether every frame is regular -- asynchronous build -- the kernel asks the device)
@@ -544,39 +548,46 @@ TrackWork track_work(vdet_ctx *c, int64_t B, double link_thres, int max_frames, 
     return w;
 }
 
-// reserve and clear: recorded nodes (0xFF: none), one link memo per call (a link step depends on the boxes and link_thres
-// only), and -- with tracks to make -- wm warm chains per state, the visited marks and the lazy-list state of the pick
-// (t1 | head | nkp | pos, [F*C] int32 each)
-int track_scratch(vdet_ctx *c, int64_t Ftot, int64_t B, int64_t C, int T, int wm, int64_t n_states)
+hipError_t reserve_cleared(vdet_ctx *c, DevBuf &b, int byte, size_t bytes)
 {
-    auto cleared = [&](DevBuf &b, int byte, size_t bytes) {
-        const hipError_t e = b.reserve(bytes);
-        return e != hipSuccess ? e : hipMemsetAsync(b.p, byte, bytes, c->stream);
-    };
+    const hipError_t e = b.reserve(bytes);
+    return e != hipSuccess ? e : hipMemsetAsync(b.p, byte, bytes, c->stream);
+}
+
+// the scratch of the pick, which every greedy tracker runs: the states, the visited marks and the lazy-list state (t1 | head |
+// nkp | pos, [F*C] int32 each), cleared.  The recorded nodes of the call before describe tracks that are about to be replaced
+int pick_scratch(vdet_ctx *c, int64_t Ftot, int64_t C, int64_t n_states)
+{
     c->nodes_valid = false;
-    HIPCHK(c, cleared(c->tracknode, 0xFF, (size_t)std::max<int64_t>(C * T * Ftot, 1) * 4));
-    HIPCHK(c, cleared(c->linkmemo, 0, (size_t)2 * Ftot * B * 8));
-    HIPCHK(c, cleared(c->linkstats, 0, 16));
     HIPCHK(c, c->tstate.reserve((size_t)n_states * sizeof(TrackState)));
-    if (T == 0) return VDET_OK;
-    HIPCHK(c, c->linkwarm.reserve((size_t)n_states * wm * 4));
-    HIPCHK(c, c->linkchains.reserve((size_t)C * wm * Ftot * 5 * 4));
-    HIPCHK(c, cleared(c->linknodes, 0xFF, (size_t)C * wm * Ftot * 4));
-    HIPCHK(c, cleared(c->visited, 0, (size_t)(Ftot * C)));
-    HIPCHK(c, cleared(c->heads, 0, (size_t)(Ftot * C) * 16));
+    HIPCHK(c, reserve_cleared(c, c->visited, 0, (size_t)(Ftot * C)));
+    HIPCHK(c, reserve_cleared(c, c->heads, 0, (size_t)(Ftot * C) * 16));
     return VDET_OK;
 }
 
-// ... and what vdet_track_volume_pixels needs of it: the states, the visited marks and the pick's lazy-list state.  No
-// recorded nodes, no link memo and no warm chains: its tubelet boxes are no proposals and its tracker links nothing
-int pixel_track_scratch(vdet_ctx *c, int64_t F, int64_t C)
+// ... and what the IoU-linking trackers add to it: recorded nodes (0xFF: none), one link memo per call (a link step depends on
+// the boxes and link_thres only), and -- with tracks to make -- wm warm chains per state.  (The pixel route needs none of it:
+// its tubelet boxes are no proposals and its tracker links nothing.)
+int track_scratch(vdet_ctx *c, int64_t Ftot, int64_t B, int64_t C, int T, int wm, int64_t n_states)
 {
-    c->nodes_valid = false;
-    HIPCHK(c, c->tstate.reserve((size_t)C * sizeof(TrackState)));
-    HIPCHK(c, c->visited.reserve((size_t)(F * C)));
-    HIPCHK(c, hipMemsetAsync(c->visited.p, 0, (size_t)(F * C), c->stream));
-    HIPCHK(c, c->heads.reserve((size_t)(F * C) * 16));
-    HIPCHK(c, hipMemsetAsync(c->heads.p, 0, (size_t)(F * C) * 16, c->stream));
+    const int rc = pick_scratch(c, Ftot, C, n_states);
+    if (rc) return rc;
+    HIPCHK(c, reserve_cleared(c, c->tracknode, 0xFF, (size_t)std::max<int64_t>(C * T * Ftot, 1) * 4));
+    HIPCHK(c, reserve_cleared(c, c->linkmemo, 0, (size_t)2 * Ftot * B * 8));
+    HIPCHK(c, reserve_cleared(c, c->linkstats, 0, 16));
+    if (T == 0) return VDET_OK;
+    HIPCHK(c, c->linkwarm.reserve((size_t)n_states * wm * 4));
+    HIPCHK(c, c->linkchains.reserve((size_t)C * wm * Ftot * 5 * 4));
+    HIPCHK(c, reserve_cleared(c, c->linknodes, 0xFF, (size_t)C * wm * Ftot * 4));
+    return VDET_OK;
+}
+
+// the limits of a contiguous [F,B,4] / [F,B,C] volume that every kernel of the volume routes relies on
+int check_volume(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, int64_t C)
+{
+    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
+    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
     return VDET_OK;
 }
 
@@ -1060,6 +1071,83 @@ int launch_sort_walk(vdet_ctx *c, const SortWalkArgs &a, int nmax, int64_t order
         hipLaunchKernelGGL(walk_kernel, dim3(nblk), dim3(256), (size_t)wp.wave_words * 4 * 4, c->stream, wp);
     }
     HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---- the front half of the greedy volume trackers (vdet_nms_track_volume, vdet_track_volume_pixels; its first step also
+// opens vdet_video_batch).  In this order: volume_lists, track_work, the caller's scratch and warm-up, track_begin, greedy_args.
+// The suppression graph of the boxes and the descending lists per (frame, class), always through the transposed keys (the pick
+// needs them).  reuse (as ensure_volume_graph's): resident ones that match may serve.  lists_valid is left alone: the link
+// route still walks the NMS survivors over the lists before track_begin gives them to the tracker.
+int volume_lists(vdet_ctx *c, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, bool reuse)
+{
+    bool same_geo = false;
+    const int rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, reuse, &same_geo);
+    if (rc || (same_geo && lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, 0, 0.f, 0}, F, B))) return rc;
+    return launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B);
+}
+
+// The lists are the tracker's from here (it compacts them in place): every class at "no track yet", ntracks = 0.  With nothing
+// to track the caller returns, and a launch error of the calls so far is reported by THIS call.
+int track_begin(vdet_ctx *c, int64_t C, int max_tracks, int32_t *d_ntracks)
+{
+    c->lists_valid = false;
+    hipLaunchKernelGGL(track_init_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->stream, c->tstate.as<TrackState>(), (int)C);
+    HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
+    if (max_tracks == 0) HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// What pick, lazy lists and the eager pass read, from the context's buffers (graph: build_graph; lists: volume_lists; scratch:
+// pick_scratch), the TrackWork and the caller's pointers.  A tracker that links adds its own fields of LoopArgs.
+struct GreedyArgs { SuppressParams sp; LazyLists lz; LoopArgs la; };
+
+GreedyArgs greedy_args(vdet_ctx *c, const TrackWork &w, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C,
+                       double nms_thres, double thres, int max_tracks, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    GreedyArgs g{};
+    SuppressParams &sp = g.sp;
+    sp.boxes = reinterpret_cast<const float4 *>(d_boxes);
+    sp.F = (int)F; sp.B = (int)B; sp.C = (int)C; sp.max_tracks = max_tracks;
+    sp.groups = c->groups.as<GroupDesc>();
+    sp.row_meta = c->rowmeta.as<uint2>();
+    sp.adj = c->adj.as<uint16_t>();
+    sp.group_z = c->groupz.as<uint32_t>();
+    sp.group_flags = w.flags; sp.ix = w.ix;
+    sp.thres = nms_thres;
+    sp.lists = c->order.as<uint16_t>();
+    sp.cnt = c->ncand.as<int32_t>();
+    sp.visited = c->visited.as<uint8_t>();
+    sp.st = c->tstate.as<TrackState>();
+    sp.tracks = d_tracks;
+    sp.t32 = thresh_to_f32(nms_thres);
+    sp.status = &c->d_cnt->status;
+    sp.mask_words = w.mask_words; sp.lazy = w.lazy;
+    sp.n_irregular = &c->d_cnt->irregular;
+    LazyLists &lz = g.lz;
+    lz.boxes = sp.boxes; lz.tracks = d_tracks; lz.t32 = sp.t32;
+    lz.t1 = c->heads.as<int32_t>(); lz.head = lz.t1 + F * C; lz.nkp = lz.head + F * C; lz.pos = lz.nkp + F * C;
+    lz.group_flags = sp.lazy ? sp.group_flags : nullptr;
+    LoopArgs &la = g.la;
+    la.keys = c->tkeys.as<uint32_t>(); la.lists = sp.lists; la.cnt = sp.cnt;
+    la.scores = d_scores; la.thres = thres; la.anchors = d_anchors;
+    la.ntracks_out = d_ntracks;
+    la.need_suppress = w.need_suppress ? 1 : 0;
+    return g;
+}
+
+// the checks of the pixel tracker's settings, shared by vdet_track_pixels[_scaled] and vdet_track_volume_pixels[_scaled]
+int pix_settings_check(vdet_ctx *c, int64_t H, int64_t W, int S, int R, double min_conf, int max_frames, int step, const PixScaleArgs *sc)
+{
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (S < 4 || S > kPixMaxS || S % 4) return fail(c, VDET_EINVAL, "grid = %d; a multiple of 4 in 4 .. %d", S, kPixMaxS);
+    if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
+    if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
+    if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
+    if (!sc) return VDET_OK;
+    if (sc->ns < 0 || sc->ns > kPixMaxScales) return fail(c, VDET_EINVAL, "scales = %d; 0 .. %d", sc->ns, kPixMaxScales);
+    if (sc->p < 1 || sc->p > kPixMaxScaleStep) return fail(c, VDET_EINVAL, "scale_step = %d; 1 .. %d", sc->p, kPixMaxScaleStep);
+    if (sc->q < 0 || sc->q > kPixMaxScalePenalty) return fail(c, VDET_EINVAL, "scale_penalty = %d; 0 .. %d", sc->q, kPixMaxScalePenalty);
     return VDET_OK;
 }
 
@@ -1835,9 +1923,8 @@ int vdet_nms_volume_topk(vdet_ctx *c, const float *d_boxes, const float *d_score
         return fail(c, VDET_EINVAL, "bad shape/layout");
     if (F == 0 || C == 0) return VDET_OK;
     if (!d_keep_cnt || (cap > 0 && !d_keep_idx)) return fail(c, VDET_EINVAL, "null output");
-    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
-    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    int rc = check_volume(c, d_boxes, F, B, C);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     if (B == 0) {
@@ -1845,8 +1932,7 @@ int vdet_nms_volume_topk(vdet_ctx *c, const float *d_boxes, const float *d_score
         return VDET_OK;
     }
     bool same_geo = false;
-    int rc = ensure_volume_graph(c, d_boxes, F, B, thresh, true, &same_geo);
-    if (rc) return rc;
+    if ((rc = ensure_volume_graph(c, d_boxes, F, B, thresh, true, &same_geo))) return rc;
     const ListsKey key{d_scores, C, layout, use_score_thresh, score_thresh, topk};
     SortWalkArgs a{};
     a.walk_only = same_geo && lists_match(c, key, F, B);
@@ -1988,20 +2074,11 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
     if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (!d_boxes || !d_scores || !d_ntracks || (max_tracks > 0 && (!d_tracks || !d_anchors)))
         return fail(c, VDET_EINVAL, "null buffer");
-    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
-    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    int rc = check_volume(c, d_boxes, F, B, C);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    const float t32 = thresh_to_f32(nms_thres);
-    bool same_geo = false;
-    int rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, true, &same_geo);
-    if (rc) return rc;
-    if (!(same_geo && lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, 0, 0.f, 0}, F, B))) {
-        // descending lists per (frame, class): always through the transposed keys (pick needs them)
-        rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B);
-        if (rc) return rc;
-    }
+    if ((rc = volume_lists(c, d_boxes, d_scores, F, B, C, nms_thres, true))) return rc;
     // regular-frame fast paths (lazy lists, x-window link): only when THIS graph build (or the cached
     // one being reused) ran K0 + the frame index -- gflags / the index are stale otherwise
     const TrackWork w = track_work(c, B, link_thres, max_frames, (int)F);
@@ -2025,7 +2102,8 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
         hipLaunchKernelGGL(track_warm_anchors_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, c->tkeys.as<uint32_t>(),
                            c->order.as<uint16_t>(), c->ncand.as<int32_t>(), (int)F, (int)B, (int)C, d_scores, thres, wm,
                            c->linkwarm.as<int32_t>(),
-                           WarmExtra{coherent_slots ? reinterpret_cast<const float4 *>(d_boxes) : nullptr, t32, wm_raw, max_tracks});
+                           WarmExtra{coherent_slots ? reinterpret_cast<const float4 *>(d_boxes) : nullptr, thresh_to_f32(nms_thres), wm_raw,
+                                     max_tracks});
         if (!w.filled) {
             // longest chains first, then every (chain, direction) as one block of the warm-up launch
             HIPCHK(c, c->linkorder.reserve((size_t)C * wm * 2 * 4));
@@ -2048,51 +2126,19 @@ int vdet_nms_track_volume(vdet_ctx *c, const float *d_boxes, const float *d_scor
     }
     // the NMS survivors: one walk over the lists, before they are consumed
     if (want_nms && (rc = launch_sort_walk(c, volume_walk_args(F, B, C, d_scores, d_keep_idx, d_keep_cnt, cap), (int)B, F * C * B))) return rc;
-    c->lists_valid = false;          // the lists are consumed (compacted in place) below
-    TrackState *st = c->tstate.as<TrackState>();
-    const unsigned cg = (unsigned)((C + 63) / 64);
-    hipLaunchKernelGGL(track_init_kernel, dim3(cg), dim3(64), 0, c->stream, st, (int)C);
-    HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
-    if (max_tracks == 0) {          // nothing to track: report a launch error of the walk / init above by THIS call
-        HIPCHK(c, hipGetLastError());
-        return VDET_OK;
-    }
-    SuppressParams sp{};
-    sp.boxes = reinterpret_cast<const float4 *>(d_boxes);
-    sp.F = (int)F; sp.B = (int)B; sp.C = (int)C; sp.max_tracks = max_tracks;
-    sp.groups = c->groups.as<GroupDesc>();
-    sp.row_meta = c->rowmeta.as<uint2>();
-    sp.adj = c->adj.as<uint16_t>();
-    sp.group_z = c->groupz.as<uint32_t>();
-    sp.group_flags = w.flags; sp.ix = w.ix;      // (built by build_graph)
-    sp.thres = nms_thres;
-    sp.lists = c->order.as<uint16_t>();
-    sp.cnt = c->ncand.as<int32_t>();
-    sp.visited = c->visited.as<uint8_t>();
-    sp.st = st;
-    sp.tracks = d_tracks;
-    sp.t32 = t32;
-    sp.status = &c->d_cnt->status;
-    sp.mask_words = w.mask_words; sp.lazy = w.lazy;
-    LazyLists lz{};
-    lz.boxes = sp.boxes; lz.tracks = d_tracks; lz.t32 = t32;
-    lz.t1 = c->heads.as<int32_t>(); lz.head = lz.t1 + F * C; lz.nkp = lz.head + F * C; lz.pos = lz.nkp + F * C;
-    lz.group_flags = sp.lazy ? sp.group_flags : nullptr;
-    sp.n_irregular = &c->d_cnt->irregular;
+    if ((rc = track_begin(c, C, max_tracks, d_ntracks)) || max_tracks == 0) return rc;
+    GreedyArgs g = greedy_args(c, w, d_boxes, d_scores, F, B, C, nms_thres, thres, max_tracks, d_tracks, d_anchors, d_ntracks);
+    LoopArgs &la = g.la;            // the link fields
+    la.link_thres = link_thres; la.link_t32 = w.link_t32; la.reach = w.reach;
+    la.memo = c->linkmemo.as<unsigned long long>(); la.stats = c->linkstats.as<unsigned int>();
+    la.nodes = c->tracknode.as<int32_t>();
     // predicted anchors: their tubelets exist already, the loop copies them
     ResolveArgs rv{c->linkwarm.as<int32_t>(), materialized, c->linkchains.as<float>(), c->linknodes.as<int32_t>(), d_tracks,
                    c->tracknode.as<int32_t>()};
     {
         // the whole tracking loop in one launch: one persistent block per class (track_loop_kernel)
-        LoopArgs la{};
-        la.keys = c->tkeys.as<uint32_t>(); la.lists = c->order.as<uint16_t>(); la.cnt = c->ncand.as<int32_t>();
-        la.scores = d_scores; la.thres = thres; la.link_thres = link_thres; la.anchors = d_anchors;
-        la.link_t32 = w.link_t32; la.reach = w.reach;
-        la.memo = c->linkmemo.as<unsigned long long>(); la.stats = c->linkstats.as<unsigned int>();
-        la.nodes = c->tracknode.as<int32_t>(); la.ntracks_out = d_ntracks;
-        la.need_suppress = w.need_suppress ? 1 : 0;
         StageTimer tm(c, ST_TLOOP);
-        hipLaunchKernelGGL(track_loop_kernel, dim3((unsigned)C), dim3(256), (size_t)sp.mask_words * 16, c->stream, la, lz, rv, sp);
+        hipLaunchKernelGGL(track_loop_kernel, dim3((unsigned)C), dim3(256), (size_t)w.mask_words * 16, c->stream, la, g.lz, rv, g.sp);
     }
     HIPCHK(c, hipGetLastError());
     c->nodekey.tracks = d_tracks; c->nodekey.boxes = d_boxes; c->nodekey.F = F; c->nodekey.B = B; c->nodekey.C = C;
@@ -2131,8 +2177,7 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     timing_reset(c);
     const float t32 = thresh_to_f32(nms_thres);
     // ---- the batch as one volume of F frames: graph (always rebuilt), sorted lists, NMS survivors
-    if ((rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, false))) return rc;
-    if ((rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B))) return rc;
+    if ((rc = volume_lists(c, d_boxes, d_scores, F, B, C, nms_thres, false))) return rc;
     if (want_nms && (rc = launch_sort_walk(c, volume_walk_args(F, B, C, d_scores, d_keep_idx, d_keep_cnt, cap), (int)B, F * C * B))) return rc;
     c->lists_valid = false;          // consumed by the tracking below
     HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)(V * C) * 4, c->stream));
@@ -3430,7 +3475,7 @@ int vdet_track_from_anchors(vdet_ctx *c, const float *d_boxes, int64_t F, int64_
     a.F = (int)F; a.B = (int)B; a.C = (int)C; a.T = T;
     a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
     a.link_t32 = thresh_to_f32(link_thres);
-    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)F;
+    a.reach = chain_reach(max_frames, (int)F);
     a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
     a.status = &c->d_cnt->status;
     {
@@ -3607,7 +3652,7 @@ int vdet_track_from_anchors_batch(vdet_ctx *c, const float *d_boxes, const int64
     a.vids = c->anchor_tab.dev.as<VidDesc>(); a.cls = (int)C;
     a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
     a.link_t32 = thresh_to_f32(link_thres);
-    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)Fmax;
+    a.reach = chain_reach(max_frames, (int)Fmax);
     a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
     a.status = &c->d_cnt->status;
     {
@@ -4078,29 +4123,14 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
 // ---------------------------------------------------------------------------------------------
 // Device pixel tracker (pixtrack_kernels.hpp), fixed scale and with the scale search (tests/pixtrack_scale_spec.py)
 // ---------------------------------------------------------------------------------------------
-// the checks of the three scale-search settings, shared by the two scaled calls; 0 or the failure's code
-static int pix_scale_check(vdet_ctx *c, int scales, int scale_step, int scale_penalty)
-{
-    if (scales < 0 || scales > kPixMaxScales) return fail(c, VDET_EINVAL, "scales = %d; 0 .. %d", scales, kPixMaxScales);
-    if (scale_step < 1 || scale_step > kPixMaxScaleStep) return fail(c, VDET_EINVAL, "scale_step = %d; 1 .. %d", scale_step, kPixMaxScaleStep);
-    if (scale_penalty < 0 || scale_penalty > kPixMaxScalePenalty)
-        return fail(c, VDET_EINVAL, "scale_penalty = %d; 0 .. %d", scale_penalty, kPixMaxScalePenalty);
-    return VDET_OK;
-}
-
-// vdet_track_pixels (sc null) and vdet_track_pixels_scaled
+// vdet_track_pixels (sc null) and vdet_track_pixels_scaled; the settings' checks are pix_settings_check's
 static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
                              const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
                              int max_frames, int step, const PixScaleArgs *sc, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
-    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
-    if (S < 4 || S > kPixMaxS || S % 4) return fail(c, VDET_EINVAL, "grid = %d; a multiple of 4 in 4 .. %d", S, kPixMaxS);
-    if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
-    if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
-    if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
-    if (sc && pix_scale_check(c, sc->ns, sc->p, sc->q)) return VDET_EINVAL;
+    if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
     if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
     if (!d_images || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
@@ -4116,7 +4146,7 @@ static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
     a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
     a.S = S; a.R = R;
     a.min_conf = (float)min_conf;
-    a.reach = max_frames > 0 ? (int)std::ceil((max_frames + 1) / 2.0) - 1 : (int)F;
+    a.reach = chain_reach(max_frames, (int)F);
     a.step = step;
     a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
     a.status = &c->d_cnt->status;
@@ -4152,8 +4182,9 @@ int vdet_track_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// Greedy tubelet generation with the pixel tracker (tests/greedy_pixel_spec.py): vdet_nms_track_volume's front half and
-// pick / lazy lists / eager pass, with pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
+// Greedy tubelet generation with the pixel tracker (tests/greedy_pixel_spec.py): the greedy volume trackers' front half
+// (volume_lists .. greedy_args, shared with vdet_nms_track_volume) and pick / lazy lists / eager pass, with
+// pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
 // ---------------------------------------------------------------------------------------------
 // vdet_track_volume_pixels (sc null) and vdet_track_volume_pixels_scaled
 static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
@@ -4165,64 +4196,18 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
     if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
     if (!d_images || !d_boxes || !d_scores || !d_ntracks || (max_tracks > 0 && (!d_tracks || !d_anchors)))
         return fail(c, VDET_EINVAL, "null buffer");
-    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
-    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
-    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
-    if (S < 4 || S > kPixMaxS || S % 4) return fail(c, VDET_EINVAL, "grid = %d; a multiple of 4 in 4 .. %d", S, kPixMaxS);
-    if (R < 1 || R > kPixMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", R, kPixMaxR);
-    if (step < 1 || max_frames < 0) return fail(c, VDET_EINVAL, "step must be >= 1 and max_frames >= 0");
-    if (!std::isfinite(min_conf)) return fail(c, VDET_EINVAL, "min_conf must be finite");
-    if (sc && pix_scale_check(c, sc->ns, sc->p, sc->q)) return VDET_EINVAL;
+    int rc = check_volume(c, d_boxes, F, B, C);
+    if (rc) return rc;
+    if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
     if (C * (int64_t)std::max(max_tracks, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(max_tracks, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*max_tracks*F must stay below 2^31 - 16)");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    const float t32 = thresh_to_f32(nms_thres);
-    bool same_geo = false;
-    int rc = ensure_volume_graph(c, d_boxes, F, B, nms_thres, true, &same_geo);
-    if (rc) return rc;
-    if (!(same_geo && lists_match(c, ListsKey{d_scores, C, VDET_LAYOUT_FBC, 0, 0.f, 0}, F, B))) {
-        rc = launch_sort_walk(c, volume_sort_args(F, B, C, d_scores), (int)B, F * C * B);
-        if (rc) return rc;
-    }
+    if ((rc = volume_lists(c, d_boxes, d_scores, F, B, C, nms_thres, true))) return rc;
     const TrackWork w = track_work(c, B, 0.5, max_frames, (int)F);      // (no link: link_thres is not used)
-    if ((rc = pixel_track_scratch(c, F, C))) return rc;
-    c->lists_valid = false;          // the lists are consumed (compacted in place) below
-    TrackState *st = c->tstate.as<TrackState>();
-    hipLaunchKernelGGL(track_init_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, c->stream, st, (int)C);
-    HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
-    if (max_tracks == 0) {
-        HIPCHK(c, hipGetLastError());
-        return VDET_OK;
-    }
-    SuppressParams sp{};
-    sp.boxes = reinterpret_cast<const float4 *>(d_boxes);
-    sp.F = (int)F; sp.B = (int)B; sp.C = (int)C; sp.max_tracks = max_tracks;
-    sp.groups = c->groups.as<GroupDesc>();
-    sp.row_meta = c->rowmeta.as<uint2>();
-    sp.adj = c->adj.as<uint16_t>();
-    sp.group_z = c->groupz.as<uint32_t>();
-    sp.group_flags = w.flags; sp.ix = w.ix;
-    sp.thres = nms_thres;
-    sp.lists = c->order.as<uint16_t>();
-    sp.cnt = c->ncand.as<int32_t>();
-    sp.visited = c->visited.as<uint8_t>();
-    sp.st = st;
-    sp.tracks = d_tracks;
-    sp.t32 = t32;
-    sp.status = &c->d_cnt->status;
-    sp.mask_words = w.mask_words; sp.lazy = w.lazy;
-    sp.n_irregular = &c->d_cnt->irregular;
-    LazyLists lz{};
-    lz.boxes = sp.boxes; lz.tracks = d_tracks; lz.t32 = t32;
-    lz.t1 = c->heads.as<int32_t>(); lz.head = lz.t1 + F * C; lz.nkp = lz.head + F * C; lz.pos = lz.nkp + F * C;
-    lz.group_flags = sp.lazy ? sp.group_flags : nullptr;
-    LoopArgs la{};
-    la.keys = c->tkeys.as<uint32_t>(); la.lists = c->order.as<uint16_t>(); la.cnt = c->ncand.as<int32_t>();
-    la.scores = d_scores; la.thres = thres; la.anchors = d_anchors;
-    la.ntracks_out = d_ntracks;
-    la.need_suppress = w.need_suppress ? 1 : 0;
+    if ((rc = pick_scratch(c, F, C, C))) return rc;
+    if ((rc = track_begin(c, C, max_tracks, d_ntracks)) || max_tracks == 0) return rc;
+    const GreedyArgs g = greedy_args(c, w, d_boxes, d_scores, F, B, C, nms_thres, thres, max_tracks, d_tracks, d_anchors, d_ntracks);
     PixTrackArgs pa{};
     pa.images = d_images;
     pa.F = (int)F; pa.H = (int)H; pa.W = (int)W;
@@ -4232,12 +4217,12 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
     {
         StageTimer tm(c, ST_TLOOP);
         for (int t = 0; t < max_tracks; ++t) {
-            hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, la, lz, sp);
+            hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, g.la, g.lz, g.sp);
             if (sc) hipLaunchKernelGGL(track_pixel_chain_scaled_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
-                                       (const TrackState *)st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
-            else hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, (const TrackState *)st,
-                                    d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
-            hipLaunchKernelGGL(track_suppress_commit_kernel, dim3((unsigned)C), dim3(256), (size_t)sp.mask_words * 16, c->stream, la, sp);
+                                       (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            else hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa,
+                                    (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            hipLaunchKernelGGL(track_suppress_commit_kernel, dim3((unsigned)C), dim3(256), (size_t)w.mask_words * 16, c->stream, g.la, g.sp);
         }
     }
     HIPCHK(c, hipGetLastError());

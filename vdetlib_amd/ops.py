@@ -60,25 +60,8 @@ def nms_volume(boxes, scores, thresh=0.3, score_thresh=None, cap=None, layout="F
     Returns (keep_idx int32 [F,C,cap], keep_cnt int32 [F,C]); keep_idx[f,c,:cnt] are box indices in
     descending score order, the rest is -1 (pad=False: left uninitialised, saves one fill of the buffer).
     """
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    boxes = boxes.contiguous()
-    scores = scores.contiguous()
-    F, B = boxes.shape[0], boxes.shape[1]
-    if layout == "FBC":
-        C = scores.shape[2]
-        if tuple(scores.shape) != (F, B, C):
-            raise ValueError("scores must be [F,B,C]")
-        lay = _lib.LAYOUT_FBC
-    elif layout == "FCB":
-        C = scores.shape[1]
-        if tuple(scores.shape) != (F, C, B):
-            raise ValueError("scores must be [F,C,B]")
-        lay = _lib.LAYOUT_FCB
-    else:
-        raise ValueError("layout must be 'FBC' or 'FCB'")
-    if boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
+    boxes, scores, F, B, C = _volume(boxes, scores, layout=layout)
+    lay = _lib.LAYOUT_FBC if layout == "FBC" else _lib.LAYOUT_FCB
     cap = B if cap is None else int(cap)
     ctx = _ctx_for(boxes, ctx)
     keep_idx = _keep_buffer((F, C, cap), boxes.device, pad)
@@ -112,6 +95,7 @@ def det_nms_volume(boxes, scores, score_thresh=0.05, topk=100, nms_thresh=0.3, f
     boxes = boxes.contiguous()
     if tuple(boxes.shape) not in ((F, B, K, 4), (F, B, 4 * K)):
         raise ValueError("boxes must be [F,B,K,4] or [F,B,4K]")
+    _same_gpu((boxes, scores), "boxes and scores")
     topk = int(topk)
     ctx = _ctx_for(boxes, ctx)
     dev = boxes.device
@@ -137,15 +121,13 @@ def nms_volume_ordered(boxes, order, ncand, thresh=0.3, cap=None, ctx=None, pad=
     """``nms_volume`` walking the CALLER's lists: order int16/uint16 [F,C,B] (box indices, e.g. ``argsort_volume``'s with
     ties rearranged as some machine's unstable ``scores.argsort()[::-1]`` left them, utils/nms.pyx:25), ncand int32 [F,C]
     (how many entries of each list are candidates).  Returns (keep_idx [F,C,cap], keep_cnt [F,C])."""
-    if boxes.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if order.dtype not in (torch.int16, torch.uint16) or ncand.dtype != torch.int32:
-        raise ValueError("order must be (u)int16 [F,C,B], ncand int32 [F,C]")
+    F, B, _ = _volume_layout(boxes)
+    if order.dtype not in (torch.int16, torch.uint16) or ncand.dtype != torch.int32 or order.dim() != 3 or \
+            tuple(order.shape) != (F, order.shape[1], B) or tuple(ncand.shape) != (F, order.shape[1]):
+        raise ValueError("order must be (u)int16 [F,C,B], ncand int32 [F,C], for boxes [F,B,4]")
+    _same_gpu((boxes, order, ncand), "boxes, order and ncand")
     boxes, order, ncand = boxes.contiguous(), order.contiguous(), ncand.contiguous()
-    F, B = boxes.shape[0], boxes.shape[1]
     C = order.shape[1]
-    if tuple(order.shape) != (F, C, B) or tuple(ncand.shape) != (F, C) or boxes.shape[2] != 4:
-        raise ValueError("boxes [F,B,4], order [F,C,B], ncand [F,C]")
     cap = B if cap is None else int(cap)
     ctx = _ctx_for(boxes, ctx)
     keep_idx = _keep_buffer((F, C, cap), boxes.device, pad)
@@ -309,9 +291,110 @@ def _same_gpu(tensors, who, device=None):
     """ValueError unless every tensor lives on one GPU (``device``, or the first tensor's).  Called AFTER every layout check, so
     that a wrong layout fails as a layout whatever memory it is in."""
     device = tensors[0].device if device is None else device
-    for t in tensors:
-        if not t.is_cuda or t.device != device:
-            raise ValueError("%s must live on the same GPU (vdetlib_amd has no CPU path)" % who)
+    ok = device.type == 'cuda'
+    for t in tensors:           # (None: an optional tensor that was not given)
+        ok = ok and (t is None or t.device == device)
+    if not ok:
+        raise ValueError("%s must live on the same GPU (vdetlib_amd has no CPU path)" % who)
+
+
+# ---- the checked readers of the entry points' inputs.  Attribute checks only (no device query, no copy to the host): the batch
+# routes pay them per call.  All but ``_volume`` check the LAYOUT only; the entry point follows with ONE ``_same_gpu`` (or ends
+# with ``_volume``, which takes the tensors read so far as ``also``), so that nothing reaches a kernel from the wrong memory.
+def _volume_layout(boxes, scores=None, layout="FBC", F=None, C=None, nonempty=False):
+    """(F, B, C) of a video's detections: boxes f32 [F,B,4] and -- unless None -- scores f32 [F,B,C] ('FCB': [F,C,B]), checked
+    against each other and against a given ``F`` / ``C``; ``nonempty``: at least one frame, box and class."""
+    bs = boxes.shape
+    if boxes.dtype != torch.float32 or len(bs) != 3 or bs[2] != 4 or (F is not None and bs[0] != F):
+        raise ValueError("boxes must be float32 [F,B,4]" + ("" if F is None else " with F = %d" % F))
+    F, B = bs[0], bs[1]
+    if scores is not None:
+        if layout not in ("FBC", "FCB"):
+            raise ValueError("layout must be 'FBC' or 'FCB'")
+        ss = scores.shape
+        Cs = ss[2 if layout == "FBC" else 1] if len(ss) == 3 else None
+        if scores.dtype != torch.float32 or ss != ((F, B, Cs) if layout == "FBC" else (F, Cs, B)) or (C is not None and Cs != C):
+            raise ValueError("scores must be float32 [%s] for boxes [%d,%d,4]%s" % (
+                ','.join(layout), F, B, "" if C is None else " with C = %d" % C))
+        C = Cs
+    if nonempty and (F < 1 or B < 1 or (scores is not None and C < 1)):
+        raise ValueError("boxes%s must hold at least one frame, one box per frame%s" % (
+            ("", "") if scores is None else (" and scores", " and one class")))
+    return F, B, C
+
+
+def _volume(boxes, scores, also=(), who="boxes and scores", layout="FBC", F=None, C=None, nonempty=False):
+    """The reader of a volume that goes to a kernel: ``_volume_layout``, then boxes, scores and the tensors of the tuple ``also``
+    (whose layout the caller has checked) on one GPU.  Returns (boxes, scores, F, B, C), the tensors contiguous."""
+    F, B, C = _volume_layout(boxes, scores, layout, F, C, nonempty)
+    _same_gpu((boxes, scores) + also, who)
+    return boxes.contiguous(), scores.contiguous(), F, B, C
+
+
+def _tubelets_layout(tracks, ntracks, anchors=None):
+    """(C, T, F) of one video's tubelets: tracks f32 [C,T,F,5], ntracks int32 [C] and -- unless None -- anchors f32 [C,T,3]."""
+    ts = tracks.shape
+    if tracks.dtype != torch.float32 or len(ts) != 4 or ts[3] != 5:
+        raise ValueError("tracks must be float32 [C,T,F,5]")
+    if ntracks.dtype != torch.int32 or ntracks.shape != ts[:1]:
+        raise ValueError("ntracks must be int32 [C]")
+    if anchors is not None and (anchors.dtype != torch.float32 or anchors.shape != (ts[0], ts[1], 3)):
+        raise ValueError("anchors must be float32 [C,T,3]")
+    return ts[0], ts[1], ts[2]
+
+
+def _anchor_slots(anchor_frames, anchor_boxes, anchor_scores=None, V=None):
+    """Caller-supplied anchors: anchor_frames int32 [C,T], anchor_boxes f32 [C,T,4], anchor_scores f32 [C,T] or None -- with
+    ``V`` all under a leading [V,...].  Returns them contiguous, and C, T."""
+    lead, nd = ("C,T", 2) if V is None else ("V,C,T", 3)
+    if anchor_frames.dtype != torch.int32 or anchor_frames.dim() != nd or (V is not None and anchor_frames.shape[0] != V) or \
+            anchor_frames.shape[-2] < 1:
+        raise ValueError("anchor_frames must be int32 [%s] with C >= 1" % lead)
+    shape = tuple(anchor_frames.shape)
+    if anchor_boxes.dtype != torch.float32 or anchor_boxes.shape != shape + (4,):
+        raise ValueError("anchor_boxes must be float32 [%s,4]" % lead)
+    if anchor_scores is not None and (anchor_scores.dtype != torch.float32 or anchor_scores.shape != shape):
+        raise ValueError("anchor_scores must be float32 [%s] or None" % lead)
+    return (anchor_frames.contiguous(), anchor_boxes.contiguous(), None if anchor_scores is None else anchor_scores.contiguous(),
+            shape[-2], shape[-1])
+
+
+def _images(images):
+    """(F, H, W) of the frames images uint8 [F,H,W,3]: contiguous, at least one frame, 1 .. 32767 rows and columns."""
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or \
+            not images.is_contiguous():
+        raise ValueError("images must be uint8 [F,H,W,3], contiguous")
+    F, H, W = images.shape[:3]
+    if F < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767:
+        raise ValueError("images must hold at least one frame of 1 .. 32767 rows and columns, not [%d,%d,%d,3]" % (F, H, W))
+    return F, H, W
+
+
+def _pixel_settings(grid, radius, min_conf, max_frames, step):
+    """the five checked settings of the pixel tracker, in the order of the C-ABI's arguments"""
+    grid, radius, max_frames, step, min_conf = int(grid), int(radius), int(max_frames), int(step), float(min_conf)
+    if grid % 4 or not 4 <= grid <= 64:
+        raise ValueError("grid = %d; a multiple of 4 in 4 .. 64" % grid)
+    if not 1 <= radius <= 16:
+        raise ValueError("radius = %d; 1 .. 16" % radius)
+    if step < 1 or max_frames < 0:
+        raise ValueError("step must be >= 1 and max_frames >= 0")
+    if not math.isfinite(min_conf):
+        raise ValueError("min_conf must be finite")
+    return grid, radius, min_conf, max_frames, step
+
+
+def _track_outputs(C, T, F, device, early_stop, V=None):
+    """The tracks / anchors / ntracks outputs of a tracker: [C,T,F,5] f32, [C,T,3] f32, [C] int32 -- with ``V`` in
+    ``video_batch``'s layout: flat tracks, [V,C,T,3], [V,C].  ``early_stop``: the call may end before it has written every
+    slot, so they start as NaN, zero, zero; a call that writes every element takes them uninitialised."""
+    lead = (C,) if V is None else (V, C)
+    shape = (C, T, F, 5) if V is None else (C * T * F * 5,)
+    if not early_stop:
+        return (torch.empty(shape, dtype=torch.float32, device=device), torch.empty(lead + (T, 3), dtype=torch.float32, device=device),
+                torch.empty(lead, dtype=torch.int32, device=device))
+    return (torch.full(shape, float('nan'), dtype=torch.float32, device=device),
+            torch.zeros(lead + (T, 3), dtype=torch.float32, device=device), torch.zeros(lead, dtype=torch.int32, device=device))
 
 
 def _batch_views(flat, off, C, T, per):
@@ -436,22 +519,17 @@ def video_batch(boxes, scores, frame_off, nms_thres=0.3, thres=0.0, max_tracks=1
     ``nms_track_volume`` + ``rescore_tracks`` return for it alone.  Returns a dict in the batch layout (``_batch_read``):
     tracks, det / pooled f64 and tboxes (rescore; else empty lists), anchors, ntracks, frame_off -- plus keep_idx [F,C,cap] /
     keep_cnt [F,C] (nms)."""
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    boxes, scores = boxes.contiguous(), scores.contiguous()
-    F, B, C = scores.shape
-    if tuple(boxes.shape) != (F, B, 4):
-        raise ValueError("boxes must be [F,B,4]")
+    F, B, C = _volume_layout(boxes, scores)
     off = _frame_offsets(frame_off, F)
+    _same_gpu((boxes, scores), "boxes and scores")
+    boxes, scores = boxes.contiguous(), scores.contiguous()
     V, T = len(off) - 1, int(max_tracks)
     ctx = _ctx_for(boxes, ctx)
     dev = boxes.device
     cap = B if cap is None else int(cap)
     keep_idx = _keep_buffer((F, C, cap), dev, pad) if nms else None
     keep_cnt = torch.zeros((F, C), dtype=torch.int32, device=dev) if nms else None
-    tracks = torch.full((C * max(T, 1) * F * 5,), float('nan'), dtype=torch.float32, device=dev)
-    anchors = torch.zeros((V, C, max(T, 1), 3), dtype=torch.float32, device=dev)
-    ntracks = torch.zeros((V, C), dtype=torch.int32, device=dev)
+    tracks, anchors, ntracks = _track_outputs(C, max(T, 1), F, dev, True, V=V)
     det = torch.empty((C * max(T, 1) * F,), dtype=torch.float64, device=dev) if rescore else None
     pooled = torch.empty_like(det) if rescore else None
     tboxes = torch.empty((C * max(T, 1) * F * 4,), dtype=torch.float32, device=dev) if rescore else None
@@ -501,17 +579,9 @@ def track_volume(boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, link_th
     boxes [F,B,4] f32, scores [F,B,C] f32.  Returns
       tracks  [C, max_tracks, F, 5] f32 rows (x1,y1,x2,y2,score), NaN where a track has no box,
       anchors [C, max_tracks, 3] f32 (1-based frame, box index, score),  ntracks [C] int32."""
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    boxes = boxes.contiguous()
-    scores = scores.contiguous()
-    F, B, C = scores.shape
-    if tuple(boxes.shape) != (F, B, 4):
-        raise ValueError("boxes must be [F,B,4]")
+    boxes, scores, F, B, C = _volume(boxes, scores)
     ctx = _ctx_for(boxes, ctx)
-    tracks = torch.full((C, max_tracks, F, 5), float('nan'), dtype=torch.float32, device=boxes.device)
-    anchors = torch.zeros((C, max_tracks, 3), dtype=torch.float32, device=boxes.device)
-    ntracks = torch.zeros((C,), dtype=torch.int32, device=boxes.device)
+    tracks, anchors, ntracks = _track_outputs(C, max_tracks, F, boxes.device, True)
     _finish(ctx, lambda: ctx.check(ctx.lib.vdet_track_volume(
         ctx.h, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), int(max_tracks),
         float(link_thres), int(max_frames), tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())), sync,
@@ -527,13 +597,7 @@ def nms_track_volume(boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, lin
     bit-identical to the two separate calls.  ``keep_out``: a caller-owned contiguous int32 tensor of >= F*C*cap elements
     to hold keep_idx (the returned keep_idx is a view of it).
     Returns (keep_idx, keep_cnt, tracks, anchors, ntracks)."""
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    boxes = boxes.contiguous()
-    scores = scores.contiguous()
-    F, B, C = scores.shape
-    if tuple(boxes.shape) != (F, B, 4):
-        raise ValueError("boxes must be [F,B,4]")
+    boxes, scores, F, B, C = _volume(boxes, scores)
     cap = B if cap is None else int(cap)
     ctx = _ctx_for(boxes, ctx)
     if keep_out is None:
@@ -545,9 +609,7 @@ def nms_track_volume(boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, lin
         if pad:
             keep_idx.fill_(-1)
     keep_cnt = torch.zeros((F, C), dtype=torch.int32, device=boxes.device)
-    tracks = torch.full((C, max_tracks, F, 5), float('nan'), dtype=torch.float32, device=boxes.device)
-    anchors = torch.zeros((C, max_tracks, 3), dtype=torch.float32, device=boxes.device)
-    ntracks = torch.zeros((C,), dtype=torch.int32, device=boxes.device)
+    tracks, anchors, ntracks = _track_outputs(C, max_tracks, F, boxes.device, True)
     _finish(ctx, lambda: ctx.check(ctx.lib.vdet_nms_track_volume(
         ctx.h, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), int(max_tracks),
         float(link_thres), int(max_frames), tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr(), cap,
@@ -583,32 +645,16 @@ def rescore_tracks(tracks, ntracks, boxes, scores, overlap_thres=0.7, window=3, 
     (:386-414).  Returns (det_score f64 [C,T,F], pooled f64 [C,T,F], boxes f32 [C,T,F,4])."""
     if window % 2 != 1:
         raise ValueError('Window size must be odd!')
-    if tracks.dtype != torch.float32 or boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if ntracks.dtype != torch.int32:
-        raise ValueError("ntracks must be int32")
-    if tracks.dim() != 4 or tracks.shape[3] != 5:
-        raise ValueError("tracks must be [C,T,F,5]")
-    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
-    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    B = boxes.shape[1]
-    if tuple(scores.shape) != (F, B, C):
-        raise ValueError("scores must be [F,B,C]")
-    if tuple(ntracks.shape) != (C,):
-        raise ValueError("ntracks must be [C]")
-    for t in (tracks, ntracks, scores):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("tracks, ntracks, boxes and scores must live on the same GPU")
+    C, T, F = _tubelets_layout(tracks, ntracks)
+    boxes, scores, F, B, C = _volume(boxes, scores, (tracks, ntracks), "tracks, ntracks, boxes and scores", F=F, C=C)
     ntracks = ntracks.contiguous()
     ctx = _ctx_for(boxes, ctx)
     det = torch.empty((C, T, F), dtype=torch.float64, device=boxes.device)
     pooled = torch.empty((C, T, F), dtype=torch.float64, device=boxes.device)
     ob = torch.empty((C, T, F, 4), dtype=torch.float32, device=boxes.device)
-    ctx.check(ctx.lib.vdet_rescore_tracks(ctx.h, tracks.contiguous().data_ptr(), ntracks.data_ptr(),
-                                          boxes.contiguous().data_ptr(), scores.contiguous().data_ptr(), F, B, C, T,
-                                          float(overlap_thres), int(window), det.data_ptr(), pooled.data_ptr(),
-                                          ob.data_ptr()))
+    ctx.check(ctx.lib.vdet_rescore_tracks(ctx.h, tracks.contiguous().data_ptr(), ntracks.data_ptr(), boxes.data_ptr(),
+                                          scores.data_ptr(), F, B, C, T, float(overlap_thres), int(window), det.data_ptr(),
+                                          pooled.data_ptr(), ob.data_ptr()))
     if sync:
         ctx.sync()
     return det, pooled, ob
@@ -625,34 +671,12 @@ def track_from_anchors(boxes, anchor_frames, anchor_boxes, anchor_scores=None, l
       tracks  [C,T,F,5] f32 rows (x1,y1,x2,y2,score), NaN where a tubelet has no box (an empty slot: everywhere),
       anchors [C,T,3] f32 (frame, -1, score or 0),  ntracks [C] int32 = 1 + the last live slot of the class.
     ValueError for an anchor frame outside 0..F (reported when the call, or a later ``ctx.sync()``, waits)."""
-    if boxes.dtype != torch.float32 or anchor_boxes.dtype != torch.float32 or \
-            (anchor_scores is not None and anchor_scores.dtype != torch.float32):
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if anchor_frames.dtype != torch.int32:
-        raise ValueError("anchor_frames must be int32")
-    if boxes.dim() != 3 or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    F, B = boxes.shape[0], boxes.shape[1]
-    if F < 1 or B < 1:
-        raise ValueError("boxes must hold at least one frame and one box per frame")
-    if anchor_frames.dim() != 2:
-        raise ValueError("anchor_frames must be [C,T]")
-    C, T = anchor_frames.shape
-    if C < 1:
-        raise ValueError("anchor_frames must be [C,T] with C >= 1")
-    if tuple(anchor_boxes.shape) != (C, T, 4):
-        raise ValueError("anchor_boxes must be [C,T,4]")
-    if anchor_scores is not None and tuple(anchor_scores.shape) != (C, T):
-        raise ValueError("anchor_scores must be [C,T]")
-    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("boxes, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
+    F, B, _ = _volume_layout(boxes, nonempty=True)
+    anchor_frames, anchor_boxes, anchor_scores, C, T = _anchor_slots(anchor_frames, anchor_boxes, anchor_scores)
+    _same_gpu((boxes, anchor_frames, anchor_boxes, anchor_scores), "boxes, anchor_frames, anchor_boxes and anchor_scores")
     ctx = _ctx_for(boxes, ctx)
-    boxes, anchor_frames, anchor_boxes = boxes.contiguous(), anchor_frames.contiguous(), anchor_boxes.contiguous()
-    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
-    tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=boxes.device)
-    anchors = torch.empty((C, T, 3), dtype=torch.float32, device=boxes.device)
-    ntracks = torch.empty((C,), dtype=torch.int32, device=boxes.device)
+    boxes = boxes.contiguous()
+    tracks, anchors, ntracks = _track_outputs(C, T, F, boxes.device, False)
     ctx.check(ctx.lib.vdet_track_from_anchors(
         ctx.h, boxes.data_ptr(), F, B, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
         anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, float(link_thres), int(max_frames),
@@ -697,50 +721,16 @@ def _scale_settings(scales, scale_step, scale_penalty):
 
 def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx):
     """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
-    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
-        raise ValueError("images must be uint8 [F,H,W,3]")
-    if not images.is_cuda:
-        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
-    if not images.is_contiguous():
-        raise ValueError("images must be contiguous")
-    F, H, W = images.shape[0], images.shape[1], images.shape[2]
-    if F < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767:
-        raise ValueError("images must hold at least one frame of 1 .. 32767 rows and columns")
-    if anchor_boxes.dtype != torch.float32 or (anchor_scores is not None and anchor_scores.dtype != torch.float32):
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if anchor_frames.dtype != torch.int32:
-        raise ValueError("anchor_frames must be int32")
-    if anchor_frames.dim() != 2:
-        raise ValueError("anchor_frames must be [C,T]")
-    C, T = anchor_frames.shape
-    if C < 1:
-        raise ValueError("anchor_frames must be [C,T] with C >= 1")
-    if tuple(anchor_boxes.shape) != (C, T, 4):
-        raise ValueError("anchor_boxes must be [C,T,4]")
-    if anchor_scores is not None and tuple(anchor_scores.shape) != (C, T):
-        raise ValueError("anchor_scores must be [C,T]")
-    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
-        if not t.is_cuda or t.device != images.device:
-            raise ValueError("images, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
-    grid, radius, max_frames, step, min_conf = int(grid), int(radius), int(max_frames), int(step), float(min_conf)
-    if grid % 4 or not 4 <= grid <= 64:
-        raise ValueError("grid = %d; a multiple of 4 in 4 .. 64" % grid)
-    if not 1 <= radius <= 16:
-        raise ValueError("radius = %d; 1 .. 16" % radius)
-    if step < 1 or max_frames < 0:
-        raise ValueError("step must be >= 1 and max_frames >= 0")
-    if not math.isfinite(min_conf):
-        raise ValueError("min_conf must be finite")
+    F, H, W = _images(images)
+    anchor_frames, anchor_boxes, anchor_scores, C, T = _anchor_slots(anchor_frames, anchor_boxes, anchor_scores)
+    settings = _pixel_settings(grid, radius, min_conf, max_frames, step)
     if scale is not None:
         scale = _scale_settings(*scale)
+    _same_gpu((images, anchor_frames, anchor_boxes, anchor_scores), "images, anchor_frames, anchor_boxes and anchor_scores")
     ctx = _ctx_for(images, ctx)
-    anchor_frames, anchor_boxes = anchor_frames.contiguous(), anchor_boxes.contiguous()
-    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
-    tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=images.device)
-    anchors = torch.empty((C, T, 3), dtype=torch.float32, device=images.device)
-    ntracks = torch.empty((C,), dtype=torch.int32, device=images.device)
+    tracks, anchors, ntracks = _track_outputs(C, T, F, images.device, False)
     head = (ctx.h, images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
-            anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, grid, radius, min_conf, max_frames, step)
+            anchor_scores.data_ptr() if anchor_scores is not None else None, C, T) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
     if scale is None:
         ctx.check(ctx.lib.vdet_track_pixels(*(head + out)))
@@ -789,51 +779,18 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
 def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step, sync,
                          ctx):
     """track_volume_pixels (scale None) and track_volume_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
-    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
-        raise ValueError("images must be uint8 [F,H,W,3]")
-    if not images.is_cuda:
-        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
-    if not images.is_contiguous():
-        raise ValueError("images must be contiguous")
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if scores.dim() != 3:
-        raise ValueError("scores must be [F,B,C]")
-    F, B, C = scores.shape
-    if tuple(boxes.shape) != (F, B, 4):
-        raise ValueError("boxes must be [F,B,4]")
-    if F < 1 or B < 1 or C < 1:
-        raise ValueError("scores must hold at least one frame, one box per frame and one class")
-    if images.shape[0] != F:
-        raise ValueError("images hold %d frames, boxes and scores %d" % (images.shape[0], F))
-    H, W = images.shape[1], images.shape[2]
-    if not 1 <= H <= 32767 or not 1 <= W <= 32767:
-        raise ValueError("images must hold frames of 1 .. 32767 rows and columns")
-    for t in (boxes, scores):
-        if not t.is_cuda or t.device != images.device:
-            raise ValueError("images, boxes and scores must live on the same GPU")
-    grid, radius, max_frames, step, min_conf = int(grid), int(radius), int(max_frames), int(step), float(min_conf)
+    F, H, W = _images(images)
     max_tracks = int(max_tracks)
     if max_tracks < 0:
         raise ValueError("max_tracks must be >= 0")
-    if grid % 4 or not 4 <= grid <= 64:
-        raise ValueError("grid = %d; a multiple of 4 in 4 .. 64" % grid)
-    if not 1 <= radius <= 16:
-        raise ValueError("radius = %d; 1 .. 16" % radius)
-    if step < 1 or max_frames < 0:
-        raise ValueError("step must be >= 1 and max_frames >= 0")
-    if not math.isfinite(min_conf):
-        raise ValueError("min_conf must be finite")
+    settings = _pixel_settings(grid, radius, min_conf, max_frames, step)
     if scale is not None:
         scale = _scale_settings(*scale)
-    boxes = boxes.contiguous()
-    scores = scores.contiguous()
+    boxes, scores, F, B, C = _volume(boxes, scores, (images,), "images, boxes and scores", F=F, nonempty=True)
     ctx = _ctx_for(images, ctx)
-    tracks = torch.full((C, max_tracks, F, 5), float('nan'), dtype=torch.float32, device=images.device)
-    anchors = torch.zeros((C, max_tracks, 3), dtype=torch.float32, device=images.device)
-    ntracks = torch.zeros((C,), dtype=torch.int32, device=images.device)
-    head = (ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), max_tracks,
-            grid, radius, min_conf, max_frames, step)
+    tracks, anchors, ntracks = _track_outputs(C, max_tracks, F, images.device, True)
+    head = (ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres),
+            max_tracks) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
     if scale is None:
         call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(*(head + out)))
@@ -862,32 +819,15 @@ def anchor_propagate_tracks(tracks, ntracks, anchors, boxes, scores, sync=True, 
     tracks [C,T,F,5] f32 / ntracks [C] int32 / anchors [C,T,3] f32 (track_from_anchors, track_volume, nms_track_volume),
     boxes [F,B,4] f32, scores [F,B,C] f32.  Returns (det_score [C,T,F] f64: the score where the tubelet has a box, NaN
     elsewhere; best [C,T] int32: the detection's index on the anchor frame, -1 for a slot without anchor box)."""
-    if tracks.dtype != torch.float32 or anchors.dtype != torch.float32 or boxes.dtype != torch.float32 or \
-            scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if ntracks.dtype != torch.int32:
-        raise ValueError("ntracks must be int32")
-    if tracks.dim() != 4 or tracks.shape[3] != 5:
-        raise ValueError("tracks must be [C,T,F,5]")
-    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
-    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    B = boxes.shape[1]
-    if F < 1 or B < 1 or C < 1:
-        raise ValueError("at least one class, one frame and one box per frame")
-    if tuple(scores.shape) != (F, B, C):
-        raise ValueError("scores must be [F,B,C]")
-    if tuple(ntracks.shape) != (C,) or tuple(anchors.shape) != (C, T, 3):
-        raise ValueError("ntracks must be [C], anchors [C,T,3]")
-    for t in (tracks, ntracks, anchors, scores):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("tracks, ntracks, anchors, boxes and scores must live on the same GPU")
+    C, T, F = _tubelets_layout(tracks, ntracks, anchors)
+    boxes, scores, F, B, C = _volume(boxes, scores, (tracks, ntracks, anchors), "tracks, ntracks, anchors, boxes and scores",
+                                     F=F, C=C, nonempty=True)
     ctx = _ctx_for(boxes, ctx)
     det = torch.empty((C, T, F), dtype=torch.float64, device=boxes.device)
     best = torch.empty((C, T), dtype=torch.int32, device=boxes.device)
     ctx.check(ctx.lib.vdet_anchor_propagate_tracks(
         ctx.h, tracks.contiguous().data_ptr(), ntracks.contiguous().data_ptr(), anchors.contiguous().data_ptr(),
-        boxes.contiguous().data_ptr(), scores.contiguous().data_ptr(), F, B, C, T, det.data_ptr(), best.data_ptr()))
+        boxes.data_ptr(), scores.data_ptr(), F, B, C, T, det.data_ptr(), best.data_ptr()))
     if sync:
         ctx.sync()
     return det, best
@@ -911,8 +851,6 @@ def top_anchors(boxes, scores, top_num, mode='video', score_thresh=None, frame_o
     Returns anchor_frames [C,T] int32 (1-based, 0 = empty slot), anchor_boxes [C,T,4] f32 (the proposal's box, not
     truncated), anchor_scores [C,T] f32, anchor_index [C,T] int32 (box index in its frame, -1 = empty); an empty slot's box
     and score are 0."""
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
     if mode not in ('video', 'frame'):
         raise ValueError("mode must be 'video' or 'frame'")
     if mode == 'frame' and frame_off is not None:
@@ -922,18 +860,9 @@ def top_anchors(boxes, scores, top_num, mode='video', score_thresh=None, frame_o
         raise ValueError("top_num must be at least 1")
     if top_num > (1024 if mode == 'video' else 128):
         raise ValueError("top_num is limited to 1024 (mode='video') / 128 (mode='frame')")
-    if boxes.dim() != 3 or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    F, B = boxes.shape[0], boxes.shape[1]
-    if scores.dim() != 3 or scores.shape[0] != F or scores.shape[1] != B:
-        raise ValueError("scores must be [F,B,C]")
-    C = scores.shape[2]
-    if F < 1 or B < 1 or C < 1:
-        raise ValueError("at least one frame, one box per frame and one class")
-    if not scores.is_cuda or scores.device != boxes.device:
-        if boxes.is_cuda:
-            raise ValueError("boxes and scores must live on the same GPU")
+    F, B, C = _volume_layout(boxes, scores, nonempty=True)
     off = None if frame_off is None else _frame_offsets(frame_off, F)
+    _same_gpu((boxes, scores), "boxes and scores")
     ctx = _ctx_for(boxes, ctx)
     boxes, scores = boxes.contiguous(), scores.contiguous()
     T = top_num if mode == 'video' else F * top_num
@@ -961,35 +890,14 @@ def track_from_anchors_batch(boxes, frame_off, anchor_frames, anchor_boxes, anch
     video's first and last frame; per video the rows are bit for bit ``track_from_anchors``' on that video alone.
     Returns a dict in ``video_batch``'s layout (``_batch_read``): tracks, anchors, ntracks, frame_off.  ValueError for an anchor
     frame outside 0..F_v."""
-    if boxes.dtype != torch.float32 or anchor_boxes.dtype != torch.float32 or \
-            (anchor_scores is not None and anchor_scores.dtype != torch.float32):
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if anchor_frames.dtype != torch.int32:
-        raise ValueError("anchor_frames must be int32")
-    if boxes.dim() != 3 or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    F, B = boxes.shape[0], boxes.shape[1]
-    if F < 1 or B < 1:
-        raise ValueError("boxes must hold at least one frame and one box per frame")
+    F, B, _ = _volume_layout(boxes, nonempty=True)
     off = _frame_offsets(frame_off, F)
     V = len(off) - 1
-    if anchor_frames.dim() != 3 or anchor_frames.shape[0] != V or anchor_frames.shape[1] < 1:
-        raise ValueError("anchor_frames must be [V,C,T] with C >= 1")
-    C, T = anchor_frames.shape[1], anchor_frames.shape[2]
-    if tuple(anchor_boxes.shape) != (V, C, T, 4):
-        raise ValueError("anchor_boxes must be [V,C,T,4]")
-    if anchor_scores is not None and tuple(anchor_scores.shape) != (V, C, T):
-        raise ValueError("anchor_scores must be [V,C,T]")
-    for t in (anchor_frames, anchor_boxes) + (() if anchor_scores is None else (anchor_scores,)):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("boxes, anchor_frames, anchor_boxes and anchor_scores must live on the same GPU")
+    anchor_frames, anchor_boxes, anchor_scores, C, T = _anchor_slots(anchor_frames, anchor_boxes, anchor_scores, V)
+    _same_gpu((boxes, anchor_frames, anchor_boxes, anchor_scores), "boxes, anchor_frames, anchor_boxes and anchor_scores")
     ctx = _ctx_for(boxes, ctx)
-    boxes, anchor_frames, anchor_boxes = boxes.contiguous(), anchor_frames.contiguous(), anchor_boxes.contiguous()
-    anchor_scores = None if anchor_scores is None else anchor_scores.contiguous()
-    dev = boxes.device
-    tracks = torch.empty((C * T * F * 5,), dtype=torch.float32, device=dev)
-    anchors = torch.empty((V, C, T, 3), dtype=torch.float32, device=dev)
-    ntracks = torch.empty((V, C), dtype=torch.int32, device=dev)
+    boxes = boxes.contiguous()
+    tracks, anchors, ntracks = _track_outputs(C, T, F, boxes.device, False, V=V)
     ctx.check(ctx.lib.vdet_track_from_anchors_batch(
         ctx.h, boxes.data_ptr(), off.ctypes.data, V, B, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
         anchor_scores.data_ptr() if anchor_scores is not None else None, C, T, float(link_thres), int(max_frames),
@@ -1006,21 +914,14 @@ def anchor_propagate_tracks_batch(batch_out, boxes, scores, sync=True, ctx=None)
     it -- and best [V,C,T] int32.  Per video both equal the single-video call's."""
     b = _batch_read(batch_out, need=('anchors',))
     off, V, F, C, T, tracks, ntracks, anchors = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks, b.anchors
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4] over all frames of the batch")
-    B = boxes.shape[1]
-    if tuple(scores.shape) != (F, B, C):
-        raise ValueError("scores must be [F,B,C]")
-    _same_gpu((boxes, scores, tracks, ntracks, anchors), "the batch result, boxes and scores")
+    boxes, scores, F, B, C = _volume(boxes, scores, (tracks, ntracks, anchors), "the batch result, boxes and scores", F=F, C=C)
     ctx = _ctx_for(boxes, ctx)
     dev = boxes.device
     det = torch.empty((C * T * F,), dtype=torch.float64, device=dev)
     best = torch.empty((V, C, T), dtype=torch.int32, device=dev)
     ctx.check(ctx.lib.vdet_anchor_propagate_tracks_batch(
-        ctx.h, tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), boxes.contiguous().data_ptr(),
-        scores.contiguous().data_ptr(), off.ctypes.data, V, B, C, T, det.data_ptr(), best.data_ptr()))
+        ctx.h, tracks.data_ptr(), ntracks.data_ptr(), anchors.data_ptr(), boxes.data_ptr(), scores.data_ptr(), off.ctypes.data,
+        V, B, C, T, det.data_ptr(), best.data_ptr()))
     if sync:
         ctx.sync()
     dv = _batch_views(det, off, C, T, 1)
@@ -1051,11 +952,10 @@ def _tcn_check(tracks, ntracks, anchors, det_score, gt_overlap, V, C, T, n, code
         raise ValueError("gt_overlap must be float64 [C,T,F]")
     if gt_overlap is None and any(int(q) in (4, 5) for q in codes):
         raise ValueError("the net reads gt_overlaps / labels: pass gt_overlap (ops.tubelets_overlap)")
-    for t in (tracks, ntracks, anchors, det_score) + (() if gt_overlap is None else (gt_overlap,)):
-        if not t.is_cuda or t.device != tracks.device:
-            raise ValueError("tracks, ntracks, anchors, det_score and gt_overlap must live on the same GPU")
-        if not t.is_contiguous():
-            raise ValueError("tensors must be contiguous")
+    every = (tracks, ntracks, anchors, det_score) + (() if gt_overlap is None else (gt_overlap,))
+    if not all(t.is_contiguous() for t in every):
+        raise ValueError("tensors must be contiguous")
+    _same_gpu(every, "tracks, ntracks, anchors, det_score and gt_overlap")
 
 
 _TCN_ROW_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}      # include/vdet_hip.h
@@ -1081,10 +981,9 @@ def _tcn_wide_args(net, wide, rows_of, device):
         rows = rows_of(name, wide[name], ch)
         if rows.dtype not in _TCN_ROW_DTYPES:
             raise ValueError("wide rows must be float32 / float16 / bfloat16 / float64; %r is %s" % (name, rows.dtype))
-        if not rows.is_cuda or rows.device != device:
-            raise ValueError("wide rows must live on the tracks' GPU; %r does not" % name)
         if not rows.is_contiguous():
             raise ValueError("wide rows must be contiguous; %r is not" % name)
+        _same_gpu((rows,), "tracks and the wide rows %r" % name, device)
         ptrs[i], dtypes[i] = rows.data_ptr(), _TCN_ROW_DTYPES[rows.dtype]
         keep.append(rows)
     return params, shapes, codes[codes >= 0].copy(), (codes, widths, ptrs, dtypes), keep
@@ -1250,8 +1149,7 @@ def _interp_series(series, n, device):
             raise ValueError("every series must be a float32 / float64 tensor [C,T,Fs]")
         if x.dtype != series[0].dtype:
             raise ValueError("the series of one call must share one dtype")
-        if not x.is_cuda or x.device != device:
-            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    _same_gpu(series, "tracks, ntracks, anchors, boxes and the series", device)
     return tuple(x.contiguous() for x in series)
 
 
@@ -1309,9 +1207,7 @@ def interpolate_tracks(tracks, ntracks, anchors, series, boxes=None, frames=None
         raise ValueError("anchors must be float32 [C,T,3]")
     if boxes is not None and (boxes.dtype != torch.float32 or tuple(boxes.shape) != (C, T, Fs, 4)):
         raise ValueError("boxes must be float32 [C,T,Fs,4]")
-    for x in (tracks, ntracks, anchors) + (() if boxes is None else (boxes,)):
-        if not x.is_cuda or x.device != tracks.device:
-            raise ValueError("tracks, ntracks, anchors, boxes and the series must live on the same GPU")
+    _same_gpu((tracks, ntracks, anchors, boxes), "tracks, ntracks, anchors, boxes and the series")
     series = _interp_series(series, C * T * Fs, tracks.device)
     for x in series:
         if tuple(x.shape) != (C, T, Fs):
@@ -1346,7 +1242,7 @@ def interpolate_tracks_batch(batch_out, frames, num_frames, sync=True, ctx=None)
     series = (field('det', 1, _F32_F64), field('pooled', 1, _F32_F64)) if rescored else ()
     boxes = field('tboxes', 4, _F32) if rescored else None
     series = _interp_series(series, C * T * Fs, b.device)
-    _same_gpu((tracks, ntracks, anchors) + (() if boxes is None else (boxes,)), "tracks, ntracks, anchors, boxes and the series")
+    _same_gpu((tracks, ntracks, anchors, boxes), "tracks, ntracks, anchors, boxes and the series")
     fr, nf = _interp_frames(frames, soff, num_frames)
     doff = np.concatenate([[0], np.cumsum(nf)]).astype(np.int64)
     ctx = _ctx_for(tracks, ctx)
@@ -1450,10 +1346,7 @@ def merge_tracks(a, b, scheme='combine', sync=True, ctx=None):
         raise ValueError("a and b must have the same number of series")
     if (sa[3] is None) != (sb[3] is None):
         raise ValueError("tboxes: in both sets or in neither")
-    flat = lambda s: [x for x in s[:4] if x is not None] + list(s[4])
-    for x in flat(sa) + flat(sb):
-        if not x.is_cuda or x.device != sa[0].device:
-            raise ValueError("every tensor of a and b must live on the same GPU (vdetlib_amd has no CPU path)")
+    _same_gpu(sa[:4] + sa[4] + sb[:4] + sb[4], "every tensor of a and b")
     cont = lambda s: tuple(None if x is None else x.contiguous() for x in s[:4]) + (tuple(x.contiguous() for x in s[4]),)
     sa, sb = cont(sa), cont(sb)
     ctx = _ctx_for(sa[0], ctx)
@@ -1614,10 +1507,7 @@ def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh
         raise ValueError("tboxes must be float32 [C,T,F,4]")
     still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
     R = _tn_limits(C, T, F, top_still, cap)
-    every = [tracks, ntracks, score] + ([tboxes] if tboxes is not None else []) + list(still or ())
-    for x in every:
-        if not x.is_cuda or x.device != ntracks.device:
-            raise ValueError("every tensor must live on the same GPU (vdetlib_amd has no CPU path)")
+    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
     tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
     tboxes = None if tboxes is None else tboxes.contiguous()
     still = None if still is None else tuple(x.contiguous() for x in still)
@@ -1645,7 +1535,7 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
     still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
     R = _tn_limits(C, T, Ft, top_still, cap)
-    _same_gpu([ntracks, tracks, sc] + ([tboxes] if tboxes is not None else []) + list(still or ()), "every tensor")
+    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
     still = None if still is None else tuple(x.contiguous() for x in still)
     ctx = _ctx_for(ntracks, ctx)
     ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
@@ -1696,34 +1586,15 @@ def rescore_tubelets(tracks, ntracks, boxes, scores, floor=None, overlap_thres=0
     later ``ctx.sync()`` with ``sync=False``)."""
     if window % 2 != 1:
         raise ValueError('Window size must be odd!')
-    if tracks.dtype != torch.float32 or boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if ntracks.dtype != torch.int32:
-        raise ValueError("ntracks must be int32")
-    if floor is not None and floor.dtype not in (torch.float32, torch.float64):
-        raise ValueError("floor must be float32 or float64")
-    if tracks.dim() != 4 or tracks.shape[3] != 5:
-        raise ValueError("tracks must be [C,T,F,5]")
-    C, T, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
-    if boxes.dim() != 3 or boxes.shape[0] != F or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4]")
-    B = boxes.shape[1]
-    if F < 1 or B < 1 or C < 1:
-        raise ValueError("at least one frame, one box per frame and one class")
-    if tuple(scores.shape) != (F, B, C):
-        raise ValueError("scores must be [F,B,C]")
-    if tuple(ntracks.shape) != (C,):
-        raise ValueError("ntracks must be [C]")
-    if floor is not None and tuple(floor.shape) != (C, T, F):
-        raise ValueError("floor must be [C,T,F]")
-    for t in (tracks, ntracks, scores) + (() if floor is None else (floor,)):
-        if not t.is_cuda or t.device != boxes.device:
-            raise ValueError("tracks, ntracks, boxes, scores and floor must live on the same GPU")
+    C, T, F = _tubelets_layout(tracks, ntracks)
+    if floor is not None and (floor.dtype not in _F32_F64 or tuple(floor.shape) != (C, T, F)):
+        raise ValueError("floor must be float32 or float64 [C,T,F]")
+    boxes, scores, F, B, C = _volume(boxes, scores, (tracks, ntracks, floor), "tracks, ntracks, boxes, scores and floor", F=F, C=C,
+                                     nonempty=True)
     ctx = _ctx_for(boxes, ctx)
     off = np.array([0, F], dtype=np.int64)
-    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks.contiguous(), ntracks.contiguous(), boxes.contiguous(),
-                                        scores.contiguous(), None if floor is None else floor.contiguous(), overlap_thres,
-                                        complete, window, sync)
+    det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks.contiguous(), ntracks.contiguous(), boxes, scores,
+                                        None if floor is None else floor.contiguous(), overlap_thres, complete, window, sync)
     return det.view(C, T, F), pooled.view(C, T, F), tboxes.view(C, T, F, 4), src.view(C, T, F)
 
 
@@ -1738,15 +1609,7 @@ def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0
         raise ValueError('Window size must be odd!')
     b = _batch_read(batch_out)
     off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
-    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
-        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
-    if boxes.dim() != 3 or boxes.shape[0] != Ft or boxes.shape[2] != 4:
-        raise ValueError("boxes must be [F,B,4] over all frames of the batch")
-    B = boxes.shape[1]
-    if B < 1 or C < 1:
-        raise ValueError("at least one box per frame and one class")
-    if tuple(scores.shape) != (Ft, B, C):
-        raise ValueError("scores must be [F,B,C]")
+    _, B, _ = _volume_layout(boxes, scores, F=Ft, C=C, nonempty=True)
     if floor is not None:
         if isinstance(floor, (list, tuple)):
             floor = _batch_field(b, floor, 1, _F32_F64, 'floor', 'rescore_tubelets_batch', gather=True)
@@ -1755,7 +1618,7 @@ def rescore_tubelets_batch(batch_out, boxes, scores, floor=None, overlap_thres=0
         if floor.dtype not in _F32_F64:
             raise ValueError("floor must be float32 or float64")
         floor = floor.contiguous()
-    _same_gpu((boxes, scores, tracks, ntracks) + (() if floor is None else (floor,)), "the batch result, boxes, scores and floor")
+    _same_gpu((boxes, scores, tracks, ntracks, floor), "the batch result, boxes, scores and floor")
     ctx = _ctx_for(boxes, ctx)
     det, pooled, tboxes, src = _rt_call(ctx, off, B, C, T, tracks, ntracks, boxes.contiguous(), scores.contiguous(), floor,
                                         overlap_thres, complete, window, sync)
@@ -1773,15 +1636,9 @@ _PATCH_MODES = {'warp': 0, 'square': 1}
 
 def _patch_common(images, crop_size, padding, mean, mode, dtype):
     """The checks rcnn_patches and tubelet_patches share: (S, padding, mode code, dtype code, mean tensor or None)."""
-    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
-        raise ValueError("images must be uint8 [Fi,H,W,3]")
+    _images(images)
     if not images.is_cuda:
         raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
-    if not images.is_contiguous():
-        raise ValueError("images must be contiguous")
-    Fi, H, W = images.shape[0], images.shape[1], images.shape[2]
-    if Fi < 1 or not 1 <= H <= 32767 or not 1 <= W <= 32767:
-        raise ValueError("images must hold at least one frame of 1 .. 32767 rows and columns")
     S, padding = int(crop_size), int(padding)
     if not 1 <= S <= 1024:
         raise ValueError("crop_size = %d; 1 .. 1024" % S)
@@ -1839,11 +1696,9 @@ def rcnn_patches(images, boxes, image_idx=None, offsets=None, crop_size=224, pad
     M = N * (num + 1)
     if M >= 2 ** 31 - 16:
         raise ValueError("too many windows (below 2^31 - 16)")
-    for x in (boxes, image_idx, offsets):
-        if x is not None and (not x.is_cuda or x.device != images.device):
-            raise ValueError("images, boxes, image_idx and offsets must live on the same GPU")
-        if x is not None and not x.is_contiguous():
-            raise ValueError("boxes, image_idx and offsets must be contiguous")
+    if not all(x is None or x.is_contiguous() for x in (boxes, image_idx, offsets)):
+        raise ValueError("boxes, image_idx and offsets must be contiguous")
+    _same_gpu((images, boxes, image_idx, offsets), "images, boxes, image_idx and offsets")
     dev = images.device
     patches = torch.empty((M, 3, S, S), dtype=dtype, device=dev)
     ok = torch.empty((M,), dtype=torch.uint8, device=dev)
@@ -1899,11 +1754,9 @@ def tubelet_patches(images, tracks, ntracks, frames, cap, crop_size=224, padding
     cap = int(cap)
     if not 0 <= cap < 2 ** 31 - 16:
         raise ValueError("cap must be 0 .. 2^31 - 17 windows")
-    for x in (tracks, ntracks):
-        if not x.is_cuda or x.device != images.device:
-            raise ValueError("images, tracks and ntracks must live on the same GPU")
-        if not x.is_contiguous():
-            raise ValueError("tracks and ntracks must be contiguous")
+    if not tracks.is_contiguous() or not ntracks.is_contiguous():
+        raise ValueError("tracks and ntracks must be contiguous")
+    _same_gpu((images, tracks, ntracks), "images, tracks and ntracks")
     dev = images.device
     patches = torch.empty((cap, 3, S, S), dtype=dtype, device=dev)
     ok = torch.empty((cap,), dtype=torch.uint8, device=dev)
@@ -1942,11 +1795,9 @@ def _svm_model(model, dev):
         if B.dtype not in (torch.float32, torch.float64) or B.numel() != W.shape[1] or (B.dim() > 1 and tuple(B.shape) != (1, W.shape[1])):
             raise ValueError("B must be float32 / float64 [M] (or [1,M])")
         B = B.reshape(-1)
-    for x in (W, B):
-        if x is not None and (not x.is_cuda or x.device != dev):
-            raise ValueError("features, W and B must live on the same GPU")
-        if x is not None and not x.is_contiguous():
-            raise ValueError("W and B must be contiguous")
+    if not W.is_contiguous() or not (B is None or B.is_contiguous()):
+        raise ValueError("W and B must be contiguous")
+    _same_gpu((W, B), "features, W and B", dev)
     return W, B, float(np.asarray(scale).reshape(())), bool(small)
 
 
@@ -2030,11 +1881,9 @@ def svm_head(features, model, group=1, slot=None, count=None, shape=None, cols=N
         raise ValueError("sboxes must be float64 [N,group,4]")
     if ok is not None and (not torch.is_tensor(ok) or ok.dtype != torch.uint8 or ok.numel() != N * G):
         raise ValueError("ok must be uint8 with N*group elements")
-    for x in (slot, count, cols, sboxes, ok):
-        if x is not None and (not x.is_cuda or x.device != dev):
-            raise ValueError("features, slot, count, cols, sboxes and ok must live on the same GPU")
-        if x is not None and not x.is_contiguous():
-            raise ValueError("slot, count, cols, sboxes and ok must be contiguous")
+    if not all(x is None or x.is_contiguous() for x in (slot, count, cols, sboxes, ok)):
+        raise ValueError("slot, count, cols, sboxes and ok must be contiguous")
+    _same_gpu((slot, count, cols, sboxes, ok), "features, slot, count, cols, sboxes and ok", dev)
     det = arg = tboxes = None
     if slot is not None:
         if out is not None:
@@ -2043,9 +1892,9 @@ def svm_head(features, model, group=1, slot=None, count=None, shape=None, cols=N
                 raise ValueError("out's det / arg do not fit this call (compute dtype %s, shape %s)" % (cdt, (C, T, F)))
             if sboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float64 or tuple(tboxes.shape) != (C, T, F, 4)):
                 raise ValueError("out's tboxes must be float64 [C,T,F,4] when sboxes are given")
-            for x in (det, arg, tboxes):
-                if x is not None and (x.device != dev or not x.is_contiguous()):
-                    raise ValueError("out's tensors must be contiguous on the features' GPU")
+            if not all(x is None or x.is_contiguous() for x in (det, arg, tboxes)):
+                raise ValueError("out's tensors must be contiguous on the features' GPU")
+            _same_gpu((det, arg, tboxes), "features and out's tensors", dev)
         else:
             det = torch.full((C, T, F), float('nan'), dtype=cdt, device=dev)
             arg = torch.full((C, T, F), -1, dtype=torch.int32, device=dev)
@@ -2273,9 +2122,7 @@ class DetEvaluator(object):
         return int(cnt.value)
 
     def _check(self, *ts):
-        for t in ts:
-            if not t.is_cuda or t.device != self.device:
-                raise ValueError("every tensor must live on the evaluator's GPU (%s)" % self.device)
+        _same_gpu(ts, "the evaluator (%s) and every tensor" % self.device, self.device)
 
     def add_tracks(self, video, tracks, ntracks, scores, boxes=None):
         """Tubelets of one video: tracks [C,T,F,5] f32 (track_volume), ntracks [C] int32, scores [C,T,F] f64 or f32
