@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from temporal_cases import expected, score_key  # noqa: F401  (the key and list reference, shared with the seam tests)
 from vdetlib_amd import ops, _lib
 
 pytestmark = pytest.mark.gpu
@@ -28,33 +29,6 @@ def ctx_for(binsort):
             else:
                 os.environ["VDET_BINSORT"] = old
     return _ctxs[binsort]
-
-
-def score_key(s):
-    """sortable key of a float32 score (csrc/nms_kernels.hpp score_key): larger = earlier; -0.0 == +0.0; NaN first"""
-    s = np.asarray(s, dtype=np.float32).copy()
-    s[s == 0] = 0.0
-    b = s.view(np.uint32)
-    k = np.where(b & 0x80000000, ~b, b | 0x80000000).astype(np.uint32)
-    k[np.isnan(s)] = 0xFFFFFFFF
-    return k
-
-
-def expected(scores_fbc, thr=None):
-    """[F,B,C] -> order [F,C,B], ncand [F,C]: descending key, ties by descending index; non-candidates last"""
-    F, B, C = scores_fbc.shape
-    order = np.empty((F, C, B), dtype=np.int64)
-    ncand = np.empty((F, C), dtype=np.int32)
-    idx = np.arange(B)
-    for f in range(F):
-        for c in range(C):
-            col = scores_fbc[f, :, c]
-            k = score_key(col).astype(np.int64)
-            if thr is not None:
-                k[~(col > np.float32(thr))] = 0
-            order[f, c] = np.lexsort((-idx, -k))
-            ncand[f, c] = int((k != 0).sum())
-    return order, ncand
 
 
 def run(scores_fbc, thr=None, layout="FBC", binsort=True):
