@@ -97,6 +97,13 @@
  *                                          0 <= scale_penalty <= 65535                            VDET_EINVAL; bad anchor data as in
  *                                                                     the call without the search.  A level whose box has a side
  *                                                                     below 1 or above 2^21 is skipped, never an error
+ *   luma integral image                    (vdet_luma_integral) H, W <= 32767, H*W <= 2^24 (255 * H * W fits in 32 bits),
+ *                                          F*H/4 and F*ceil((W+1)/128) < 2^31 - 16                VDET_EINVAL.  One path for every size
+ *   pixel tracker with box sampling        (vdet_track_pixels_box, vdet_track_volume_pixels_box) the row of the call with the
+ *                                          scale search (scales = 0 allowed), and H*W <= 2^24, a non-NULL integral
+ *                                                                     VDET_EINVAL; bad anchor data as in the call with point
+ *                                                                     sampling.  A cell outside the image or narrower than a
+ *                                                                     pixel is a single column / row, never an error
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1120,6 +1127,40 @@ int vdet_track_volume_pixels_scaled(vdet_ctx *ctx, const uint8_t *d_images, int6
                                     const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
                                     int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
                                     int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+/* ---- box-filter sampling for the pixel tracker, from an integral image of the luma that the caller builds once per video and
+ *      reuses.  The rule is tests/pixtrack_box_spec.py; everything it does not restate is the point-sampling calls' ------------
+ *
+ * vdet_luma_integral: d_images uint8 [F,H,W,3] -> d_integral uint32 [F,H+1,W+1],
+ *   I[f, y, x] = sum of L[f, r, c] over r < y, c < x  (L: vdet_track_pixels' luma; row 0 and column 0 are zero).
+ * Every element is written by the call (two launches: a scan along the rows, luma in flight, then a scan down the columns in
+ * place; no luma plane is staged, no scratch of the context's is used); exact.  H*W <= 2^24, so the largest entry, 255 * 2^24,
+ * fits.  The table takes 4/3 of the images' bytes.  Timed under "other".
+ *
+ * vdet_track_pixels_box / vdet_track_volume_pixels_box: vdet_track_pixels_scaled's / vdet_track_volume_pixels_scaled's
+ * arguments with d_integral (the table of the SAME video, F, H, W the images') in the place of d_images; scales = 0 is the
+ * fixed-scale chain.  A cell's value is the rounded mean of its pixels instead of one pixel.  On one axis, from the (level) box's
+ * origin o, extent e (w or h), the side S, the limit N (W or H), for any integer k (template: 0..S-1, region: -R..S+R-1):
+ *   edges     a = o + floor(k*e / S), b = o + floor((k+1)*e / S); a' = clamp(a, 0, N-1), b' = min(max(b, a'+1), N): a cell partly
+ *             outside the image averages its inside part; a cell wholly outside, or narrower than a pixel (e < S), is the nearest
+ *             single column / row
+ *   value     tot = I[rb',cb'] - I[ra',cb'] - I[rb',ca'] + I[ra',ca'], area = (rb'-ra') * (cb'-ca'), (tot + (area >> 1)) / area
+ * SAD, key, confidence, move, chain ends, levels, bad anchor data (latched), outputs, layouts, timing buckets and launch
+ * sequences (ONE launch; three per track) are those of the calls they mirror.  With w == h == S and scales = 0 every cell is one
+ * pixel: vdet_track_pixels' bits.  Argument checks: those of the calls they mirror, H*W <= 2^24 and a non-NULL d_integral, before
+ * any launch.  ctx NULL: VDET_EINVAL, nothing touched.  Limits: the table at the top of this file.
+ */
+int vdet_luma_integral(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, uint32_t *d_integral);
+
+int vdet_track_pixels_box(vdet_ctx *ctx, const uint32_t *d_integral, int64_t F, int64_t H, int64_t W,
+                          const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C,
+                          int T, int S, int R, double min_conf, int max_frames, int step, int scales, int scale_step,
+                          int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+int vdet_track_volume_pixels_box(vdet_ctx *ctx, const uint32_t *d_integral, int64_t H, int64_t W, const float *d_boxes,
+                                 const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                 int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
+                                 int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

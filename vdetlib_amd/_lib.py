@@ -109,6 +109,11 @@ SYMBOLS = {
                                        _vp, _vp, _vp]),
     "vdet_track_volume_pixels_scaled": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci,
                                               _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "vdet_luma_integral": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "vdet_track_pixels_box": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _ci, _ci, _ci,
+                                    _vp, _vp, _vp]),
+    "vdet_track_volume_pixels_box": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci,
+                                           _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
 }
 
 

@@ -39,6 +39,23 @@
 // registers, and the ONE reduction of the step follows the last level.  The key is (SAD + |l|*q | |l| | dy^2+dx^2 | dy+R | dx+R
 // | l+3): the raw SAD of the winner is key_hi - |l|*q.  The box state (x1, y1, w, h) stays scalar; the winner's level box,
 // moved, is the new box.  pix_chain<false> is the fixed-scale chain, the code it was before the template.
+//
+// Box sampling (tests/pixtrack_box_spec.py; track_pixels_box_kernel, track_pixel_chain_box_kernel): pix_chain<true, true>.
+// A cell's value is the rounded mean of its pixels instead of one pixel, read from a summed-area table of the luma:
+//   integral  I[f, y, x] = sum of L[f, r, c] over r < y, c < x, uint32 [F, H+1, W+1]; H*W <= 2^24, so 255 * 2^24 fits
+//   edges     per axis: a = o + floor(k*e / S), b = o + floor((k+1)*e / S), a' = clamp(a, 0, N-1), b' = min(max(b, a'+1), N)
+//   value     tot = I[rb', cb'] - I[ra', cb'] - I[rb', ca'] + I[ra', ca'], area = (rb'-ra') * (cb'-ca'), (tot + (area >> 1)) / area
+// The step's tables hold a' and b' per cell and axis (two floor divisions a thread), the gather reads four integral entries
+// per cell and divides (an exact u32 division); the template is gathered the same way from the anchor frame's integral.  The
+// SAD pass, the reduction and the box state are the point chain's.  PixTrackArgs::images carries the integral in this mode; the
+// chain always runs the level loop (scales = 0: one trip, the fixed-scale chain's winner).  LDS: two more tables, 15.0 KiB.
+//
+// The integral is made by two launches (vdet_luma_integral), luma in flight, no luma plane in memory:
+//   luma_integral_rows_kernel  a wave per image row: 64 pixels a trip, a wave scan, the carry of the trips so far in a register;
+//                              writes I[f, y+1, 1..W] = the row's prefix sums and I[f, y+1, 0] = 0
+//   luma_integral_cols_kernel  a thread per column of a frame, rows top to bottom (a wave reads and writes 256 contiguous
+//                              bytes of a row), eight rows' loads in flight; writes row 0 = 0 and the sums in place
+// Sums are exact, so the order of the additions is free.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,10 +73,11 @@ constexpr int kPixMaxP = kPixMaxS + 2 * kPixMaxR;       // region side
 constexpr int kPixMaxPitch = kPixMaxP / 4 + 1;          // region row pitch in dwords (one spare: see the pair read)
 constexpr int kPixCoordMax = 1 << 20;
 constexpr int kPixSideMax = 1 << 21;     // scale search: a level whose box is wider or higher is skipped (products stay in int32)
+constexpr int64_t kPixBoxMaxArea = 1 << 24;       // box sampling: H * W of a frame (255 * 2^24 is the largest integral entry)
 constexpr int kPixMaxScales = 3, kPixMaxScaleStep = 25, kPixMaxScalePenalty = 65535;
 
 struct PixTrackArgs {
-    const uint8_t *images;      // [F,H,W,3]
+    const uint8_t *images;      // [F,H,W,3]; box sampling: the integral, uint32 [F,H+1,W+1]
     int F, H, W, C, T;
     const int32_t *aframes;     // [C,T] 1-based, 0: empty slot
     const float *aboxes;        // [C,T,4]
@@ -158,6 +176,51 @@ __device__ __forceinline__ void pix_gather(uint32_t *dst, int pitch, const int *
     }
 }
 
+// box sampling: the edges of the cells k = k0 .. k0+n-1 of the box, ca/cb[i] = a'/b' of the columns, ra/rb[i] of the rows.
+// |k| <= 80 and e <= 2^21 + 1: the products stay below 2^28.  n <= kPixMaxP, 2n <= kPixLT.
+__device__ __forceinline__ void pix_tables_box(int *ca, int *cb, int *ra, int *rb, int x1, int y1, int w, int h, int S, int k0, int n,
+                                               int H, int W)
+{
+    const int tid = threadIdx.x;
+    if (tid < 2 * n) {
+        const bool isrow = tid >= n;
+        const int i = isrow ? tid - n : tid;
+        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W;
+        int lo = o + pix_floordiv((k0 + i) * e, S), hi = o + pix_floordiv((k0 + i + 1) * e, S);
+        lo = lo < 0 ? 0 : (lo > lim - 1 ? lim - 1 : lo);
+        hi = hi < lo + 1 ? lo + 1 : hi;
+        hi = hi > lim ? lim : hi;
+        if (isrow) { ra[i] = lo; rb[i] = hi; }
+        else { ca[i] = lo; cb[i] = hi; }
+    }
+}
+
+// pix_gather from one frame's integral I (row pitch pw = W + 1): n x n rounded cell means.  Every index is inside the frame's
+// table: 0 <= a' < b' <= N.  tot <= 255 * area and area <= 2^24: the sums stay in 32 bits
+__device__ __forceinline__ void pix_gather_box(uint32_t *dst, int pitch, const int *ca, const int *cb, const int *ra, const int *rb,
+                                               int n, const uint32_t *I, int pw)
+{
+    const int total = n * pitch;
+    for (int d = threadIdx.x; d < total; d += kPixLT) {
+        const int i = d / pitch, q = d - i * pitch;
+        const int r0 = ra[i], r1 = rb[i];
+        const uint32_t *p0 = I + (int64_t)r0 * pw, *p1 = I + (int64_t)r1 * pw;
+        const uint32_t hgt = (uint32_t)(r1 - r0);
+        uint32_t v = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int j = 4 * q + b;
+            if (j < n) {
+                const int c0 = ca[j], c1 = cb[j];
+                const uint32_t tot = (p1[c1] - p0[c1]) - (p1[c0] - p0[c0]);
+                const uint32_t area = hgt * (uint32_t)(c1 - c0);
+                v |= ((tot + (area >> 1)) / area) << (8 * b);
+            }
+        }
+        dst[d] = v;
+    }
+}
+
 // every row of a slot without a tubelet
 __device__ __forceinline__ void pix_no_rows(float *trk, int F)
 {
@@ -170,13 +233,15 @@ __device__ __forceinline__ void pix_no_rows(float *trk, int F)
 // the chain's own by thread 0, those it does not reach -- beyond its end and on the frames step > 1 skips -- by the whole block
 // afterwards.  Reads of a: images, F, H, W, S, R, min_conf, reach, step.  Block-uniform control flow.
 // SCALED: the scale search over the levels -sc.ns .. sc.ns (see the top of this file); otherwise sc is not read.
-template <bool SCALED>
+// BOX: box sampling from the integral a.images carries (see the top of this file).
+template <bool SCALED, bool BOX = false>
 __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, const int af, const int4 ab, const int dir,
                                           const PixScaleArgs sc)
 {
     __shared__ uint32_t sreg[kPixMaxP * kPixMaxPitch];
     __shared__ uint32_t stm[kPixMaxS * (kPixMaxS / 4)];
     __shared__ int tcol[kPixMaxP], trow[kPixMaxP];
+    __shared__ int tcolb[BOX ? kPixMaxP : 1], trowb[BOX ? kPixMaxP : 1];         // (BOX: tcol / trow hold a', these b')
     __shared__ unsigned long long skey[2][kPixWaves];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int F = a.F, H = a.H, W = a.W, S = a.S, R = a.R;
@@ -189,11 +254,19 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
         r[0] = (float)(x1 + 1); r[1] = (float)(y1 + 1); r[2] = (float)(x1 + w); r[3] = (float)(y1 + h); r[4] = 1.0f;
     }
     const int64_t frame_bytes = (int64_t)H * W * 3;
+    const uint32_t *integ = reinterpret_cast<const uint32_t *>(a.images);       // (BOX)
+    const int64_t frame_cells = (int64_t)(H + 1) * (W + 1);
     const int P = S + 2 * R, pitch = P / 4 + 1, tq = S / 4, side = 2 * R + 1, ncand = side * side;
     // the template
-    pix_tables(tcol, trow, x1, y1, w, h, S, 0, S, H, W);
-    __syncthreads();
-    pix_gather(stm, tq, tcol, trow, S, a.images + (int64_t)af * frame_bytes, W);
+    if constexpr (BOX) {
+        pix_tables_box(tcol, tcolb, trow, trowb, x1, y1, w, h, S, 0, S, H, W);
+        __syncthreads();
+        pix_gather_box(stm, tq, tcol, tcolb, trow, trowb, S, integ + (int64_t)af * frame_cells, W + 1);
+    } else {
+        pix_tables(tcol, trow, x1, y1, w, h, S, 0, S, H, W);
+        __syncthreads();
+        pix_gather(stm, tq, tcol, trow, S, a.images + (int64_t)af * frame_bytes, W);
+    }
     __syncthreads();
     const float denom = (float)(255 * S * S);
 
@@ -220,9 +293,15 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
             // Between two levels of a step no barrier is added: the tables are read by the gather only, which every thread has
             // left at the barrier behind it, and the barrier behind these tables stands between the previous level's SAD reads
             // of the region and this level's gather, which overwrites it)
-            pix_tables(tcol, trow, lx1, ly1, lw, lh, S, -R, P, H, W);
-            __syncthreads();
-            pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
+            if constexpr (BOX) {
+                pix_tables_box(tcol, tcolb, trow, trowb, lx1, ly1, lw, lh, S, -R, P, H, W);
+                __syncthreads();
+                pix_gather_box(sreg, pitch, tcol, tcolb, trow, trowb, P, integ + (int64_t)g * frame_cells, W + 1);
+            } else {
+                pix_tables(tcol, trow, lx1, ly1, lw, lh, S, -R, P, H, W);
+                __syncthreads();
+                pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
+            }
             __syncthreads();
             for (int cand = tid; cand < ncand; cand += kPixLT) {
                 const int cy = cand / side, cx = cand - cy * side;      // dy + R, dx + R
@@ -309,7 +388,7 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
 
 // grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
 // slot 0 of a class -- the class's ntracks), 1 backward.  The body of track_pixels_kernel and track_pixels_scaled_kernel.
-template <bool SCALED>
+template <bool SCALED, bool BOX = false>
 __device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixScaleArgs sc)
 {
     __shared__ int snt;
@@ -347,7 +426,7 @@ __device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixS
         if (dir > 0) pix_no_rows(trk, F);
         return;
     }
-    pix_chain<SCALED>(a, trk, af, ab, dir, sc);
+    pix_chain<SCALED, BOX>(a, trk, af, ab, dir, sc);
 }
 
 __global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
@@ -361,13 +440,19 @@ __global__ __launch_bounds__(kPixLT) void track_pixels_scaled_kernel(const PixTr
     pix_slots_body<true>(a, sc);
 }
 
+// vdet_track_pixels_box: the same launch with box sampling in every chain (a.images: the integral); sc.ns = 0: the fixed scale
+__global__ __launch_bounds__(kPixLT) void track_pixels_box_kernel(const PixTrackArgs a, const PixScaleArgs sc)
+{
+    pix_slots_body<true, true>(a, sc);
+}
+
 // The tracker launch of the greedy loop (vdet_track_volume_pixels): grid (C, 2), one block per class and direction.  The anchor
 // is the one track_pick_kernel left in the class's TrackState -- frame anchor_frame, box boxes[anchor_frame, anchor_box]
 // truncated toward zero (vdet/track.py:224, map(int, bbox)) --, the tubelet goes into slot ntracks of the class, every row of
 // which this launch writes exactly once.  A class that is not active returns at once.  An anchor that cannot be tracked
 // (pix_box_state) latches kStBadPixAnchor and leaves a slot of NaN rows: the loop goes on and nothing is suppressed by it.
 // Reads of a: what pix_chain reads.  The body of track_pixel_chain_kernel and track_pixel_chain_scaled_kernel.
-template <bool SCALED>
+template <bool SCALED, bool BOX = false>
 __device__ __forceinline__ void pix_greedy_body(const PixTrackArgs &a, const PixScaleArgs sc, const TrackState *__restrict__ st,
                                                 const float *__restrict__ boxes, int B, int max_tracks, float *__restrict__ tracks,
                                                 int *status)
@@ -385,7 +470,7 @@ __device__ __forceinline__ void pix_greedy_body(const PixTrackArgs &a, const Pix
         }
         return;
     }
-    pix_chain<SCALED>(a, trk, s.anchor_frame, ab, dir, sc);
+    pix_chain<SCALED, BOX>(a, trk, s.anchor_frame, ab, dir, sc);
 }
 
 __global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrackArgs a, const TrackState *__restrict__ st,
@@ -402,6 +487,74 @@ __global__ __launch_bounds__(kPixLT) void track_pixel_chain_scaled_kernel(const 
                                                                           float *__restrict__ tracks, int *status)
 {
     pix_greedy_body<true>(a, sc, st, boxes, B, max_tracks, tracks, status);
+}
+
+// vdet_track_volume_pixels_box: the same launch with box sampling in the chain (a.images: the integral)
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_box_kernel(const PixTrackArgs a, const PixScaleArgs sc,
+                                                                       const TrackState *__restrict__ st,
+                                                                       const float *__restrict__ boxes, int B, int max_tracks,
+                                                                       float *__restrict__ tracks, int *status)
+{
+    pix_greedy_body<true, true>(a, sc, st, boxes, B, max_tracks, tracks, status);
+}
+
+// ---- the integral image of the luma (vdet_luma_integral): uint8 [F,H,W,3] -> uint32 [F,H+1,W+1], two launches that between
+// them write every element once (rows: columns 0 .. W of the rows 1 .. H; cols: row 0, then rows 1 .. H in place)
+constexpr int kPixIntRowLT = 256, kPixIntRowWaves = kPixIntRowLT / 64;       // a wave per image row
+constexpr int kPixIntColLT = 128, kPixIntColDepth = 8;
+
+// grid ceil(F*H / 4): wave r of the launch scans image row r (frame r / H, row r % H) into I[f, y+1, :]
+__global__ __launch_bounds__(kPixIntRowLT) void luma_integral_rows_kernel(const uint8_t *__restrict__ images, int64_t nrows, int H, int W,
+                                                                          uint32_t *__restrict__ integ)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * kPixIntRowWaves + (threadIdx.x >> 6);
+    if (row >= nrows) return;                // (the whole wave; no barrier below)
+    const int64_t f = row / H;
+    const int y = (int)(row - f * H);
+    const uint8_t *src = images + row * W * 3;
+    uint32_t *dst = integ + (f * (H + 1) + y + 1) * (int64_t)(W + 1);
+    if (lane == 0) dst[0] = 0;
+    uint32_t carry = 0;                      // the sum of the trips so far
+    for (int x0 = 0; x0 < W; x0 += 64) {     // (wave-uniform)
+        const int x = x0 + lane;
+        uint32_t v = x < W ? pix_luma(src + 3 * x) : 0u;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t u = __shfl_up(v, d, 64);
+            if (lane >= d) v += u;
+        }
+        v += carry;
+        if (x < W) dst[x + 1] = v;
+        carry = __shfl(v, 63, 64);
+    }
+}
+
+// grid F * ceil((W+1) / 128): a thread per column of a frame's table
+__global__ __launch_bounds__(kPixIntColLT) void luma_integral_cols_kernel(uint32_t *__restrict__ integ, int H, int W, int nbx)
+{
+    const int64_t f = blockIdx.x / nbx;
+    const int x = (int)(blockIdx.x - f * nbx) * kPixIntColLT + threadIdx.x;
+    if (x > W) return;
+    const int64_t pw = W + 1;
+    uint32_t *p = integ + f * (H + 1) * pw + x;
+    p[0] = 0;
+    uint32_t acc = 0;
+    int y = 1;
+    for (; y + kPixIntColDepth - 1 <= H; y += kPixIntColDepth) {
+        uint32_t v[kPixIntColDepth];
+#pragma unroll
+        for (int k = 0; k < kPixIntColDepth; ++k) v[k] = p[(y + k) * pw];
+#pragma unroll
+        for (int k = 0; k < kPixIntColDepth; ++k) {
+            acc += v[k];
+            p[(y + k) * pw] = acc;
+        }
+    }
+    for (; y <= H; ++y) {
+        acc += p[y * pw];
+        p[y * pw] = acc;
+    }
 }
 
 }  // namespace vdet

@@ -4123,14 +4123,24 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
 // ---------------------------------------------------------------------------------------------
 // Device pixel tracker (pixtrack_kernels.hpp), fixed scale and with the scale search (tests/pixtrack_scale_spec.py)
 // ---------------------------------------------------------------------------------------------
-// vdet_track_pixels (sc null) and vdet_track_pixels_scaled; the settings' checks are pix_settings_check's
+// box sampling (tests/pixtrack_box_spec.py): the largest entry of a frame's integral, 255 * H * W, must fit in 32 bits
+static int pix_box_check(vdet_ctx *c, int64_t H, int64_t W)
+{
+    if (H * W > kPixBoxMaxArea) return fail(c, VDET_EINVAL, "box sampling: frames of at most 2^24 pixels (H * W)");
+    return VDET_OK;
+}
+
+// vdet_track_pixels (sc null), vdet_track_pixels_scaled and -- box: d_images is the integral uint32 [F,H+1,W+1], sc is given --
+// vdet_track_pixels_box; the settings' checks are pix_settings_check's
 static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
                              const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
-                             int max_frames, int step, const PixScaleArgs *sc, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+                             int max_frames, int step, const PixScaleArgs *sc, float *d_tracks, float *d_anchors, int32_t *d_ntracks,
+                             bool box = false)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
+    if (box && pix_box_check(c, H, W)) return VDET_EINVAL;
     if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
     if (!d_images || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
@@ -4152,7 +4162,8 @@ static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
     a.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_OTHER);
-        if (sc) hipLaunchKernelGGL(track_pixels_scaled_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
+        if (box) hipLaunchKernelGGL(track_pixels_box_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
+        else if (sc) hipLaunchKernelGGL(track_pixels_scaled_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
         else hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
@@ -4179,6 +4190,40 @@ int vdet_track_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
                              step, &sc, d_tracks, d_anchors, d_ntracks);
 }
 
+int vdet_luma_integral(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, uint32_t *d_integral)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (pix_box_check(c, H, W)) return VDET_EINVAL;
+    const int64_t nbx = (W + kPixIntColLT) / kPixIntColLT;                   // blocks over the W + 1 columns of a frame's table
+    const int64_t row_blocks = (F * H + kPixIntRowWaves - 1) / kPixIntRowWaves;
+    if (F >= 0x7FFFFFF0ll || row_blocks >= 0x7FFFFFF0ll || F * nbx >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "video too large (F*H/4 and F*ceil((W+1)/128) must stay below 2^31 - 16)");
+    if (!d_images || !d_integral) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(luma_integral_rows_kernel, dim3((unsigned)row_blocks), dim3(kPixIntRowLT), 0, c->stream, d_images, F * H, (int)H,
+                           (int)W, d_integral);
+        hipLaunchKernelGGL(luma_integral_cols_kernel, dim3((unsigned)(F * nbx)), dim3(kPixIntColLT), 0, c->stream, d_integral, (int)H,
+                           (int)W, (int)nbx);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_track_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
+                          const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
+                          int max_frames, int step, int scales, int scale_step, int scale_penalty, float *d_tracks, float *d_anchors,
+                          int32_t *d_ntracks)
+{
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    return track_pixels_impl(c, reinterpret_cast<const uint8_t *>(d_integral), F, H, W, d_anchor_frames, d_anchor_boxes, d_anchor_scores,
+                             C, T, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, true);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -4186,11 +4231,12 @@ int vdet_track_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
 // (volume_lists .. greedy_args, shared with vdet_nms_track_volume) and pick / lazy lists / eager pass, with
 // pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
 // ---------------------------------------------------------------------------------------------
-// vdet_track_volume_pixels (sc null) and vdet_track_volume_pixels_scaled
+// vdet_track_volume_pixels (sc null), vdet_track_volume_pixels_scaled and -- box: d_images is the integral uint32 [F,H+1,W+1], sc
+// is given -- vdet_track_volume_pixels_box
 static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
                                     int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
                                     double min_conf, int max_frames, int step, const PixScaleArgs *sc, float *d_tracks,
-                                    float *d_anchors, int32_t *d_ntracks)
+                                    float *d_anchors, int32_t *d_ntracks, bool box = false)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -4199,6 +4245,7 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
     int rc = check_volume(c, d_boxes, F, B, C);
     if (rc) return rc;
     if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
+    if (box && pix_box_check(c, H, W)) return VDET_EINVAL;
     if (C * (int64_t)std::max(max_tracks, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(max_tracks, 1) >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*max_tracks*F must stay below 2^31 - 16)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4218,7 +4265,9 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
         StageTimer tm(c, ST_TLOOP);
         for (int t = 0; t < max_tracks; ++t) {
             hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, g.la, g.lz, g.sp);
-            if (sc) hipLaunchKernelGGL(track_pixel_chain_scaled_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
+            if (box) hipLaunchKernelGGL(track_pixel_chain_box_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
+                                        (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            else if (sc) hipLaunchKernelGGL(track_pixel_chain_scaled_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
                                        (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
             else hipLaunchKernelGGL(track_pixel_chain_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa,
                                     (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
@@ -4247,6 +4296,16 @@ int vdet_track_volume_pixels_scaled(vdet_ctx *c, const uint8_t *d_images, int64_
     const PixScaleArgs sc{scales, scale_step, scale_penalty};
     return track_volume_pixels_impl(c, d_images, H, W, d_boxes, d_scores, F, B, C, nms_thres, thres, max_tracks, S, R, min_conf,
                                     max_frames, step, &sc, d_tracks, d_anchors, d_ntracks);
+}
+
+int vdet_track_volume_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_t H, int64_t W, const float *d_boxes,
+                                 const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                 int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales, int scale_step,
+                                 int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    return track_volume_pixels_impl(c, reinterpret_cast<const uint8_t *>(d_integral), H, W, d_boxes, d_scores, F, B, C, nms_thres, thres,
+                                    max_tracks, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, true);
 }
 
 }  // extern "C"

@@ -6,6 +6,8 @@ A c2-size video (300 frames x 10k boxes x 200 classes) cannot travel as protocol
 ``vdetlib_amd.vdet`` is built on.
 """
 import ctypes
+import functools
+import inspect
 import itertools
 import math
 
@@ -384,6 +386,42 @@ def _pixel_settings(grid, radius, min_conf, max_frames, step):
     return grid, radius, min_conf, max_frames, step
 
 
+def _pixel_sampling(sampling, integral, images, F, H, W):
+    """The checked ``sampling`` / ``integral`` pair of a pixel-tracker call: True for 'box'.  Layout checks only; the entry
+    point's ``_same_gpu`` takes the integral with the other tensors."""
+    if sampling not in ('point', 'box'):
+        raise ValueError("sampling = %r; 'point' or 'box'" % (sampling,))
+    if sampling == 'point':
+        if integral is not None:
+            raise ValueError("an integral is read by sampling='box' only")
+        return False
+    if H * W > 1 << 24:
+        raise ValueError("sampling='box': frames of at most 2^24 pixels, not %d x %d" % (H, W))
+    if integral is not None and (not torch.is_tensor(integral) or integral.dtype != torch.uint32 or
+                                 tuple(integral.shape) != (F, H + 1, W + 1) or not integral.is_contiguous()):
+        raise ValueError("integral must be uint32 [F,H+1,W+1] = [%d,%d,%d], contiguous (ops.luma_integral of the images)" % (F, H + 1, W + 1))
+    return True
+
+
+def luma_integral(images, sync=True, ctx=None):
+    """The integral image (summed-area table) of every frame's luma, the input of the pixel tracker's ``sampling='box'``
+    (include/vdet_hip.h: vdet_luma_integral; the rule is tests/pixtrack_box_spec.py): build it once per video and pass it as
+    ``integral=`` to as many tracker calls as read that video.
+
+    images uint8 [F,H,W,3], contiguous, H*W <= 2^24 -> uint32 [F,H+1,W+1] on the images' GPU:
+    out[f, y, x] = sum of L[f, r, c] over r < y, c < x with L = (29*c0 + 150*c1 + 77*c2 + 128) >> 8; row 0 and column 0 are
+    zero.  Exact.  Two launches, no host wait; 4/3 of the images' bytes.  ValueError for images of another layout or of more
+    than 2^24 pixels a frame (before any launch)."""
+    F, H, W = _images(images)
+    _pixel_sampling('box', None, images, F, H, W)
+    ctx = _ctx_for(images, ctx)
+    out = torch.empty((F, H + 1, W + 1), dtype=torch.uint32, device=images.device)
+    ctx.check(ctx.lib.vdet_luma_integral(ctx.h, images.data_ptr(), F, H, W, out.data_ptr()))
+    if sync:
+        ctx.sync()
+    return out
+
+
 def _track_outputs(C, T, F, device, early_stop, V=None):
     """The tracks / anchors / ntracks outputs of a tracker: [C,T,F,5] f32, [C,T,3] f32, [C] int32 -- with ``V`` in
     ``video_batch``'s layout: flat tracks, [V,C,T,3], [V,C].  ``early_stop``: the call may end before it has written every
@@ -686,6 +724,29 @@ def track_from_anchors(boxes, anchor_frames, anchor_boxes, anchor_scores=None, l
     return tracks, anchors, ntracks
 
 
+def _box_option(impl):
+    """Gives a pixel-tracker call the two KEYWORD-ONLY options of box sampling, ``sampling='point'`` and ``integral=None``,
+    behind its own parameters, whose names, order and defaults stay what they were (``inspect.signature`` reports those: it
+    follows ``__wrapped__``; the two options are in the call's docstring).  With both at their defaults the decorated call runs
+    as it is written; otherwise its bound arguments go to ``impl()(scale, ..., sampling=, integral=)``, the function the call
+    itself ends in, with scale = (scales, scale_step, scale_penalty) where the call has them, else None."""
+    def decorate(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(*args, sampling='point', integral=None, **kw):
+            if sampling == 'point' and integral is None:
+                return fn(*args, **kw)
+            bound = sig.bind(*args, **kw)
+            bound.apply_defaults()
+            a = dict(bound.arguments)
+            scale = (a.pop('scales'), a.pop('scale_step'), a.pop('scale_penalty')) if 'scales' in a else None
+            return impl()(scale, sampling=sampling, integral=integral, **a)
+        return call
+    return decorate
+
+
+@_box_option(lambda: _track_pixels)
 def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
                  sync=True, ctx=None):
     """Tubelets that follow the PIXELS of the anchor boxes (include/vdet_hip.h: vdet_track_pixels; the rule is
@@ -703,7 +764,15 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
       anchors [C,T,3] f32 (frame, -1, score or 0),  ntracks [C] int32 = 1 + the last live slot of the class.
     ValueError for grid not a multiple of 4 in 4..64, radius outside 1..16, step < 1, max_frames < 0 or a min_conf that is not
     finite (before any launch); and for an anchor frame outside 0..F or an anchor box that is not finite, beyond 2^20, empty or
-    wholly outside the image (reported when the call, or a later ``ctx.sync()``, waits; the slot is written as an empty one)."""
+    wholly outside the image (reported when the call, or a later ``ctx.sync()``, waits; the slot is written as an empty one).
+
+    Keyword-only: ``sampling='box'`` (the rule is tests/pixtrack_box_spec.py; vdet_track_pixels_box): a cell's value is the rounded mean of
+    the pixels of its ``w/grid`` x ``h/grid`` rectangle instead of the one pixel at its centre, so detail finer than the pitch
+    is averaged, not aliased, and motion below the pitch is followed.  The means come from ``integral``, the frames'
+    ``luma_integral`` (uint32 [F,H+1,W+1], contiguous, on the images' GPU): given, the images are read for their shape only;
+    None, the call builds one (two more launches).  Frames of at most 2^24 pixels.  With w == h == grid the bits are
+    ``sampling='point'``'s.  ValueError (before any launch) for another ``sampling``, an integral of the wrong dtype, shape or
+    device, an integral given with 'point', and H*W > 2^24 with 'box'."""
     return _track_pixels(None, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx)
 
 
@@ -719,20 +788,28 @@ def _scale_settings(scales, scale_step, scale_penalty):
     return scales, scale_step, scale_penalty
 
 
-def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx):
-    """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
+def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx,
+                  sampling='point', integral=None):
+    """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty)); with sampling='box'
+    both are vdet_track_pixels_box (scale None: scales = 0)"""
     F, H, W = _images(images)
+    box = _pixel_sampling(sampling, integral, images, F, H, W)
     anchor_frames, anchor_boxes, anchor_scores, C, T = _anchor_slots(anchor_frames, anchor_boxes, anchor_scores)
     settings = _pixel_settings(grid, radius, min_conf, max_frames, step)
     if scale is not None:
         scale = _scale_settings(*scale)
-    _same_gpu((images, anchor_frames, anchor_boxes, anchor_scores), "images, anchor_frames, anchor_boxes and anchor_scores")
+    _same_gpu((images, anchor_frames, anchor_boxes, anchor_scores, integral),
+              "images, anchor_frames, anchor_boxes, anchor_scores and integral")
     ctx = _ctx_for(images, ctx)
+    if box and integral is None:
+        integral = luma_integral(images, sync=False, ctx=ctx)
     tracks, anchors, ntracks = _track_outputs(C, T, F, images.device, False)
-    head = (ctx.h, images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+    head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
             anchor_scores.data_ptr() if anchor_scores is not None else None, C, T) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    if scale is None:
+    if box:
+        ctx.check(ctx.lib.vdet_track_pixels_box(*(head + (scale or (0, 1, 0)) + out)))
+    elif scale is None:
         ctx.check(ctx.lib.vdet_track_pixels(*(head + out)))
     else:
         ctx.check(ctx.lib.vdet_track_pixels_scaled(*(head + scale + out)))
@@ -741,6 +818,7 @@ def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, gri
     return tracks, anchors, ntracks
 
 
+@_box_option(lambda: _track_pixels)
 def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
                         scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
     """``track_pixels`` with a scale search: the tubelet's box grows and shrinks with the object (include/vdet_hip.h:
@@ -750,11 +828,13 @@ def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None,
     anchor's fixed template; the smallest (SAD + level * ``scale_penalty``, level, shift) wins, the confidence is the winner's
     raw SAD's, and the winner's box, moved, is the next box.  A level whose box would have a side below 1 or above 2^21 is
     skipped.  ``scales = 0`` gives ``track_pixels``' bits.  Arguments, layouts and errors are ``track_pixels``'; in addition
-    ValueError for scales outside 0..3, scale_step outside 1..25 or scale_penalty outside 0..65535 (before any launch)."""
+    ValueError for scales outside 0..3, scale_step outside 1..25 or scale_penalty outside 0..65535 (before any launch).
+    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``; every level's cells are box-filtered."""
     return _track_pixels((scales, scale_step, scale_penalty), images, anchor_frames, anchor_boxes, anchor_scores, grid, radius,
                          min_conf, max_frames, step, sync, ctx)
 
 
+@_box_option(lambda: _track_volume_pixels)
 def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
                         max_frames=0, step=1, sync=True, ctx=None):
     """Greedy tubelet generation for EVERY class of a video with the pixel tracker as ``track_method``: the array form of
@@ -771,28 +851,35 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
     ``tracks_to_proto(..., method='pixel_tracker')`` turns one class of the result into a .track dict.
     ValueError for the arguments ``track_volume`` and ``track_pixels`` refuse (before any launch); and for an anchor whose box
     is not finite, beyond 2^20, empty after truncation or wholly outside the image (reported when the call, or a later
-    ``ctx.sync()``, waits): its slot is taken with NaN rows, it suppresses nothing, and the loop goes on."""
+    ``ctx.sync()``, waits): its slot is taken with NaN rows, it suppresses nothing, and the loop goes on.
+    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels`` (include/vdet_hip.h: vdet_track_volume_pixels_box)."""
     return _track_volume_pixels(None, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step,
                                 sync, ctx)
 
 
 def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step, sync,
-                         ctx):
-    """track_volume_pixels (scale None) and track_volume_pixels_scaled (scale = (scales, scale_step, scale_penalty))"""
+                         ctx, sampling='point', integral=None):
+    """track_volume_pixels (scale None) and track_volume_pixels_scaled (scale = (scales, scale_step, scale_penalty)); with
+    sampling='box' both are vdet_track_volume_pixels_box (scale None: scales = 0)"""
     F, H, W = _images(images)
+    box = _pixel_sampling(sampling, integral, images, F, H, W)
     max_tracks = int(max_tracks)
     if max_tracks < 0:
         raise ValueError("max_tracks must be >= 0")
     settings = _pixel_settings(grid, radius, min_conf, max_frames, step)
     if scale is not None:
         scale = _scale_settings(*scale)
-    boxes, scores, F, B, C = _volume(boxes, scores, (images,), "images, boxes and scores", F=F, nonempty=True)
+    boxes, scores, F, B, C = _volume(boxes, scores, (images, integral), "images, integral, boxes and scores", F=F, nonempty=True)
     ctx = _ctx_for(images, ctx)
+    if box and integral is None:
+        integral = luma_integral(images, sync=False, ctx=ctx)
     tracks, anchors, ntracks = _track_outputs(C, max_tracks, F, images.device, True)
-    head = (ctx.h, images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres),
+    head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres),
             max_tracks) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    if scale is None:
+    if box:
+        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels_box(*(head + (scale or (0, 1, 0)) + out)))
+    elif scale is None:
         call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(*(head + out)))
     else:
         call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels_scaled(*(head + scale + out)))
@@ -800,13 +887,14 @@ def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tra
     return tracks, anchors, ntracks
 
 
+@_box_option(lambda: _track_volume_pixels)
 def track_volume_pixels_scaled(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
                                max_frames=0, step=1, scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
     """``track_volume_pixels`` with ``track_pixels_scaled``'s chain as the tracker: the tubelet that suppresses the detections it
     explains has a box that follows the object's size (include/vdet_hip.h: vdet_track_volume_pixels_scaled; the rule is the
     greedy loop of tests/pixtrack_scale_spec.py).  ``scales = 0`` gives ``track_volume_pixels``' bits.  Arguments, layouts,
     launches and errors are ``track_volume_pixels``'; in addition ValueError for scales outside 0..3, scale_step outside 1..25
-    or scale_penalty outside 0..65535 (before any launch)."""
+    or scale_penalty outside 0..65535 (before any launch).  Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``."""
     return _track_volume_pixels((scales, scale_step, scale_penalty), images, boxes, scores, nms_thres, thres, max_tracks, grid,
                                 radius, min_conf, max_frames, step, sync, ctx)
 

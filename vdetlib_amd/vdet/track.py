@@ -48,12 +48,24 @@ def _pixel_frames(vid_proto):
     return images
 
 
+def _pixel_integral(images):
+    """ops.luma_integral of the cached video's frames, made once per video (it lives and dies with ``_pixel_video``'s entry)."""
+    from .. import ops
+    key = ('integral', id(images))
+    integral = _pixel_video.get(key)
+    if integral is None:
+        integral = _pixel_video[key] = ops.luma_integral(images)
+    return integral
+
+
 def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     """A ``track_method`` that follows the pixels of ``bbox`` forward and backward from ``anchor_frame_id`` on the GPU
     (ops.track_pixels, one call with C = T = 1).  Reads ``opts.step`` and ``opts.max_frames`` as fcn_tracker does (:64-71),
     and the optional ``opts.grid`` / ``opts.radius`` / ``opts.min_conf``.  With ``opts.scales`` > 0 the box follows the object's
     size (ops.track_pixels_scaled, with the optional ``opts.scale_step`` / ``opts.scale_penalty``); absent or 0: the fixed-scale
-    call, unchanged.  The frames are uploaded once per video (a module
+    call, unchanged.  ``opts.sampling`` = 'box' box-filters every cell (ops.track_pixels' ``sampling``; the video's integral
+    image is built once and kept beside its frames); absent or 'point': point sampling, unchanged.  The frames are uploaded once
+    per video (a module
     cache keyed by the video's name and frame count).  Returns ``tracks_proto_from_boxes`` over the visited frames only, with
     fcn_tracker's ``start_frame`` and ``step`` (:100-102)."""
     import torch
@@ -70,6 +82,9 @@ def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     else:
         track = ops.track_pixels_scaled
         scale = dict(scales=scales, scale_step=getattr(opts, 'scale_step', 5), scale_penalty=getattr(opts, 'scale_penalty', 0))
+    sampling = getattr(opts, 'sampling', None)
+    if sampling is not None and sampling != 'point':
+        scale = dict(scale, sampling=sampling, integral=_pixel_integral(images) if sampling == 'box' else None)
     tracks, _, _ = track(
         images, torch.tensor([[pos + 1]], dtype=torch.int32, device=dev),
         torch.tensor([[[float(v) for v in bbox]]], dtype=torch.float32, device=dev), None,
