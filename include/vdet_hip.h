@@ -1076,7 +1076,7 @@ int vdet_track_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t
                       int max_frames, int step, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 /* ---- greedy tubelet generation with the pixel tracker: greedily_track_from_raw_dets (vdet/track.py:189-252) for every class of
- *      a video with vdet_track_pixels' chain as track_method.  The rule is tests/greedy_pixel_spec.py -----------------------
+ *      a video with vdet_track_pixels' chain as track_method.  The rule is tests/pixtrack_spec.py's greedy loop --------------
  *
  * d_images uint8 [F,H,W,3]; d_boxes [F,B,4] f32 (16-byte aligned), d_scores [F,B,C] f32 as vdet_track_volume.  Per class, up to
  * max_tracks times: the best remaining detection after the monotone cursor is the anchor (stable descending order of the
@@ -1100,7 +1100,7 @@ int vdet_track_volume_pixels(vdet_ctx *ctx, const uint8_t *d_images, int64_t H, 
                              float *d_anchors, int32_t *d_ntracks);
 
 /* ---- the pixel tracker with a scale search: tubelet boxes that grow and shrink with the object.  The rule is
- *      tests/pixtrack_scale_spec.py; everything it does not restate is vdet_track_pixels' (vdet_track_volume_pixels') --------
+ *      tests/pixtrack_spec.py's scale search; everything it does not restate is vdet_track_pixels' (vdet_track_volume_pixels')
  *
  * scales = ns levels each side (0 .. 3), scale_step = p percent per level (1 .. 25), scale_penalty = q SAD units per level
  * (0 .. 65535).  Per step f -> g with the current box b = (x1,y1,x2,y2), w = x2-x1+1, h = y2-y1+1:
@@ -1129,7 +1129,7 @@ int vdet_track_volume_pixels_scaled(vdet_ctx *ctx, const uint8_t *d_images, int6
                                     int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 /* ---- box-filter sampling for the pixel tracker, from an integral image of the luma that the caller builds once per video and
- *      reuses.  The rule is tests/pixtrack_box_spec.py; everything it does not restate is the point-sampling calls' ------------
+ *      reuses.  The rule is tests/pixtrack_spec.py's box sampling; everything it does not restate is the point-sampling calls'
  *
  * vdet_luma_integral: d_images uint8 [F,H,W,3] -> d_integral uint32 [F,H+1,W+1],
  *   I[f, y, x] = sum of L[f, r, c] over r < y, c < x  (L: vdet_track_pixels' luma; row 0 and column 0 are zero).

@@ -102,7 +102,7 @@ _cache = {}
 def main_case():
     """the main case and the spec's result on it, computed once and shared (do not modify)"""
     if 'main' not in _cache:
-        import greedy_pixel_spec as gs
+        import pixtrack_spec as px
         case = two_objects(4100)
-        _cache['main'] = (case, gs.track_volume_pixels(case[0], case[1], case[2], **MAIN))
+        _cache['main'] = (case, px.track_volume_pixels(case[0], case[1], case[2], **MAIN))
     return _cache['main']

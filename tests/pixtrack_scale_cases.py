@@ -6,6 +6,8 @@ fixed to the image.  F = 12 frames of 200 x 240.  Frame f: half-side hs(f), cent
 columns cx-hs .. cx+hs-1, rows cy-hs .. cy+hs-1 (0-based), side 2 hs."""
 import numpy as np
 
+import pixtrack_cases as pc
+
 F, H, W = 12, 200, 240
 S, R = 32, 8
 KINDS = {'grow': lambda f: 20 + f, 'shrink': lambda f: 32 - f, 'const': lambda f: 24}
@@ -79,20 +81,18 @@ def largest_error(rows, truth):
 # ---------------------------------------------------------------------------------------------------------------------
 # the mixed [3,5] slot table: one video per (grid, radius), every kind of slot in one call
 # ---------------------------------------------------------------------------------------------------------------------
-LEAVES = 3                # the leaver's chain ends on this frame (test_pixel_track_gpu.py's LEAVER construction)
+LEAVES = pc.LEAVES        # the leaver's chain ends on this frame (pixtrack_cases' LEAVER construction)
 MIXED_AT = {'grow': (30, 40), 'shrink': (130, 40), 'const': (60, 140)}      # (cx0, cy0): the three objects never overlap
 _mixed = {}
 
 
 def mixed_case(S, R):
     """12 frames of 200 x 240, smooth background, with (1) the growing, the shrinking and the constant object of the planted
-    scene at MIXED_AT, (2) a 37 x 53 white-noise object that moves (2, 2) pixels a frame, (3) on the right a strip for the box
-    that leaves the image: vertical stripes on frames 0 .. LEAVES-1, from frame LEAVES on only row 0 keeps them and the rows
-    below are noise, so that the window of dy = -R -- all of it the replicated row 0 -- is the only one with SAD 0.
+    scene at MIXED_AT, (2) a 37 x 53 white-noise object that moves (2, 2) pixels a frame, (3) on the right pixtrack_cases'
+    strip for the box that leaves the image (see LEAVER there).
     -> (images, anchor_frames [3,5], anchor_boxes [3,5,4], anchor_scores [3,5], truth {kind: [F,4]})"""
     if (S, R) not in _mixed:
         rng = np.random.RandomState(5300 + S)
-        sw = S // 2 + R + 4
         planes = np.repeat(background(5301)[None], F, axis=0)
         truth = {}
         for k, kind in enumerate(('grow', 'shrink', 'const')):
@@ -104,12 +104,7 @@ def mixed_case(S, R):
         tex = rng.randint(0, 256, size=(53, 37, 3)).astype(np.uint8)
         for f in range(F):
             images[f, 100 + 2 * f:153 + 2 * f, 118 + 2 * f:155 + 2 * f] = tex
-        strip = rng.randint(0, 256, size=(F, H, sw, 3)).astype(np.uint8)
-        stripes = rng.randint(0, 256, size=(sw, 3)).astype(np.uint8)
-        strip[:LEAVES] = stripes
-        strip[LEAVES:, 0] = stripes
-        images[:, :, W - sw:] = strip
-        x3 = W - sw + R // 2 + 2
+        images[:, :, W - pc.strip_width(S, R):] = pc.leaver_strip(rng, F, H, S, R)
         fr = np.array([[0, 1, F, 6, 0],
                        [4, 3, 5, 7, 9],
                        [1, 11, 2, 0, 0]], np.int32)
@@ -123,7 +118,7 @@ def mixed_case(S, R):
         bx[1, 2] = [100, 95, 101, 96]                                          # 2 x 2: levels collapse or are skipped
         bx[1, 3] = [-30.5, -25, 25, 40.25]                                     # over the left and the top edge, negative
         bx[1, 4] = [150, -15, 185.75, 30]                                      # the top
-        bx[2, 0] = [x3 + 1, 2 * R - 2 * S + 1, x3 + S // 2, 2 * R]             # the leaver, anchored on frame 1
+        bx[2, 0] = pc.leaver_box(W, S, R)                                      # the leaver, anchored on frame 1
         bx[2, 1] = [80, 170, 130, 230]                                         # the bottom
         bx[2, 2] = [W - 20, 80, W + 25.5, 140]                                 # the right
         sc = rng.rand(3, 5).astype(np.float32)
@@ -196,9 +191,8 @@ def greedy_case():
 def greedy_specs():
     """the scaled and the fixed-scale spec's results on greedy_case(), computed once and shared (do not modify)"""
     if 'specs' not in _greedy:
-        import greedy_pixel_spec as gs
-        import pixtrack_scale_spec as ps
+        import pixtrack_spec as px
         images, boxes, scores, _ = greedy_case()
-        _greedy['specs'] = (ps.track_volume_pixels(images, boxes, scores, scales=1, scale_step=5, scale_penalty=0, **GREEDY),
-                            gs.track_volume_pixels(images, boxes, scores, **GREEDY))
+        _greedy['specs'] = (px.track_volume_pixels(images, boxes, scores, scales=1, scale_step=5, scale_penalty=0, **GREEDY),
+                            px.track_volume_pixels(images, boxes, scores, **GREEDY))
     return _greedy['specs']

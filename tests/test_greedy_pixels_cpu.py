@@ -1,4 +1,4 @@
-"""No GPU: tests/greedy_pixel_spec.py, the rule of ops.track_volume_pixels, against the design of the seeded case -- so that
+"""No GPU: the greedy loop of tests/pixtrack_spec.py, the rule of ops.track_volume_pixels, against the design of the seeded case -- so that
 the device's comparison with the spec (test_greedy_pixels_gpu.py) cannot be vacuous -- and the symbol's declaration."""
 import numpy as np
 
@@ -52,12 +52,12 @@ def test_spec_on_the_main_case():
 
 
 def test_spec_takes_a_slot_for_an_untrackable_anchor():
-    import greedy_pixel_spec as gs
+    import pixtrack_spec as px
     (images, boxes, scores, posa, posb), want = gc.main_case()
     boxes, scores = boxes.copy(), scores.copy()
     boxes[7, gc.IDIS[0]] = [10, 10, 9.5, 30]                   # empty after truncation
     scores[7, gc.IDIS[0], 0] = 2.0
-    tracks, anchors, ntracks, bad = gs.track_volume_pixels(images, boxes, scores, **gc.MAIN)
+    tracks, anchors, ntracks, bad = px.track_volume_pixels(images, boxes, scores, **gc.MAIN)
     assert bad and ntracks.tolist() == [3, 1]
     assert np.isnan(tracks[0, 0]).all() and anchors[0, 0].tolist() == [8, gc.IDIS[0], 2.0]
     # it suppresses nothing: the next two slots are the main case's first two

@@ -1,5 +1,5 @@
 """-m gpu: greedy tubelet generation with the pixel tracker on the device (ops.track_volume_pixels; csrc/pixtrack_kernels.hpp,
-track_kernels.hpp) against tests/greedy_pixel_spec.py ON BITS: equal NaN masks, every other element the same bit pattern.
+track_kernels.hpp) against tests/pixtrack_spec.py (its greedy loop) ON BITS: equal NaN masks, every other element the same bit pattern.
   a. the main case;  b. the dict-level host loop with vdet.track.pixel_tracker on the same inputs;  c. step and max_frames;
   d. min_conf with a vanishing object;  e. against the anchor route (top_anchors + track_pixels): no duplicates;
   f. lazy and eager list maintenance;  g. an irregular frame (the eager pass under the default switches);
@@ -8,44 +8,11 @@ import numpy as np
 import pytest
 
 import greedy_pixel_cases as gc
-import greedy_pixel_spec as gs
 import pixtrack_cases as pc
+import pixtrack_spec as px
+from pixtrack_harness import assert_greedy_spec as assert_spec, assert_same, bits_equal, g, greedy_device as device, host
 
 pytestmark = pytest.mark.gpu
-
-
-def g(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits_equal(got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return False
-    if got.dtype.kind != 'f':
-        return np.array_equal(got, want)
-    nan = np.isnan(want)
-    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(u)[~nan], want.view(u)[~nan])
-
-
-def device(images, boxes, scores, **kw):
-    from vdetlib_amd import ops
-    return tuple(x.cpu().numpy() for x in ops.track_volume_pixels(g(images), g(boxes), g(scores), **kw))
-
-
-def assert_same(got, want):
-    for k, name in enumerate(('tracks', 'anchors', 'ntracks')):
-        assert bits_equal(got[k], want[k]), name
-
-
-def assert_spec(images, boxes, scores, ctx=None, **kw):
-    """device == spec on bits; returns the spec's outputs"""
-    want = gs.track_volume_pixels(images, boxes, scores, **kw)
-    assert not want[3]
-    assert_same(device(images, boxes, scores, ctx=ctx, **kw), want)
-    return want
 
 
 # a. -------------------------------------------------------------------------------------------------------------------
@@ -78,10 +45,10 @@ def test_dict_level_loop_gives_the_same_tubelets():
     try:
         track.imread = lambda path: images[int(path.split('/')[-1].split('.')[0])]
         for c in range(gc.C):
-            host = track.greedily_track_from_raw_dets(vid, det_info, track.pixel_tracker, c + 1, opts)
+            hostp = track.greedily_track_from_raw_dets(vid, det_info, track.pixel_tracker, c + 1, opts)
             mine = ops.tracks_to_proto('pixvid', tracks[c], anchors[c], ntracks[c], method='pixel_tracker')
-            assert host['method'] == mine['method'] == 'pixel_tracker'
-            assert len(host['tracks']) == int(ntracks[c]) and view(host) == view(mine), c
+            assert hostp['method'] == mine['method'] == 'pixel_tracker'
+            assert len(hostp['tracks']) == int(ntracks[c]) and view(hostp) == view(mine), c
     finally:
         track.imread = saved
         track._pixel_video.clear()
@@ -179,7 +146,7 @@ def test_untrackable_anchor_takes_its_slot_and_is_latched():
     boxes, scores = boxes.copy(), scores.copy()
     boxes[7, gc.IDIS[0]] = [10, 10, 9.5, 30]           # empty after truncation
     scores[7, gc.IDIS[0], 0] = 2.0                     # the best of class 0
-    want = gs.track_volume_pixels(images, boxes, scores, **gc.MAIN)
+    want = px.track_volume_pixels(images, boxes, scores, **gc.MAIN)
     assert want[3] and np.isnan(want[0][0, 0]).all() and want[1][0, 0].tolist() == [8, gc.IDIS[0], 2.0]
     assert np.array_equal(want[0][0, 1:], main[0][0, :2])          # it suppressed nothing
     ti, tb, ts = g(images), g(boxes), g(scores)
@@ -190,7 +157,7 @@ def test_untrackable_anchor_takes_its_slot_and_is_latched():
         out = ops.track_volume_pixels(ti, tb, ts, sync=False, ctx=cx, **gc.MAIN)
         with pytest.raises(ValueError):
             cx.sync()
-        assert_same(tuple(x.cpu().numpy() for x in out), want)
+        assert_same(host(out), want)
         cx.sync()                                      # the latch is cleared
     finally:
         cx.close()
@@ -242,7 +209,7 @@ def test_argument_errors_before_any_launch():
                    dict(H=32768)):
             assert call(**kw) == _lib.VDET_EINVAL, kw
         assert sum(n for _, n in cx.last_timing().values()) == 0, "an argument error launched a kernel"
-        assert_same(tuple(x.cpu().numpy() for x in run()), want)       # the context still works
+        assert_same(host(run()), want)       # the context still works
     finally:
         cx.close()
 

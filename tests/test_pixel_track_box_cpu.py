@@ -1,4 +1,4 @@
-"""CPU: tests/pixtrack_box_spec.py, the rule of ``sampling='box'``, against hand-written values, against the point rule where
+"""CPU: ``sampling='box'`` of the rule (tests/pixtrack_spec.py) against hand-written values, against the point rule where
 the two must agree, and on the videos the point rule loses (tests/pixtrack_box_cases.py).  The device is compared with this
 spec on bits in test_pixel_track_box_gpu.py."""
 import math
@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 import pixtrack_box_cases as bc
-import pixtrack_box_spec as bs
-import pixtrack_scale_spec as ps
 import pixtrack_spec as px
+
+BOX = dict(sampling='box')
 
 
 # a. -------------------------------------------------------------------------------------------------------------------
@@ -17,7 +17,7 @@ def test_integral_against_a_double_loop():
     rng = np.random.RandomState(7600)
     images = rng.randint(0, 256, size=(2, 5, 7, 3)).astype(np.uint8)
     L = px.luma(images)
-    I = bs.luma_integral(images)
+    I = px.luma_integral(images)
     assert I.dtype == np.uint32 and I.shape == (2, 6, 8)
     for f in range(2):
         for y in range(6):
@@ -25,12 +25,12 @@ def test_integral_against_a_double_loop():
                 want = sum(int(L[f, r, c]) for r in range(y) for c in range(x))
                 assert int(I[f, y, x]) == want, (f, y, x)
     assert not I[:, 0].any() and not I[:, :, 0].any()
-    full = bs.integral(np.full((1, 4096, 4096), 255, np.uint8))
+    full = px.integral(np.full((1, 4096, 4096), 255, np.uint8))
     assert int(full[0, -1, -1]) == 255 << 24            # the largest entry the rule allows: it fits
 
 
 def edges(o, e, S, k, N):
-    a, b = bs.cell_edges(o, e, S, k, N)
+    a, b = px.cell_edges(o, e, S, k, N)
     return int(a), int(b)
 
 
@@ -56,16 +56,16 @@ def test_cell_edges_by_hand():
     # the same function serves rows: limit H
     assert edges(-6, 16, 4, 0, 30) == (0, 1) and edges(-6, 16, 4, 1, 30) == (0, 2) and edges(20, 16, 4, 2, 30) == (28, 30)
     # arrays of k
-    a, b = bs.cell_edges(10, 20, 8, np.arange(-5, 3), 100)
+    a, b = px.cell_edges(10, 20, 8, np.arange(-5, 3), 100)
     assert a.tolist() == [0, 0, 2, 5, 7, 10, 12, 15] and b.tolist() == [1, 2, 5, 7, 10, 12, 15, 17]
 
 
 def test_cell_value_is_the_rounded_mean():
     rng = np.random.RandomState(7601)
     L = rng.randint(0, 256, size=(1, 30, 40)).astype(np.uint8)
-    I = bs.integral(L)[0]
+    I = px.integral(L)[0]
     box = (-7, 4, 51, 28)              # 59 x 25 under side 4: cells of 14-15 x 6-7 pixels, over the left and the right border
-    got = bs.sample(I, box, 4, -1, 5)
+    got = px.sample_box(I, box, 4, -1, 5)
     for i, k in enumerate(range(-1, 5)):
         ra, rb = edges(4, 25, 4, k, 30)
         for j, m in enumerate(range(-1, 5)):
@@ -84,7 +84,7 @@ def test_sub_cell_motion(seed, w, h):
     fr, bx = bc.anchor_of(pos, w, h)
     moves = np.diff(pos, axis=0)
     assert np.abs(moves).max() <= 3 and np.abs(moves).min() >= 1 and w / float(bc.S) > 3 and h / float(bc.S) > 3
-    box = bs.track_pixels(images, fr, bx, None, **bc.KW)[0][0, 0]
+    box = px.track_pixels(images, fr, bx, None, **BOX, **bc.KW)[0][0, 0]
     point = px.track_pixels(images, fr, bx, None, **bc.KW)[0][0, 0]
     ex, ey = bc.errors(box, pos)
     print("seed %d %dx%d box: max |dx| %g |dy| %g conf >= %.4f" % (seed, w, h, ex.max(), ey.max(), box[:, 4].min()))
@@ -97,7 +97,7 @@ def test_sub_cell_motion(seed, w, h):
 
 # c. -------------------------------------------------------------------------------------------------------------------
 def test_one_pixel_cells_are_the_point_rule():
-    """w == h == S: a cell is a pixel, so the box spec returns the point spec's bits -- on chains that touch every image edge:
+    """w == h == S: a cell is a pixel, so the box sampler gives the point sampler's bits -- on chains that touch every image edge:
     the anchors sit in the four corners and on the four sides, partly outside, and the region (R cells around the box) reads
     beyond each edge from the first step on."""
     rng = np.random.RandomState(7602)
@@ -109,7 +109,7 @@ def test_one_pixel_cells_are_the_point_rule():
     bx = np.array([boxes], np.float32)
     for kw in (dict(min_conf=0.0), dict(min_conf=0.0, step=2), dict()):
         want = px.track_pixels(images, fr, bx, None, S, R, **kw)
-        got = bs.track_pixels(images, fr, bx, None, S, R, **kw)
+        got = px.track_pixels(images, fr, bx, None, S, R, **BOX, **kw)
         assert not want[3] and not got[3]
         for a, b in zip(got[:3], want[:3]):
             assert a.dtype == b.dtype and np.array_equal(a.view(np.uint32) if a.dtype == np.float32 else a,
@@ -117,27 +117,26 @@ def test_one_pixel_cells_are_the_point_rule():
     live = np.isfinite(want[0][0, :, :, 0])
     assert live.sum(axis=1).min() >= 2                  # every chain walks
     # the sample itself, cell by cell, far outside included
-    I = bs.luma_integral(images)
+    I = px.luma_integral(images)
     L = px.luma(images)
     for b in ((-3, -3, 4, 4), (W - 5, H - 5, W + 2, H + 2), (-40, 5, -33, 12), (W + 9, H + 9, W + 16, H + 16)):
-        assert np.array_equal(bs.sample(I[0], b, S, -R, S + R), px.sample(L[0], b, S, -R, S + R))
+        assert np.array_equal(px.sample_box(I[0], b, S, -R, S + R), px.sample(L[0], b, S, -R, S + R))
 
 
 def test_scale_search_and_greedy_loop_run_the_box_chain():
-    """scales > 0 and the greedy form go through pixtrack_scale_spec's loops with the box chain as the tracker; with one-pixel
-    cells and scales = 0 the greedy loop is greedy_pixel_spec's on bits"""
+    """scales > 0 and the greedy form run the one walk on the integral; a point walk after it is a point walk still (the
+    sampling is the call's, not the module's); with one-pixel cells and scales = 0 the greedy loop is the point loop on bits"""
     import greedy_pixel_cases as gc
-    import greedy_pixel_spec as gs
     images, pos = bc.sub_cell_video(bc.SEEDS[0], 40, 40)
     fr, bx = bc.anchor_of(pos, 40, 40)
     lumas = px.luma(images)
-    rows = bs.track_pixels(images, fr, bx, None, scales=1, scale_step=5, **bc.KW)[0][0, 0]
-    assert np.isfinite(rows).all() and ps.track_slot(lumas, 1, (0, 0, 7, 7), 8, 3).shape == rows.shape        # (the name is restored)
+    rows = px.track_pixels(images, fr, bx, None, scales=1, scale_step=5, **BOX, **bc.KW)[0][0, 0]
+    assert np.isfinite(rows).all() and px.track_slot(lumas, 1, (0, 0, 7, 7), 8, 3).shape == rows.shape
     (images, boxes, scores, _, _), _ = gc.main_case()
     sq = boxes.copy()                                   # every proposal made 8 x 8: one pixel per cell
     sq[..., 2], sq[..., 3] = sq[..., 0] + 7, sq[..., 1] + 7
-    want = gs.track_volume_pixels(images, sq, scores, **gc.MAIN)
-    got = bs.track_volume_pixels(images, sq, scores, **gc.MAIN)
+    want = px.track_volume_pixels(images, sq, scores, **gc.MAIN)
+    got = px.track_volume_pixels(images, sq, scores, **BOX, **gc.MAIN)
     for a, b in zip(got[:3], want[:3]):
         assert np.array_equal(a, b, equal_nan=True)
     assert int(want[2].sum()) >= 2

@@ -1,6 +1,6 @@
 """-m gpu: box-filter sampling for the pixel tracker on the device (ops.luma_integral; ``sampling='box'`` of ops.track_pixels,
 track_pixels_scaled, track_volume_pixels, track_volume_pixels_scaled and of vdet.track.pixel_tracker;
-csrc/pixtrack_kernels.hpp) against tests/pixtrack_box_spec.py ON BITS: the NaN masks are equal and every other element has
+csrc/pixtrack_kernels.hpp) against tests/pixtrack_spec.py (``sampling='box'``) ON BITS: the NaN masks are equal and every other element has
 the same bit pattern.
   a. luma_integral;  b. the mixed [3,5] slot table, four (grid, radius) pairs x four scale settings;  c. where box sampling is
   point sampling, and the degenerate cells;  d. ties, step and max_frames, the defaults;  e. the ``integral=`` argument;
@@ -9,53 +9,19 @@ the same bit pattern.
 import numpy as np
 import pytest
 
+import functools
+
 import pixtrack_box_cases as bc
-import pixtrack_box_spec as bs
+import pixtrack_harness as ph
 import pixtrack_scale_cases as sc
 import pixtrack_spec as px
+from pixtrack_harness import assert_same, bits_equal, g, host
 
 pytestmark = pytest.mark.gpu
 
-
-def g(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits_equal(got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return False
-    if got.dtype.kind != 'f':
-        return np.array_equal(got, want)
-    nan = np.isnan(want)
-    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(u)[~nan], want.view(u)[~nan])
-
-
-def host(out):
-    return tuple(x.cpu().numpy() for x in out)
-
-
-def device(images, fr, bx, scr=None, **kw):
-    """sampling='box': ops.track_pixels without ``scales``, ops.track_pixels_scaled with"""
-    from vdetlib_amd import ops
-    fn = ops.track_pixels_scaled if 'scales' in kw else ops.track_pixels
-    return host(fn(g(images), g(fr), g(bx), None if scr is None else g(scr), sampling='box', **kw))
-
-
-def assert_same(got, want):
-    for k, name in enumerate(('tracks', 'anchors', 'ntracks')):
-        assert bits_equal(got[k], want[k]), name
-
-
-def assert_spec(images, fr, bx, scr=None, **kw):
-    """device == spec on bits; returns the spec's outputs"""
-    want = bs.track_pixels(images, fr, bx, scr, **kw)
-    assert not want[3]
-    assert_same(device(images, fr, bx, scr, **kw), want)
-    return want
-
+BOX = dict(sampling='box')
+device = functools.partial(ph.device, **BOX)                # ops.track_pixels without ``scales``, ops.track_pixels_scaled with
+assert_spec = functools.partial(ph.assert_spec, **BOX)      # device == spec on bits; returns the spec's outputs
 
 # a. -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", ((1, 1, 1), (2, 3, 5), (3, 37, 259), (2, 130, 64)))
@@ -66,7 +32,7 @@ def test_luma_integral(shape):
     from vdetlib_amd import _lib, ops
     F, H, W = shape
     images = np.random.RandomState(7800 + W).randint(0, 256, size=(F, H, W, 3)).astype(np.uint8)
-    want = bs.luma_integral(images)
+    want = px.luma_integral(images)
     ti = g(images)
     out = ops.luma_integral(ti)
     assert out.dtype == torch.uint32 and tuple(out.shape) == (F, H + 1, W + 1) and out.is_contiguous() and out.device == ti.device
@@ -133,7 +99,7 @@ def test_one_pixel_cells_give_the_point_calls_bits():
         point = host(ops.track_pixels(ti, tf, tb, grid=S, radius=R, **kw))
         assert_same(host(ops.track_pixels(ti, tf, tb, grid=S, radius=R, sampling='box', **kw)), point)
         assert_same(host(ops.track_pixels_scaled(ti, tf, tb, grid=S, radius=R, scales=0, sampling='box', **kw)), point)
-        assert_same(point, bs.track_pixels(images, fr, bx, None, S, R, **kw))
+        assert_same(point, px.track_pixels(images, fr, bx, None, S, R, **BOX, **kw))
     assert np.isfinite(point[0][0, :, :, 0]).sum(axis=1).min() >= 2
 
 
@@ -182,7 +148,7 @@ def test_default_settings():
     images, fr, bx, _, _ = sc.mixed_case(32, 8)
     tracks = assert_spec(images, fr, bx)[0]
     assert np.isfinite(tracks[0, 1:4, :, 0]).sum() >= 6
-    assert_same(device(images, fr, bx, scales=1), bs.track_pixels(images, fr, bx, scales=1, scale_step=5, scale_penalty=0))
+    assert_same(device(images, fr, bx, scales=1), px.track_pixels(images, fr, bx, scales=1, scale_step=5, scale_penalty=0, **BOX))
 
 
 # e. -------------------------------------------------------------------------------------------------------------------
@@ -199,18 +165,18 @@ def test_one_integral_serves_every_call():
     sk = dict(scales=1, scale_step=10, scale_penalty=0)
     mine = host(ops.track_pixels(ti, tf, tb, sampling='box', integral=integ, **kw))
     assert_same(mine, host(ops.track_pixels(ti, tf, tb, sampling='box', **kw)))
-    assert_same(mine, bs.track_pixels(images, fr, bx, None, **kw))
+    assert_same(mine, px.track_pixels(images, fr, bx, None, **BOX, **kw))
     mine = host(ops.track_pixels_scaled(ti, tf, tb, sampling='box', integral=integ, **dict(kw, **sk)))
     assert_same(mine, host(ops.track_pixels_scaled(ti, tf, tb, sampling='box', **dict(kw, **sk))))
-    assert_same(mine, bs.track_pixels(images, fr, bx, None, **dict(kw, **sk)))
+    assert_same(mine, px.track_pixels(images, fr, bx, None, **BOX, **dict(kw, **sk)))
     mine = host(ops.track_volume_pixels_scaled(ti, tbx, ts, sampling='box', integral=integ, **dict(gc.MAIN, **sk)))
     assert_same(mine, host(ops.track_volume_pixels_scaled(ti, tbx, ts, sampling='box', **dict(gc.MAIN, **sk))))
-    assert_same(mine, bs.track_volume_pixels(images, boxes, scores, **dict(gc.MAIN, **sk)))
+    assert_same(mine, px.track_volume_pixels(images, boxes, scores, **BOX, **dict(gc.MAIN, **sk)))
     assert np.array_equal(integ.cpu().numpy(), before)                  # read, never written
     # with an integral the images are read for their shape only: frames of zeros give the same tubelets
     import torch
     assert_same(host(ops.track_pixels(torch.zeros_like(ti), tf, tb, sampling='box', integral=integ, **kw)),
-                bs.track_pixels(images, fr, bx, None, **kw))
+                px.track_pixels(images, fr, bx, None, **BOX, **kw))
 
 
 # f. -------------------------------------------------------------------------------------------------------------------
@@ -223,19 +189,17 @@ def greedy_wants():
     if not _greedy:
         import greedy_pixel_cases as gc
         (images, boxes, scores, _, _), point = gc.main_case()
-        _greedy['fixed'] = bs.track_volume_pixels(images, boxes, scores, **gc.MAIN)
-        _greedy['scaled'] = bs.track_volume_pixels(images, boxes, scores, **dict(gc.MAIN, **SCALE))
+        _greedy['fixed'] = px.track_volume_pixels(images, boxes, scores, **BOX, **gc.MAIN)
+        _greedy['scaled'] = px.track_volume_pixels(images, boxes, scores, **BOX, **dict(gc.MAIN, **SCALE))
         assert not _greedy['fixed'][3] and not _greedy['scaled'][3] and int(_greedy['fixed'][2].sum()) >= 3
     return _greedy['fixed'], _greedy['scaled']
 
 
 def greedy_device(scaled, ctx=None, **kw):
+    """ops.track_volume_pixels_scaled at SCALE where ``scaled``, else ops.track_volume_pixels, on the main volume"""
     import greedy_pixel_cases as gc
-    from vdetlib_amd import ops
     (images, boxes, scores, _, _), _ = gc.main_case()
-    if scaled:
-        return host(ops.track_volume_pixels_scaled(g(images), g(boxes), g(scores), sampling='box', ctx=ctx, **dict(gc.MAIN, **dict(SCALE, **kw))))
-    return host(ops.track_volume_pixels(g(images), g(boxes), g(scores), sampling='box', ctx=ctx, **dict(gc.MAIN, **kw)))
+    return ph.greedy_device(images, boxes, scores, ctx=ctx, **BOX, **dict(gc.MAIN, **dict(SCALE if scaled else {}, **kw)))
 
 
 def test_greedy_forms_against_the_spec():
@@ -245,7 +209,7 @@ def test_greedy_forms_against_the_spec():
     assert_same(greedy_device(True), scaled)
     (images, boxes, scores, _, _), _ = gc.main_case()
     kw = dict(step=2, max_frames=7)
-    assert_same(greedy_device(False, **kw), bs.track_volume_pixels(images, boxes, scores, **dict(gc.MAIN, **kw)))
+    assert_same(greedy_device(False, **kw), px.track_volume_pixels(images, boxes, scores, **BOX, **dict(gc.MAIN, **kw)))
 
 
 def test_greedy_forms_eager_and_lazy_list_maintenance_agree(monkeypatch):
@@ -307,38 +271,9 @@ def test_dict_level_tracker_with_the_sampling_option():
 
 
 # g. -------------------------------------------------------------------------------------------------------------------
-FI = 6
-BAD_SLOTS = ((FI + 1, [10, 10, 30, 30]), (-1, [10, 10, 30, 30]), (2, [np.nan, 10, 30, 30]), (2, [10, 10, np.inf, 30]),
-             (2, [10, 10, 9.5, 30]), (2, [10, 30, 30, 29]), (2, [70, 10, 90, 30]), (2, [10, -30, 30, 0.5]), (2, [10, 10, 2.0 ** 21, 30]))
-
-
-@pytest.mark.parametrize("k", range(len(BAD_SLOTS)))
+@pytest.mark.parametrize("k", range(len(ph.BAD_SLOTS)))
 def test_invalid_anchor_data_is_latched(k):
-    from vdetlib_amd import _lib, ops
-    frame, box = BAD_SLOTS[k]
-    images = np.random.RandomState(5500).randint(0, 256, size=(FI, 48, 64, 3)).astype(np.uint8)
-    ok = [20, 12, 43, 35]
-    fr = np.array([[3, frame, 4]], np.int32)
-    bx = np.array([[ok, box, ok]], np.float32)
-    kw = dict(grid=8, radius=2)
-    want = bs.track_pixels(images, fr, bx, None, **kw)
-    assert want[3] and np.isnan(want[0][0, 1]).all() and want[2].tolist() == [3]
-    good = bs.track_pixels(images, fr[:, ::2], bx[:, ::2], None, **kw)
-    assert not good[3] and bits_equal(want[0][0, ::2], good[0][0])           # the neighbours are what they are without it
-    ti, tf, tb = g(images), g(fr), g(bx)
-    cx = _lib.Context()
-    try:
-        with pytest.raises(ValueError):
-            ops.track_pixels(ti, tf, tb, ctx=cx, sampling='box', **kw)
-        out = ops.track_pixels(ti, tf, tb, sync=False, ctx=cx, sampling='box', **kw)
-        with pytest.raises(ValueError):
-            cx.sync()
-        assert_same(host(out), want)
-        cx.sync()                                                             # the latch is cleared ...
-        out = ops.track_pixels(ti, g(fr[:, ::2]), g(bx[:, ::2]), ctx=cx, sampling='box', **kw)        # ... and the context works
-        assert_same(host(out), good)
-    finally:
-        cx.close()
+    ph.invalid_anchor_data_is_latched('track_pixels', k, 5500, grid=8, radius=2, **BOX)
 
 
 def test_argument_errors():
@@ -408,7 +343,7 @@ def test_argument_errors():
         out = ops.track_pixels_scaled(ti, tf, tb, g(scr), grid=8, radius=2, scales=3, scale_step=25, scale_penalty=65535, sampling='box',
                                       integral=integ, ctx=cx)
         assert cx.last_timing()['other'][1] == 1
-        assert_same(host(out), bs.track_pixels(images, fr, bx, scr, grid=8, radius=2, scales=3, scale_step=25, scale_penalty=65535))
+        assert_same(host(out), px.track_pixels(images, fr, bx, scr, grid=8, radius=2, scales=3, scale_step=25, scale_penalty=65535, **BOX))
     finally:
         cx.close()
 
@@ -432,8 +367,8 @@ def test_prep_cache_is_left_alone():
         cx.close()
     for a, b in zip(first, second):
         assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-    assert np.array_equal(integ.cpu().numpy(), bs.luma_integral(images))
-    assert_same(host(mine), bs.track_pixels(images, fr, bx, scr, 8, 2))
+    assert np.array_equal(integ.cpu().numpy(), px.luma_integral(images))
+    assert_same(host(mine), px.track_pixels(images, fr, bx, scr, 8, 2, **BOX))
 
 
 # h. -------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,6 @@
 planted objects whose positions are known, and the C-ABI surface of the device form (vdet_track_pixels)."""
 import ctypes
 import inspect
-import os
 import re
 
 import numpy as np
@@ -10,8 +9,7 @@ import pytest
 
 import pixtrack_cases as pc
 import pixtrack_spec as px
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from pixtrack_harness import ctype_of, header, prototype
 
 
 def grey(plane):
@@ -91,8 +89,8 @@ def test_shift_rounding():
     # region columns 2,3,3,4,4,5 -> 60,80,80,100,100,120; dx = -1: [60,80,80,100] vs [60,60,80,80] -> 40 a row; dx = 0:
     # [80,80,100,100] -> 80; dx = +1: [80,100,100,120] -> 120.  Half a cell cannot be matched: dx = -1, SAD 160, and the box moves
     # (2*(-1)*2 + 4) // 8 = 0
-    box, conf, (dy, dx), sad = px.step_once(Tm, Lm, (3, 2, 4, 4), 4, 1)
-    assert (dy, dx, sad) == (0, -1, 160) and box == (3, 2, 4, 4)
+    box, conf, (l, dy, dx), sad = px.step_once(Tm, Lm, (3, 2, 4, 4), 4, 1)
+    assert (l, dy, dx, sad) == (0, 0, -1, 160) and box == (3, 2, 4, 4)
     assert conf == np.float32(1.0) - np.float32(160) / np.float32(4080)
 
 
@@ -115,13 +113,13 @@ def test_chain_by_hand():
     Rg = px.sample(L[2], (2, 2, 5, 5), 4, -1, 5)
     sads = {(dy, dx): int(np.abs(Tm.astype(int) - Rg[1 + dy:5 + dy, 1 + dx:5 + dx].astype(int)).sum()) for dy in (-1, 0, 1) for dx in (-1, 0, 1)}
     assert sads == {(dy, dx): 16 * abs(10 * dy + dx - 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)}
-    assert px.step_once(Tm, L[2], (2, 2, 5, 5), 4, 1)[:3] == ((3, 2, 6, 5), np.float32(1.0), (0, 1))
-    assert px.step_once(Tm, L[0], (2, 2, 5, 5), 4, 1)[:3] == ((1, 2, 4, 5), np.float32(1.0), (0, -1))
+    assert px.step_once(Tm, L[2], (2, 2, 5, 5), 4, 1)[:3] == ((3, 2, 6, 5), np.float32(1.0), (0, 0, 1))
+    assert px.step_once(Tm, L[0], (2, 2, 5, 5), 4, 1)[:3] == ((1, 2, 4, 5), np.float32(1.0), (0, 0, -1))
     # frame 3: moved once more, and pixel (row 3, column 5) -- inside the moved box (4,2,7,5) -- is 51 brighter: the right
     # candidate has SAD 51; every other one has 15 or 16 pixels off by >= 1 and the bumped one off by >= 50: >= 65
     box, conf, d, sad = px.step_once(Tm, L[3], (3, 2, 6, 5), 4, 1)
     c51 = np.float32(1.0) - np.float32(51) / np.float32(4080)
-    assert (box, d, sad) == ((4, 2, 7, 5), (0, 1), 51) and conf == c51
+    assert (box, d, sad) == ((4, 2, 7, 5), (0, 0, 1), 51) and conf == c51
     one = np.float32(1.0)
     want = np.array([[2, 3, 5, 6, one], [3, 3, 6, 6, one], [4, 3, 7, 6, one], [5, 3, 8, 6, c51]], np.float32)
     fr, bx = np.array([[2]], np.int32), np.array([[[3.9, 3.2, 6.99, 6.5]]], np.float32)      # fractional: truncated to (3,3,6,6)
@@ -199,32 +197,15 @@ def test_flat_image_stays_put():
 
 # ---- e. the binding --------------------------------------------------------------------------------------------------------
 
-def _header():
-    return open(os.path.join(ROOT, 'include', 'vdet_hip.h')).read()
-
-
-def _prototype(name):
-    src = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
-    m = re.search(r'\bint\s+%s\s*\(([^;]*?)\)\s*;' % name, src, flags=re.S)
-    assert m, "%s is not declared in include/vdet_hip.h" % name
-    return [re.sub(r'\s+', ' ', a).strip() for a in m.group(1).split(',')]
-
-
-def _ctype_of(arg):
-    if '*' in arg:
-        return ctypes.c_void_p
-    return {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'double': ctypes.c_double, 'float': ctypes.c_float}[arg.split()[-2]]
-
-
 def test_header_prototype_and_symbol_row():
     from vdetlib_amd import _lib
-    proto = _prototype('vdet_track_pixels')
+    proto = prototype('vdet_track_pixels')
     assert proto[0] == 'vdet_ctx *ctx' and proto[1] == 'const uint8_t *d_images'
     assert [a.split()[-1].lstrip('*') for a in proto[2:]] == ['F', 'H', 'W', 'd_anchor_frames', 'd_anchor_boxes', 'd_anchor_scores', 'C', 'T',
                                                               'S', 'R', 'min_conf', 'max_frames', 'step', 'd_tracks', 'd_anchors',
                                                               'd_ntracks']
     res, args = _lib.SYMBOLS['vdet_track_pixels']
-    assert res is ctypes.c_int and args == [_ctype_of(a) for a in proto]
+    assert res is ctypes.c_int and args == [ctype_of(a) for a in proto]
 
 
 def test_null_context_refused():
@@ -235,7 +216,7 @@ def test_null_context_refused():
 
 
 def test_limits_table_row():
-    head = _header().split('#ifndef VDET_HIP_H')[0]
+    head = header().split('#ifndef VDET_HIP_H')[0]
     m = re.search(r'\n \*   device pixel tracker(.*?)\n \*/', head, flags=re.S)
     assert m, "the limits table has no 'device pixel tracker' row"
     row = re.sub(r'\s*\n \*\s*', ' ', m.group(1))

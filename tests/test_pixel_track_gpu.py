@@ -9,103 +9,17 @@ import numpy as np
 import pytest
 
 import pixtrack_cases as pc
+import pixtrack_harness as ph
 import pixtrack_spec as px
+from pixtrack_cases import FM, HM, LEAVES, WM, mixed_case
+from pixtrack_harness import assert_spec, bits_equal, g
 
 pytestmark = pytest.mark.gpu
 
 
-def g(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits_equal(got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return False
-    if got.dtype.kind != 'f':
-        return np.array_equal(got, want)
-    nan = np.isnan(want)
-    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(u)[~nan], want.view(u)[~nan])
-
-
-def device(images, fr, bx, sc=None, **kw):
-    from vdetlib_amd import ops
-    out = ops.track_pixels(g(images), g(fr), g(bx), None if sc is None else g(sc), **kw)
-    return tuple(x.cpu().numpy() for x in out)
-
-
-def assert_spec(images, fr, bx, sc=None, **kw):
-    """device == spec on bits; returns the spec's outputs"""
-    want = px.track_pixels(images, fr, bx, sc, **kw)
-    assert not want[3]
-    got = device(images, fr, bx, sc, **kw)
-    for k, name in enumerate(('tracks', 'anchors', 'ntracks')):
-        assert bits_equal(got[k], want[k]), name
-    return want
-
-
 # ---------------------------------------------------------------------------------------------------------------------
-# f. the mixed slot table
+# f. the mixed slot table (pixtrack_cases.mixed_case)
 # ---------------------------------------------------------------------------------------------------------------------
-FM, HM, WM = 12, 96, 128
-# LEAVER.  A step can only take a box out of the image when nothing of the winning window is inside it, so a moving object is
-# never followed out: its last visible sliver decides.  The case that ends a chain "wholly outside" is built on the edge
-# replication instead.  The strip is vertical stripes (every row the same) on frames 0 .. LEAVES-1; from frame LEAVES on only
-# row 0 keeps the stripes, the rows below are noise.  The box is S/2 wide and 2S high (a cell is two rows) with its bottom row
-# on image row 2R - 1, most of it above the image.  On the striped frames every dy ties and the box stays.  On frame LEAVES
-# the window of dy = -R ends on row -1: all of it is the replicated row 0, SAD 0; dy = -R + 1 ends on row 1, which is noise.
-LEAVES = 3
-PLANT = {8: (16, 8), 32: (64, 64), 64: (64, 64), 12: (24, 36)}     # the planted mover's w, h: whole multiples of the grid
-_mixed = {}
-
-
-def mixed_case(S, R):
-    """12 frames of 96 x 128 noise with (1) a planted mover (pixtrack_cases), (2) a 37 x 53 white-noise object that moves
-    (3, 2) pixels a frame -- the pitch is no integer, the spec itself drifts --, (3) on the right a strip for the box that
-    leaves the image (see LEAVER)."""
-    if (S, R) not in _mixed:
-        w, h = PLANT[S]
-        anchor = 6
-        sw = S // 2 + R + 4                                     # the strip's width
-        images, pos = pc.planted_video(3000 + S, FM, HM, WM - sw, w, h, S, R, anchor)
-        rng = np.random.RandomState(3100 + S)
-        tex2 = rng.randint(0, 256, size=(53, 37, 3)).astype(np.uint8)
-        for f in range(FM):
-            x2, y2 = 5 + 3 * f, 10 + 2 * f
-            images[f, y2:y2 + 53, x2:x2 + 37] = tex2
-            images[f, pos[f, 1]:pos[f, 1] + h, pos[f, 0]:pos[f, 0] + w] = pc.planted_texture(3000 + S, w, h)   # the mover on top
-        strip = rng.randint(0, 256, size=(FM, HM, sw, 3)).astype(np.uint8)
-        stripes = rng.randint(0, 256, size=(sw, 3)).astype(np.uint8)
-        strip[:LEAVES] = stripes
-        strip[LEAVES:, 0] = stripes
-        images = np.concatenate([images, strip], axis=2)
-        x3 = WM - sw + R // 2 + 2
-        px1, py1 = pos[anchor]
-        pxl, pyl = pos[FM - 1]
-        mover = [px1 + 1, py1 + 1, px1 + w, py1 + h]
-        fr = np.array([[0, anchor + 1, 4, 2, 0],
-                       [3, 5, 7, 9, 11],
-                       [1, FM, anchor + 1, 0, 0]], np.int32)
-        bx = np.zeros((3, 5, 4), np.float32)
-        bx[0, 1] = mover
-        bx[0, 2] = [5 + 9 + 1, 10 + 6 + 1, 5 + 9 + 37, 10 + 6 + 53]           # the 37 x 53 object on frame 4 (index 3)
-        bx[0, 3] = [60, 40, 64, 46]                                           # 5 x 7: w < S
-        bx[0, 4] = [7, 7, 9, 9]                                               # (an empty slot's box is not looked at)
-        bx[1, 0] = [-20.5, 30, 25, 70]                                        # over the left edge
-        bx[1, 1] = [40, -15, 80, 20]                                          # the top
-        bx[1, 2] = [110, 20, 150.75, 60]                                      # the right
-        bx[1, 3] = [30, 80, 70, 120]                                          # the bottom
-        bx[1, 4] = [-30, -25, 10.5, 12.25]                                    # negative coordinates
-        bx[2, 0] = [x3 + 1, 2 * R - 2 * S + 1, x3 + S // 2, 2 * R]            # the leaver, anchored on frame 1: forward only
-        bx[2, 1] = [pxl + 1, pyl + 1, pxl + w, pyl + h]                       # the mover anchored on frame F: backward only
-        bx[2, 2] = np.array(mover, np.float32) + np.float32([0.75, 0.5, 0.25, 0.99])     # fractional: truncated to the mover
-        sc = rng.rand(3, 5).astype(np.float32)
-        _mixed[(S, R)] = (images, fr, bx, sc, pos, (w, h))
-    return _mixed[(S, R)]
-
-
 @pytest.mark.parametrize("S,R", ((8, 2), (32, 8), (64, 16), (12, 3)))
 def test_mixed_slot_table(S, R):
     images, fr, bx, sc, pos, (w, h) = mixed_case(S, R)
@@ -203,39 +117,9 @@ def test_confidence_equal_to_the_threshold_goes_on():
 # ---------------------------------------------------------------------------------------------------------------------
 # i. invalid anchor data
 # ---------------------------------------------------------------------------------------------------------------------
-FI = 6
-BAD_SLOTS = ((FI + 1, [10, 10, 30, 30]), (-1, [10, 10, 30, 30]), (2, [np.nan, 10, 30, 30]), (2, [10, 10, np.inf, 30]),
-             (2, [10, 10, 9.5, 30]), (2, [10, 30, 30, 29]), (2, [70, 10, 90, 30]), (2, [10, -30, 30, 0.5]), (2, [10, 10, 2.0 ** 21, 30]))
-
-
-@pytest.mark.parametrize("k", range(len(BAD_SLOTS)))
+@pytest.mark.parametrize("k", range(len(ph.BAD_SLOTS)))
 def test_invalid_anchor_data_is_latched(k):
-    from vdetlib_amd import _lib, ops
-    frame, box = BAD_SLOTS[k]
-    images = np.random.RandomState(3400).randint(0, 256, size=(FI, 48, 64, 3)).astype(np.uint8)
-    ok = [20, 12, 43, 35]
-    fr = np.array([[3, frame, 4]], np.int32)
-    bx = np.array([[ok, box, ok]], np.float32)
-    want = px.track_pixels(images, fr, bx, None, 8, 2)
-    assert want[3] and np.isnan(want[0][0, 1]).all() and want[2].tolist() == [3]
-    good = px.track_pixels(images, fr[:, ::2], bx[:, ::2], None, 8, 2)
-    assert not good[3] and bits_equal(want[0][0, ::2], good[0][0])           # the neighbours are what they are without it
-    ti, tf, tb = g(images), g(fr), g(bx)
-    cx = _lib.Context()
-    try:
-        with pytest.raises(ValueError):
-            ops.track_pixels(ti, tf, tb, grid=8, radius=2, ctx=cx)
-        out = ops.track_pixels(ti, tf, tb, grid=8, radius=2, sync=False, ctx=cx)
-        with pytest.raises(ValueError):
-            cx.sync()
-        for a, b in zip(out, want[:3]):
-            assert bits_equal(a.cpu().numpy(), b)
-        cx.sync()                                                             # the latch is cleared ...
-        out = ops.track_pixels(ti, g(fr[:, ::2]), g(bx[:, ::2]), grid=8, radius=2, ctx=cx)      # ... and the context works
-        for a, b in zip(out, good[:3]):
-            assert bits_equal(a.cpu().numpy(), b)
-    finally:
-        cx.close()
+    ph.invalid_anchor_data_is_latched('track_pixels', k, 3400, grid=8, radius=2)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """-m gpu: the pixel tracker's scale search on the device (ops.track_pixels_scaled, ops.track_volume_pixels_scaled;
-csrc/pixtrack_kernels.hpp) against tests/pixtrack_scale_spec.py ON BITS: the NaN masks are equal and every other element has
+csrc/pixtrack_kernels.hpp) against tests/pixtrack_spec.py ON BITS: the NaN masks are equal and every other element has
 the same bit pattern.  The rule is all integer but for one f32 division and one f32 subtraction per step.
   a. scales = 0 against ops.track_pixels;  b. a [3,5] slot table that mixes every kind of slot, four (grid, radius) pairs x four
   scale settings;  c. a tie on every key;  d. step and max_frames, interpolate_tracks;  e. invalid anchor data;  f. argument
@@ -8,46 +8,12 @@ the same bit pattern.  The rule is all integer but for one f32 division and one 
 import numpy as np
 import pytest
 
+import pixtrack_harness as ph
 import pixtrack_scale_cases as sc
-import pixtrack_scale_spec as ps
 import pixtrack_spec as px
+from pixtrack_harness import assert_same, assert_spec, bits_equal, device, g, greedy_device, host
 
 pytestmark = pytest.mark.gpu
-
-
-def g(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits_equal(got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        return False
-    if got.dtype.kind != 'f':
-        return np.array_equal(got, want)
-    nan = np.isnan(want)
-    u = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    return np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(u)[~nan], want.view(u)[~nan])
-
-
-def device(images, fr, bx, scr=None, **kw):
-    from vdetlib_amd import ops
-    out = ops.track_pixels_scaled(g(images), g(fr), g(bx), None if scr is None else g(scr), **kw)
-    return tuple(x.cpu().numpy() for x in out)
-
-
-def assert_same(got, want):
-    for k, name in enumerate(('tracks', 'anchors', 'ntracks')):
-        assert bits_equal(got[k], want[k]), name
-
-
-def assert_spec(images, fr, bx, scr=None, **kw):
-    """device == spec on bits; returns the spec's outputs"""
-    want = ps.track_pixels(images, fr, bx, scr, **kw)
-    assert not want[3]
-    assert_same(device(images, fr, bx, scr, **kw), want)
-    return want
 
 
 # a. -------------------------------------------------------------------------------------------------------------------
@@ -86,8 +52,12 @@ def test_mixed_slot_table(S, R, scales, scale_step, scale_penalty):
 
 def test_default_settings():
     """grid 32, radius 8, min_conf 0.5, scales 1, scale_step 5, no scores: the call with nothing but the data"""
+    from vdetlib_amd import ops
     images, fr, bx, _, _ = sc.mixed_case(32, 8)
-    tracks = assert_spec(images, fr, bx)[0]
+    want = px.track_pixels(images, fr, bx, scales=1, scale_step=5, scale_penalty=0)
+    assert not want[3]
+    assert_same(host(ops.track_pixels_scaled(g(images), g(fr), g(bx))), want)
+    tracks = want[0]
     assert np.isfinite(tracks[0, 1:4, :, 0]).all()
 
 
@@ -134,7 +104,7 @@ def test_step_and_max_frames_then_interpolation():
                 assert all((f - f0) % 3 == 0 and abs(f - f0) // 3 <= reach for f in np.flatnonzero(live[c, t])), (mf, c, t)
         # anchored on the last frame, index 11: 8, 5, 2 are in reach; max_frames = 5 allows ceil(6/2) - 1 = 2 steps, 6 allows 3
         assert np.flatnonzero(live[0, 2]).tolist() == ([5, 8, 11] if mf == 5 else [2, 5, 8, 11])
-    tracks, anchors, nt, _ = ps.track_pixels(images, fr, bx, scr, step=3, **kw)
+    tracks, anchors, nt, _ = px.track_pixels(images, fr, bx, scr, step=3, **kw)
     out = ops.track_pixels_scaled(g(images), g(fr), g(bx), g(scr), step=3, **kw)
     dense = ops.interpolate_tracks(out[0], out[2], out[1], [])
     dt = dense['tracks'].cpu().numpy()
@@ -153,38 +123,9 @@ def test_step_and_max_frames_then_interpolation():
 
 
 # e. -------------------------------------------------------------------------------------------------------------------
-FI = 6
-BAD_SLOTS = ((FI + 1, [10, 10, 30, 30]), (-1, [10, 10, 30, 30]), (2, [np.nan, 10, 30, 30]), (2, [10, 10, np.inf, 30]),
-             (2, [10, 10, 9.5, 30]), (2, [10, 30, 30, 29]), (2, [70, 10, 90, 30]), (2, [10, -30, 30, 0.5]), (2, [10, 10, 2.0 ** 21, 30]))
-
-
-@pytest.mark.parametrize("k", range(len(BAD_SLOTS)))
+@pytest.mark.parametrize("k", range(len(ph.BAD_SLOTS)))
 def test_invalid_anchor_data_is_latched(k):
-    from vdetlib_amd import _lib, ops
-    frame, box = BAD_SLOTS[k]
-    images = np.random.RandomState(5500).randint(0, 256, size=(FI, 48, 64, 3)).astype(np.uint8)
-    ok = [20, 12, 43, 35]
-    fr = np.array([[3, frame, 4]], np.int32)
-    bx = np.array([[ok, box, ok]], np.float32)
-    kw = dict(grid=8, radius=2, scales=2, scale_step=10)
-    want = ps.track_pixels(images, fr, bx, None, **kw)
-    assert want[3] and np.isnan(want[0][0, 1]).all() and want[2].tolist() == [3]
-    good = ps.track_pixels(images, fr[:, ::2], bx[:, ::2], None, **kw)
-    assert not good[3] and bits_equal(want[0][0, ::2], good[0][0])           # the neighbours are what they are without it
-    ti, tf, tb = g(images), g(fr), g(bx)
-    cx = _lib.Context()
-    try:
-        with pytest.raises(ValueError):
-            ops.track_pixels_scaled(ti, tf, tb, ctx=cx, **kw)
-        out = ops.track_pixels_scaled(ti, tf, tb, sync=False, ctx=cx, **kw)
-        with pytest.raises(ValueError):
-            cx.sync()
-        assert_same(tuple(x.cpu().numpy() for x in out), want)
-        cx.sync()                                                             # the latch is cleared ...
-        out = ops.track_pixels_scaled(ti, g(fr[:, ::2]), g(bx[:, ::2]), ctx=cx, **kw)         # ... and the context works
-        assert_same(tuple(x.cpu().numpy() for x in out), good)
-    finally:
-        cx.close()
+    ph.invalid_anchor_data_is_latched('track_pixels_scaled', k, 5500, grid=8, radius=2, scales=2, scale_step=10)
 
 
 # f. -------------------------------------------------------------------------------------------------------------------
@@ -219,7 +160,7 @@ def test_argument_errors():
         kw = dict(grid=8, radius=2, scales=3, scale_step=25, scale_penalty=65535)          # the bounds themselves are legal
         out = run(s=ts, **kw)
         assert cx.last_timing()['other'][1] == 1                                             # ONE launch, timed under 'other'
-        assert_same(tuple(x.cpu().numpy() for x in out), ps.track_pixels(images, fr, bx, scr, **kw))
+        assert_same(host(out), px.track_pixels(images, fr, bx, scr, **kw))
     finally:
         cx.close()
 
@@ -243,7 +184,7 @@ def test_prep_cache_is_left_alone():
         cx.close()
     for a, b in zip(first, second):
         assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-    assert_same(tuple(x.cpu().numpy() for x in mine), ps.track_pixels(images, fr, bx, scr, 8, 2))
+    assert_same(host(mine), px.track_pixels(images, fr, bx, scr, 8, 2, scales=1))
 
 
 # h. -------------------------------------------------------------------------------------------------------------------
@@ -256,7 +197,7 @@ def test_downstream_from_top_anchors_to_nms_tracks():
     fr, ab, asc, _ = ops.top_anchors(tb, ts, T)
     kw = dict(grid=sc.S, radius=sc.R, min_conf=0.0, scales=1, scale_step=5)
     tracks, anchors, nt = ops.track_pixels_scaled(g(images), fr, ab, asc, **kw)
-    want = ps.track_pixels(images, fr.cpu().numpy(), ab.cpu().numpy(), asc.cpu().numpy(), **kw)
+    want = px.track_pixels(images, fr.cpu().numpy(), ab.cpu().numpy(), asc.cpu().numpy(), **kw)
     assert_same(tuple(x.cpu().numpy() for x in (tracks, anchors, nt)), want)
     assert want[2].tolist() == [T, T] and fr.cpu().numpy()[0, 0] == 1           # class 0's first anchor: the growing object
     assert sc.largest_error(want[0][0, 0], truth['grow']) <= 4
@@ -273,11 +214,6 @@ def test_downstream_from_top_anchors_to_nms_tracks():
 SCALE = dict(scales=1, scale_step=5, scale_penalty=0)
 
 
-def greedy_device(images, boxes, scores, **kw):
-    from vdetlib_amd import ops
-    return tuple(x.cpu().numpy() for x in ops.track_volume_pixels_scaled(g(images), g(boxes), g(scores), **kw))
-
-
 def test_greedy_loop_against_the_spec():
     images, boxes, scores, _ = sc.greedy_case()
     want, fixed = sc.greedy_specs()
@@ -287,7 +223,7 @@ def test_greedy_loop_against_the_spec():
     # with the search and one of the growing object's late proposals without it
     assert int(got[1][0, 2, 1]) in sc.GIDIS and int(fixed[1][0, 2, 1]) in (sc.GIA,) + sc.GIJA
     kw = dict(sc.GREEDY, step=2, max_frames=7, scales=2, scale_step=10, scale_penalty=32)
-    assert_same(greedy_device(images, boxes, scores, **kw), ps.track_volume_pixels(images, boxes, scores, **kw))
+    assert_same(greedy_device(images, boxes, scores, **kw), px.track_volume_pixels(images, boxes, scores, **kw))
 
 
 def test_greedy_loop_without_levels_equals_the_fixed_scale_call():
@@ -338,7 +274,7 @@ def test_greedy_loop_argument_errors_and_timing():
                    dict(st=0)):
             assert call(**kw) == _lib.VDET_EINVAL, kw
         assert sum(n for _, n in cx.last_timing().values()) == 0, "an argument error launched a kernel"
-        assert_same(tuple(x.cpu().numpy() for x in run()), want)           # the context still works
+        assert_same(host(run()), want)           # the context still works
         assert cx.last_timing()['track_loop'][1] == 1          # the loop's launches are ONE timed span, under 'track_loop'
     finally:
         cx.close()
@@ -370,10 +306,10 @@ def test_dict_level_loop_with_and_without_the_scale_options():
         for opts, (tracks, anchors, ntracks) in ((Opts(scales=1, **base), scaled), (Opts(scales=1, scale_step=5, scale_penalty=0, **base), scaled),
                                                  (Opts(**base), plain), (Opts(scales=0, scale_step=25, **base), plain)):
             for c in range(sc.GC):
-                host = track.greedily_track_from_raw_dets(vid, det_info, track.pixel_tracker, c + 1, opts)
+                hostp = track.greedily_track_from_raw_dets(vid, det_info, track.pixel_tracker, c + 1, opts)
                 mine = ops.tracks_to_proto('pixvid', tracks[c], anchors[c], ntracks[c], method='pixel_tracker')
-                assert host['method'] == mine['method'] == 'pixel_tracker'
-                assert len(host['tracks']) == int(ntracks[c]) and view(host) == view(mine), (sorted(opts.__dict__), c)
+                assert hostp['method'] == mine['method'] == 'pixel_tracker'
+                assert len(hostp['tracks']) == int(ntracks[c]) and view(hostp) == view(mine), (sorted(opts.__dict__), c)
     finally:
         track.imread = saved
         track._pixel_video.clear()

@@ -30,9 +30,9 @@
 // 14.2 KiB, static.  Nothing of the context's cached graph, lists, index or link memo is read or written.
 //
 // The chain is pix_chain, a device function: track_pixels_kernel runs it from a slot table, track_pixel_chain_kernel -- the
-// tracker of the greedy loop vdet_track_volume_pixels (tests/greedy_pixel_spec.py) -- from the anchor the pick left in TrackState.
+// tracker of the greedy loop vdet_track_volume_pixels (the rule's greedy loop) -- from the anchor the pick left in TrackState.
 //
-// Scale search (tests/pixtrack_scale_spec.py; track_pixels_scaled_kernel, track_pixel_chain_scaled_kernel): pix_chain<true>.
+// Scale search (the rule's ``scales``; track_pixels_scaled_kernel, track_pixel_chain_scaled_kernel): pix_chain<true>.
 // Per step, for every level l in -ns..ns the box is grown about its centre by ex = sgn(l) * floor((|l|*p*w + 100) / 200) columns
 // and ey rows a side (l != 0 is skipped when a side falls below 1 or exceeds 2^21: block-uniform); each admissible level gets
 // its own tables, gather and SAD pass over the SAME S x S template, a lane keeps its smallest key across the levels in
@@ -40,7 +40,7 @@
 // | l+3): the raw SAD of the winner is key_hi - |l|*q.  The box state (x1, y1, w, h) stays scalar; the winner's level box,
 // moved, is the new box.  pix_chain<false> is the fixed-scale chain, the code it was before the template.
 //
-// Box sampling (tests/pixtrack_box_spec.py; track_pixels_box_kernel, track_pixel_chain_box_kernel): pix_chain<true, true>.
+// Box sampling (the rule's ``sampling='box'``; track_pixels_box_kernel, track_pixel_chain_box_kernel): pix_chain<true, true>.
 // A cell's value is the rounded mean of its pixels instead of one pixel, read from a summed-area table of the luma:
 //   integral  I[f, y, x] = sum of L[f, r, c] over r < y, c < x, uint32 [F, H+1, W+1]; H*W <= 2^24, so 255 * 2^24 fits
 //   edges     per axis: a = o + floor(k*e / S), b = o + floor((k+1)*e / S), a' = clamp(a, 0, N-1), b' = min(max(b, a'+1), N)

@@ -4121,9 +4121,9 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// Device pixel tracker (pixtrack_kernels.hpp), fixed scale and with the scale search (tests/pixtrack_scale_spec.py)
+// Device pixel tracker (pixtrack_kernels.hpp), fixed scale and with the scale search (tests/pixtrack_spec.py)
 // ---------------------------------------------------------------------------------------------
-// box sampling (tests/pixtrack_box_spec.py): the largest entry of a frame's integral, 255 * H * W, must fit in 32 bits
+// box sampling (tests/pixtrack_spec.py): the largest entry of a frame's integral, 255 * H * W, must fit in 32 bits
 static int pix_box_check(vdet_ctx *c, int64_t H, int64_t W)
 {
     if (H * W > kPixBoxMaxArea) return fail(c, VDET_EINVAL, "box sampling: frames of at most 2^24 pixels (H * W)");
@@ -4227,7 +4227,7 @@ int vdet_track_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_t F, in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// Greedy tubelet generation with the pixel tracker (tests/greedy_pixel_spec.py): the greedy volume trackers' front half
+// Greedy tubelet generation with the pixel tracker (tests/pixtrack_spec.py): the greedy volume trackers' front half
 // (volume_lists .. greedy_args, shared with vdet_nms_track_volume) and pick / lazy lists / eager pass, with
 // pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
 // ---------------------------------------------------------------------------------------------

@@ -405,7 +405,7 @@ def _pixel_sampling(sampling, integral, images, F, H, W):
 
 def luma_integral(images, sync=True, ctx=None):
     """The integral image (summed-area table) of every frame's luma, the input of the pixel tracker's ``sampling='box'``
-    (include/vdet_hip.h: vdet_luma_integral; the rule is tests/pixtrack_box_spec.py): build it once per video and pass it as
+    (include/vdet_hip.h: vdet_luma_integral; the rule is tests/pixtrack_spec.py): build it once per video and pass it as
     ``integral=`` to as many tracker calls as read that video.
 
     images uint8 [F,H,W,3], contiguous, H*W <= 2^24 -> uint32 [F,H+1,W+1] on the images' GPU:
@@ -766,7 +766,7 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
     finite (before any launch); and for an anchor frame outside 0..F or an anchor box that is not finite, beyond 2^20, empty or
     wholly outside the image (reported when the call, or a later ``ctx.sync()``, waits; the slot is written as an empty one).
 
-    Keyword-only: ``sampling='box'`` (the rule is tests/pixtrack_box_spec.py; vdet_track_pixels_box): a cell's value is the rounded mean of
+    Keyword-only: ``sampling='box'`` (the rule's box sampling; vdet_track_pixels_box): a cell's value is the rounded mean of
     the pixels of its ``w/grid`` x ``h/grid`` rectangle instead of the one pixel at its centre, so detail finer than the pitch
     is averaged, not aliased, and motion below the pitch is followed.  The means come from ``integral``, the frames'
     ``luma_integral`` (uint32 [F,H+1,W+1], contiguous, on the images' GPU): given, the images are read for their shape only;
@@ -788,6 +788,17 @@ def _scale_settings(scales, scale_step, scale_penalty):
     return scales, scale_step, scale_penalty
 
 
+def _pixel_export(ctx, stem, box, scale):
+    """The export a pixel-tracker call ends in, and the arguments it takes between the settings and the outputs: ``stem`` +
+    '_box' with the scale settings (scale None: scales = 0) where ``box``, else ``stem`` itself with none (scale None) or
+    ``stem`` + '_scaled' with ``scale``"""
+    if box:
+        return getattr(ctx.lib, stem + '_box'), scale or (0, 1, 0)
+    if scale is None:
+        return getattr(ctx.lib, stem), ()
+    return getattr(ctx.lib, stem + '_scaled'), scale
+
+
 def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx,
                   sampling='point', integral=None):
     """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty)); with sampling='box'
@@ -807,12 +818,8 @@ def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, gri
     head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
             anchor_scores.data_ptr() if anchor_scores is not None else None, C, T) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    if box:
-        ctx.check(ctx.lib.vdet_track_pixels_box(*(head + (scale or (0, 1, 0)) + out)))
-    elif scale is None:
-        ctx.check(ctx.lib.vdet_track_pixels(*(head + out)))
-    else:
-        ctx.check(ctx.lib.vdet_track_pixels_scaled(*(head + scale + out)))
+    fn, extra = _pixel_export(ctx, 'vdet_track_pixels', box, scale)
+    ctx.check(fn(*(head + extra + out)))
     if sync:
         ctx.sync()
     return tracks, anchors, ntracks
@@ -822,7 +829,7 @@ def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, gri
 def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
                         scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
     """``track_pixels`` with a scale search: the tubelet's box grows and shrinks with the object (include/vdet_hip.h:
-    vdet_track_pixels_scaled; the rule is tests/pixtrack_scale_spec.py).  On every step the current box is also tried grown and
+    vdet_track_pixels_scaled; the rule is tests/pixtrack_spec.py's ``scales``).  On every step the current box is also tried grown and
     shrunk about its centre by ``scale_step`` percent per level, ``scales`` levels each side (0 .. 3; a side changes by
     2 * ((level * scale_step * side + 100) // 200) pixels), each level sampled on the same ``grid`` x ``grid`` cells against the
     anchor's fixed template; the smallest (SAD + level * ``scale_penalty``, level, shift) wins, the confidence is the winner's
@@ -842,7 +849,7 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
     (``track_pixels``' rule) instead of being linked through the proposals.  Per class: the best remaining detection is the
     anchor, its tubelet is tracked, every detection the tubelet explains is removed (track_det_nms at ``nms_thres`` on the frames
     the tubelet has a box on), up to ``max_tracks`` times or until an anchor scores below ``thres``.  The rule is
-    tests/greedy_pixel_spec.py; include/vdet_hip.h: vdet_track_volume_pixels.  Three launches per track, no host wait.
+    tests/pixtrack_spec.py's greedy loop; include/vdet_hip.h: vdet_track_volume_pixels.  Three launches per track, no host wait.
 
     images uint8 [F,H,W,3] contiguous, boxes [F,B,4] f32, scores [F,B,C] f32, all on one GPU.  Returns, in ``track_volume``'s
     layout,
@@ -877,13 +884,8 @@ def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tra
     head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres),
             max_tracks) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    if box:
-        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels_box(*(head + (scale or (0, 1, 0)) + out)))
-    elif scale is None:
-        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels(*(head + out)))
-    else:
-        call = lambda: ctx.check(ctx.lib.vdet_track_volume_pixels_scaled(*(head + scale + out)))
-    _finish(ctx, call, sync, reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
+    fn, extra = _pixel_export(ctx, 'vdet_track_volume_pixels', box, scale)
+    _finish(ctx, lambda: ctx.check(fn(*(head + extra + out))), sync, reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
     return tracks, anchors, ntracks
 
 
@@ -892,7 +894,7 @@ def track_volume_pixels_scaled(images, boxes, scores, nms_thres=0.3, thres=0.0, 
                                max_frames=0, step=1, scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
     """``track_volume_pixels`` with ``track_pixels_scaled``'s chain as the tracker: the tubelet that suppresses the detections it
     explains has a box that follows the object's size (include/vdet_hip.h: vdet_track_volume_pixels_scaled; the rule is the
-    greedy loop of tests/pixtrack_scale_spec.py).  ``scales = 0`` gives ``track_volume_pixels``' bits.  Arguments, layouts,
+    greedy loop of tests/pixtrack_spec.py).  ``scales = 0`` gives ``track_volume_pixels``' bits.  Arguments, layouts,
     launches and errors are ``track_volume_pixels``'; in addition ValueError for scales outside 0..3, scale_step outside 1..25
     or scale_penalty outside 0..65535 (before any launch).  Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``."""
     return _track_volume_pixels((scales, scale_step, scale_penalty), images, boxes, scores, nms_thres, thres, max_tracks, grid,
