@@ -104,6 +104,12 @@
  *                                                                     VDET_EINVAL; bad anchor data as in the call with point
  *                                                                     sampling.  A cell outside the image or narrower than a
  *                                                                     pixel is a single column / row, never an error
+ *   pixel tracker with template update     (vdet_track_pixels_adaptive, vdet_track_volume_pixels_adaptive) the row of the call with
+ *                                          the scale search (scales = 0 allowed; box = 1: the row with box sampling), and
+ *                                          box 0 or 1, 0 <= update <= 256, update_conf and drift_conf finite
+ *                                                                     VDET_EINVAL; bad anchor data as in the siblings.  A
+ *                                                                     confidence no step reaches (2.0) is the fixed template,
+ *                                                                     never an error
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1161,6 +1167,47 @@ int vdet_track_volume_pixels_box(vdet_ctx *ctx, const uint32_t *d_integral, int6
                                  const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
                                  int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
                                  int scale_step, int scale_penalty, float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+/* ---- the pixel tracker with a template update and an anchor guard: the template follows an object that turns, deforms or
+ *      changes lighting, and the guard keeps it from drifting onto something else.  The rule is tests/pixtrack_adapt_spec.py;
+ *      everything it does not restate is tests/pixtrack_spec.py's (luma, grid, box cells, levels, key, tie order, confidence,
+ *      move, outside test, bad anchors, step, max_frames, greedy loop) ----------------------------------------------------------
+ *
+ * vdet_track_pixels_adaptive / vdet_track_volume_pixels_adaptive: vdet_track_pixels_box's / vdet_track_volume_pixels_box's
+ * arguments with d_planes and box in the place of d_integral -- box = 0: d_planes is the images uint8 [F,H,W,3] (point
+ * sampling); box = 1: the integral uint32 [F,H+1,W+1] (box sampling) -- and, after the scale settings (scales = 0 allowed),
+ *   update = a (0 .. 256), the weight of the new patch in 1/256;  update_conf, drift_conf: finite.
+ *   state     per chain -- per slot AND direction -- A[S,S], 8.8 fixed-point integers in 0 .. 65280, initialised to Tm0 << 8.
+ *             Tm0 is the anchor's template: cells 0..S-1 of the truncated anchor box on the anchor frame, point or box sampled.
+ *             The backward chain starts from Tm0 again, never from what the forward chain made of it
+ *   match     a step matches against Tm = (A + 128) >> 8 (uint8) in the place of the fixed template; nothing else in the step
+ *             changes
+ *   patch     after a step the chain keeps (conf >= min_conf and the moved box not wholly outside), with winner (l, dy, dx):
+ *             P[S,S] = cells dx .. dx+S-1 (columns) by dy .. dy+S-1 (rows) of the winner's level box b_l on frame g, before
+ *             the move: the window that won
+ *   guard     SAD0 = sum |Tm0 - P|, c0 = 1.0f - (float)SAD0 / (float)(255*S*S)
+ *   accept    a > 0 and conf >= (float)update_conf and c0 >= (float)drift_conf (f32 compares)
+ *   update    on accept, element by element: A = ((256 - a) * A + a * (P << 8) + 128) >> 8.  The largest intermediate is
+ *             256 * 65280 + 128; A stays within 0 .. 65280; a = 256 makes A = P << 8 (replace every frame).  With a uint8 state
+ *             a small a would stall as soon as a * |P - Tm| < 128; the 8.8 state does not
+ * The rows, the confidence in column 4 (the step's conf, against the CURRENT template), the NaN pattern, anchors and ntracks
+ * are laid out as in the siblings: no new output.  With a = 0, or an update_conf or drift_conf no step can reach (2.0), the bits
+ * are the fixed-template call's.  Launch sequences (ONE launch; three per track, no host wait) and timing buckets ("other";
+ * "track_loop") are the siblings'.  Argument checks, before any launch, VDET_EINVAL: the sibling's, 0 <= update <= 256, both
+ * confidences finite, box 0 or 1 (box = 1: H*W <= 2^24).  ctx NULL: VDET_EINVAL, nothing touched.  Limits: the table at the top
+ * of this file.
+ */
+int vdet_track_pixels_adaptive(vdet_ctx *ctx, const void *d_planes, int box, int64_t F, int64_t H, int64_t W,
+                               const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C,
+                               int T, int S, int R, double min_conf, int max_frames, int step, int scales, int scale_step,
+                               int scale_penalty, int update, double update_conf, double drift_conf, float *d_tracks,
+                               float *d_anchors, int32_t *d_ntracks);
+
+int vdet_track_volume_pixels_adaptive(vdet_ctx *ctx, const void *d_planes, int box, int64_t H, int64_t W, const float *d_boxes,
+                                      const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                      int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
+                                      int scale_step, int scale_penalty, int update, double update_conf, double drift_conf,
+                                      float *d_tracks, float *d_anchors, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

@@ -114,6 +114,10 @@ SYMBOLS = {
                                     _vp, _vp, _vp]),
     "vdet_track_volume_pixels_box": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci, _f64, _ci,
                                            _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "vdet_track_pixels_adaptive": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _ci, _ci, _ci, _f64, _ci, _ci, _ci,
+                                         _ci, _ci, _ci, _f64, _f64, _vp, _vp, _vp]),
+    "vdet_track_volume_pixels_adaptive": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci,
+                                                _f64, _ci, _ci, _ci, _ci, _ci, _ci, _f64, _f64, _vp, _vp, _vp]),
 }
 
 

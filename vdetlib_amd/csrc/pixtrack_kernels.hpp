@@ -50,6 +50,21 @@
 // SAD pass, the reduction and the box state are the point chain's.  PixTrackArgs::images carries the integral in this mode; the
 // chain always runs the level loop (scales = 0: one trip, the fixed-scale chain's winner).  LDS: two more tables, 15.0 KiB.
 //
+// Template update with an anchor guard (the rule's ``update``, tests/pixtrack_adapt_spec.py; track_pixels_adaptive[_box]_kernel,
+// track_pixel_chain_adaptive[_box]_kernel): pix_chain<true, BOX, true>.  Per chain (slot AND direction) the state is A[S,S] in 8.8
+// fixed point, A = Tm0 << 8 at the start; a step matches against Tm = (A + 128) >> 8, which is what stm holds.  After a step the
+// chain keeps, with P the S x S window that won (cells dx.., dy.. of the winner's level box on frame g, before the move):
+//   guard     SAD0 = sum |Tm0 - P|, c0 = 1.0f - float(SAD0) / float(255*S*S)
+//   accept    a > 0 and conf >= (float)update_conf and c0 >= (float)drift_conf
+//   update    A = ((256 - a) * A + a * (P << 8) + 128) >> 8 per cell (<= 256 * 65280 + 128: 32 bits), Tm follows
+// The state costs no LDS: thread t owns the template dwords t, t + 256, ... (at most 4: 16 cells at S = 64) and keeps their Tm0
+// bytes (4 registers) and their A as 16-bit pairs (8 registers); after an accepted step it rewrites only its own dwords of stm.
+// P is read from the region still in sreg when the winner's level was the last one gathered, else the S x S window is gathered
+// again (the tables take one first cell per axis for this).  SAD0 is one v_sad_u8 per owned dword, wave shuffles, a slot per
+// wave in LDS (16 bytes) and one barrier; the decision is block-uniform.  The barriers that order the hazards -- the SAD pass's
+// reads of stm before the update's writes, those writes before the next SAD pass, sreg and the tables under the re-gather --
+// are named where the code stands, in pix_chain.
+//
 // The integral is made by two launches (vdet_luma_integral), luma in flight, no luma plane in memory:
 //   luma_integral_rows_kernel  a wave per image row: 64 pixels a trip, a wave scan, the carry of the trips so far in a register;
 //                              writes I[f, y+1, 1..W] = the row's prefix sums and I[f, y+1, 0] = 0
@@ -95,6 +110,14 @@ struct PixTrackArgs {
 struct PixScaleArgs {
     int ns, p, q;
 };
+
+// the template update of pix_chain<true, BOX, true>: a = the weight of the new patch in 1/256 (0 .. 256; 0: never), the update
+// is accepted at conf >= update_conf and c0 >= drift_conf (f32 compares)
+struct PixAdaptArgs {
+    int a;
+    float update_conf, drift_conf;
+};
+constexpr int kPixOwn = kPixMaxS * (kPixMaxS / 4) / kPixLT;     // template dwords a thread owns (tid, tid + 256, ...): 4, 16 cells
 
 __device__ __forceinline__ int pix_floordiv(int a, int b)      // b > 0
 {
@@ -143,14 +166,16 @@ __device__ __forceinline__ uint32_t pix_luma(const uint8_t *p)
     return (29u * p[0] + 150u * p[1] + 77u * p[2] + 128u) >> 8;
 }
 
-// the tables of the grid k = k0 .. k0+n-1 of the box: tcol[i] = 3 * column, trow[i] = row.  n <= kPixMaxP, 2n <= kPixLT.
-__device__ __forceinline__ void pix_tables(int *tcol, int *trow, int x1, int y1, int w, int h, int S, int k0, int n, int H, int W)
+// the tables of the grid k = k0x .. k0x+n-1 (columns), k0y .. k0y+n-1 (rows) of the box: tcol[i] = 3 * column, trow[i] = row.
+// n <= kPixMaxP, 2n <= kPixLT.
+__device__ __forceinline__ void pix_tables(int *tcol, int *trow, int x1, int y1, int w, int h, int S, int k0x, int k0y, int n, int H,
+                                           int W)
 {
     const int tid = threadIdx.x;
     if (tid < 2 * n) {
         const bool isrow = tid >= n;
         const int i = isrow ? tid - n : tid;
-        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W;
+        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W, k0 = isrow ? k0y : k0x;
         int v = o + pix_floordiv((2 * (k0 + i) + 1) * e, 2 * S);
         v = v < 0 ? 0 : (v > lim - 1 ? lim - 1 : v);
         if (isrow) trow[i] = v;
@@ -176,16 +201,16 @@ __device__ __forceinline__ void pix_gather(uint32_t *dst, int pitch, const int *
     }
 }
 
-// box sampling: the edges of the cells k = k0 .. k0+n-1 of the box, ca/cb[i] = a'/b' of the columns, ra/rb[i] of the rows.
-// |k| <= 80 and e <= 2^21 + 1: the products stay below 2^28.  n <= kPixMaxP, 2n <= kPixLT.
-__device__ __forceinline__ void pix_tables_box(int *ca, int *cb, int *ra, int *rb, int x1, int y1, int w, int h, int S, int k0, int n,
-                                               int H, int W)
+// box sampling: the edges of the cells k = k0x .. k0x+n-1 (columns), k0y .. k0y+n-1 (rows) of the box, ca/cb[i] = a'/b' of the
+// columns, ra/rb[i] of the rows.  |k| <= 80 and e <= 2^21 + 1: the products stay below 2^28.  n <= kPixMaxP, 2n <= kPixLT.
+__device__ __forceinline__ void pix_tables_box(int *ca, int *cb, int *ra, int *rb, int x1, int y1, int w, int h, int S, int k0x, int k0y,
+                                               int n, int H, int W)
 {
     const int tid = threadIdx.x;
     if (tid < 2 * n) {
         const bool isrow = tid >= n;
         const int i = isrow ? tid - n : tid;
-        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W;
+        const int o = isrow ? y1 : x1, e = isrow ? h : w, lim = isrow ? H : W, k0 = isrow ? k0y : k0x;
         int lo = o + pix_floordiv((k0 + i) * e, S), hi = o + pix_floordiv((k0 + i + 1) * e, S);
         lo = lo < 0 ? 0 : (lo > lim - 1 ? lim - 1 : lo);
         hi = hi < lo + 1 ? lo + 1 : hi;
@@ -234,10 +259,13 @@ __device__ __forceinline__ void pix_no_rows(float *trk, int F)
 // afterwards.  Reads of a: images, F, H, W, S, R, min_conf, reach, step.  Block-uniform control flow.
 // SCALED: the scale search over the levels -sc.ns .. sc.ns (see the top of this file); otherwise sc is not read.
 // BOX: box sampling from the integral a.images carries (see the top of this file).
-template <bool SCALED, bool BOX = false>
+// ADAPT: the template update with the anchor guard (see the top of this file); otherwise ad is not read.
+template <bool SCALED, bool BOX = false, bool ADAPT = false>
 __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, const int af, const int4 ab, const int dir,
-                                          const PixScaleArgs sc)
+                                          const PixScaleArgs sc, const PixAdaptArgs ad = PixAdaptArgs{0, 0.0f, 0.0f})
 {
+    static_assert(SCALED || !ADAPT, "the adaptive chain always runs the level loop");
+    __shared__ uint32_t ssad0[ADAPT ? kPixWaves : 1];           // (ADAPT) the guard's SAD, a slot per wave
     __shared__ uint32_t sreg[kPixMaxP * kPixMaxPitch];
     __shared__ uint32_t stm[kPixMaxS * (kPixMaxS / 4)];
     __shared__ int tcol[kPixMaxP], trow[kPixMaxP];
@@ -259,16 +287,31 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
     const int P = S + 2 * R, pitch = P / 4 + 1, tq = S / 4, side = 2 * R + 1, ncand = side * side;
     // the template
     if constexpr (BOX) {
-        pix_tables_box(tcol, tcolb, trow, trowb, x1, y1, w, h, S, 0, S, H, W);
+        pix_tables_box(tcol, tcolb, trow, trowb, x1, y1, w, h, S, 0, 0, S, H, W);
         __syncthreads();
         pix_gather_box(stm, tq, tcol, tcolb, trow, trowb, S, integ + (int64_t)af * frame_cells, W + 1);
     } else {
-        pix_tables(tcol, trow, x1, y1, w, h, S, 0, S, H, W);
+        pix_tables(tcol, trow, x1, y1, w, h, S, 0, 0, S, H, W);
         __syncthreads();
         pix_gather(stm, tq, tcol, trow, S, a.images + (int64_t)af * frame_bytes, W);
     }
     __syncthreads();
     const float denom = (float)(255 * S * S);
+    // (ADAPT) the chain's state, in the registers of the thread that owns the cells: thread t owns the template dwords
+    // t, t + 256, ... (kPixOwn of them at S = 64; none beyond S*S/4), that is four cells a dword.  tm0: the anchor's template
+    // Tm0, as gathered; acc: A in 8.8, cells 0|1 and 2|3 of a dword packed in 16-bit halves.  Every loop over them is fully
+    // unrolled, so the arrays are registers.
+    uint32_t tm0[ADAPT ? kPixOwn : 1], acc[ADAPT ? 2 * kPixOwn : 1];
+    if constexpr (ADAPT) {
+#pragma unroll
+        for (int k = 0; k < kPixOwn; ++k) {
+            const int d = tid + k * kPixLT;
+            const uint32_t v = d < S * tq ? stm[d] : 0u;
+            tm0[k] = v;
+            acc[2 * k] = ((v & 0xFFu) << 8) | ((v & 0xFF00u) << 16);
+            acc[2 * k + 1] = ((v >> 8) & 0xFF00u) | (v & 0xFF000000u);
+        }
+    }
 
     int n = 0;                   // steps taken so far (block-uniform)
     for (int s = 1; s <= a.reach; ++s) {
@@ -294,11 +337,11 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
             // left at the barrier behind it, and the barrier behind these tables stands between the previous level's SAD reads
             // of the region and this level's gather, which overwrites it)
             if constexpr (BOX) {
-                pix_tables_box(tcol, tcolb, trow, trowb, lx1, ly1, lw, lh, S, -R, P, H, W);
+                pix_tables_box(tcol, tcolb, trow, trowb, lx1, ly1, lw, lh, S, -R, -R, P, H, W);
                 __syncthreads();
                 pix_gather_box(sreg, pitch, tcol, tcolb, trow, trowb, P, integ + (int64_t)g * frame_cells, W + 1);
             } else {
-                pix_tables(tcol, trow, lx1, ly1, lw, lh, S, -R, P, H, W);
+                pix_tables(tcol, trow, lx1, ly1, lw, lh, S, -R, -R, P, H, W);
                 __syncthreads();
                 pix_gather(sreg, pitch, tcol, trow, P, a.images + (int64_t)g * frame_bytes, W);
             }
@@ -376,6 +419,87 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
             r[0] = (float)(x1 + 1); r[1] = (float)(y1 + 1); r[2] = (float)(x1 + w); r[3] = (float)(y1 + h); r[4] = conf;
         }
         n = s;
+        if constexpr (ADAPT) {
+            // The template update.  Every condition below is block-uniform: ad and conf are, c0 is read by every thread from
+            // the same LDS slots.  (conf < update_conf skips the guard: it could not change the decision.)
+            if (ad.a > 0 && conf >= ad.update_conf) {
+                // P, the window that won: cells dx .. dx+S-1 by dy .. dy+S-1 of the winner's level box on frame g.  It is in
+                // sreg, at row R+dy and byte R+dx of the region, when the winner's level is ns, the one the loop gathered last
+                // (a winner was admissible); otherwise -- also when level ns was skipped -- the S x S window is gathered again
+                // at the head of sreg (pitch tq, byte shift 0).
+                const int udy = __builtin_amdgcn_readfirstlane(dy), udx = __builtin_amdgcn_readfirstlane(dx);
+                const int lwin = __builtin_amdgcn_readfirstlane((int)((uint32_t)key & 7u) - kPixMaxScales);
+                int pbase = (udy + R) * pitch + ((udx + R) >> 2), ppitch = pitch, psh = (udx + R) & 3;
+                if (lwin != ns) {
+                    // (the winner's level box before the move: the move, taken back)
+                    const int bx1 = x1 - pix_floordiv(2 * udx * w + S, 2 * S), by1 = y1 - pix_floordiv(2 * udy * h + S, 2 * S);
+                    // Hazards of the re-gather: the tables' last readers (the last level's gather) and sreg's last readers
+                    // (the last level's SAD pass) are behind the barrier of the key reduction above, which every thread has
+                    // passed; the barrier behind the tables orders them before the gather, the one behind the gather orders
+                    // sreg before the reads of P below.
+                    if constexpr (BOX) {
+                        pix_tables_box(tcol, tcolb, trow, trowb, bx1, by1, w, h, S, udx, udy, S, H, W);
+                        __syncthreads();
+                        pix_gather_box(sreg, tq, tcol, tcolb, trow, trowb, S, integ + (int64_t)g * frame_cells, W + 1);
+                    } else {
+                        pix_tables(tcol, trow, bx1, by1, w, h, S, udx, udy, S, H, W);
+                        __syncthreads();
+                        pix_gather(sreg, tq, tcol, trow, S, a.images + (int64_t)g * frame_bytes, W);
+                    }
+                    __syncthreads();
+                    pbase = 0;
+                    ppitch = tq;
+                    psh = 0;
+                }
+                // the guard: SAD0 = sum |Tm0 - P|, every thread over the cells it owns, then over the block
+                uint32_t pw[kPixOwn], sad0 = 0;
+#pragma unroll
+                for (int k = 0; k < kPixOwn; ++k) {
+                    const int d = tid + k * kPixLT;
+                    pw[k] = 0;
+                    if (d < S * tq) {
+                        const int i = d / tq, o = pbase + i * ppitch + (d - i * tq);
+                        const uint32_t lo = sreg[o], hi = psh ? sreg[o + 1] : 0u;       // (o + 1: the row's spare dword at most)
+                        pw[k] = __builtin_amdgcn_alignbyte(hi, lo, psh);
+                        sad0 = __builtin_amdgcn_sad_u8(tm0[k], pw[k], sad0);
+                    }
+                }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) sad0 += __shfl_xor(sad0, d, 64);
+                // ssad0 is single-buffered: its readers of the last accepted-or-refused update are behind the barriers of
+                // this step's tables and gather
+                if (lane == 0) ssad0[wv] = sad0;
+                __syncthreads();
+                sad0 = ssad0[0];
+#pragma unroll
+                for (int k = 1; k < kPixWaves; ++k) sad0 += ssad0[k];
+                const float c0 = 1.0f - (float)sad0 / denom;
+                if (c0 >= ad.drift_conf) {
+                    // A = ((256 - a) * A + a * (P << 8) + 128) >> 8 on the cells the thread owns, and Tm = (A + 128) >> 8 into
+                    // its own dwords of stm.  Hazards: the last SAD pass that read stm is behind the barrier of the key
+                    // reduction (and the guard's); the next step's SAD pass is behind the two barriers of its tables and
+                    // gather, which follow these writes.
+                    const uint32_t wa = (uint32_t)ad.a, wk = 256u - wa;
+#pragma unroll
+                    for (int k = 0; k < kPixOwn; ++k) {
+                        const int d = tid + k * kPixLT;
+                        if (d < S * tq) {
+                            uint32_t tmv = 0;
+#pragma unroll
+                            for (int b = 0; b < 4; ++b) {
+                                const int sft = 16 * (b & 1);
+                                uint32_t &pair = acc[2 * k + (b >> 1)];
+                                const uint32_t av = (pair >> sft) & 0xFFFFu, pv = (pw[k] >> (8 * b)) & 0xFFu;
+                                const uint32_t nv = (wk * av + wa * (pv << 8) + 128u) >> 8;      // <= 256 * 65280 + 128
+                                pair = (pair & ~(0xFFFFu << sft)) | (nv << sft);
+                                tmv |= ((nv + 128u) >> 8) << (8 * b);
+                            }
+                            stm[d] = tmv;
+                        }
+                    }
+                }
+            }
+        }
     }
     // the rows of this half the chain did not write: beyond its end, and the frames a step > 1 skips
     const int nf = dir > 0 ? F - 1 - af : af;         // frames of the half, at distance 1 .. nf from the anchor
@@ -388,8 +512,9 @@ __device__ __forceinline__ void pix_chain(const PixTrackArgs &a, float *trk, con
 
 // grid (C*T, 2): blockIdx.y = 0 tracks forward (and owns the slot's anchor row, its anchors entry, a dead slot's rows and --
 // slot 0 of a class -- the class's ntracks), 1 backward.  The body of track_pixels_kernel and track_pixels_scaled_kernel.
-template <bool SCALED, bool BOX = false>
-__device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixScaleArgs sc)
+template <bool SCALED, bool BOX = false, bool ADAPT = false>
+__device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixScaleArgs sc,
+                                               const PixAdaptArgs ad = PixAdaptArgs{0, 0.0f, 0.0f})
 {
     __shared__ int snt;
     const int tid = threadIdx.x;
@@ -426,7 +551,8 @@ __device__ __forceinline__ void pix_slots_body(const PixTrackArgs &a, const PixS
         if (dir > 0) pix_no_rows(trk, F);
         return;
     }
-    pix_chain<SCALED, BOX>(a, trk, af, ab, dir, sc);
+    if constexpr (ADAPT) pix_chain<SCALED, BOX, true>(a, trk, af, ab, dir, sc, ad);
+    else pix_chain<SCALED, BOX>(a, trk, af, ab, dir, sc);
 }
 
 __global__ __launch_bounds__(kPixLT) void track_pixels_kernel(const PixTrackArgs a)
@@ -452,10 +578,10 @@ __global__ __launch_bounds__(kPixLT) void track_pixels_box_kernel(const PixTrack
 // which this launch writes exactly once.  A class that is not active returns at once.  An anchor that cannot be tracked
 // (pix_box_state) latches kStBadPixAnchor and leaves a slot of NaN rows: the loop goes on and nothing is suppressed by it.
 // Reads of a: what pix_chain reads.  The body of track_pixel_chain_kernel and track_pixel_chain_scaled_kernel.
-template <bool SCALED, bool BOX = false>
+template <bool SCALED, bool BOX = false, bool ADAPT = false>
 __device__ __forceinline__ void pix_greedy_body(const PixTrackArgs &a, const PixScaleArgs sc, const TrackState *__restrict__ st,
                                                 const float *__restrict__ boxes, int B, int max_tracks, float *__restrict__ tracks,
-                                                int *status)
+                                                int *status, const PixAdaptArgs ad = PixAdaptArgs{0, 0.0f, 0.0f})
 {
     const int c = blockIdx.x;
     const int dir = blockIdx.y == 0 ? 1 : -1;
@@ -470,7 +596,8 @@ __device__ __forceinline__ void pix_greedy_body(const PixTrackArgs &a, const Pix
         }
         return;
     }
-    pix_chain<SCALED, BOX>(a, trk, s.anchor_frame, ab, dir, sc);
+    if constexpr (ADAPT) pix_chain<SCALED, BOX, true>(a, trk, s.anchor_frame, ab, dir, sc, ad);
+    else pix_chain<SCALED, BOX>(a, trk, s.anchor_frame, ab, dir, sc);
 }
 
 __global__ __launch_bounds__(kPixLT) void track_pixel_chain_kernel(const PixTrackArgs a, const TrackState *__restrict__ st,
@@ -496,6 +623,36 @@ __global__ __launch_bounds__(kPixLT) void track_pixel_chain_box_kernel(const Pix
                                                                        float *__restrict__ tracks, int *status)
 {
     pix_greedy_body<true, true>(a, sc, st, boxes, B, max_tracks, tracks, status);
+}
+
+// vdet_track_pixels_adaptive / vdet_track_volume_pixels_adaptive: the same launches with the template update in every chain, for
+// point sampling (a.images: the images) and box sampling (a.images: the integral); sc.ns = 0: the fixed scale
+__global__ __launch_bounds__(kPixLT) void track_pixels_adaptive_kernel(const PixTrackArgs a, const PixScaleArgs sc, const PixAdaptArgs ad)
+{
+    pix_slots_body<true, false, true>(a, sc, ad);
+}
+
+__global__ __launch_bounds__(kPixLT) void track_pixels_adaptive_box_kernel(const PixTrackArgs a, const PixScaleArgs sc,
+                                                                           const PixAdaptArgs ad)
+{
+    pix_slots_body<true, true, true>(a, sc, ad);
+}
+
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_adaptive_kernel(const PixTrackArgs a, const PixScaleArgs sc,
+                                                                            const PixAdaptArgs ad, const TrackState *__restrict__ st,
+                                                                            const float *__restrict__ boxes, int B, int max_tracks,
+                                                                            float *__restrict__ tracks, int *status)
+{
+    pix_greedy_body<true, false, true>(a, sc, st, boxes, B, max_tracks, tracks, status, ad);
+}
+
+__global__ __launch_bounds__(kPixLT) void track_pixel_chain_adaptive_box_kernel(const PixTrackArgs a, const PixScaleArgs sc,
+                                                                                const PixAdaptArgs ad,
+                                                                                const TrackState *__restrict__ st,
+                                                                                const float *__restrict__ boxes, int B, int max_tracks,
+                                                                                float *__restrict__ tracks, int *status)
+{
+    pix_greedy_body<true, true, true>(a, sc, st, boxes, B, max_tracks, tracks, status, ad);
 }
 
 // ---- the integral image of the luma (vdet_luma_integral): uint8 [F,H,W,3] -> uint32 [F,H+1,W+1], two launches that between

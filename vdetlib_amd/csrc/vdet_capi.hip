@@ -4130,12 +4130,21 @@ static int pix_box_check(vdet_ctx *c, int64_t H, int64_t W)
     return VDET_OK;
 }
 
+// the template update's settings (vdet_track_pixels_adaptive, vdet_track_volume_pixels_adaptive; tests/pixtrack_adapt_spec.py)
+static int pix_adapt_check(vdet_ctx *c, int box, int update, double update_conf, double drift_conf)
+{
+    if (box != 0 && box != 1) return fail(c, VDET_EINVAL, "box = %d; 0 (images) or 1 (integral)", box);
+    if (update < 0 || update > 256) return fail(c, VDET_EINVAL, "update = %d; 0 .. 256", update);
+    if (!std::isfinite(update_conf) || !std::isfinite(drift_conf)) return fail(c, VDET_EINVAL, "update_conf and drift_conf must be finite");
+    return VDET_OK;
+}
+
 // vdet_track_pixels (sc null), vdet_track_pixels_scaled and -- box: d_images is the integral uint32 [F,H+1,W+1], sc is given --
-// vdet_track_pixels_box; the settings' checks are pix_settings_check's
+// vdet_track_pixels_box; ad given (with sc): vdet_track_pixels_adaptive.  The settings' checks are pix_settings_check's
 static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, const int32_t *d_anchor_frames,
                              const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, int S, int R, double min_conf,
                              int max_frames, int step, const PixScaleArgs *sc, float *d_tracks, float *d_anchors, int32_t *d_ntracks,
-                             bool box = false)
+                             bool box = false, const PixAdaptArgs *ad = nullptr)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -4162,7 +4171,9 @@ static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
     a.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_OTHER);
-        if (box) hipLaunchKernelGGL(track_pixels_box_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
+        if (ad && box) hipLaunchKernelGGL(track_pixels_adaptive_box_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc, *ad);
+        else if (ad) hipLaunchKernelGGL(track_pixels_adaptive_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc, *ad);
+        else if (box) hipLaunchKernelGGL(track_pixels_box_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
         else if (sc) hipLaunchKernelGGL(track_pixels_scaled_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a, *sc);
         else hipLaunchKernelGGL(track_pixels_kernel, dim3((unsigned)(C * T), 2), dim3(kPixLT), 0, c->stream, a);
     }
@@ -4224,6 +4235,20 @@ int vdet_track_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_t F, in
                              C, T, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, true);
 }
 
+int vdet_track_pixels_adaptive(vdet_ctx *c, const void *d_planes, int box, int64_t F, int64_t H, int64_t W,
+                               const int32_t *d_anchor_frames, const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C,
+                               int T, int S, int R, double min_conf, int max_frames, int step, int scales, int scale_step,
+                               int scale_penalty, int update, double update_conf, double drift_conf, float *d_tracks,
+                               float *d_anchors, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (pix_adapt_check(c, box, update, update_conf, drift_conf)) return VDET_EINVAL;
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    const PixAdaptArgs ad{update, (float)update_conf, (float)drift_conf};
+    return track_pixels_impl(c, static_cast<const uint8_t *>(d_planes), F, H, W, d_anchor_frames, d_anchor_boxes, d_anchor_scores, C, T,
+                             S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, box == 1, &ad);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
@@ -4232,11 +4257,11 @@ int vdet_track_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_t F, in
 // pixtrack_kernels.hpp's chains as the tracker.  Three launches per track, no host wait.
 // ---------------------------------------------------------------------------------------------
 // vdet_track_volume_pixels (sc null), vdet_track_volume_pixels_scaled and -- box: d_images is the integral uint32 [F,H+1,W+1], sc
-// is given -- vdet_track_volume_pixels_box
+// is given -- vdet_track_volume_pixels_box; ad given (with sc): vdet_track_volume_pixels_adaptive
 static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t H, int64_t W, const float *d_boxes, const float *d_scores,
                                     int64_t F, int64_t B, int64_t C, double nms_thres, double thres, int max_tracks, int S, int R,
                                     double min_conf, int max_frames, int step, const PixScaleArgs *sc, float *d_tracks,
-                                    float *d_anchors, int32_t *d_ntracks, bool box = false)
+                                    float *d_anchors, int32_t *d_ntracks, bool box = false, const PixAdaptArgs *ad = nullptr)
 {
     if (!c) return VDET_EINVAL;
     if (F <= 0 || B <= 0 || C <= 0 || max_tracks < 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -4265,7 +4290,12 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
         StageTimer tm(c, ST_TLOOP);
         for (int t = 0; t < max_tracks; ++t) {
             hipLaunchKernelGGL(track_pick_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, g.la, g.lz, g.sp);
-            if (box) hipLaunchKernelGGL(track_pixel_chain_box_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
+            if (ad && box) hipLaunchKernelGGL(track_pixel_chain_adaptive_box_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa,
+                                              *sc, *ad, (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks,
+                                              &c->d_cnt->status);
+            else if (ad) hipLaunchKernelGGL(track_pixel_chain_adaptive_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
+                                            *ad, (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
+            else if (box) hipLaunchKernelGGL(track_pixel_chain_box_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
                                         (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
             else if (sc) hipLaunchKernelGGL(track_pixel_chain_scaled_kernel, dim3((unsigned)C, 2), dim3(kPixLT), 0, c->stream, pa, *sc,
                                        (const TrackState *)g.sp.st, d_boxes, (int)B, max_tracks, d_tracks, &c->d_cnt->status);
@@ -4306,6 +4336,20 @@ int vdet_track_volume_pixels_box(vdet_ctx *c, const uint32_t *d_integral, int64_
     const PixScaleArgs sc{scales, scale_step, scale_penalty};
     return track_volume_pixels_impl(c, reinterpret_cast<const uint8_t *>(d_integral), H, W, d_boxes, d_scores, F, B, C, nms_thres, thres,
                                     max_tracks, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, true);
+}
+
+int vdet_track_volume_pixels_adaptive(vdet_ctx *c, const void *d_planes, int box, int64_t H, int64_t W, const float *d_boxes,
+                                      const float *d_scores, int64_t F, int64_t B, int64_t C, double nms_thres, double thres,
+                                      int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
+                                      int scale_step, int scale_penalty, int update, double update_conf, double drift_conf,
+                                      float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (pix_adapt_check(c, box, update, update_conf, drift_conf)) return VDET_EINVAL;
+    const PixScaleArgs sc{scales, scale_step, scale_penalty};
+    const PixAdaptArgs ad{update, (float)update_conf, (float)drift_conf};
+    return track_volume_pixels_impl(c, static_cast<const uint8_t *>(d_planes), H, W, d_boxes, d_scores, F, B, C, nms_thres, thres,
+                                    max_tracks, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, box == 1, &ad);
 }
 
 }  // extern "C"

@@ -746,6 +746,39 @@ def _box_option(impl):
     return decorate
 
 
+def _update_option(impl):
+    """Gives a pixel-tracker call the three KEYWORD-ONLY options of the template update, ``update=0``, ``update_conf=0.8`` and
+    ``drift_conf=0.7``, by ``_box_option``'s mechanism and on top of it (the visible signature stays the call's own).  The
+    three are checked on every call; with ``update == 0`` the call then runs as it does without them, else its bound arguments
+    go to ``impl()(scale, ..., sampling=, integral=, adapt=(update, update_conf, drift_conf))``."""
+    def decorate(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def call(*args, update=0, update_conf=0.8, drift_conf=0.7, sampling='point', integral=None, **kw):
+            adapt = _update_settings(update, update_conf, drift_conf)
+            if adapt[0] == 0:
+                return fn(*args, sampling=sampling, integral=integral, **kw)
+            bound = sig.bind(*args, **kw)
+            bound.apply_defaults()
+            a = dict(bound.arguments)
+            scale = (a.pop('scales'), a.pop('scale_step'), a.pop('scale_penalty')) if 'scales' in a else None
+            return impl()(scale, sampling=sampling, integral=integral, adapt=adapt, **a)
+        return call
+    return decorate
+
+
+def _update_settings(update, update_conf, drift_conf):
+    """the three checked settings of the template update"""
+    update, update_conf, drift_conf = int(update), float(update_conf), float(drift_conf)
+    if not 0 <= update <= 256:
+        raise ValueError("update = %d; 0 .. 256" % update)
+    if not math.isfinite(update_conf) or not math.isfinite(drift_conf):
+        raise ValueError("update_conf and drift_conf must be finite")
+    return update, update_conf, drift_conf
+
+
+@_update_option(lambda: _track_pixels)
 @_box_option(lambda: _track_pixels)
 def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
                  sync=True, ctx=None):
@@ -772,7 +805,20 @@ def track_pixels(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=3
     ``luma_integral`` (uint32 [F,H+1,W+1], contiguous, on the images' GPU): given, the images are read for their shape only;
     None, the call builds one (two more launches).  Frames of at most 2^24 pixels.  With w == h == grid the bits are
     ``sampling='point'``'s.  ValueError (before any launch) for another ``sampling``, an integral of the wrong dtype, shape or
-    device, an integral given with 'point', and H*W > 2^24 with 'box'."""
+    device, an integral given with 'point', and H*W > 2^24 with 'box'.
+
+    Keyword-only: ``update=0, update_conf=0.8, drift_conf=0.7``, the template update with an anchor guard (the rule is
+    tests/pixtrack_adapt_spec.py; vdet_track_pixels_adaptive).  ``update`` = a in 0 .. 256 is the weight of the new patch in
+    1/256; 0: the fixed template, this call as it is without the three keywords, same export, same bits.  With a > 0 every
+    chain (slot AND direction; the backward chain starts from the anchor's template again) keeps A[grid,grid] in 8.8 fixed
+    point, A = Tm0 << 8 at the start, and matches against Tm = (A + 128) >> 8.  After a step the chain keeps, with P the
+    grid x grid window that won (on the winner's level box, before the move): c0 = 1 - sum|Tm0 - P| / (255 * grid^2) in f32;
+    the update is accepted when conf >= update_conf and c0 >= drift_conf (f32 compares), and then
+    A = ((256 - a) * A + a * (P << 8) + 128) >> 8 per cell.  a = 256 replaces the template every frame.  The confidence in
+    column 4 is the step's, against the current template; no output is added.  An update_conf or drift_conf no step reaches
+    (2.0) gives the fixed template's bits.  The guard keeps the template from absorbing something that is not the anchor's
+    object.  The two default confidences are starting points that nobody has tuned on real video.  ValueError (before any
+    launch) for update outside 0 .. 256 or a confidence that is not finite."""
     return _track_pixels(None, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx)
 
 
@@ -788,10 +834,13 @@ def _scale_settings(scales, scale_step, scale_penalty):
     return scales, scale_step, scale_penalty
 
 
-def _pixel_export(ctx, stem, box, scale):
+def _pixel_export(ctx, stem, box, scale, adapt=None):
     """The export a pixel-tracker call ends in, and the arguments it takes between the settings and the outputs: ``stem`` +
     '_box' with the scale settings (scale None: scales = 0) where ``box``, else ``stem`` itself with none (scale None) or
-    ``stem`` + '_scaled' with ``scale``"""
+    ``stem`` + '_scaled' with ``scale``.  With ``adapt`` (the template update's checked settings): ``stem`` + '_adaptive', with
+    the scale settings and ``adapt``; its ``box`` argument follows the planes (``_pixel_planes``)"""
+    if adapt:
+        return getattr(ctx.lib, stem + '_adaptive'), (scale or (0, 1, 0)) + adapt
     if box:
         return getattr(ctx.lib, stem + '_box'), scale or (0, 1, 0)
     if scale is None:
@@ -799,10 +848,16 @@ def _pixel_export(ctx, stem, box, scale):
     return getattr(ctx.lib, stem + '_scaled'), scale
 
 
+def _pixel_planes(images, integral, box, adapt):
+    """the arguments between the context and the shape: the planes a chain reads, and -- for the '_adaptive' exports -- ``box``"""
+    planes = (integral.data_ptr() if box else images.data_ptr(),)
+    return planes + (int(box),) if adapt else planes
+
+
 def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, grid, radius, min_conf, max_frames, step, sync, ctx,
-                  sampling='point', integral=None):
+                  sampling='point', integral=None, adapt=None):
     """track_pixels (scale None) and track_pixels_scaled (scale = (scales, scale_step, scale_penalty)); with sampling='box'
-    both are vdet_track_pixels_box (scale None: scales = 0)"""
+    both are vdet_track_pixels_box (scale None: scales = 0); with ``adapt`` vdet_track_pixels_adaptive"""
     F, H, W = _images(images)
     box = _pixel_sampling(sampling, integral, images, F, H, W)
     anchor_frames, anchor_boxes, anchor_scores, C, T = _anchor_slots(anchor_frames, anchor_boxes, anchor_scores)
@@ -815,16 +870,18 @@ def _track_pixels(scale, images, anchor_frames, anchor_boxes, anchor_scores, gri
     if box and integral is None:
         integral = luma_integral(images, sync=False, ctx=ctx)
     tracks, anchors, ntracks = _track_outputs(C, T, F, images.device, False)
-    head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
-            anchor_scores.data_ptr() if anchor_scores is not None else None, C, T) + settings
+    head = (ctx.h,) + _pixel_planes(images, integral, box, adapt) + (
+        F, H, W, anchor_frames.data_ptr(), anchor_boxes.data_ptr(),
+        anchor_scores.data_ptr() if anchor_scores is not None else None, C, T) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    fn, extra = _pixel_export(ctx, 'vdet_track_pixels', box, scale)
+    fn, extra = _pixel_export(ctx, 'vdet_track_pixels', box, scale, adapt)
     ctx.check(fn(*(head + extra + out)))
     if sync:
         ctx.sync()
     return tracks, anchors, ntracks
 
 
+@_update_option(lambda: _track_pixels)
 @_box_option(lambda: _track_pixels)
 def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None, grid=32, radius=8, min_conf=0.5, max_frames=0, step=1,
                         scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
@@ -836,11 +893,15 @@ def track_pixels_scaled(images, anchor_frames, anchor_boxes, anchor_scores=None,
     raw SAD's, and the winner's box, moved, is the next box.  A level whose box would have a side below 1 or above 2^21 is
     skipped.  ``scales = 0`` gives ``track_pixels``' bits.  Arguments, layouts and errors are ``track_pixels``'; in addition
     ValueError for scales outside 0..3, scale_step outside 1..25 or scale_penalty outside 0..65535 (before any launch).
-    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``; every level's cells are box-filtered."""
+    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``; every level's cells are box-filtered.
+    Keyword-only ``update`` / ``update_conf`` / ``drift_conf``: the template update with an anchor guard, as in ``track_pixels``
+    (vdet_track_pixels_adaptive); the patch is the winning window of the winner's level box.  The two default confidences are
+    starting points that nobody has tuned on real video."""
     return _track_pixels((scales, scale_step, scale_penalty), images, anchor_frames, anchor_boxes, anchor_scores, grid, radius,
                          min_conf, max_frames, step, sync, ctx)
 
 
+@_update_option(lambda: _track_volume_pixels)
 @_box_option(lambda: _track_volume_pixels)
 def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
                         max_frames=0, step=1, sync=True, ctx=None):
@@ -859,15 +920,19 @@ def track_volume_pixels(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tra
     ValueError for the arguments ``track_volume`` and ``track_pixels`` refuse (before any launch); and for an anchor whose box
     is not finite, beyond 2^20, empty after truncation or wholly outside the image (reported when the call, or a later
     ``ctx.sync()``, waits): its slot is taken with NaN rows, it suppresses nothing, and the loop goes on.
-    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels`` (include/vdet_hip.h: vdet_track_volume_pixels_box)."""
+    Keyword-only ``sampling`` / ``integral``: as in ``track_pixels`` (include/vdet_hip.h: vdet_track_volume_pixels_box).
+    Keyword-only ``update`` / ``update_conf`` / ``drift_conf``: the template update with an anchor guard in every tubelet's
+    chains, as in ``track_pixels`` (vdet_track_volume_pixels_adaptive; 0: this call as it is).  The two default confidences
+    are starting points that nobody has tuned on real video."""
     return _track_volume_pixels(None, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step,
                                 sync, ctx)
 
 
 def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tracks, grid, radius, min_conf, max_frames, step, sync,
-                         ctx, sampling='point', integral=None):
+                         ctx, sampling='point', integral=None, adapt=None):
     """track_volume_pixels (scale None) and track_volume_pixels_scaled (scale = (scales, scale_step, scale_penalty)); with
-    sampling='box' both are vdet_track_volume_pixels_box (scale None: scales = 0)"""
+    sampling='box' both are vdet_track_volume_pixels_box (scale None: scales = 0); with ``adapt``
+    vdet_track_volume_pixels_adaptive"""
     F, H, W = _images(images)
     box = _pixel_sampling(sampling, integral, images, F, H, W)
     max_tracks = int(max_tracks)
@@ -881,14 +946,15 @@ def _track_volume_pixels(scale, images, boxes, scores, nms_thres, thres, max_tra
     if box and integral is None:
         integral = luma_integral(images, sync=False, ctx=ctx)
     tracks, anchors, ntracks = _track_outputs(C, max_tracks, F, images.device, True)
-    head = (ctx.h, integral.data_ptr() if box else images.data_ptr(), H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres),
-            max_tracks) + settings
+    head = (ctx.h,) + _pixel_planes(images, integral, box, adapt) + (
+        H, W, boxes.data_ptr(), scores.data_ptr(), F, B, C, float(nms_thres), float(thres), max_tracks) + settings
     out = (tracks.data_ptr(), anchors.data_ptr(), ntracks.data_ptr())
-    fn, extra = _pixel_export(ctx, 'vdet_track_volume_pixels', box, scale)
+    fn, extra = _pixel_export(ctx, 'vdet_track_volume_pixels', box, scale, adapt)
     _finish(ctx, lambda: ctx.check(fn(*(head + extra + out))), sync, reset=lambda: (tracks.fill_(float('nan')), anchors.zero_()))
     return tracks, anchors, ntracks
 
 
+@_update_option(lambda: _track_volume_pixels)
 @_box_option(lambda: _track_volume_pixels)
 def track_volume_pixels_scaled(images, boxes, scores, nms_thres=0.3, thres=0.0, max_tracks=10, grid=32, radius=8, min_conf=0.5,
                                max_frames=0, step=1, scales=1, scale_step=5, scale_penalty=0, sync=True, ctx=None):
@@ -896,7 +962,9 @@ def track_volume_pixels_scaled(images, boxes, scores, nms_thres=0.3, thres=0.0, 
     explains has a box that follows the object's size (include/vdet_hip.h: vdet_track_volume_pixels_scaled; the rule is the
     greedy loop of tests/pixtrack_spec.py).  ``scales = 0`` gives ``track_volume_pixels``' bits.  Arguments, layouts,
     launches and errors are ``track_volume_pixels``'; in addition ValueError for scales outside 0..3, scale_step outside 1..25
-    or scale_penalty outside 0..65535 (before any launch).  Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``."""
+    or scale_penalty outside 0..65535 (before any launch).  Keyword-only ``sampling`` / ``integral``: as in ``track_pixels``.
+    Keyword-only ``update`` / ``update_conf`` / ``drift_conf``: as in ``track_volume_pixels``
+    (vdet_track_volume_pixels_adaptive); the two default confidences are starting points that nobody has tuned on real video."""
     return _track_volume_pixels((scales, scale_step, scale_penalty), images, boxes, scores, nms_thres, thres, max_tracks, grid,
                                 radius, min_conf, max_frames, step, sync, ctx)
 

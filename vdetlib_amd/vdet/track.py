@@ -64,8 +64,9 @@ def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     and the optional ``opts.grid`` / ``opts.radius`` / ``opts.min_conf``.  With ``opts.scales`` > 0 the box follows the object's
     size (ops.track_pixels_scaled, with the optional ``opts.scale_step`` / ``opts.scale_penalty``); absent or 0: the fixed-scale
     call, unchanged.  ``opts.sampling`` = 'box' box-filters every cell (ops.track_pixels' ``sampling``; the video's integral
-    image is built once and kept beside its frames); absent or 'point': point sampling, unchanged.  The frames are uploaded once
-    per video (a module
+    image is built once and kept beside its frames); absent or 'point': point sampling, unchanged.  ``opts.update`` > 0 updates
+    the template with an anchor guard (ops.track_pixels' ``update``, with the optional ``opts.update_conf`` /
+    ``opts.drift_conf``); absent or 0: the fixed template, unchanged.  The frames are uploaded once per video (a module
     cache keyed by the video's name and frame count).  Returns ``tracks_proto_from_boxes`` over the visited frames only, with
     fcn_tracker's ``start_frame`` and ``step`` (:100-102)."""
     import torch
@@ -85,6 +86,9 @@ def pixel_tracker(vid_proto, anchor_frame_id, bbox, opts):
     sampling = getattr(opts, 'sampling', None)
     if sampling is not None and sampling != 'point':
         scale = dict(scale, sampling=sampling, integral=_pixel_integral(images) if sampling == 'box' else None)
+    update = getattr(opts, 'update', None)
+    if update:
+        scale = dict(scale, update=update, update_conf=getattr(opts, 'update_conf', 0.8), drift_conf=getattr(opts, 'drift_conf', 0.7))
     tracks, _, _ = track(
         images, torch.tensor([[pos + 1]], dtype=torch.int32, device=dev),
         torch.tensor([[[float(v) for v in bbox]]], dtype=torch.float32, device=dev), None,
