@@ -110,6 +110,17 @@
  *                                                                     VDET_EINVAL; bad anchor data as in the siblings.  A
  *                                                                     confidence no step reaches (2.0) is the fixed template,
  *                                                                     never an error
+ *   block-motion field                     (vdet_motion_field) block 8, 16 or 32, 1 <= radius <= 16, H, W <= 32767, every output
+ *                                          below 2^31 - 16 elements (the largest: 2*F*(Hb+1)*(Wb+1)*2)      VDET_EINVAL.  One path
+ *                                                                     for every size
+ *   summed table of a motion field         (vdet_motion_table) 1 <= Hb, Wb <= 4096, 2*F*(Hb+1)*(Wb+1)*2 < 2^31 - 16      VDET_EINVAL
+ *   propagation of detections              (vdet_propagate_boxes) the motion field's row for block, H, W, Hb, Wb, and
+ *                                          1 <= top <= kcap, 1 <= reach <= 16, 2*reach*top <= 1024 (vdet_nms_tracks' list limit),
+ *                                          B <= 32767, C*T*F < 2^31 - 16, decay finite and >= 0      VDET_EINVAL; a keep_cnt
+ *                                                                     outside 0..kcap, a read keep_idx outside 0..B-1, a source
+ *                                                                     box that is not finite or beyond 2^20: VDET_EINVAL latched
+ *                                                                     (vdet_sync), the source writes NaN rows.  One path for
+ *                                                                     every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1208,6 +1219,64 @@ int vdet_track_volume_pixels_adaptive(vdet_ctx *ctx, const void *d_planes, int b
                                       int max_tracks, int S, int R, double min_conf, int max_frames, int step, int scales,
                                       int scale_step, int scale_penalty, int update, double update_conf, double drift_conf,
                                       float *d_tracks, float *d_anchors, int32_t *d_ntracks);
+
+/* ---- motion-guided propagation of detections: a frame's confident still-image detections copied to the frames around it
+ *      along the motion of their pixels, so that a frame where the detector missed the object still holds a box before NMS and
+ *      before tubelets are seeded (the stage T-CNN runs).  The pixels are matched ONCE per frame pair into a dense block-motion
+ *      field; every box is then a lookup in a summed table of that field.  The rule is tests/motion_spec.py ----------------------
+ *
+ * vdet_motion_field: d_images uint8 [F,H,W,3], block P (8, 16, 32), radius R (1 .. 16), Hb = ceil(H/P), Wb = ceil(W/P) ->
+ *   d_field int16 [2,F,Hb,Wb,2]     (dx, dy) of the block's best match; direction 0 is f -> f+1, direction 1 is f -> f-1
+ *   d_cost  int32 [2,F,Hb,Wb]       its SAD
+ *   d_fsum  int32 [2,F,Hb+1,Wb+1,2] fsum[d,f,y,x,:] = sum of field[d,f,r,c,:] over r < y, c < x (row 0 and column 0 are zero)
+ *   match     block (by,bx) of frame f against frame g = f +- 1, with L vdet_track_pixels' luma: for every (dy,dx) in [-R,R]^2
+ *             SAD = sum over i,j in 0..P-1 of |L_f[cy(by*P+i), cx(bx*P+j)] - L_g[cy(by*P+i+dy), cx(bx*P+j+dx)]|, cx / cy clamped
+ *             to 0..W-1 / 0..H-1 (edge replication, which also defines the partial blocks at the right and at the bottom); the
+ *             smallest key (SAD, dy*dy+dx*dx, dy, dx) wins: the tracker's tie order, zero motion on flat content
+ *   no pair   the frame without a partner ([0,F-1] and [1,0]) is all zero in the three outputs
+ * Two launches: the matching over every frame pair in both directions (no luma plane is staged), then the table; between them
+ * every element of the three outputs is written exactly once.  No fill pass, no atomics, no scratch, no host wait; nothing for
+ * vdet_sync to report.  Timed under "other" (one span).  d_field must be 4-byte and d_fsum 8-byte aligned.
+ *
+ * vdet_motion_table: the second launch alone, d_field int16 [2,F,Hb,Wb,2] -> d_fsum as above, for a caller that edits the field
+ * (zeroing the vectors of blocks whose cost is high, say) before boxes are moved along it.
+ *
+ * vdet_propagate_boxes: the table of a video (block P, images H x W, Hb and Wb as above) and its still-image detections --
+ * d_boxes f32 [F,B,4], d_scores f32 [F,B,C], d_keep_idx int32 [F,C,kcap], d_keep_cnt int32 [F,C]: vdet_nms_tracks' still-image
+ * source, layout [F,B,C] only -- -> tubelet layout with T = 2*reach*top slots:
+ *   sources   the first min(top, d_keep_cnt[f,c]) entries of every keep list; entry j names box b = d_keep_idx[f,c,j], whose
+ *             integer box is ib = (int)v - 1 per coordinate (toward zero, as the tracker's anchors)
+ *   range     on one axis, the box X1..X2 (0-based inclusive), h = P/2, N blocks: a0 = -floor((h - X1) / P), the first block
+ *             whose centre pixel P*b + h is >= X1, a1 = floor((X2 - h) / P); a1 < a0 (no centre inside, a degenerate box too):
+ *             a0 = a1 = floor(floor((X1 + X2) / 2) / P); both clamped to 0..N-1, then a1 = max(a1, a0)
+ *   shift     with n the blocks in the two ranges and s a component summed over them (four entries of d_fsum):
+ *             floor((2*s + n) / (2*n)), the mean rounded half up
+ *   walk      per direction, m = 1 .. reach: the shift of step m is read from the field of the frame the box is on, in that
+ *             direction, at ib + (Sx,Sy), the shift accumulated so far; after the move a box wholly outside the image
+ *             (vdet_track_pixels' test) ends the chain, as does the video's end
+ *   d_tracks  f32 [C,T,F,5]  slot t = di*top + j, di enumerating delta = -reach..-1, 1..reach; on g = f + delta the row is
+ *             (x1 + (float)Sx, y1 + (float)Sy, x2 + (float)Sx, y2 + (float)Sy, s_m): one f32 add to the source's own coordinate;
+ *             s_0 = d_scores[f,b,c], s_m = s_{m-1} * (float)decay in f32 (decay = 1: the source's bits)
+ *   d_score   f32 [C,T,F] s_m;  d_src int32 [C,T,F] b;  d_ntracks int32 [C] T
+ * Rows no chain reaches -- a source frame outside the video, j >= d_keep_cnt[f,c], everything behind a chain's end -- are NaN
+ * with d_src = INT32_MIN.  A d_keep_cnt outside 0..kcap, a read d_keep_idx outside 0..B-1, or a source box that is not finite or
+ * has |coordinate| > 2^20 latches VDET_EINVAL (vdet_sync, a message of its own); that source writes NaN rows.  A degenerate box
+ * (x2 < x1) is not bad data.  ONE launch; every output element is written exactly once by it (the NaN rows are no fill pass);
+ * asynchronous, no host wait, no scratch.  Timed under "other".  The outputs feed vdet_nms_tracks (with the same still-image
+ * source) and every other consumer of tubelets unchanged.
+ *
+ * All three: argument checks before any launch, VDET_EINVAL; ctx NULL: VDET_EINVAL, nothing touched; nothing of the context's
+ * cached graph, lists, index or link memo is read or written.  Limits: the table at the top of this file.
+ */
+int vdet_motion_field(vdet_ctx *ctx, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, int block, int radius,
+                      int16_t *d_field, int32_t *d_cost, int32_t *d_fsum);
+
+int vdet_motion_table(vdet_ctx *ctx, const int16_t *d_field, int64_t F, int64_t Hb, int64_t Wb, int32_t *d_fsum);
+
+int vdet_propagate_boxes(vdet_ctx *ctx, const int32_t *d_fsum, int64_t F, int64_t Hb, int64_t Wb, int block, int64_t H, int64_t W,
+                         int64_t B, int64_t C, const float *d_boxes, const float *d_scores, const int32_t *d_keep_idx, int64_t kcap,
+                         const int32_t *d_keep_cnt, int top, int reach, double decay, float *d_tracks, float *d_score,
+                         int32_t *d_src, int32_t *d_ntracks);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,10 @@ SYMBOLS = {
                                          _ci, _ci, _ci, _f64, _f64, _vp, _vp, _vp]),
     "vdet_track_volume_pixels_adaptive": (_ci, [_vp, _vp, _ci, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _ci, _ci,
                                                 _f64, _ci, _ci, _ci, _ci, _ci, _ci, _f64, _f64, _vp, _vp, _vp]),
+    "vdet_motion_field": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _vp, _vp]),
+    "vdet_motion_table": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "vdet_propagate_boxes": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _ci, _ci, _f64,
+                                   _vp, _vp, _vp, _vp]),
 }
 
 

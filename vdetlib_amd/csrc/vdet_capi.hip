@@ -39,6 +39,7 @@
 #include "patch_kernels.hpp"
 #include "svmhead_kernels.hpp"
 #include "pixtrack_kernels.hpp"
+#include "motion_kernels.hpp"
 
 using namespace vdet;
 
@@ -348,6 +349,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadAnchor) return fail(c, VDET_EINVAL, "an anchor frame lies outside the video");
     if (st & kStBadPixAnchor) return fail(c, VDET_EINVAL, "track_pixels: an anchor frame outside the video, or an anchor box that is not finite, beyond 2^20, empty or wholly outside the image (the slot is written as an empty one)");
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
+    if (st & kStBadPropagate) return fail(c, VDET_EINVAL, "propagate_boxes: a keep_cnt outside 0..cap, a keep_idx outside 0..B-1, or a source box that is not finite or beyond 2^20 (the source writes NaN rows)");
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
     if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
     if (st & kStSvmBad) return fail(c, VDET_EINVAL, "svm_head: a slot row outside shape or a class column outside W (the group is skipped, nothing is written for it)");
@@ -4350,6 +4352,137 @@ int vdet_track_volume_pixels_adaptive(vdet_ctx *c, const void *d_planes, int box
     const PixAdaptArgs ad{update, (float)update_conf, (float)drift_conf};
     return track_volume_pixels_impl(c, static_cast<const uint8_t *>(d_planes), H, W, d_boxes, d_scores, F, B, C, nms_thres, thres,
                                     max_tracks, S, R, min_conf, max_frames, step, &sc, d_tracks, d_anchors, d_ntracks, box == 1, &ad);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Motion-guided propagation of detections (motion_kernels.hpp; the rule is tests/motion_spec.py): the block-motion field of
+// every frame pair with its summed table, and the boxes of the keep lists moved along it.  No scratch, no host wait; nothing
+// of the prep cache is read or written.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// the launch of motion_table_kernel, inside the caller's timed span
+void motion_table_launch(vdet_ctx *c, const int16_t *d_field, int64_t F, int64_t Hb, int64_t Wb, int32_t *d_fsum)
+{
+    hipLaunchKernelGGL(motion_table_kernel, dim3((unsigned)(2 * F)), dim3(64), 0, c->stream, reinterpret_cast<const uint32_t *>(d_field),
+                       (int)Hb, (int)Wb, reinterpret_cast<int2 *>(d_fsum));
+}
+
+// the shape of a field and its table: 1 .. 4096 block rows and columns, every element count below 2^31 - 16
+int motion_table_check(vdet_ctx *c, int64_t F, int64_t Hb, int64_t Wb)
+{
+    if (F <= 0 || Hb <= 0 || Wb <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (Hb > kMoTabRows || Wb > kMoTabRows) return fail(c, VDET_EINVAL, "a motion field of at most %d block rows and columns", kMoTabRows);
+    if (F >= 0x7FFFFFF0ll || 4 * F * (Hb + 1) * (Wb + 1) >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "motion field too large (2*F*(Hb+1)*(Wb+1)*2 must stay below 2^31 - 16)");
+    return VDET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdet_motion_table(vdet_ctx *c, const int16_t *d_field, int64_t F, int64_t Hb, int64_t Wb, int32_t *d_fsum)
+{
+    if (!c) return VDET_EINVAL;
+    if (motion_table_check(c, F, Hb, Wb)) return VDET_EINVAL;
+    if (!d_field || !d_fsum) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_field & 3) != 0 || ((uintptr_t)d_fsum & 7) != 0) return fail(c, VDET_EINVAL, "d_field must be 4-byte and d_fsum 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        motion_table_launch(c, d_field, F, Hb, Wb, d_fsum);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_motion_field(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t H, int64_t W, int block, int radius, int16_t *d_field,
+                      int32_t *d_cost, int32_t *d_fsum)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || H <= 0 || W <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (block != 8 && block != 16 && block != 32) return fail(c, VDET_EINVAL, "block = %d; 8, 16 or 32", block);
+    if (radius < 1 || radius > kMoMaxR) return fail(c, VDET_EINVAL, "radius = %d; 1 .. %d", radius, kMoMaxR);
+    const int64_t Hb = (H + block - 1) / block, Wb = (W + block - 1) / block;
+    if (motion_table_check(c, F, Hb, Wb)) return VDET_EINVAL;
+    const int64_t ty = (H + kMoTile - 1) / kMoTile, tx = (W + kMoTile - 1) / kMoTile;
+    if (!d_images || !d_field || !d_cost || !d_fsum) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_field & 3) != 0 || ((uintptr_t)d_fsum & 7) != 0) return fail(c, VDET_EINVAL, "d_field must be 4-byte and d_fsum 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    MotionArgs a{};
+    a.images = d_images;
+    a.F = (int)F; a.H = (int)H; a.W = (int)W; a.R = radius;
+    a.Hb = (int)Hb; a.Wb = (int)Wb; a.ty = (int)ty; a.tx = (int)tx;
+    // lanes per block: the width that wastes the fewest lanes on (2R+1)^2 candidates, among those that divide the tile's
+    // (64/block)^2 blocks evenly over the waves
+    const int nblk = (kMoTile / block) * (kMoTile / block), ncand = (2 * radius + 1) * (2 * radius + 1);
+    int best = 0;
+    for (int gw = 64; gw >= 16; gw >>= 1) {
+        if (nblk % (kMoWaves * 64 / gw)) continue;
+        const int trips = (ncand + gw - 1) / gw * gw;
+        if (!best || trips < (ncand + best - 1) / best * best) best = gw;
+    }
+    a.gw = best;
+    a.field = reinterpret_cast<uint32_t *>(d_field);
+    a.cost = d_cost;
+    const dim3 grid((unsigned)(ty * tx * F * 2));            // (<= 2 * F * Hb * Wb: checked above)
+    {
+        StageTimer tm(c, ST_OTHER);
+        if (block == 8) hipLaunchKernelGGL(motion_match_kernel<8>, grid, dim3(kMoLT), 0, c->stream, a);
+        else if (block == 16) hipLaunchKernelGGL(motion_match_kernel<16>, grid, dim3(kMoLT), 0, c->stream, a);
+        else hipLaunchKernelGGL(motion_match_kernel<32>, grid, dim3(kMoLT), 0, c->stream, a);
+        motion_table_launch(c, d_field, F, Hb, Wb, d_fsum);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_propagate_boxes(vdet_ctx *c, const int32_t *d_fsum, int64_t F, int64_t Hb, int64_t Wb, int block, int64_t H, int64_t W,
+                         int64_t B, int64_t C, const float *d_boxes, const float *d_scores, const int32_t *d_keep_idx, int64_t kcap,
+                         const int32_t *d_keep_cnt, int top, int reach, double decay, float *d_tracks, float *d_score,
+                         int32_t *d_src, int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (F <= 0 || H <= 0 || W <= 0 || B <= 0 || C <= 0 || kcap <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
+    if (block != 8 && block != 16 && block != 32) return fail(c, VDET_EINVAL, "block = %d; 8, 16 or 32", block);
+    if (Hb != (H + block - 1) / block || Wb != (W + block - 1) / block)
+        return fail(c, VDET_EINVAL, "the table is not the one of %lld x %lld images in blocks of %d", (long long)H, (long long)W, block);
+    if (motion_table_check(c, F, Hb, Wb)) return VDET_EINVAL;
+    if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
+    if (top < 1 || top > kcap) return fail(c, VDET_EINVAL, "top = %d; 1 .. the capacity of the keep lists (%lld)", top, (long long)kcap);
+    if (reach < 1 || reach > kMoMaxReach) return fail(c, VDET_EINVAL, "reach = %d; 1 .. %d", reach, kMoMaxReach);
+    const int64_t T = 2 * (int64_t)reach * top;
+    if (T > 1024) return fail(c, VDET_EINVAL, "2*reach*top = %lld slots per class; the limit is 1024", (long long)T);
+    if (!(decay >= 0.0) || !std::isfinite(decay)) return fail(c, VDET_EINVAL, "decay must be finite and >= 0");
+    if (C * T * F >= 0x7FFFFFF0ll || kcap >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
+    if (!d_fsum || !d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt || !d_tracks || !d_score || !d_src || !d_ntracks)
+        return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_fsum & 7) != 0) return fail(c, VDET_EINVAL, "d_fsum must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    PropagateArgs a{};
+    a.fsum = reinterpret_cast<const int2 *>(d_fsum);
+    a.F = (int)F; a.Hb = (int)Hb; a.Wb = (int)Wb; a.P = block; a.H = (int)H; a.W = (int)W; a.B = (int)B; a.C = (int)C;
+    a.boxes = d_boxes; a.scores = d_scores; a.keep_idx = d_keep_idx; a.keep_cnt = d_keep_cnt;
+    a.kcap = (int)kcap; a.top = top; a.reach = reach;
+    a.decay = (float)decay;
+    a.tracks = d_tracks; a.score = d_score; a.src = d_src; a.ntracks = d_ntracks;
+    a.status = &c->d_cnt->status;
+    const int64_t threads = C * 2 * top * F;                 // (= C*T*F / reach)
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(propagate_boxes_kernel, dim3((unsigned)((threads + kMoPropLT - 1) / kMoPropLT)), dim3(kMoPropLT), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
 }
 
 }  // extern "C"

@@ -1701,6 +1701,140 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
 
 
+_MOTION_BLOCKS = (8, 16, 32)       # include/vdet_hip.h: vdet_motion_field
+_MOTION_MAX_REACH = 16
+
+
+def motion_field(images, block=16, radius=8, sync=True, ctx=None):
+    """The block-motion field of a video, both directions, with its summed table: what ``propagate_detections`` moves boxes
+    along (include/vdet_hip.h: vdet_motion_field; the rule is tests/motion_spec.py).  Build it once per video.
+
+    images uint8 [F,H,W,3], contiguous; ``block`` P in (8, 16, 32); ``radius`` R in 1 .. 16.  With Hb = ceil(H/P), Wb = ceil(W/P):
+    ``field`` int16 [2,F,Hb,Wb,2] is (dx, dy) of every block's best match on the next (direction 0) and on the previous
+    (direction 1) frame -- SAD of the tracker's luma over [-R,R]^2 with the image's edges replicated, the tracker's tie order (zero
+    motion on flat content) --, ``cost`` int32 [2,F,Hb,Wb] its SAD, ``fsum`` int32 [2,F,Hb+1,Wb+1,2] the summed table of the field
+    (row 0 and column 0 zero).  The frame without a partner is zero.  Exact.  Two launches, no host wait.
+
+    Returns dict(field, cost, fsum, block, size=(H, W)).  ValueError for another layout, block or radius, or a video whose table
+    would pass 2^31 - 16 elements (before any launch)."""
+    F, H, W = _images(images)
+    block, radius = int(block), int(radius)
+    if block not in _MOTION_BLOCKS:
+        raise ValueError("block = %d; 8, 16 or 32" % block)
+    if not 1 <= radius <= 16:
+        raise ValueError("radius = %d; 1 .. 16" % radius)
+    Hb, Wb = -(-H // block), -(-W // block)
+    if 4 * F * (Hb + 1) * (Wb + 1) >= 2 ** 31 - 16:
+        raise ValueError("motion field too large (2*F*(Hb+1)*(Wb+1)*2 must stay below 2^31 - 16)")
+    ctx = _ctx_for(images, ctx)
+    dev = images.device
+    field = torch.empty((2, F, Hb, Wb, 2), dtype=torch.int16, device=dev)
+    cost = torch.empty((2, F, Hb, Wb), dtype=torch.int32, device=dev)
+    fsum = torch.empty((2, F, Hb + 1, Wb + 1, 2), dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.vdet_motion_field(ctx.h, images.data_ptr(), F, H, W, block, radius, field.data_ptr(), cost.data_ptr(),
+                                        fsum.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(field=field, cost=cost, fsum=fsum, block=block, size=(H, W))
+
+
+def _pd_motion(motion):
+    """The checked ``motion_field`` dict of propagate_detections: (fsum, block, H, W, F, Hb, Wb).  Layout checks only."""
+    if not isinstance(motion, dict) or any(k not in motion for k in ('fsum', 'block', 'size')):
+        raise ValueError("motion must be the dict ops.motion_field returns (fsum, block, size)")
+    fsum, block, size = motion['fsum'], motion['block'], motion['size']
+    if block not in _MOTION_BLOCKS:
+        raise ValueError("motion: block = %r; 8, 16 or 32" % (block,))
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or not all(isinstance(v, int) and 1 <= v <= 32767 for v in size):
+        raise ValueError("motion: size must be (H, W) with 1 .. 32767 rows and columns")
+    H, W = size
+    Hb, Wb = -(-H // block), -(-W // block)
+    if not torch.is_tensor(fsum) or fsum.dtype != torch.int32 or fsum.dim() != 5 or fsum.shape[1] < 1 or \
+            tuple(fsum.shape) != (2, fsum.shape[1], Hb + 1, Wb + 1, 2) or not fsum.is_contiguous():
+        raise ValueError("motion: fsum must be int32 [2,F,%d,%d,2], contiguous (%d x %d images in blocks of %d)" % (
+            Hb + 1, Wb + 1, H, W, block))
+    return fsum, block, H, W, fsum.shape[1], Hb, Wb
+
+
+def _pd_still(still, Ft):
+    """The still-image source of propagate_detections, checked as ``_tn_still`` checks nms_tracks': ((boxes, scores, keep_idx,
+    keep_cnt), B, C, keep capacity)."""
+    if not isinstance(still, (tuple, list)) or len(still) != 4 or not all(torch.is_tensor(x) for x in still):
+        raise ValueError("still must be (boxes, scores, keep_idx, keep_cnt)")
+    boxes, scores, keep_idx, keep_cnt = still
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if boxes.dim() != 3 or tuple(boxes.shape[::2]) != (Ft, 4) or boxes.shape[1] < 1:
+        raise ValueError("still: boxes must be float32 [F,B,4] over the frames of the motion field (F = %d)" % Ft)
+    B = boxes.shape[1]
+    if B > 32767:
+        raise ValueError("B = %d boxes per frame; the limit is 32767" % B)
+    if scores.dim() != 3 or tuple(scores.shape[:2]) != (Ft, B) or scores.shape[2] < 1:
+        raise ValueError("still: scores must be float32 [F,B,C] (layout 'FBC' only)")
+    C = scores.shape[2]
+    if keep_idx.dtype != torch.int32 or keep_idx.dim() != 3 or tuple(keep_idx.shape[:2]) != (Ft, C) or keep_idx.shape[2] < 1:
+        raise ValueError("still: keep_idx must be int32 [F,C,cap]")
+    if keep_cnt.dtype != torch.int32 or tuple(keep_cnt.shape) != (Ft, C):
+        raise ValueError("still: keep_cnt must be int32 [F,C]")
+    return (boxes, scores, keep_idx, keep_cnt), B, C, keep_idx.shape[2]
+
+
+def propagate_detections(motion, still, top, reach=3, decay=1.0, sync=True, ctx=None):
+    """Motion-guided propagation: every frame's confident still-image detections copied to the ``reach`` frames on either side
+    of it, moved along the motion of their pixels, so that a frame where the detector missed the object still holds a box before
+    NMS and before tubelets are seeded (include/vdet_hip.h: vdet_propagate_boxes; the rule is tests/motion_spec.py).  One launch,
+    no host wait.
+
+    ``motion``: the dict of ``motion_field`` of the same video.  ``still`` = (boxes [F,B,4] f32, scores [F,B,C] f32, keep_idx
+    [F,C,k] int32, keep_cnt [F,C] int32): NMS survivors as ``nms_tracks`` takes them ('FBC').  The sources are the first
+    min(``top``, keep_cnt) entries of every list.  A box moves, step by step, by the mean vector (rounded half up) of the blocks
+    whose centre lies in it; a box wholly outside the image, or the video's end, ends its chain.  ``decay`` multiplies the score
+    once per step (f32); 1.0 keeps the source's bits.
+
+    Returns a dict in the tubelet layout, T = 2*reach*top slots (slot di*top + j for the j-th source of the frame ``delta`` away,
+    di enumerating delta = -reach..-1, 1..reach): ``tracks`` [C,T,F,5] f32 (the source's coordinates plus the shift, the score),
+    ``score`` [C,T,F] f32, ``src`` [C,T,F] int32 (the source's box index; INT32_MIN where no chain arrives), ``ntracks`` [C]
+    int32 (T) -- NaN where no chain arrives.  A keep count or index out of range, or a source box that is not finite or beyond
+    2^20, raises ValueError when the call -- or with ``sync=False`` a later ``ctx.sync()`` -- waits; that source writes NaN rows.
+
+        idx, cnt = nms_volume(boxes, scores, 0.3);  still = (boxes, scores, idx, cnt)
+        m = motion_field(images)
+        p = propagate_detections(m, still, top=100)
+        dets = nms_tracks(p['tracks'], p['ntracks'], p['score'], still=still, thresh=0.3)
+
+    and ``dets`` goes to ``DetEvaluator.add_detections``, or -- ``tracks`` / ``ntracks`` / ``score`` -- to ``top_anchors``.
+    ValueError for arguments beyond the limits (1 <= top <= k, 1 <= reach <= 16, 2*reach*top <= 1024, C*T*F < 2^31 - 16, decay
+    finite and >= 0), before any launch."""
+    fsum, block, H, W, F, Hb, Wb = _pd_motion(motion)
+    still, B, C, kcap = _pd_still(still, F)
+    top, reach, decay = int(top), int(reach), float(decay)
+    if not 1 <= top <= kcap:
+        raise ValueError("top = %d; 1 .. the capacity of the keep lists (%d)" % (top, kcap))
+    if not 1 <= reach <= _MOTION_MAX_REACH:
+        raise ValueError("reach = %d; 1 .. %d" % (reach, _MOTION_MAX_REACH))
+    T = 2 * reach * top
+    if T > _TN_MAX:
+        raise ValueError("2*reach*top = %d slots per class; the limit is %d" % (T, _TN_MAX))
+    if not math.isfinite(decay) or decay < 0:
+        raise ValueError("decay must be finite and >= 0")
+    if C * T * F >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16)")
+    _same_gpu((fsum,) + tuple(still), "motion and still")
+    boxes, scores, keep_idx, keep_cnt = (x.contiguous() for x in still)
+    ctx = _ctx_for(fsum, ctx)
+    dev = fsum.device
+    tracks = torch.empty((C, T, F, 5), dtype=torch.float32, device=dev)
+    score = torch.empty((C, T, F), dtype=torch.float32, device=dev)
+    src = torch.empty((C, T, F), dtype=torch.int32, device=dev)
+    ntracks = torch.empty((C,), dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.vdet_propagate_boxes(ctx.h, fsum.data_ptr(), F, Hb, Wb, block, H, W, B, C, boxes.data_ptr(), scores.data_ptr(),
+                                           keep_idx.data_ptr(), kcap, keep_cnt.data_ptr(), top, reach, decay, tracks.data_ptr(),
+                                           score.data_ptr(), src.data_ptr(), ntracks.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(tracks=tracks, ntracks=ntracks, score=score, src=src)
+
+
 def _rt_call(ctx, off, B, C, T, tracks, ntracks, boxes, scores, floor, overlap_thres, complete, window, sync):
     """The one call behind rescore_tubelets / rescore_tubelets_batch: flat tensors in, flat outputs back."""
     V, Ft = len(off) - 1, int(off[-1])
