@@ -199,10 +199,13 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * radix kernel (tied / quantised / thresholded columns; synchronises the stream), -1 if that sort did not use it;
  * what = 10 -> number of times the device TCN's parameters were uploaded (a call with the resident net uploads nothing);
  * what = 11 -> number of times the per-video table of vdet_top_anchors (batch form), vdet_track_from_anchors_batch and
- * vdet_anchor_propagate_tracks_batch was staged (calls with the same frame offsets stage it once).
+ * vdet_anchor_propagate_tracks_batch was staged (calls with the same frame offsets stage it once);
+ * what = 12 -> which kernel the last vdet_volume_pass[_batch] launched: 4 the current fused kernel, 2 the lean one
+ * (vdet_set_vpass), 0 the separate temporal kernels; 104: the current kernel held to one block per compute unit.
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
- * inputs or devices, with identical results; none selects a tuning variant):
+ * inputs or devices, with identical results; none selects a tuning variant -- the one switch that does, VDET_VPASS_FORM,
+ * is described with vdet_set_vpass):
  *   VDET_FORCE_GENERAL=1  the all-pairs predicate kernel + one-survivor walk on every frame (what irregular frames take)
  *   VDET_NO_INDEX=1       no x-sorted proposal index (what frames too large for it take)
  *   VDET_NO_LAZY=1        eager track_det_nms of every crossed list (what irregular frames take)
@@ -475,6 +478,29 @@ int vdet_temporal_maxpool_conv_f32(vdet_ctx *ctx, const float *d_in, float *d_ou
 int vdet_volume_pass(vdet_ctx *ctx, const float *d_scores, int64_t F, int64_t B, int64_t C, int window,
                      float pad_max, const float *h_taps, float bias, float pad_conv, float *d_out_max,
                      float *d_out_conv, int use_score_thresh, float score_thresh);
+
+/*
+ * Which form of the fused kernel vdet_volume_pass[_batch] launches.  Every form computes the same outputs bit for bit; they
+ * differ in what a resident block takes from a compute unit (DESIGN.md section 7 has the registers and the LDS of each).
+ *   VDET_VPASS_AUTO       the host chooses: VDET_VPASS_ONE_PER_CU for a context that runs asynchronously with the cache on
+ *                         (vdet_set_async + vdet_set_cache: the multi-video pipeline, whose streams share the chip), window 3
+ *                         and the 512-thread tiling (C > 128); VDET_VPASS_CURRENT otherwise
+ *   VDET_VPASS_CURRENT    4 items per thread, one block per (tile, frame chunk)
+ *   VDET_VPASS_LEAN       (measurements only: it bought nothing) 2 items per thread, half the tile, 2 blocks per compute unit
+ *                         that stride over the work; window 3 only, and a class count
+ *                         whose 16-box tile does not fit 512 x 2 items (C > 256) takes the current form
+ *   VDET_VPASS_ONE_PER_CU the current form, its dynamic LDS padded so that one block is resident per compute unit: alone the
+ *                         HBM-bound pass is as fast as with two, and kernels of other streams find room next to it
+ * fchunk > 0 sets the frames per chunk (0: the host's formula; a value that would make more than 65 535 chunks is raised
+ * until they fit); tests force chunk seams into short videos with it.
+ * The environment variables VDET_VPASS_FORM=<number> and VDET_VPASS_FCHUNK=<frames>, read once by vdet_create, set the
+ * same two values for every context of the process.
+ */
+#define VDET_VPASS_AUTO 0
+#define VDET_VPASS_CURRENT 1
+#define VDET_VPASS_LEAN 2
+#define VDET_VPASS_ONE_PER_CU 3
+int vdet_set_vpass(vdet_ctx *ctx, int form, int fchunk);
 
 /*
  * Greedy tubelet generation for every class of a score volume, device-resident: the array form of

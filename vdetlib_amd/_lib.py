@@ -31,6 +31,7 @@ SYMBOLS = {
     "vdet_set_cache": (_ci, [_vp, _ci]),
     "vdet_invalidate": (_ci, [_vp]),
     "vdet_set_async": (_ci, [_vp, _ci]),
+    "vdet_set_vpass": (_ci, [_vp, _ci, _ci]),
     "vdet_nms_f32": (_ci, [_vp, _vp, _i64, _i64, _ci, _f64, _vp, _vp, ctypes.POINTER(_i64)]),
     "vdet_track_det_nms_f32": (_ci, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _f64, _vp, ctypes.POINTER(_i64)]),
     "vdet_track_det_nms_batch": (_ci, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f64, _vp, _vp]),
@@ -234,6 +235,11 @@ class Context(object):
     def set_async(self, on):
         """No host synchronisation inside the volume entry points (include/vdet_hip.h: vdet_set_async)."""
         self.check(self.lib.vdet_set_async(self.h, 1 if on else 0))
+
+    def set_vpass(self, form=0, fchunk=0):
+        """Form of the fused volume pass (0 automatic, 1 current, 2 lean, 3 current with one block per compute unit) and frames per chunk
+        (0: the host's formula) -- include/vdet_hip.h: vdet_set_vpass."""
+        self.check(self.lib.vdet_set_vpass(self.h, int(form), int(fchunk)))
 
     def query(self, what):
         return int(self.lib.vdet_query(self.h, int(what)))

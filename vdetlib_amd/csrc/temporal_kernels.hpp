@@ -321,6 +321,158 @@ __global__ __launch_bounds__(NT) void volume_pass_kernel(const float4 *__restric
     }
 }
 
+// The lean form of the pass, for a context whose kernels share the chip with those of other videos' streams.  The pass is
+// HBM-bound with the VALU almost idle, yet volume_pass_kernel<3, 4, true, 512> holds most of a CU while it runs:
+//   volume_pass_kernel<3,4,true,512>       116 VGPRs, 4 waves/SIMD, 51 200 B LDS at C = 200 (TB = 32)
+//       a CU holds 2 blocks = 16 waves: 464 of a SIMD's 512 VGPRs, 102 400 B (100 KiB) of LDS -- room for one walk_kernel wave (48 VGPRs)
+//       per SIMD, for no wave of graph_lists_kernel (80) or binsort_kernel (128)
+//   volume_pass_lean_kernel<3,2,true,512>  58 VGPRs, no spills, 8 waves/SIMD, 25 600 B LDS at C = 200 (TB = 16)
+//       the host launches 2 blocks per CU = 16 waves: 256 VGPRs and 4 of 8 wave slots per SIMD and 110 KB of LDS stay free
+// (devtools/kernel_resources.py prints the figures of the build at hand; DESIGN.md section 7 has the table.)
+// Measured 4 videos in flight it bought nothing (LABNOTES "Lean volume pass"); what did was volume_pass_kernel itself held
+// to ONE block per CU by the host, which is what an asynchronous cached context launches.  This kernel stays selectable
+// (vdet_set_vpass) for measurements.
+// Same tile scheme at ITEMS = 2, same arithmetic per element and the same stores: the outputs equal volume_pass_kernel's bit
+// for bit.  What differs: a block strides over the list of (tile, frame chunk) work items, w = blockIdx.x, + gridDim.x, ...
+// (no counter, no block waits for another), and every item
+// is addressed by an UNSIGNED 32-bit byte offset from a wave-uniform base (the frame's slab is < 2^31 B), which keeps the
+// addresses out of the vector registers.  amdgpu_waves_per_eu(8, 8) makes 64 VGPRs the allocator's budget; the build must
+// show no spill under it (devtools/kernel_resources.py).
+template <int W, int ITEMS, bool CONV, int NT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void volume_pass_lean_kernel(const float4 *__restrict__ in, float4 *__restrict__ out_max, float4 *__restrict__ out_conv,
+                             uint32_t *__restrict__ keys, int F, int B, int C4, int TB, int tb_shift, int fchunk,
+                             float pad_max, float pad_conv, float bias, Taps taps, int use_thr, float thr,
+                             const int2 *__restrict__ seg)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char vp_smem[];
+    uint32_t *tile = reinterpret_cast<uint32_t *>(vp_smem);      // [2][C][TB] keys, swizzled as in volume_pass_kernel
+    constexpr int H = W / 2;
+    const int tid = threadIdx.x;
+    const int ntiles = (B + TB - 1) / TB;
+    const int nwork = ntiles * ((F + fchunk - 1) / fchunk);
+    const int64_t S4 = (int64_t)B * C4;
+    const int tile_sz = C4 * 4 * TB;
+    const int qmask = (TB >> 2) - 1;
+    const bool vec_ok = (B & 3) == 0;                            // every key row starts 16-byte aligned
+    const float4 pm = splat4(pad_max), pc = splat4(pad_conv);
+    for (int w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int wy = w / ntiles;
+        const int b0 = (w - wy * ntiles) * TB;
+        const int rows = min(TB, B - b0);
+        const int n4 = rows * C4;                                // valid float4 of this tile
+        const int f0 = wy * fchunk;
+        const int f1 = min(F, f0 + fchunk);
+        const char *in_t = reinterpret_cast<const char *>(in + (int64_t)b0 * C4);
+        char *om_t = reinterpret_cast<char *>(out_max + (int64_t)b0 * C4);
+        char *oc_t = CONV ? reinterpret_cast<char *>(out_conv + (int64_t)b0 * C4) : nullptr;
+        uint32_t goff[ITEMS];     // byte offset of the item's float4 inside the tile (clamped: every load address is valid)
+        int loff[ITEMS];          // LDS slot of the item's keys: [c4][b]
+        bool on[ITEMS];
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            const int idx = tid + NT * i;
+            on[i] = idx < n4;
+            const int idc = min(idx, n4 - 1);
+            const int b = idc / C4, c4 = idc - b * C4;
+            goff[i] = (uint32_t)idc * 16u;
+            loff[i] = 4 * c4 * TB + (b ^ ((c4 & qmask) << 2));
+        }
+        float4 win[ITEMS][W];
+        float4 nxt[ITEMS];        // frame f + H + 1, in flight while frame f is processed
+        bool ok[W];
+#pragma unroll
+        for (int k = 0; k < W - 1; ++k) {
+            const int g = f0 - H + k;
+            const int gc = min(max(g, 0), F - 1);
+            const char *fin = in_t + (int64_t)gc * S4 * 16;
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) win[i][k + 1] = *reinterpret_cast<const float4 *>(fin + goff[i]);
+            ok[k + 1] = (g == gc);
+        }
+        {
+            const char *fin = in_t + (int64_t)min(f0 + H, F - 1) * S4 * 16;
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) nxt[i] = *reinterpret_cast<const float4 *>(fin + goff[i]);
+        }
+        if (w != (int)blockIdx.x) __syncthreads();     // the key tile changes hands: the last item's copy-out has been read
+        for (int f = f0; f < f1; ++f) {
+#pragma unroll
+            for (int k = 0; k < W - 1; ++k) {
+                ok[k] = ok[k + 1];
+#pragma unroll
+                for (int i = 0; i < ITEMS; ++i) win[i][k] = win[i][k + 1];
+            }
+            ok[W - 1] = (f + H <= F - 1);
+            if (seg) {      // batched videos: the window stops at the video's first / last frame (wave-uniform: scalar loads)
+#pragma unroll
+                for (int k = 0; k < W; ++k) ok[k] = seg_in(seg, f, f - H + k, F);
+            }
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) win[i][W - 1] = nxt[i];
+            {   // next iteration's newest frame: issued now, first used after this iteration's stores and barrier
+                const char *fin = in_t + (int64_t)min(f + 1 + H, F - 1) * S4 * 16;
+#pragma unroll
+                for (int i = 0; i < ITEMS; ++i) nxt[i] = *reinterpret_cast<const float4 *>(fin + goff[i]);
+            }
+            uint32_t *tb = tile + (f & 1) * tile_sz;
+            char *om = om_t + (int64_t)f * S4 * 16;
+            char *oc = CONV ? oc_t + (int64_t)f * S4 * 16 : nullptr;
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                if (!on[i]) continue;
+                MaxAcc a;
+                a.init(ok[0] ? win[i][0] : pm);
+#pragma unroll
+                for (int k = 1; k < W; ++k) a.add(ok[k] ? win[i][k] : pm);
+                vp_store(reinterpret_cast<float4 *>(om + goff[i]), a.get());
+                if (CONV) {
+                    float4 r = splat4(bias);
+#pragma unroll
+                    for (int k = 0; k < W; ++k) {
+                        const float t = taps.w[k];
+                        const float4 v = ok[k] ? win[i][k] : pc;
+                        r.x = r.x + t * v.x; r.y = r.y + t * v.y;
+                        r.z = r.z + t * v.z; r.w = r.w + t * v.w;
+                    }
+                    vp_store(reinterpret_cast<float4 *>(oc + goff[i]), r);
+                }
+                const float4 s = win[i][H];
+                uint4 k4 = make_uint4(score_key(s.x), score_key(s.y), score_key(s.z), score_key(s.w));
+                if (use_thr) {
+                    if (!(s.x > thr)) k4.x = 0u;
+                    if (!(s.y > thr)) k4.y = 0u;
+                    if (!(s.z > thr)) k4.z = 0u;
+                    if (!(s.w > thr)) k4.w = 0u;
+                }
+                tb[loff[i]] = k4.x; tb[loff[i] + TB] = k4.y; tb[loff[i] + 2 * TB] = k4.z; tb[loff[i] + 3 * TB] = k4.w;
+            }
+            __syncthreads();       // (the other buffer was last read one iteration ago, before this barrier's predecessor)
+            char *kf = reinterpret_cast<char *>(keys + (int64_t)f * C4 * 4 * B + b0);
+            int ct = tid;
+            asm volatile("" : "+v"(ct));       // the copy-out's indices are derived anew per frame (a few VALU operations of an
+                                               // idle VALU) instead of living in registers across the whole pass
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                const int idx = ct + NT * i;                         // now (class c, 16-byte chunk q of its row), q fastest:
+                const int cc = idx >> (tb_shift - 2), q = idx & qmask;   // a quad of lanes stores 64 contiguous bytes
+                if (cc < C4 * 4 && 4 * q < rows) {
+                    const uint4 k4 = *reinterpret_cast<const uint4 *>(tb + cc * TB + ((4 * q) ^ (((cc >> 2) & qmask) << 2)));
+                    uint32_t *ko = reinterpret_cast<uint32_t *>(kf + (uint32_t)(cc * B + 4 * q) * 4u);
+                    if (vec_ok && 4 * q + 3 < rows) {
+                        vp_store_u4(reinterpret_cast<uint4 *>(ko), k4);
+                    } else {
+                        ko[0] = k4.x;
+                        if (4 * q + 1 < rows) ko[1] = k4.y;
+                        if (4 * q + 2 < rows) ko[2] = k4.z;
+                        if (4 * q + 3 < rows) ko[3] = k4.w;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // Generic fallback: any odd window, any S (no alignment requirement); one thread per element.
 template <int MODE>
 __global__ __launch_bounds__(256) void temporal_scalar_kernel(const float *__restrict__ in, float *__restrict__ out,

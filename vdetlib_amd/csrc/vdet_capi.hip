@@ -126,6 +126,7 @@ struct NmsPlan {
     int nmax = 0;
 };
 
+
 }  // namespace
 
 struct vdet_ctx {
@@ -159,6 +160,10 @@ struct vdet_ctx {
     struct KeySrc { const void *scores = nullptr; int64_t F = 0, B = 0, C = 0; int use_thr = 0; float thr = 0; } keysrc;
     bool keys_valid = false;
     bool vpass_attr_set = false;
+    int vpass_form = VDET_VPASS_AUTO;   // vdet_set_vpass / VDET_VPASS_FORM: which form of the volume pass (include/vdet_hip.h)
+    int vpass_fchunk = 0;               // ... and frames per chunk (0: the host's formula); VDET_VPASS_FCHUNK
+    int vpass_last_items = 0;           // vdet_query 12: items per thread of the last volume pass's fused kernel (0: the separate kernels
+                                        // ran), + 100 if it was held to one block per compute unit
     bool index_valid = false; const void *index_boxes = nullptr; int64_t index_F = 0, index_B = 0;
     bool all_regular = false;     // last graph build: every frame regular
     bool wave_transpose = false;  // wave_transpose64 verified on this device (vdet_create); VDET_WAVE_TRANSPOSE=0 disables
@@ -1492,6 +1497,8 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_SMALL_LISTS")) c->small_lists = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_GLOBAL")) c->tcn_global = atoi(e) != 0;
+    if (const char *e = getenv("VDET_VPASS_FORM")) { const int v = atoi(e); if (v >= VDET_VPASS_AUTO && v <= VDET_VPASS_ONE_PER_CU) c->vpass_form = v; }
+    if (const char *e = getenv("VDET_VPASS_FCHUNK")) { const int v = atoi(e); if (v >= 1) c->vpass_fchunk = v; }
     {   // probe: do returning LDS atomics resolve same-address lanes in ascending lane order?
         const int npat = 4096;
         std::vector<uint8_t> pats((size_t)npat * 64);
@@ -1620,6 +1627,7 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 8) return (int)std::min<long long>(c->n_host_syncs, 0x7FFFFFFF);
     if (what == 10) return (int)std::min<long long>(c->tcn_params.uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
     if (what == 11) return (int)std::min<long long>(c->anchor_tab.uploads, 0x7FFFFFFF);   // per-video tables of the anchor route's batch forms staged so far
+    if (what == 12) return c->vpass_last_items;   // 4: the current fused kernel, 2: the lean one, 0: the separate temporal kernels; + 100: one block per unit
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -1715,6 +1723,15 @@ int vdet_set_async(vdet_ctx *c, int enable)
 {
     if (!c) return VDET_EINVAL;
     c->async_enabled = enable != 0;
+    return VDET_OK;
+}
+
+int vdet_set_vpass(vdet_ctx *c, int form, int fchunk)
+{
+    if (!c) return VDET_EINVAL;
+    if (form < VDET_VPASS_AUTO || form > VDET_VPASS_ONE_PER_CU || fchunk < 0) return fail(c, VDET_EINVAL, "bad volume pass form");
+    c->vpass_form = form;
+    c->vpass_fchunk = fchunk;
     return VDET_OK;
 }
 
@@ -2715,19 +2732,34 @@ static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64
         return fail(c, VDET_EINVAL, "bad volume_pass arguments");
     if (B > 32767 || F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
     c->keys_valid = false;
+    c->vpass_last_items = 0;
     // tile: TB boxes (a power of two, >= 16 so that a key row segment is >= 64 B) x C classes in <= NT * ITEMS float4;
     // 4 items per thread (the window of every item lives in registers: more would cost occupancy), 256 or 512 threads
     const int64_t C4 = C / 4;
+    // the lean form (temporal_kernels.hpp: volume_pass_lean_kernel): 2 items per thread, 512 threads, window 3
     int items = 0, TB = 0, NT = 0;
+    const int form = c->vpass_form;
     if (C % 4 == 0 && (window == 3 || window == 5) &&
         (((uintptr_t)d_scores | (uintptr_t)d_out_max | (uintptr_t)(conv ? d_out_conv : d_out_max)) & 15) == 0) {
-        for (int nt : {256, 512}) {
+        if (window == 3 && form == VDET_VPASS_LEAN) {
             int tb = 64;
-            while (tb >= 16 && (int64_t)tb * C4 > (int64_t)nt * 4) tb >>= 1;
-            if (tb >= 16 && (nt == 512 || tb >= 32)) { items = 4; TB = tb; NT = nt; break; }
+            while (tb >= 16 && (int64_t)tb * C4 > 512 * 2) tb >>= 1;
+            if (tb >= 16) { items = 2; TB = tb; NT = 512; }
+        }
+        if (!items) {
+            for (int nt : {256, 512}) {
+                int tb = 64;
+                while (tb >= 16 && (int64_t)tb * C4 > (int64_t)nt * 4) tb >>= 1;
+                if (tb >= 16 && (nt == 512 || tb >= 32)) { items = 4; TB = tb; NT = nt; break; }
+            }
         }
         if (items && (size_t)2 * C4 * TB * 16 > c->max_lds / 2) items = 0;
     }
+    // one resident block per compute unit: the dynamic LDS is padded past half of a unit's (the kernel touches its tile only).
+    // VDET_VPASS_AUTO takes it for an asynchronous context with the cache on (the multi-video pipeline, whose streams share the
+    // chip): 4 videos in flight it measured 0.17-0.27 ms of 8.9-9.0 per step, the lean kernel nothing (LABNOTES "Lean volume pass")
+    const bool one_per_cu = items == 4 && (form == VDET_VPASS_ONE_PER_CU ||
+                                           (form == VDET_VPASS_AUTO && c->async_enabled && c->cache_enabled && window == 3 && NT == 512));
     if (!items) {
         // shapes the fused kernel does not cover: the temporal pass(es) now, the key transpose with the sort
         if (conv) return temporal_maxpool_conv_impl(c, d_scores, d_out_max, d_out_conv, F, B * C, window, pad_max, h_taps, bias, pad_conv, d_seg);
@@ -2745,21 +2777,32 @@ static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64
     const int ntiles = (int)((B + TB - 1) / TB);
     int64_t chunks = std::min<int64_t>(std::max<int64_t>(F / 8, 1), (8 * c->n_cu + ntiles - 1) / ntiles);
     chunks = std::max<int64_t>(1, std::min<int64_t>(chunks, 65535));
-    const int fchunk = (int)((F + chunks - 1) / chunks);
-    const dim3 grid((unsigned)ntiles, (unsigned)((F + fchunk - 1) / fchunk));
-    const size_t lds = (size_t)2 * C4 * TB * 16;
+    // frames per chunk: the formula's, or the forced one (vdet_set_vpass) raised until the chunks fit the grid's y dimension
+    const int fchunk = c->vpass_fchunk > 0 ? (int)std::min<int64_t>(std::max<int64_t>(c->vpass_fchunk, (F + 65534) / 65535), F)
+                                           : (int)((F + chunks - 1) / chunks);
+    const int64_t nchunks = (F + fchunk - 1) / fchunk;
+    // the lean kernel's blocks stride over the (tile, chunk) list, 2 of them per compute unit; the current kernel: a block per
+    // (tile, chunk)
+    const dim3 grid = items == 2 ? dim3((unsigned)std::min<int64_t>(nchunks * ntiles, 2 * (int64_t)c->n_cu))
+                                 : dim3((unsigned)ntiles, (unsigned)nchunks);
+    size_t lds = (size_t)2 * C4 * TB * 16;
+    if (one_per_cu) lds = std::max(lds, c->max_lds / 2 + 16);
     int tb_shift = 0;
     while ((1 << tb_shift) < TB) ++tb_shift;
     const void *fn = nullptr;
 #define VDET_VP(WW, CV, NTV) reinterpret_cast<const void *>(volume_pass_kernel<WW, 4, CV, NTV>)
-    if (window == 3) fn = NT == 256 ? (conv ? VDET_VP(3, true, 256) : VDET_VP(3, false, 256)) : (conv ? VDET_VP(3, true, 512) : VDET_VP(3, false, 512));
+#define VDET_VPL(CV) reinterpret_cast<const void *>(volume_pass_lean_kernel<3, 2, CV, 512>)
+    if (items == 2) fn = conv ? VDET_VPL(true) : VDET_VPL(false);
+    else if (window == 3) fn = NT == 256 ? (conv ? VDET_VP(3, true, 256) : VDET_VP(3, false, 256)) : (conv ? VDET_VP(3, true, 512) : VDET_VP(3, false, 512));
     else fn = NT == 256 ? (conv ? VDET_VP(5, true, 256) : VDET_VP(5, false, 256)) : (conv ? VDET_VP(5, true, 512) : VDET_VP(5, false, 512));
     if (!c->vpass_attr_set) {
         for (const void *f : {VDET_VP(3, true, 256), VDET_VP(3, false, 256), VDET_VP(3, true, 512), VDET_VP(3, false, 512),
-                              VDET_VP(5, true, 256), VDET_VP(5, false, 256), VDET_VP(5, true, 512), VDET_VP(5, false, 512)})
+                              VDET_VP(5, true, 256), VDET_VP(5, false, 256), VDET_VP(5, true, 512), VDET_VP(5, false, 512),
+                              VDET_VPL(true), VDET_VPL(false)})
             HIPCHK(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->max_lds));
         c->vpass_attr_set = true;
     }
+#undef VDET_VPL
 #undef VDET_VP
     const float4 *in4 = reinterpret_cast<const float4 *>(d_scores);
     float4 *om = reinterpret_cast<float4 *>(d_out_max), *oc = reinterpret_cast<float4 *>(d_out_conv);
@@ -2775,6 +2818,7 @@ static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64
     c->keysrc.scores = d_scores; c->keysrc.F = F; c->keysrc.B = B; c->keysrc.C = C;
     c->keysrc.use_thr = use_score_thresh ? 1 : 0; c->keysrc.thr = score_thresh;
     c->keys_valid = true;
+    c->vpass_last_items = items + (one_per_cu ? 100 : 0);
     return VDET_OK;
 }
 
