@@ -121,6 +121,11 @@
  *                                                                     box that is not finite or beyond 2^20: VDET_EINVAL latched
  *                                                                     (vdet_sync), the source writes NaN rows.  One path for
  *                                                                     every size
+ *   multi-context suppression              (vdet_context_classes, vdet_suppress_context) F*B < 2^31 - 16, C <= 2^31 - 65536,
+ *                                          every video below 2^32 scores (32-bit counters), at most 65535 videos, ratio in
+ *                                          (0, 1] or top >= 1, min_hits >= 1, penalty finite as a float32 and >= 0      VDET_EINVAL.
+ *                                                                     A video whose records outgrow the scratch (an all-equal
+ *                                                                     volume) takes the full-read passes: same results
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -202,6 +207,9 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * vdet_anchor_propagate_tracks_batch was staged (calls with the same frame offsets stage it once);
  * what = 12 -> which kernel the last vdet_volume_pass[_batch] launched: 4 the current fused kernel, 2 the lean one
  * (vdet_set_vpass), 0 the separate temporal kernels; 104: the current kernel held to one block per compute unit.
+ * what = 13 -> full reads of the volume the last vdet_context_classes needed, the most of any of its videos: 2, 3 (the records
+ * fit only below the second digit) or 4 (they never fit, or VDET_CTX_RECORDS=0); 0 when no video had a candidate; -1 before
+ * the first call (synchronises the stream).
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant -- the one switch that does, VDET_VPASS_FORM,
@@ -218,6 +226,8 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  *   VDET_TCN_TILED=1      device TCN: every series cut into the smallest tiles, 16 positions or the net's halo (what long series
  *                         and wide nets take)
  *   VDET_TCN_GLOBAL=1     device TCN: the activations in global memory (what nets too wide for the LDS budget take)
+ *   VDET_CTX_RECORDS=0    vdet_context_classes: no record scratch, every digit round and the per-class count by a full read of
+ *                         the volume (what a video takes whose records outgrow the scratch: an all-equal volume)
  *   VDET_ATOMIC_RANK=0 / VDET_WAVE_TRANSPOSE=0   the variants selected when the start-up hardware probes fail
  *   VDET_BITS_BUDGET_MB=n bytes of bit-matrix scratch per graph-build batch (default 1024) */
 int vdet_query(vdet_ctx *ctx, int what);
@@ -1303,6 +1313,43 @@ int vdet_propagate_boxes(vdet_ctx *ctx, const int32_t *d_fsum, int64_t F, int64_
                          int64_t B, int64_t C, const float *d_boxes, const float *d_scores, const int32_t *d_keep_idx, int64_t kcap,
                          const int32_t *d_keep_cnt, int top, int reach, double decay, float *d_tracks, float *d_score,
                          int32_t *d_src, int32_t *d_ntracks);
+
+/* ---- multi-context suppression (csrc/context_kernels.hpp): the classes among a video's highest-ranked detection scores, and a
+ *      constant off every other class's scores -- the stage T-CNN runs with the propagation, before per-frame NMS and tubelet
+ *      seeding.  The reference library has no function for it; the rule is tests/context_spec.py -----------------------------
+ *
+ * d_scores f32 [F,B,C], class innermost, 4-byte aligned (a view may start anywhere).  h_frame_off NULL: one video, outputs
+ * without the V axis, no host table; h_frame_off [V+1]: V videos along F, every step per video.
+ *
+ * vdet_context_classes, per video:
+ *   candidates  the scores that are not NaN and -- use_score_thresh != 0 -- are > (float)score_thresh (f32 compare, as
+ *               vdet_top_anchors; -inf is a candidate without a threshold); n their number
+ *   rank        top >= 1: k = min(top, n).  top == 0: k = max(1, floor((double)ratio * (double)n)) clamped to n, ONE f64 product,
+ *               taken on the device (n is known only there)
+ *   d_thresh    f32 [V]   the k-th largest candidate by float order (-0.0 == +0.0, written as +0.0); +inf when n == 0
+ *   d_n         int64 [V] n
+ *   d_hits      int32 [V,C] candidates of class c that are >= thresh: every tie counts, so the result depends on no index order,
+ *               grid shape or run order; all zero when n == 0
+ *   d_high      uint8 [V,C] hits >= min_hits
+ * A radix select over the volume as it lies, integer counts only: two full reads when the keys at or above the first digit's
+ * bin of rank k fit the record scratch, three when they fit only below the second digit (uniform scores), four when they never
+ * do (an all-equal volume); same results.  Scratch owned by the context: 8 KiB + 32 bytes per video, and per video 8-byte records for a 64th of
+ * its scores, at least 4096 and at most 2^21 of them (16 MiB).  Asynchronous, no host wait; the batch form stages the per-video
+ * table keyed by the offsets and the shape.  Timed under "track_pick".
+ *
+ * vdet_suppress_context: d_out[f,b,c] = d_scores[f,b,c] - (float)penalty (one f32 subtraction) where d_high[v(f),c] == 0 and the
+ * score is not NaN; every other element, NaN included, is copied bit for bit.  d_out == d_scores is allowed (in place); any other
+ * overlap is VDET_EINVAL.  One launch, one read and one write; asynchronous, no scratch.  Timed under "other".
+ *
+ * Both: argument checks before any launch, VDET_EINVAL; ctx NULL: VDET_EINVAL, nothing touched; nothing of the context's cached
+ * graph, lists, index or link memo is read or written.  Limits: the table at the top of this file.
+ */
+int vdet_context_classes(vdet_ctx *ctx, const float *d_scores, int64_t F, int64_t B, int64_t C, double ratio, int64_t top,
+                         int64_t min_hits, int use_score_thresh, double score_thresh, const int64_t *h_frame_off, int64_t V,
+                         float *d_thresh, int64_t *d_n, int32_t *d_hits, uint8_t *d_high);
+
+int vdet_suppress_context(vdet_ctx *ctx, const float *d_scores, int64_t F, int64_t B, int64_t C, const uint8_t *d_high,
+                          double penalty, const int64_t *h_frame_off, int64_t V, float *d_out);
 
 #ifdef __cplusplus
 }

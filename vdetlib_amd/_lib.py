@@ -123,6 +123,8 @@ SYMBOLS = {
     "vdet_motion_table": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "vdet_propagate_boxes": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _ci, _ci, _f64,
                                    _vp, _vp, _vp, _vp]),
+    "vdet_context_classes": (_ci, [_vp, _vp, _i64, _i64, _i64, _f64, _i64, _i64, _ci, _f64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "vdet_suppress_context": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _i64, _vp]),
 }
 
 

@@ -33,6 +33,7 @@
 #include "interp_kernels.hpp"
 #include "anchor_kernels.hpp"
 #include "topanchor_kernels.hpp"
+#include "context_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "tracknms_kernels.hpp"
 #include "rescore_kernels.hpp"
@@ -230,6 +231,13 @@ struct vdet_ctx {
     DevBuf topa_hist, topa_state, topa_cnt, topa_nrec, topa_rec;
     bool topa_hist_clean = false; // the histogram holds zeros (every selection round clears what it read)
     DevBuf svm_wt, svm_wavebad;   // SVM head (svmhead_kernels.hpp): the W^T copy of the call and the per-wave counts of empty groups
+    // multi-context suppression (context_kernels.hpp): the per-video {elements, record slice} table of the batch forms, keyed by
+    // the offsets and the shape, and the selection's scratch
+    StagedTab ctxs_tab;
+    DevBuf ctxs_hist, ctxs_state, ctxs_rec;
+    int64_t ctxs_last_videos = 0; // videos of the last vdet_context_classes (vdet_query 13)
+    bool ctxs_records = true;     // VDET_CTX_RECORDS=0: no record scratch, every video through the full-read passes (the path of a video
+                                  // whose records outgrow it twice: an all-equal volume)
 };
 
 namespace {
@@ -1497,6 +1505,7 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_SMALL_LISTS")) c->small_lists = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_GLOBAL")) c->tcn_global = atoi(e) != 0;
+    if (const char *e = getenv("VDET_CTX_RECORDS")) c->ctxs_records = atoi(e) != 0;
     if (const char *e = getenv("VDET_VPASS_FORM")) { const int v = atoi(e); if (v >= VDET_VPASS_AUTO && v <= VDET_VPASS_ONE_PER_CU) c->vpass_form = v; }
     if (const char *e = getenv("VDET_VPASS_FCHUNK")) { const int v = atoi(e); if (v >= 1) c->vpass_fchunk = v; }
     {   // probe: do returning LDS atomics resolve same-address lanes in ascending lane order?
@@ -1572,7 +1581,8 @@ int vdet_destroy(vdet_ctx *c)
                       &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
-                      &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad};
+                      &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad,
+                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1628,6 +1638,15 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 10) return (int)std::min<long long>(c->tcn_params.uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
     if (what == 11) return (int)std::min<long long>(c->anchor_tab.uploads, 0x7FFFFFFF);   // per-video tables of the anchor route's batch forms staged so far
     if (what == 12) return c->vpass_last_items;   // 4: the current fused kernel, 2: the lean one, 0: the separate temporal kernels; + 100: one block per unit
+    if (what == 13) {  // full reads of the volume the last vdet_context_classes needed (-1: no call yet)
+        if (c->ctxs_last_videos <= 0 || !c->ctxs_state.p) return -1;
+        std::vector<CtxState> h((size_t)c->ctxs_last_videos);
+        if (hipMemcpyAsync(h.data(), c->ctxs_state.p, h.size() * sizeof(CtxState), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            host_sync(c) != hipSuccess) return VDET_EHIP;
+        int reads = 0;
+        for (const CtxState &st : h) reads = std::max(reads, st.empty ? 0 : 2 + (int)st.path);
+        return reads;
+    }
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -4524,6 +4543,146 @@ int vdet_propagate_boxes(vdet_ctx *c, const int32_t *d_fsum, int64_t F, int64_t 
     {
         StageTimer tm(c, ST_OTHER);
         hipLaunchKernelGGL(propagate_boxes_kernel, dim3((unsigned)((threads + kMoPropLT - 1) / kMoPropLT)), dim3(kMoPropLT), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-context suppression (context_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// records a video of `ne` elements may write (0: none, the full-read passes)
+uint32_t ctxs_cap(const vdet_ctx *c, int64_t ne)
+{
+    if (!c->ctxs_records) return 0u;
+    return (uint32_t)std::min<int64_t>(kCtxRecMax, std::max<int64_t>(kCtxRecMin, ne / 64));
+}
+
+// THE shape check and video table of both entry points: one video by value (*one, no host table), or the staged table of V
+// videos keyed by the offsets and the shape.  *chunks: chunks of the longest video; *cap_max / *rec_total: the record slices.
+int ctxs_videos(vdet_ctx *c, int64_t F, int64_t B, int64_t C, const int64_t *h_frame_off, int64_t V, CtxVid *one, int64_t *nv,
+                int64_t *chunks, uint32_t *cap_max, int64_t *rec_total)
+{
+    if (F <= 0 || B <= 0 || C <= 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
+    // the class of an element is (class of the chunk's first element + offset in the chunk) % C in 32-bit arithmetic: the sum
+    // (< C + kCtxChunk + 4) and the suppress kernel's running class (< 2 C) must fit 32 bits.  No other limit on C.
+    if (C > 0x7FFF0000ll) return fail(c, VDET_EINVAL, "C = %lld classes; the limit is 2^31 - 65536", (long long)C);
+    int64_t Fmax = F;
+    *nv = 1;
+    if (h_frame_off) {
+        int64_t Ft = 0;
+        const int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
+        if (rc) return rc;
+        if (Ft != F) return fail(c, VDET_EINVAL, "frame_off must end at F");
+        *nv = V;
+    }
+    if (Fmax * B > 0xFFFFFFFFll / C) return fail(c, VDET_EINVAL, "a video of 2^32 scores or more (the counters are 32 bits wide)");
+    *chunks = (Fmax * B * C + kCtxChunk - 1) / kCtxChunk;
+    *cap_max = ctxs_cap(c, Fmax * B * C);
+    if (!h_frame_off) {
+        *one = CtxVid{0, F * B * C, 0, *cap_max, 0u};
+        *rec_total = *cap_max;
+        return VDET_OK;
+    }
+    int64_t total = 0;
+    for (int64_t v = 0; v < V; ++v) total += ctxs_cap(c, (h_frame_off[v + 1] - h_frame_off[v]) * B * C);
+    *rec_total = total;
+    std::vector<int64_t> key(h_frame_off, h_frame_off + V + 1);
+    key.push_back(B); key.push_back(C); key.push_back(c->ctxs_records ? 1 : 0);
+    return stage_keyed(c, c->ctxs_tab, key.data(), key.size() * 8, (size_t)V * sizeof(CtxVid), [&](char *dst) {
+        CtxVid *tab = reinterpret_cast<CtxVid *>(dst);
+        int64_t rec0 = 0;
+        for (int64_t v = 0; v < V; ++v) {
+            const int64_t ne = (h_frame_off[v + 1] - h_frame_off[v]) * B * C;
+            tab[v] = CtxVid{h_frame_off[v] * B * C, ne, rec0, ctxs_cap(c, ne), 0u};
+            rec0 += tab[v].cap;
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdet_context_classes(vdet_ctx *c, const float *d_scores, int64_t F, int64_t B, int64_t C, double ratio, int64_t top,
+                         int64_t min_hits, int use_score_thresh, double score_thresh, const int64_t *h_frame_off, int64_t V,
+                         float *d_thresh, int64_t *d_n, int32_t *d_hits, uint8_t *d_high)
+{
+    if (!c) return VDET_EINVAL;
+    if (top < 0) return fail(c, VDET_EINVAL, "top must be at least 1 (0: by ratio)");
+    if (top == 0 && !(ratio > 0.0 && ratio <= 1.0)) return fail(c, VDET_EINVAL, "ratio must lie in (0, 1]");
+    if (min_hits < 1) return fail(c, VDET_EINVAL, "min_hits must be at least 1");
+    if (!d_scores || !d_thresh || !d_n || !d_hits || !d_high) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_scores & 3) != 0) return fail(c, VDET_EINVAL, "d_scores must be 4-byte aligned");
+    CtxArgs a{};
+    int64_t nv = 1, chunks = 0, rec_total = 0;
+    uint32_t cap_max = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ctxs_videos(c, F, B, C, h_frame_off, V, &a.one, &nv, &chunks, &cap_max, &rec_total);
+    if (rc) return rc;
+    timing_reset(c);
+    HIPCHK(c, c->ctxs_hist.reserve((size_t)nv * kCtxBins * 4));
+    HIPCHK(c, c->ctxs_state.reserve((size_t)nv * sizeof(CtxState)));
+    HIPCHK(c, c->ctxs_rec.reserve(std::max<size_t>((size_t)rec_total * 8, 16)));
+    HIPCHK(c, hipMemsetAsync(c->ctxs_hist.p, 0, (size_t)nv * kCtxBins * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_hits, 0, (size_t)(nv * C) * 4, c->stream));
+    c->ctxs_last_videos = nv;
+    a.scores = d_scores;
+    a.vids = h_frame_off ? c->ctxs_tab.dev.as<CtxVid>() : nullptr;
+    a.V = (int)nv; a.C = (int)C;
+    a.use_thr = use_score_thresh ? 1 : 0; a.thr = (float)score_thresh;
+    a.ratio = ratio; a.top = top; a.min_hits = min_hits;
+    a.hist = c->ctxs_hist.as<uint32_t>(); a.state = c->ctxs_state.as<CtxState>(); a.rec = c->ctxs_rec.as<uint2>();
+    a.othresh = d_thresh; a.on = d_n; a.ohits = d_hits; a.ohigh = d_high;
+    const dim3 gvol((unsigned)chunks, (unsigned)nv), gsel((unsigned)nv);
+    const dim3 grec((unsigned)((cap_max + 1023u) / 1024u), (unsigned)nv);
+    {
+        StageTimer tm(c, ST_TPICK);
+        hipLaunchKernelGGL(ctxs_hist_kernel<0>, gvol, dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_select_kernel, gsel, dim3(256), 0, c->stream, a, 0);
+        hipLaunchKernelGGL(ctxs_hist_kernel<1>, gvol, dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_select_kernel, gsel, dim3(256), 0, c->stream, a, 1);
+        if (cap_max) hipLaunchKernelGGL(ctxs_rec_hist_kernel, grec, dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_hist_kernel<2>, gvol, dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_select_kernel, gsel, dim3(256), 0, c->stream, a, 2);
+        if (cap_max) hipLaunchKernelGGL(ctxs_rec_hits_kernel, dim3((cap_max + kCtxHitsPer - 1) / kCtxHitsPer, (unsigned)nv), dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_hits_kernel, gvol, dim3(kCtxLT), 0, c->stream, a);
+        hipLaunchKernelGGL(ctxs_finish_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)nv), dim3(256), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_suppress_context(vdet_ctx *c, const float *d_scores, int64_t F, int64_t B, int64_t C, const uint8_t *d_high,
+                          double penalty, const int64_t *h_frame_off, int64_t V, float *d_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (!std::isfinite(penalty) || penalty < 0.0 || !std::isfinite((float)penalty))
+        return fail(c, VDET_EINVAL, "penalty must be finite (as a float32) and >= 0");
+    if (!d_scores || !d_high || !d_out) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_scores & 3) != 0 || ((uintptr_t)d_out & 3) != 0) return fail(c, VDET_EINVAL, "d_scores and d_out must be 4-byte aligned");
+    CtxSuppressArgs a{};
+    int64_t nv = 1, chunks = 0, rec_total = 0;
+    uint32_t cap_max = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ctxs_videos(c, F, B, C, h_frame_off, V, &a.one, &nv, &chunks, &cap_max, &rec_total);
+    if (rc) return rc;
+    if (d_out != d_scores) {
+        const uintptr_t s0 = (uintptr_t)d_scores, o0 = (uintptr_t)d_out, bytes = (uintptr_t)(F * B * C) * 4;
+        if (s0 < o0 + bytes && o0 < s0 + bytes) return fail(c, VDET_EINVAL, "d_out must be d_scores itself or not overlap it");
+    }
+    timing_reset(c);
+    a.in = d_scores; a.out = d_out; a.high = d_high;
+    a.vids = h_frame_off ? c->ctxs_tab.dev.as<CtxVid>() : nullptr;
+    a.C = (int)C; a.penalty = (float)penalty;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(ctxs_suppress_kernel, dim3((unsigned)chunks, (unsigned)nv), dim3(kCtxLT), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;

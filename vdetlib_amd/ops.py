@@ -1835,6 +1835,100 @@ def propagate_detections(motion, still, top, reach=3, decay=1.0, sync=True, ctx=
     return dict(tracks=tracks, ntracks=ntracks, score=score, src=src)
 
 
+def _context_videos(scores, frame_off, C=None):
+    """(F, B, C, offsets or None) of a score volume [F,B,C] that the context stage reads, with its optional video split.  The
+    stage has no boxes, so F and B are the scores' own (``_volume_layout`` takes them from the boxes)."""
+    ss = tuple(getattr(scores, 'shape', ()))
+    if getattr(scores, 'dtype', None) != torch.float32 or len(ss) != 3 or (C is not None and ss[2] != C):
+        raise ValueError("scores must be float32 [F,B,C]" + ("" if C is None else " with C = %d" % C))
+    if min(ss) < 1:
+        raise ValueError("scores must hold at least one frame, one box per frame and one class")
+    F, B, C = ss
+    return F, B, C, None if frame_off is None else _frame_offsets(frame_off, F)
+
+
+def context_classes(scores, ratio=0.0003, top=None, min_hits=1, score_thresh=None, frame_off=None, sync=True, ctx=None):
+    """Multi-context suppression, first half: the classes a video's highest-ranked detection scores belong to (include/vdet_hip.h:
+    vdet_context_classes; the rule is tests/context_spec.py, which the device matches on bits).  T-CNN runs the stage between
+    the still-image detector and per-frame NMS / tubelet seeding; the reference library has no function for it.
+
+    scores [F,B,C] f32, class innermost; ``frame_off`` [V+1] splits the frames into videos (as ``top_anchors``), every step
+    then runs per video.  A candidate is a score that is not NaN and -- with ``score_thresh`` -- is > score_thresh (float32
+    compare; ``-inf`` drops io.py's padding, without a threshold ``-inf`` IS a candidate); n is their number.  The rank is
+    k = min(top, n) with ``top``, else max(1, floor(ratio * n)) clamped to n (one float64 product).  ``thresh`` is the k-th
+    largest candidate (-0.0 == +0.0; +inf when n == 0), ``hits[c]`` the number of candidates of class c that are >= thresh
+    (every tie counts), ``high[c]`` = hits[c] >= min_hits.
+
+    ``ratio`` = 0.0003 (and ``suppress_context``'s penalty 0.4) are starting points recalled from the T-CNN paper: they are
+    not taken from the reference and not tuned.
+
+    Returns (thresh [V] f32, n [V] int64, hits [V,C] int32, high [V,C] bool); without ``frame_off`` the V axis is dropped.  No
+    host wait with ``sync=False``.  ValueError -- before any launch -- for a wrong dtype, device or shape, ``ratio`` outside
+    (0, 1], ``top`` < 1, ``min_hits`` < 1, and beyond the limits (F*B < 2^31 - 16, every video below 2^32 scores)."""
+    ratio = float(ratio)
+    if top is None and not 0.0 < ratio <= 1.0:
+        raise ValueError("ratio must lie in (0, 1]")
+    if top is not None and int(top) < 1:
+        raise ValueError("top must be at least 1")
+    if int(min_hits) < 1:
+        raise ValueError("min_hits must be at least 1")
+    F, B, C, off = _context_videos(scores, frame_off)
+    _same_gpu((scores,), "scores")
+    ctx = _ctx_for(scores, ctx)
+    scores = scores.contiguous()
+    lead = () if off is None else (len(off) - 1,)
+    dev = scores.device
+    thresh = torch.empty(lead, dtype=torch.float32, device=dev)
+    n = torch.empty(lead, dtype=torch.int64, device=dev)
+    hits = torch.empty(lead + (C,), dtype=torch.int32, device=dev)
+    high = torch.empty(lead + (C,), dtype=torch.bool, device=dev)
+    ctx.check(ctx.lib.vdet_context_classes(
+        ctx.h, scores.data_ptr(), F, B, C, ratio, 0 if top is None else min(int(top), 2 ** 62), min(int(min_hits), 2 ** 62),
+        0 if score_thresh is None else 1, 0.0 if score_thresh is None else float(score_thresh),
+        off.ctypes.data if off is not None else None, 0 if off is None else len(off) - 1,
+        thresh.data_ptr(), n.data_ptr(), hits.data_ptr(), high.data_ptr()))
+    if sync:
+        ctx.sync()
+    return thresh, n, hits, high
+
+
+def suppress_context(scores, high, penalty=0.4, frame_off=None, out=None, sync=True, ctx=None):
+    """Multi-context suppression, second half: ``penalty`` (as a float32, one subtraction) off every score whose class is not
+    among its video's high-confidence classes; scores of high classes and NaN are copied bit for bit, ``-inf`` stays ``-inf``
+    (include/vdet_hip.h: vdet_suppress_context).  One launch, one read and one write.
+
+    scores [F,B,C] f32; ``high`` bool [C], or [V,C] with ``frame_off`` [V+1]: ``context_classes``' last output.  ``out``: None
+    allocates; ``out=scores`` works in place (a c2 volume is 2.4 GB); any other contiguous f32 tensor of the scores' shape on
+    the same GPU that does not overlap them is written.  Returns the suppressed scores.  The default penalty is a starting
+    point recalled from the T-CNN paper, not taken from the reference and not tuned.  ValueError before any launch for a wrong
+    dtype, device or shape and for a penalty that is not finite (as a float32) or is < 0."""
+    penalty = float(penalty)
+    if not math.isfinite(penalty) or penalty < 0 or penalty > float(np.finfo(np.float32).max):
+        raise ValueError("penalty must be finite (as a float32) and >= 0")
+    F, B, C, off = _context_videos(scores, frame_off)
+    if high.dtype != torch.bool or tuple(high.shape) != ((C,) if off is None else (len(off) - 1, C)):
+        raise ValueError("high must be bool [C], or [V,C] with frame_off, for scores [F,B,%d]" % C)
+    inplace = out is scores
+    if out is not None and not inplace:
+        if out.dtype != torch.float32 or out.shape != scores.shape or not out.is_contiguous():
+            raise ValueError("out must be scores itself or a contiguous float32 tensor of the scores' shape")
+    if inplace and not scores.is_contiguous():
+        raise ValueError("out=scores needs contiguous scores")
+    _same_gpu((scores, high, out), "scores, high and out")
+    ctx = _ctx_for(scores, ctx)
+    scores, high = scores.contiguous(), high.contiguous()
+    if out is None:
+        out = torch.empty_like(scores)
+    elif inplace:
+        out = scores
+    ctx.check(ctx.lib.vdet_suppress_context(
+        ctx.h, scores.data_ptr(), F, B, C, high.data_ptr(), penalty, off.ctypes.data if off is not None else None,
+        0 if off is None else len(off) - 1, out.data_ptr()))
+    if sync:
+        ctx.sync()
+    return out
+
+
 def _rt_call(ctx, off, B, C, T, tracks, ntracks, boxes, scores, floor, overlap_thres, complete, window, sync):
     """The one call behind rescore_tubelets / rescore_tubelets_batch: flat tensors in, flat outputs back."""
     V, Ft = len(off) - 1, int(off[-1])
