@@ -126,6 +126,13 @@
  *                                          (0, 1] or top >= 1, min_hits >= 1, penalty finite as a float32 and >= 0      VDET_EINVAL.
  *                                                                     A video whose records outgrow the scratch (an all-equal
  *                                                                     volume) takes the full-read passes: same results
+ *   Seq-NMS                                (vdet_seq_nms, vdet_seq_nms_batch) 1 <= R <= 256 rows per (frame, class) (cut wider
+ *                                          lists with vdet_nms_tracks' R), 1 <= max_seqs <= 4096, C*R*F, C*max_seqs*V and the
+ *                                          link words C*F*R*ceil(R/32) below 2^31 - 16, at most 65535 videos, link_thres and
+ *                                          nms_thres finite, min_score not NaN, rescore 0 or 1                          VDET_EINVAL.
+ *                                                                     A video whose predecessor table ((F_v*Rp + F_v) int16,
+ *                                                                     Rp = R rounded up to 64) outgrows 128 KiB of LDS keeps
+ *                                                                     it in global scratch: same results
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -210,6 +217,8 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * what = 13 -> full reads of the volume the last vdet_context_classes needed, the most of any of its videos: 2, 3 (the records
  * fit only below the second digit) or 4 (they never fit, or VDET_CTX_RECORDS=0); 0 when no video had a candidate; -1 before
  * the first call (synchronises the stream).
+ * what = 14 -> where the last vdet_seq_nms[_batch] kept the predecessor table: 1 in LDS, 2 in global scratch (the longest video's
+ * table outgrew the LDS budget, or VDET_SEQNMS_LDS=0); -1 before the first call.
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant -- the one switch that does, VDET_VPASS_FORM,
@@ -228,6 +237,7 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  *   VDET_TCN_GLOBAL=1     device TCN: the activations in global memory (what nets too wide for the LDS budget take)
  *   VDET_CTX_RECORDS=0    vdet_context_classes: no record scratch, every digit round and the per-class count by a full read of
  *                         the volume (what a video takes whose records outgrow the scratch: an all-equal volume)
+ *   VDET_SEQNMS_LDS=0     vdet_seq_nms: the predecessor table of the best-path pass in global scratch (what long videos take)
  *   VDET_ATOMIC_RANK=0 / VDET_WAVE_TRANSPOSE=0   the variants selected when the start-up hardware probes fail
  *   VDET_BITS_BUDGET_MB=n bytes of bit-matrix scratch per graph-build batch (default 1024) */
 int vdet_query(vdet_ctx *ctx, int what);
@@ -1350,6 +1360,57 @@ int vdet_context_classes(vdet_ctx *ctx, const float *d_scores, int64_t F, int64_
 
 int vdet_suppress_context(vdet_ctx *ctx, const float *d_scores, int64_t F, int64_t B, int64_t C, const uint8_t *d_high,
                           double penalty, const int64_t *h_frame_off, int64_t V, float *d_out);
+
+/* ---- Seq-NMS (csrc/seqnms_kernels.hpp): Han et al. 2016 on per-frame detections in the tubelet layout -- link the boxes of
+ *      neighbouring frames that overlap, take the sequence with the largest score sum, re-score its boxes, suppress what they
+ *      overlap in their own frames, repeat.  The reference library has no function for it; the rule is tests/seqnms_spec.py ----
+ *
+ * d_tracks f32 [C,R,F,5] (x1, y1, x2, y2, score), d_ntracks int32 [C], d_score [C,R,F] f32 (score_f64 == 0) or f64, or NULL:
+ * column 4 scores the boxes -- what vdet_nms_tracks returns.  Per class:
+ *   node      row (r, f) with r < ntracks (clamped to 0..R), x1 not NaN and a finite score; the score is taken as f64 (exact)
+ *   hit       hit(a, b, t): the f32 arithmetic of nms (utils/nms.pyx:57-65: +1 areas, inter, uni = (area_a + area_b) - inter),
+ *             true iff uni > 0 and (double)(inter / uni) >= t.  A zero, negative or NaN union is false: nothing raises
+ *   link      node (q, f) -> node (r, f+1) iff hit(box[q,f], box[r,f+1], link_thres); neighbouring frames only
+ *   round k   over the nodes still live, frames ascending: best[r,f] = s[r,f] + b, b the largest best[q,f-1] among the live q that
+ *             link to (r, f) and have best[q,f-1] >= 0, ptr the lowest such q attaining it; with none best = s exactly.  (Extending
+ *             only from a non-negative sum makes it the maximum-sum path for negative scores too; a zero sum extends.)  The end
+ *             node is the live node with the largest best -- ties: lowest frame, then lowest slot.  The rounds stop when no node is
+ *             live, when best_end < min_score, or when k == max_seqs.  The sequence is ptr followed back from the end node; its
+ *             sum IS best_end (the left-to-right f64 sum; nothing is summed again).  New score of its nodes: rescore 0 best_end /
+ *             len (one f64 division), rescore 1 the largest s on the path (folded left to right, m = s > m ? s : m).  Every other
+ *             live node (q, f) of a path node (r, f)'s frame with hit(box[r,f], box[q,f], nms_thres) is suppressed; the path
+ *             nodes become members of sequence k; both leave the live set
+ *   leftover  a node still live after the rounds keeps its score
+ * Outputs (slots stay where they were: no compaction, no re-ranking), S = max_seqs:
+ *   d_tracks_out f32 [C,R,F,5]  members and leftovers: the input box bits and (float)new score; every other row five NaNs
+ *   d_score_out  f64 [C,R,F]    the new score, NaN elsewhere
+ *   d_seq_out    int32 [C,R,F]  k >= 0 member of sequence k, -1 leftover, -2 suppressed, INT32_MIN no node
+ *   d_ntracks_out int32 [C]     the clamped input;   d_nseq int32 [C] sequences taken
+ *   d_seq_sum f64 [C,S], d_seq_len int32 [C,S], d_seq_end int32 [C,S,2] (frame, slot); NaN, 0 and -1 behind nseq
+ *   d_exhausted uint8 [C]       1 iff no node was live when the rounds ended
+ * The kernels write every element of every output, whatever the inputs hold.  Launches: one that writes the outputs' initial
+ * state, the live bits and the link bits (scratch of the context: C*F*R*ceil(R/32) u32 -- 123 MB for 200 x 300 x 128), then
+ * ceil((max_seqs + 1) / rounds) launches of one block per (video, class) with rounds = max(1, 16384 / longest video) rounds
+ * each; no host wait, no block waits for another.  Timed under "track_link" and "track_loop".
+ *
+ * vdet_seq_nms_batch: V videos along the frames as in vdet_nms_tracks_batch -- h_frame_off [V+1], the arrays of video v start at
+ * element C*R*h_frame_off[v] (times 5 for the boxes) and are [C,R,F_v,...] there; d_ntracks, d_ntracks_out, d_nseq, d_exhausted
+ * [V,C]; d_seq_sum / d_seq_len [V,C,S], d_seq_end [V,C,S,2], frames counted within the video.  Per video the bits are
+ * vdet_seq_nms' on that video alone; no sequence crosses a video border.  The per-video table is the staged one of vdet_query 11.
+ *
+ * Both: argument checks before any launch, VDET_EINVAL, nothing touched; ctx NULL: VDET_EINVAL.  Nothing of the context's cached
+ * graph, lists, index or link memo is read or written.  Limits: the table at the top of this file.
+ */
+int vdet_seq_nms(vdet_ctx *ctx, int64_t F, int64_t C, int R, const float *d_tracks, const int32_t *d_ntracks, const void *d_score,
+                 int score_f64, double link_thres, double nms_thres, int rescore, int max_seqs, double min_score,
+                 float *d_tracks_out, double *d_score_out, int32_t *d_seq_out, int32_t *d_ntracks_out, int32_t *d_nseq,
+                 double *d_seq_sum, int32_t *d_seq_len, int32_t *d_seq_end, uint8_t *d_exhausted);
+
+int vdet_seq_nms_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t C, int R, const float *d_tracks,
+                       const int32_t *d_ntracks, const void *d_score, int score_f64, double link_thres, double nms_thres,
+                       int rescore, int max_seqs, double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_seq_out,
+                       int32_t *d_ntracks_out, int32_t *d_nseq, double *d_seq_sum, int32_t *d_seq_len, int32_t *d_seq_end,
+                       uint8_t *d_exhausted);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,10 @@ SYMBOLS = {
                                    _vp, _vp, _vp, _vp]),
     "vdet_context_classes": (_ci, [_vp, _vp, _i64, _i64, _i64, _f64, _i64, _i64, _ci, _f64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "vdet_suppress_context": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _f64, _vp, _i64, _vp]),
+    "vdet_seq_nms": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _f64, _f64, _ci, _ci, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp]),
+    "vdet_seq_nms_batch": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _f64, _f64, _ci, _ci, _f64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp]),
 }
 
 

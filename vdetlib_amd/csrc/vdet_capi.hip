@@ -41,6 +41,7 @@
 #include "svmhead_kernels.hpp"
 #include "pixtrack_kernels.hpp"
 #include "motion_kernels.hpp"
+#include "seqnms_kernels.hpp"
 
 using namespace vdet;
 
@@ -238,6 +239,12 @@ struct vdet_ctx {
     int64_t ctxs_last_videos = 0; // videos of the last vdet_context_classes (vdet_query 13)
     bool ctxs_records = true;     // VDET_CTX_RECORDS=0: no record scratch, every video through the full-read passes (the path of a video
                                   // whose records outgrow it twice: an all-equal volume)
+    // Seq-NMS (seqnms_kernels.hpp): the link bits, the live bits, the done flags and -- for videos whose predecessor table
+    // outgrows the LDS -- the table itself
+    DevBuf sq_link, sq_live, sq_done, sq_ptr;
+    bool sq_lds = true;           // VDET_SEQNMS_LDS=0: the predecessor table in global scratch (the path of long videos)
+    bool sq_attr_set = false;
+    int sq_last_path = -1;        // vdet_query 14: 1 the table in LDS, 2 in global scratch
 };
 
 namespace {
@@ -1506,6 +1513,7 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_GLOBAL")) c->tcn_global = atoi(e) != 0;
     if (const char *e = getenv("VDET_CTX_RECORDS")) c->ctxs_records = atoi(e) != 0;
+    if (const char *e = getenv("VDET_SEQNMS_LDS")) c->sq_lds = atoi(e) != 0;
     if (const char *e = getenv("VDET_VPASS_FORM")) { const int v = atoi(e); if (v >= VDET_VPASS_AUTO && v <= VDET_VPASS_ONE_PER_CU) c->vpass_form = v; }
     if (const char *e = getenv("VDET_VPASS_FCHUNK")) { const int v = atoi(e); if (v >= 1) c->vpass_fchunk = v; }
     {   // probe: do returning LDS atomics resolve same-address lanes in ascending lane order?
@@ -1582,7 +1590,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
                       &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad,
-                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec};
+                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec, &c->sq_link, &c->sq_live, &c->sq_done, &c->sq_ptr};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1647,6 +1655,7 @@ int vdet_query(vdet_ctx *c, int what)
         for (const CtxState &st : h) reads = std::max(reads, st.empty ? 0 : 2 + (int)st.path);
         return reads;
     }
+    if (what == 14) return c->sq_last_path;   // the last vdet_seq_nms[_batch]: 1 predecessor table in LDS, 2 in global scratch (-1: no call yet)
     if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
@@ -4686,6 +4695,91 @@ int vdet_suppress_context(vdet_ctx *c, const float *d_scores, int64_t F, int64_t
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Seq-NMS (seqnms_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_seq_nms_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int R, const float *d_tracks,
+                       const int32_t *d_ntracks, const void *d_score, int score_f64, double link_thres, double nms_thres,
+                       int rescore, int max_seqs, double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_seq_out,
+                       int32_t *d_ntracks_out, int32_t *d_nseq, double *d_seq_sum, int32_t *d_seq_len, int32_t *d_seq_end,
+                       uint8_t *d_exhausted)
+{
+    if (!c) return VDET_EINVAL;
+    if (C < 1) return fail(c, VDET_EINVAL, "bad shape");
+    int64_t F = 0, Fmax = 0;
+    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    if (rc) return rc;
+    if (R < 1 || R > kSqMaxR) return fail(c, VDET_EINVAL, "R = %d rows per (frame, class); 1 .. %d (cut wider lists with vdet_nms_tracks' R)", R, kSqMaxR);
+    if (max_seqs < 1 || max_seqs > kSqMaxSeqs) return fail(c, VDET_EINVAL, "max_seqs = %d; 1 .. %d", max_seqs, kSqMaxSeqs);
+    if (rescore != 0 && rescore != 1) return fail(c, VDET_EINVAL, "rescore must be 0 (average) or 1 (maximum)");
+    if (!std::isfinite(link_thres) || !std::isfinite(nms_thres)) return fail(c, VDET_EINVAL, "link_thres and nms_thres must be finite");
+    if (min_score != min_score) return fail(c, VDET_EINVAL, "min_score must not be NaN");
+    const int64_t W = (R + 31) / 32, Rp = (R + 63) / 64 * 64;
+    if (C > 0x7FFFFFF0ll / R || C * R > 0x7FFFFFF0ll / F || C * (int64_t)R * F >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many boxes (C*R*F must stay below 2^31 - 16)");
+    if (C * (int64_t)R * F > 0x7FFFFFF0ll / W || C * (int64_t)R * F * W >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many link words (C*F*R*ceil(R/32) must stay below 2^31 - 16)");
+    if (C * V > 0x7FFFFFF0ll / max_seqs || C * V * max_seqs >= 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "too many sequences (C*max_seqs*V must stay below 2^31 - 16)");
+    if (!d_tracks || !d_ntracks) return fail(c, VDET_EINVAL, "null buffer");
+    if (!d_tracks_out || !d_score_out || !d_seq_out || !d_ntracks_out || !d_nseq || !d_seq_sum || !d_seq_len || !d_seq_end || !d_exhausted)
+        return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    SeqNmsArgs g{};
+    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_nms_tracks_batch)
+        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+        g.vids = c->anchor_tab.dev.as<VidDesc>();
+    }
+    // the predecessor table of the longest video: in LDS while it fits the budget (and the device's LDS), else in global scratch
+    const void *rounds_fn = reinterpret_cast<const void *>(seqnms_rounds_kernel);
+    const size_t ptr_bytes = (size_t)(Fmax * Rp + Fmax) * 2;
+    size_t budget = kSqLdsBudget;
+    if (c->max_lds < (size_t)kSqLdsBudget + 16384) budget = c->max_lds > 32768 ? c->max_lds - 16384 : 0;
+    const bool lds = c->sq_lds && ptr_bytes <= budget;
+    if (lds && !c->sq_attr_set) {
+        HIPCHK(c, hipFuncSetAttribute(rounds_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget));
+        c->sq_attr_set = true;
+    }
+    HIPCHK(c, c->sq_link.reserve((size_t)(C * R * F * W) * 4));
+    HIPCHK(c, c->sq_live.reserve((size_t)(C * F * W) * 4));
+    HIPCHK(c, c->sq_done.reserve((size_t)(V * C) * 4));
+    if (!lds) HIPCHK(c, c->sq_ptr.reserve((size_t)(C * F * (Rp + 1)) * 2));
+    g.tracks = d_tracks; g.ntracks = d_ntracks; g.score = d_score; g.score_f64 = score_f64 ? 1 : 0;
+    g.F = (int)Fmax; g.Ftot = (int)F; g.C = (int)C; g.R = R; g.W = (int)W; g.Rp = (int)Rp; g.S = max_seqs; g.rescore = rescore;
+    g.rounds = (int)std::max<int64_t>(1, kSqFrameSteps / Fmax);
+    g.ptr_lds = lds ? 1 : 0;
+    g.link_t = link_thres; g.nms_t = nms_thres; g.min_score = min_score;
+    g.otracks = d_tracks_out; g.oscore = d_score_out; g.oseq = d_seq_out; g.ontracks = d_ntracks_out; g.onseq = d_nseq;
+    g.oseq_sum = d_seq_sum; g.oseq_len = d_seq_len; g.oseq_end = d_seq_end; g.oexh = d_exhausted;
+    g.link = c->sq_link.as<uint32_t>(); g.live = c->sq_live.as<uint32_t>(); g.done = c->sq_done.as<int32_t>();
+    g.gptr = lds ? nullptr : c->sq_ptr.as<int16_t>();
+    c->sq_last_path = lds ? 1 : 2;
+    {
+        StageTimer tm(c, ST_TLINK);
+        hipLaunchKernelGGL(seqnms_link_kernel, dim3((unsigned)(C * Fmax), (unsigned)V), dim3((unsigned)Rp), 0, c->stream, g);
+    }
+    {
+        StageTimer tm(c, ST_TLOOP);
+        const int launches = (max_seqs + 1 + g.rounds - 1) / g.rounds;      // (the + 1: the iteration that finds the rounds used up)
+        for (int i = 0; i < launches; ++i)
+            hipLaunchKernelGGL(seqnms_rounds_kernel, dim3((unsigned)C, (unsigned)V), dim3((unsigned)Rp), lds ? ptr_bytes : 0, c->stream, g);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_seq_nms(vdet_ctx *c, int64_t F, int64_t C, int R, const float *d_tracks, const int32_t *d_ntracks, const void *d_score,
+                 int score_f64, double link_thres, double nms_thres, int rescore, int max_seqs, double min_score,
+                 float *d_tracks_out, double *d_score_out, int32_t *d_seq_out, int32_t *d_ntracks_out, int32_t *d_nseq,
+                 double *d_seq_sum, int32_t *d_seq_len, int32_t *d_seq_end, uint8_t *d_exhausted)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_seq_nms_batch(c, off, 1, C, R, d_tracks, d_ntracks, d_score, score_f64, link_thres, nms_thres, rescore, max_seqs,
+                              min_score, d_tracks_out, d_score_out, d_seq_out, d_ntracks_out, d_nseq, d_seq_sum, d_seq_len,
+                              d_seq_end, d_exhausted);
 }
 
 }  // extern "C"

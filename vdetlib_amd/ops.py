@@ -1701,6 +1701,138 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
 
 
+_SQ_MAX_R, _SQ_MAX_SEQS = 256, 4096     # include/vdet_hip.h: vdet_seq_nms
+_SQ_RESCORE = ('avg', 'max')
+
+
+def _sq_settings(C, R, Ft, V, link_thres, nms_thres, rescore, max_seqs, min_score):
+    """The scalar arguments of seq_nms, checked against the limits of include/vdet_hip.h: (link, nms, rescore code, S, floor)."""
+    link_thres, nms_thres, min_score = float(link_thres), float(nms_thres), float(min_score)
+    if not (math.isfinite(link_thres) and math.isfinite(nms_thres)):
+        raise ValueError("link_thres and nms_thres must be finite")
+    if math.isnan(min_score):
+        raise ValueError("min_score must not be NaN")
+    if rescore not in _SQ_RESCORE:
+        raise ValueError("rescore must be 'avg' or 'max'")
+    S = int(max_seqs)
+    if not 1 <= S <= _SQ_MAX_SEQS:
+        raise ValueError("max_seqs = %d sequences per class; 1 .. %d" % (S, _SQ_MAX_SEQS))
+    if C < 1 or Ft < 1:
+        raise ValueError("at least one class and one frame")
+    if not 1 <= R <= _SQ_MAX_R:
+        raise ValueError("R = %d rows per (frame, class); 1 .. %d (cut wider lists with nms_tracks(cap=))" % (R, _SQ_MAX_R))
+    if max(C * R * Ft * ((R + 31) // 32), C * S * V) >= 2 ** 31 - 16:
+        raise ValueError("too many boxes (C*R*F, the link words C*F*R*ceil(R/32) and C*max_seqs*V must stay below 2^31 - 16)")
+    return link_thres, nms_thres, _SQ_RESCORE.index(rescore), S, min_score
+
+
+def _sq_call(ctx, off, C, R, tracks, ntracks, score, link_thres, nms_thres, rescore, S, min_score, sync):
+    """Allocate the outputs (flat, batch layout) and enqueue the launches; every tensor contiguous and on one device."""
+    V, Ft = len(off) - 1, int(off[-1])
+    dev = ntracks.device
+    N = C * R * Ft
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    o = dict(tracks=new((N * 5,), torch.float32), score=new((N,), torch.float64), seq=new((N,), torch.int32),
+             ntracks=new((V, C), torch.int32), nseq=new((V, C), torch.int32), seq_sum=new((V, C, S), torch.float64),
+             seq_len=new((V, C, S), torch.int32), seq_end=new((V, C, S, 2), torch.int32), exhausted=new((V, C), torch.uint8))
+    tail = (C, R, tracks.data_ptr(), ntracks.data_ptr(), None if score is None else score.data_ptr(),
+            int(score is not None and score.dtype == torch.float64), link_thres, nms_thres, rescore, S, min_score) + \
+        tuple(o[k].data_ptr() for k in ('tracks', 'score', 'seq', 'ntracks', 'nseq', 'seq_sum', 'seq_len', 'seq_end', 'exhausted'))
+    if V == 1:
+        ctx.check(ctx.lib.vdet_seq_nms(ctx.h, Ft, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_seq_nms_batch(ctx.h, off.ctypes.data, V, *tail))
+    if sync:
+        ctx.sync()
+    return o
+
+
+def seq_nms(dets, ntracks=None, score=None, link_thres=0.5, nms_thres=0.3, rescore='avg', max_seqs=32, min_score=-math.inf,
+            sync=True, ctx=None):
+    """Seq-NMS (Han et al. 2016) of per-frame detections in the tubelet layout, per class: link the boxes of neighbouring frames
+    whose IoU is >= ``link_thres``, take the sequence with the largest score sum (dynamic programming over the frames), give
+    each of its boxes the sequence's average (``rescore='avg'``) or maximum (``'max'``) score, suppress the boxes of the same
+    frames that overlap them by >= ``nms_thres``, and repeat on what is left -- at most ``max_seqs`` times, and only while the
+    best sum is >= ``min_score``.  The rule in full: include/vdet_hip.h (vdet_seq_nms); tests/seqnms_spec.py states it in numpy
+    and the device matches it on bits.  The reference library has no function for it.
+
+    ``dets``: the dict ``nms_tracks`` returned, or any tubelet dict with ``tracks`` / ``ntracks`` (``ntracks`` stays None), or
+    tracks [C,R,F,5] f32 with ntracks [C] int32.  ``score``: [C,R,F] f32 / f64, or -- with a dict -- the name of one of its
+    fields or the index of one of its ``series``; default: column 4 of the boxes.  A row is a node when its slot is below
+    ntracks, its x1 is not NaN and its score is finite.  R <= 256 (cut wider lists with ``nms_tracks(cap=)``), max_seqs <= 4096.
+
+    ``link_thres`` 0.5 and ``nms_thres`` 0.3 are the paper's; ``max_seqs`` = 32 is an untuned starting point, not taken from
+    anywhere.
+
+    Returns a dict; slots stay where they were (no compaction, no re-ranking), S = max_seqs:
+      tracks [C,R,F,5] f32   members of a sequence and leftovers: the input box and (float) new score; every other row NaN
+      score [C,R,F] f64      the new score (a leftover keeps its own), NaN elsewhere
+      seq [C,R,F] int32      k >= 0 member of sequence k, -1 leftover, -2 suppressed, INT32_MIN no node
+      ntracks [C] int32      the input clamped to 0..R;   nseq [C] int32 sequences taken
+      seq_sum [C,S] f64, seq_len [C,S] int32, seq_end [C,S,2] int32 (frame, slot): NaN, 0, -1 behind nseq
+      exhausted [C] uint8    1 iff no node was left when the rounds ended
+    ``DetEvaluator.add_detections`` takes the dict; ``top_anchors`` / ``nms_tracks`` take its tracks / ntracks / score.  No
+    host wait with ``sync=False``.  ValueError before any launch for a wrong dtype, device or shape and beyond the limits."""
+    tracks = dets
+    if isinstance(dets, dict):
+        d = dets
+        if ntracks is not None or any(k not in d for k in ('tracks', 'ntracks')):
+            raise ValueError("a tubelet dict needs tracks and ntracks, and takes the place of both arguments")
+        if isinstance(score, str):
+            if not torch.is_tensor(d.get(score)):
+                raise ValueError("score must name a tensor field of the dict, one of its series by index, or be a tensor")
+            score = d[score]
+        elif score is not None and not torch.is_tensor(score):
+            ser = d.get('series')
+            ser = (ser,) if torch.is_tensor(ser) else tuple(ser or ())
+            if not isinstance(score, int) or not 0 <= score < len(ser):
+                raise ValueError("score must name a tensor field of the dict, one of its %d series by index, or be a tensor" % len(ser))
+            score = ser[score]
+        tracks, ntracks = d['tracks'], d['ntracks']
+    if not torch.is_tensor(tracks) or tracks.dtype != torch.float32 or tracks.dim() != 4 or tracks.shape[3] != 5:
+        raise ValueError("tracks must be float32 [C,R,F,5]")
+    C, R, F = tracks.shape[0], tracks.shape[1], tracks.shape[2]
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if score is not None and (not torch.is_tensor(score) or score.dtype not in _F32_F64 or tuple(score.shape) != (C, R, F)):
+        raise ValueError("score must be float32 / float64 [C,R,F], or None for column 4 of the boxes")
+    st = _sq_settings(C, R, F, 1, link_thres, nms_thres, rescore, max_seqs, min_score)
+    _same_gpu([ntracks, tracks, score], "every tensor")
+    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), None if score is None else score.contiguous()
+    ctx = _ctx_for(ntracks, ctx)
+    o = _sq_call(ctx, np.array([0, F], dtype=np.int64), C, R, tracks, ntracks, score, *st, sync=sync)
+    S = st[3]
+    return dict(tracks=o['tracks'].view(C, R, F, 5), score=o['score'].view(C, R, F), seq=o['seq'].view(C, R, F),
+                ntracks=o['ntracks'].view(C), nseq=o['nseq'].view(C), seq_sum=o['seq_sum'].view(C, S), seq_len=o['seq_len'].view(C, S),
+                seq_end=o['seq_end'].view(C, S, 2), exhausted=o['exhausted'].view(C))
+
+
+def seq_nms_batch(batch_dets, score=None, link_thres=0.5, nms_thres=0.3, rescore='avg', max_seqs=32, min_score=-math.inf, sync=True,
+                  ctx=None):
+    """``seq_nms`` for every video of a dict in ``video_batch``'s layout (``_batch_read``; what ``nms_tracks_batch`` returns) in
+    the same launches.  ``score`` names the per-video field of the dict that scores the boxes ('score', 'pooled', ...: f32 or
+    f64); None: column 4.  Per video the bits are ``seq_nms``' on that video alone -- no sequence crosses a video border.
+    Returns ``tracks`` / ``score`` / ``seq`` as per-video views in the same layout, ``ntracks`` / ``nseq`` / ``exhausted`` [V,C],
+    ``seq_sum`` / ``seq_len`` [V,C,S], ``seq_end`` [V,C,S,2] (frames counted within the video) and ``frame_off``.  The defaults
+    are ``seq_nms``' (the paper's thresholds, an untuned ``max_seqs``)."""
+    b = _batch_read(batch_dets, 'batch_dets')
+    off, V, Ft, C, R, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
+    sc = None
+    if score is not None:
+        sv = batch_dets.get(score) if isinstance(score, str) else None
+        if not isinstance(sv, (list, tuple)) or not sv:
+            raise ValueError("score must name a per-video series of batch_dets (e.g. 'score', 'pooled'), or be None for column 4")
+        sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_dets')
+    st = _sq_settings(C, R, Ft, V, link_thres, nms_thres, rescore, max_seqs, min_score)
+    _same_gpu([ntracks, tracks, sc], "every tensor")
+    ctx = _ctx_for(ntracks, ctx)
+    o = _sq_call(ctx, off, C, R, tracks, ntracks, sc, *st, sync=sync)
+    views = lambda flat, per: _batch_views(flat, off, C, R, per)
+    return dict(tracks=views(o['tracks'], 5), score=views(o['score'], 1), seq=views(o['seq'], 1), ntracks=o['ntracks'],
+                nseq=o['nseq'], seq_sum=o['seq_sum'], seq_len=o['seq_len'], seq_end=o['seq_end'], exhausted=o['exhausted'],
+                frame_off=off)
+
+
 _MOTION_BLOCKS = (8, 16, 32)       # include/vdet_hip.h: vdet_motion_field
 _MOTION_MAX_REACH = 16
 
