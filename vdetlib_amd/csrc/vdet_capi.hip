@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -226,8 +227,9 @@ struct vdet_ctx {
     bool tcn_tiled = false;       // VDET_TCN_TILED=1: every series cut into the smallest tiles (the path of long series / wide nets)
     bool tcn_global = false;      // VDET_TCN_GLOBAL=1: activations in global memory (the path of nets too wide for the LDS budget)
     StagedTab interp_tab;         // device interpolation (interp_kernels.hpp): frame offsets and the frame table of the last call
-    // device anchor selection (topanchor_kernels.hpp) and the batch forms of the anchor route: the per-video {first frame,
-    // frames} table, keyed by the frame offsets (anchor_tab.uploads: vdet_query 11), and the selection's scratch
+    // the per-video {first frame, frames} table of every tubelet-stage batch form (anchor selection and route, merge, tubelet
+    // NMS, re-scoring, Seq-NMS), keyed by the frame offsets (video_table; anchor_tab.uploads: vdet_query 11), and the scratch of
+    // the device anchor selection (topanchor_kernels.hpp)
     StagedTab anchor_tab;
     DevBuf topa_hist, topa_state, topa_cnt, topa_nrec, topa_rec;
     bool topa_hist_clean = false; // the histogram holds zeros (every selection round clears what it read)
@@ -345,6 +347,62 @@ int check_frame_off(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, bool all
     *Ftot = h_frame_off[V];
     return VDET_OK;
 }
+
+// the videos of a call, concatenated along the frame axis
+struct Videos { const int64_t *off; int64_t V, F, Fmax; };            // F: all frames, Fmax: the longest video's
+
+// THE readers of a call's frame offsets: nothing else calls check_frame_off
+int read_videos(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t max_videos, Videos *vs, bool allow_empty = false)
+{
+    *vs = Videos{h_frame_off, V, 0, 0};
+    return check_frame_off(c, h_frame_off, V, allow_empty, max_videos, &vs->F, &vs->Fmax);
+}
+
+// ... where the offsets are optional: without them one video of F frames, with them they must end at F
+int read_videos_or_one(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t F, int64_t max_videos, Videos *vs)
+{
+    if (!h_frame_off) { *vs = Videos{nullptr, 1, F, F}; return VDET_OK; }
+    const int rc = read_videos(c, h_frame_off, V, max_videos, vs);
+    if (rc == VDET_OK && vs->F != F) return fail(c, VDET_EINVAL, "frame_off must end at F");
+    return rc;
+}
+
+// the per-video {first frame, frames} table in t, keyed by the offsets: built and uploaded only when they differ from those of
+// the resident one
+int stage_video_table(vdet_ctx *c, StagedTab &t, const Videos &vs)
+{
+    return stage_keyed(c, t, vs.off, (size_t)(vs.V + 1) * 8, (size_t)vs.V * sizeof(VidDesc), [&](char *dst) {
+        VidDesc *tab = reinterpret_cast<VidDesc *>(dst);
+        for (int64_t v = 0; v < vs.V; ++v) tab[v] = VidDesc{(int32_t)vs.off[v], (int32_t)(vs.off[v + 1] - vs.off[v])};
+    });
+}
+
+// ... for the kernels that take one video in their arguments: *vids is null for it and nothing is staged
+int video_table(vdet_ctx *c, StagedTab &t, const Videos &vs, const VidDesc **vids)
+{
+    *vids = nullptr;
+    if (vs.V == 1) return VDET_OK;
+    const int rc = stage_video_table(c, t, vs);
+    if (rc == VDET_OK) *vids = t.dev.as<VidDesc>();
+    return rc;
+}
+
+// THE limit check of a product of caller-supplied sizes: every factor >= 0 and the product <= limit (fits_upto) or < limit
+// (fits_below).  The limit is divided, the factors are never multiplied: a product that would wrap int64_t is refused like
+// any other that is too large.
+bool fits_upto(int64_t limit, std::initializer_list<int64_t> factors)
+{
+    if (limit < 0) return false;
+    bool zero = false;
+    for (const int64_t f : factors) {
+        if (f < 0) return false;
+        if (f == 0) zero = true;
+        else limit /= f;          // floor(floor(limit / a) / b) == floor(limit / (a * b))
+    }
+    return zero || limit >= 1;
+}
+
+bool fits_below(int64_t limit, std::initializer_list<int64_t> factors) { return fits_upto(limit - 1, factors); }
 
 // smallest float32 f with (double)f >= thresh: "(double)ovr_f32 >= thresh" <=> "ovr_f32 >= f"
 float thresh_to_f32(double thresh)
@@ -608,7 +666,7 @@ int track_scratch(vdet_ctx *c, int64_t Ftot, int64_t B, int64_t C, int T, int wm
 int check_volume(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, int64_t C)
 {
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (!fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
     return VDET_OK;
 }
@@ -2007,7 +2065,7 @@ int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores
     if (F == 0 || K == 0) return VDET_OK;
     if (!d_det_cnt || !d_keep || !d_keep_cnt) return fail(c, VDET_EINVAL, "null output");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * K > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (!fits_upto(0x7FFFFFF0ll, {F, K}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     if (B == 0) {
@@ -2050,7 +2108,7 @@ int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d
     if (F == 0 || C == 0) return VDET_OK;
     if (!d_keep_cnt || (cap > 0 && !d_keep_idx)) return fail(c, VDET_EINVAL, "null output");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (!fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     if (B == 0) {
@@ -2082,7 +2140,7 @@ int vdet_argsort_volume(vdet_ctx *c, const float *d_scores, int layout, int64_t 
     if (F == 0 || C == 0) return VDET_OK;
     if (!d_ncand || (B > 0 && (!d_scores || !d_order))) return fail(c, VDET_EINVAL, "null buffer");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (!fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     if (B == 0) {
@@ -2216,10 +2274,11 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     if (want_rescore && (window < 1 || window % 2 != 1)) return fail(c, VDET_EINVAL, "Window size must be odd!");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
     if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 0, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 0, &vs);
     if (rc) return rc;
-    if (F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll || V * C > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    const int64_t F = vs.F, Fmax = vs.Fmax;
+    if (!fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B}) || !fits_upto(0x7FFFFFF0ll, {V, C})) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     const float t32 = thresh_to_f32(nms_thres);
@@ -2238,12 +2297,7 @@ int vdet_video_batch(vdet_ctx *c, const float *d_boxes, const float *d_scores, c
     if ((rc = track_scratch(c, F, B, C, T, wm, V * C))) return rc;
     hipLaunchKernelGGL(track_init_kernel, dim3((unsigned)((V * C + 63) / 64)), dim3(64), 0, c->stream, c->tstate.as<TrackState>(), (int)(V * C));
     // ---- all videos side by side: one launch per stage, the video is a grid dimension (batch_kernels.hpp)
-    // the {first frame, frames} table: built and uploaded only when the offsets differ from those of the resident one
-    rc = stage_keyed(c, c->vidtab, h_frame_off, (size_t)(V + 1) * 8, (size_t)V * sizeof(VidDesc), [&](char *dst) {
-        VidDesc *tab = reinterpret_cast<VidDesc *>(dst);
-        for (int64_t v = 0; v < V; ++v) tab[v] = VidDesc{(int32_t)h_frame_off[v], (int32_t)(h_frame_off[v + 1] - h_frame_off[v])};
-    });
-    if (rc) return rc;
+    if ((rc = stage_video_table(c, c->vidtab, vs))) return rc;
     BatchTrack bt{};
     bt.vids = c->vidtab.dev.as<VidDesc>();
     bt.Ftot = (int)F; bt.B = (int)B; bt.C = (int)C; bt.T = T; bt.wm = wm;
@@ -2322,8 +2376,8 @@ int vdet_rescore_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntr
     if (max_tracks == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_boxes || !d_scores || !d_det_score || !d_pooled || !d_boxes_out)
         return fail(c, VDET_EINVAL, "null buffer");
+    if (!fits_upto(0x7FFFFFF0ll, {C, max_tracks, F})) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     const int64_t nb = C * max_tracks * F;
-    if (nb > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     FrameIndex ix{};
@@ -2637,7 +2691,7 @@ int vdet_temporal_maxpool_f32(vdet_ctx *c, const float *d_in, float *d_out, int6
 {
     if (!c) return VDET_EINVAL;
     if (window < 1 || window % 2 != 1) return fail(c, VDET_EINVAL, "Window size must be odd!");
-    if (F < 0 || S < 0 || F * S > ((int64_t)1 << 40) || (F * S > 0 && (!d_in || !d_out || d_in == d_out)))
+    if (F < 0 || S < 0 || !fits_upto(1ll << 40, {F, S}) || (F * S > 0 && (!d_in || !d_out || d_in == d_out)))
         return fail(c, VDET_EINVAL, "bad temporal_maxpool arguments");
     Taps taps{};
     return temporal_launch(c, 0, d_in, d_out, F, S, window, pad, 0.0f, taps);
@@ -2648,7 +2702,7 @@ int vdet_temporal_conv_f32(vdet_ctx *c, const float *d_in, float *d_out, int64_t
 {
     if (!c) return VDET_EINVAL;
     if (K < 1 || K % 2 != 1 || K > 31 || !h_taps) return fail(c, VDET_EINVAL, "taps: K must be odd and <= 31");
-    if (F < 0 || S < 0 || F * S > ((int64_t)1 << 40) || (F * S > 0 && (!d_in || !d_out || d_in == d_out)))
+    if (F < 0 || S < 0 || !fits_upto(1ll << 40, {F, S}) || (F * S > 0 && (!d_in || !d_out || d_in == d_out)))
         return fail(c, VDET_EINVAL, "bad temporal_conv arguments");
     Taps taps{};
     for (int k = 0; k < K; ++k) taps.w[k] = h_taps[k];
@@ -2670,7 +2724,7 @@ static int temporal_maxpool_conv_impl(vdet_ctx *c, const float *d_in, float *d_o
     if (!c) return VDET_EINVAL;
     if (window < 1 || window % 2 != 1) return fail(c, VDET_EINVAL, "Window size must be odd!");
     if (window > 31 || !h_taps) return fail(c, VDET_EINVAL, "taps: K must be odd and <= 31");
-    if (F < 0 || S < 0 || F * S > ((int64_t)1 << 40) ||
+    if (F < 0 || S < 0 || !fits_upto(1ll << 40, {F, S}) ||
         (F * S > 0 && (!d_in || !d_out_max || !d_out_conv || d_in == d_out_max || d_in == d_out_conv || d_out_max == d_out_conv)))
         return fail(c, VDET_EINVAL, "bad temporal_maxpool_conv arguments");
     if (F == 0 || S == 0) return VDET_OK;
@@ -2720,13 +2774,13 @@ int vdet_volume_pass(vdet_ctx *c, const float *d_scores, int64_t F, int64_t B, i
 // frame offsets of V concatenated videos -> per-frame {first, one past last} table on the device (kept in the context)
 static int upload_segments(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t *Ftot)
 {
-    int64_t F = 0, Fmax = 0;
-    const int rc = check_frame_off(c, h_frame_off, V, true, 0, &F, &Fmax);      // (a video without frames is fine here)
+    Videos vs;
+    const int rc = read_videos(c, h_frame_off, V, 0, &vs, true);      // (a video without frames is fine here)
     if (rc) return rc;
-    if (F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many frames");
-    *Ftot = F;
+    if (vs.F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many frames");
+    *Ftot = vs.F;
     // O(F) to build: keyed by the O(V) offsets, so the same offsets again neither build nor upload it
-    return stage_keyed(c, c->segtab, h_frame_off, (size_t)(V + 1) * 8, (size_t)F * sizeof(int2), [&](char *dst) {
+    return stage_keyed(c, c->segtab, h_frame_off, (size_t)(V + 1) * 8, (size_t)vs.F * sizeof(int2), [&](char *dst) {
         int2 *seg = reinterpret_cast<int2 *>(dst);
         for (int64_t v = 0; v < V; ++v)
             for (int64_t f = h_frame_off[v]; f < h_frame_off[v + 1]; ++f) seg[f] = make_int2((int)h_frame_off[v], (int)h_frame_off[v + 1]);
@@ -2753,12 +2807,12 @@ static int volume_pass_impl(vdet_ctx *c, const float *d_scores, int64_t F, int64
     if (!c) return VDET_EINVAL;
     if (window < 1 || window % 2 != 1) return fail(c, VDET_EINVAL, "Window size must be odd!");
     if (window > 31) return fail(c, VDET_EINVAL, "taps: K must be odd and <= 31");
-    if (F < 0 || B < 0 || C < 0 || F * B * C > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "bad shape");
+    if (F < 0 || B < 0 || C < 0 || !fits_upto(1ll << 40, {F, B, C})) return fail(c, VDET_EINVAL, "bad shape");
     if (F == 0 || B == 0 || C == 0) return VDET_OK;
     const bool conv = h_taps != nullptr;
     if (!d_scores || !d_out_max || (conv && !d_out_conv) || d_scores == d_out_max || (conv && (d_scores == d_out_conv || d_out_max == d_out_conv)))
         return fail(c, VDET_EINVAL, "bad volume_pass arguments");
-    if (B > 32767 || F * C > 0x7FFFFFF0ll || F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large");
+    if (B > 32767 || !fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     c->keys_valid = false;
     c->vpass_last_items = 0;
     // tile: TB boxes (a power of two, >= 16 so that a key row segment is >= 64 B) x C classes in <= NT * ITEMS float4;
@@ -2907,8 +2961,8 @@ int vdet_eval_gt_upload(vdet_ctx *c, const int32_t *h_vid, const int64_t *h_fram
         if (h_vid_nf[v] < 0) return fail(c, VDET_EINVAL, "negative frame count");
         meta[2 * v] = total;
         meta[2 * v + 1] = h_vid_nf[v];
+        if (!fits_upto(0x7FFFFFF0ll - total, {h_vid_nf[v], K})) return fail(c, VDET_EINVAL, "ground-truth table too large (videos x frames x classes >= 2^31)");
         total += h_vid_nf[v] * K;
-        if (total > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "ground-truth table too large (videos x frames x classes >= 2^31)");
     }
     auto cell = [&](int64_t i) -> int64_t {
         const int32_t v = h_vid[i], s = h_slot[i];
@@ -2996,10 +3050,11 @@ int vdet_eval_match_tracks_batch(vdet_ctx *c, const double *d_gt_boxes, const in
     *h_count = 0;
     if (V < 1 || C < 1 || C > 65535 || T < 0 || T > kEvalMaxT || (box_stride != 4 && box_stride != 5))
         return fail(c, VDET_EINVAL, "bad shape (1 <= C <= 65535, 0 <= T <= %d, box stride 4 or 5)", kEvalMaxT);
-    int64_t Ft = 0, Fmax = 0;
-    if ((rc = check_frame_off(c, h_frame_off, V, false, 0, &Ft, &Fmax))) return rc;
+    Videos vs;
+    if ((rc = read_videos(c, h_frame_off, V, 0, &vs))) return rc;
+    const int64_t Ft = vs.F;
+    if (Ft > 0x7FFFFFF0ll || !fits_upto(0x7FFFFFF0ll, {C, T, Ft})) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     const int64_t N = C * T * Ft;
-    if (Ft > 0x7FFFFFF0ll || N > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     if (T == 0) return VDET_OK;
     if (!d_boxes || !d_scores || !d_ntracks || !d_st_slot || !d_st_score || !d_st_tp) return fail(c, VDET_EINVAL, "null buffer");
     if (st_len < 0 || st_len + N > st_cap) return fail(c, VDET_EINVAL, "stream capacity too small (%lld + %lld > %lld)",
@@ -3055,8 +3110,8 @@ int vdet_eval_match_keep(vdet_ctx *c, const double *d_gt_boxes, const int32_t *d
     *h_count = 0;
     if (layout != VDET_LAYOUT_FBC && layout != VDET_LAYOUT_FCB) return fail(c, VDET_EINVAL, "bad layout");
     if (F < 1 || B < 1 || C < 1 || C > 65535 || cap < 0 || B > 0x7FFFFFFF) return fail(c, VDET_EINVAL, "bad shape");
+    if (F > 0x7FFFFFF0ll || !fits_upto(0x7FFFFFF0ll, {F, C, cap}) || !fits_upto(1ll << 40, {F, B, C})) return fail(c, VDET_EINVAL, "too many kept entries");
     const int64_t N = F * C * cap;
-    if (F > 0x7FFFFFF0ll || N > 0x7FFFFFF0ll || F * B * C > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many kept entries");
     if (cap == 0) return VDET_OK;
     if (!d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt || !d_st_slot || !d_st_score || !d_st_tp)
         return fail(c, VDET_EINVAL, "null buffer");
@@ -3214,18 +3269,19 @@ static int tcn_tracks_impl(vdet_ctx *c, const float *h_params, const int32_t *h_
                            const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors, const void *d_det_score,
                            int det_f64, const double *d_gt_overlap, float *d_conv_score)
 {
-    int64_t Ft = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
-    if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    const int64_t Ft = vs.F, Fmax = vs.Fmax;
+    if (C < 1 || T < 0 || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1)})) return fail(c, VDET_EINVAL, "bad shape");
     bool need_gt = false, need_det = false;
     for (int q = 0; q < ch.n; ++q) {
         need_gt = need_gt || ch.code[q] == kChGtOverlap || ch.code[q] == kChLabel;
         need_det = need_det || ch.code[q] == kChDet;
     }
     if (need_gt && !d_gt_overlap) return fail(c, VDET_EINVAL, "the net reads gt_overlaps / labels: a gt_overlap buffer is needed");
+    if (!fits_upto(0x7FFFFFF0ll, {C, T, Ft}) || !fits_upto(1ll << 40, {C, T, Ft, std::max(ch.n, 1)})) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     const int64_t N = C * T * Ft;
-    if (N > 0x7FFFFFF0ll || N * std::max(ch.n, 1) > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
     if (T == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_anchors || (need_det && !d_det_score) || !d_conv_score) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3233,7 +3289,7 @@ static int tcn_tracks_impl(vdet_ctx *c, const float *h_params, const int32_t *h_
     TcnNet net;
     if ((rc = tcn_net_args(c, h_params, h_layers, n_layers, cin, net))) return rc;
     if (segs) {
-        if (N * net.l[0].cout > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many tubelet boxes");
+        if (!fits_upto(1ll << 40, {N, net.l[0].cout})) return fail(c, VDET_EINVAL, "too many tubelet boxes");
         if ((rc = stage_table(c, c->tcn_segs, segs, (size_t)nseg * sizeof(TcnSeg)))) return rc;
     }
     const int64_t *d_foff = nullptr;
@@ -3372,7 +3428,7 @@ int vdet_tcn_series_f32(vdet_ctx *c, const float *h_params, const int32_t *h_lay
     }
     const int64_t n = h_off[T];
     if (n == 0) return VDET_OK;
-    if (n * cin > ((int64_t)1 << 40)) return fail(c, VDET_EINVAL, "too many series elements");
+    if (!fits_upto(1ll << 40, {n, cin})) return fail(c, VDET_EINVAL, "too many series elements");
     if (!h_x || !h_out) return fail(c, VDET_EINVAL, "null buffer");
     if ((rc = upload(c, c->tmp[0], h_x, (size_t)n * cin * 4))) return rc;
     if ((rc = upload(c, c->tmp[1], h_off, (size_t)T * 8))) return rc;
@@ -3395,10 +3451,10 @@ int vdet_tubelets_overlap_batch(vdet_ctx *c, const double *d_gt_boxes, const int
     EvGt g;
     int rc = eval_gt_args(c, d_gt_boxes, d_gt_off, d_vid_meta, K, 0, 0.5, g);
     if (rc) return rc;
-    int64_t Ft = 0, Fmax = 0;
-    if ((rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax))) return rc;
+    Videos vs;
+    if ((rc = read_videos(c, h_frame_off, V, 65535, &vs))) return rc;
     if (!h_vid || !h_col_slot) return fail(c, VDET_EINVAL, "null buffer");
-    if (C < 1 || C > 65535 || T < 0 || C * std::max(T, 1) * Ft > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if (C < 1 || C > 65535 || T < 0 || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1), vs.F})) return fail(c, VDET_EINVAL, "bad shape");
     if (T == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_gt_overlap || !d_mean_iou || !d_gt) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3416,7 +3472,7 @@ int vdet_tubelets_overlap_batch(vdet_ctx *c, const double *d_gt_boxes, const int
     {
         StageTimer tm(c, ST_OTHER);
         hipLaunchKernelGGL(tubelets_overlap_kernel, dim3((unsigned)(C * T), (unsigned)V), dim3(64), 0, c->stream, g,
-                           one ? (const int64_t *)nullptr : reinterpret_cast<const int64_t *>(tb), Ft,
+                           one ? (const int64_t *)nullptr : reinterpret_cast<const int64_t *>(tb), vs.F,
                            one ? (const int32_t *)nullptr : reinterpret_cast<const int32_t *>(tb + o_vid), h_vid[0], (int)C, T,
                            d_tracks, d_boxes, d_ntracks, reinterpret_cast<const int32_t *>(tb + o_slot), d_gt_overlap, d_mean_iou, d_gt);
     }
@@ -3443,13 +3499,14 @@ int vdet_interp_tracks_batch(vdet_ctx *c, const int64_t *h_sframe_off, const int
                              double *d_boxes64, float *d_tboxes, double *d_series_out, double *d_anchor, float *d_anchors_out)
 {
     if (!c) return VDET_EINVAL;
-    int64_t Fst = 0, Fsmax = 0, Ft = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_sframe_off, V, false, 65535, &Fst, &Fsmax);
+    Videos sampled, dense;
+    int rc = read_videos(c, h_sframe_off, V, 65535, &sampled);
     if (rc) return rc;
-    if ((rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax))) return rc;
-    if (C < 1 || T < 0 || C * std::max(T, 1) > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if ((rc = read_videos(c, h_frame_off, V, 65535, &dense))) return rc;
+    const int64_t Fst = sampled.F, Ft = dense.F;
+    if (C < 1 || T < 0 || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1)})) return fail(c, VDET_EINVAL, "bad shape");
     if (n_series < 0 || n_series > kInterpMaxSeries) return fail(c, VDET_EINVAL, "0 to %d series", kInterpMaxSeries);
-    if (C * std::max(T, 1) * Ft > 0x7FFFFFF0ll || C * std::max(T, 1) * Fst > 0x7FFFFFF0ll)
+    if (!fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1), Ft}) || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1), Fst}))
         return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31)");
     for (int64_t v = 0; v < V; ++v) {
         const int64_t s0 = h_sframe_off[v], fs = h_sframe_off[v + 1] - s0, f = h_frame_off[v + 1] - h_frame_off[v];
@@ -3529,59 +3586,6 @@ int vdet_interp_tracks(vdet_ctx *c, int64_t Fs, int64_t F, const int32_t *h_fram
 // ---------------------------------------------------------------------------------------------
 // Device anchor route (anchor_kernels.hpp)
 // ---------------------------------------------------------------------------------------------
-int vdet_track_from_anchors(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, const int32_t *d_anchor_frames,
-                            const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, double link_thres,
-                            int max_frames, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
-{
-    if (!c) return VDET_EINVAL;
-    if (F <= 0 || B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
-    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
-    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31)");
-    if (!d_boxes || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    timing_reset(c);
-    if (T == 0) {
-        HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
-        return VDET_OK;
-    }
-    AnchorLinkArgs a{};
-    a.boxes = reinterpret_cast<const float4 *>(d_boxes);
-    a.F = (int)F; a.B = (int)B; a.C = (int)C; a.T = T;
-    a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
-    a.link_t32 = thresh_to_f32(link_thres);
-    a.reach = chain_reach(max_frames, (int)F);
-    a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
-    a.status = &c->d_cnt->status;
-    {
-        StageTimer tm(c, ST_TLINK);
-        hipLaunchKernelGGL(anchor_link_kernel<false>, dim3((unsigned)(C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VDET_OK;
-}
-
-int vdet_anchor_propagate_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
-                                 const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int T,
-                                 double *d_det_score, int32_t *d_best)
-{
-    if (!c) return VDET_EINVAL;
-    if (F <= 0 || B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
-    if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
-    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31)");
-    if (T == 0) return VDET_OK;
-    if (!d_tracks || !d_ntracks || !d_anchors || !d_boxes || !d_scores || !d_det_score || !d_best) return fail(c, VDET_EINVAL, "null buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    timing_reset(c);
-    {
-        StageTimer tm(c, ST_OTHER);
-        hipLaunchKernelGGL(anchor_propagate_kernel<false>, dim3((unsigned)(C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks, d_anchors,
-                           d_boxes, d_scores, (int)F, (int)B, (int)C, T, d_det_score, d_best, &c->d_cnt->status,
-                           (const VidDesc *)nullptr, 0);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VDET_OK;
-}
-
 int vdet_anchor_argmax_f64(vdet_ctx *c, const double *h_anchor_boxes, const int32_t *h_group, int64_t N, const double *h_det_boxes,
                            const int64_t *h_group_off, int64_t G, int64_t *h_best)
 {
@@ -3615,15 +3619,6 @@ int vdet_anchor_argmax_f64(vdet_ctx *c, const double *h_anchor_boxes, const int3
     return VDET_OK;
 }
 
-// the {first frame, frames} table of the anchor route's batch forms: one owner (anchor_tab), keyed by the offsets
-static int anchor_vidtab(vdet_ctx *c, const int64_t *h_frame_off, int64_t V)
-{
-    return stage_keyed(c, c->anchor_tab, h_frame_off, (size_t)(V + 1) * 8, (size_t)V * sizeof(VidDesc), [&](char *dst) {
-        VidDesc *tab = reinterpret_cast<VidDesc *>(dst);
-        for (int64_t v = 0; v < V; ++v) tab[v] = VidDesc{(int32_t)h_frame_off[v], (int32_t)(h_frame_off[v + 1] - h_frame_off[v])};
-    });
-}
-
 int vdet_top_anchors(vdet_ctx *c, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int top_num,
                      int mode, int use_score_thresh, double score_thresh, const int64_t *h_frame_off, int64_t V,
                      int32_t *d_anchor_frames, float *d_anchor_boxes, float *d_anchor_scores, int32_t *d_anchor_index)
@@ -3636,29 +3631,23 @@ int vdet_top_anchors(vdet_ctx *c, const float *d_boxes, const float *d_scores, i
     if (mode == 1 && top_num > kTopaMaxTFrame) return fail(c, VDET_EINVAL, "top_num = %d; the limit is %d per frame and class", top_num, kTopaMaxTFrame);
     if (mode == 1 && h_frame_off) return fail(c, VDET_EINVAL, "frame mode has no batch form");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    if (F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
+    if (!fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
     if (!d_boxes || !d_scores || !d_anchor_frames || !d_anchor_boxes || !d_anchor_scores || !d_anchor_index) return fail(c, VDET_EINVAL, "null buffer");
     if (((uintptr_t)d_boxes & 15) != 0 || ((uintptr_t)d_anchor_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes and d_anchor_boxes must be 16-byte aligned");
-    int64_t Fmax = F, nv = 1;
-    if (h_frame_off) {
-        int64_t Ft = 0;
-        const int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
-        if (rc) return rc;
-        if (Ft != F) return fail(c, VDET_EINVAL, "frame_off must end at F");
-        nv = V;
-    } else if (mode == 1) {
+    Videos vs;
+    int rc = read_videos_or_one(c, h_frame_off, V, F, 65535, &vs);
+    if (rc) return rc;
+    int64_t Fmax = vs.Fmax, nv = vs.V;
+    if (mode == 1) {            // (no offsets: every frame is a video of its own)
         if (F > 65535) return fail(c, VDET_EINVAL, "frame mode: at most 65535 frames");
         nv = F; Fmax = 1;
     }
     const int T = top_num;
     const int64_t nseg = (Fmax * B + kTopaRows - 1) / kTopaRows, ctiles = (C + 63) / 64;
-    if (nv * C * (int64_t)T > 0x7FFFFFF0ll || nv * nseg * C > 0x7FFFFFF0ll || ctiles > 65535) return fail(c, VDET_EINVAL, "too many slots");
+    if (!fits_upto(0x7FFFFFF0ll, {nv, C, T}) || !fits_upto(0x7FFFFFF0ll, {nv, nseg, C}) || ctiles > 65535) return fail(c, VDET_EINVAL, "too many slots");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    if (h_frame_off) {
-        const int rc = anchor_vidtab(c, h_frame_off, V);
-        if (rc) return rc;
-    }
+    if (h_frame_off && (rc = stage_video_table(c, c->anchor_tab, vs))) return rc;
     const size_t hist_bytes = (size_t)(nv * C) * 256 * 4;
     if (hist_bytes > c->topa_hist.cap) c->topa_hist_clean = false;
     HIPCHK(c, c->topa_hist.reserve(hist_bytes));
@@ -3707,10 +3696,10 @@ int vdet_track_from_anchors_batch(vdet_ctx *c, const float *d_boxes, const int64
     if (!c) return VDET_EINVAL;
     if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
-    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll || V * C * std::max(T, 1) > 0x7FFFFFF0ll)
+    if (!fits_upto(0x7FFFFFF0ll, {vs.F, B}) || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1), vs.F}) || !fits_upto(0x7FFFFFF0ll, {V, C, std::max(T, 1)}))
         return fail(c, VDET_EINVAL, "volume too large (F*B, C*T*F and V*C*T must stay below 2^31)");
     if (!d_boxes || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3719,19 +3708,22 @@ int vdet_track_from_anchors_batch(vdet_ctx *c, const float *d_boxes, const int64
         HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)(V * C) * 4, c->stream));
         return VDET_OK;
     }
-    if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+    // one video travels in the kernel arguments alone; more run the batch kernel on the per-video table
     AnchorLinkArgs a{};
+    if ((rc = video_table(c, c->anchor_tab, vs, &a.vids))) return rc;
     a.boxes = reinterpret_cast<const float4 *>(d_boxes);
-    a.F = (int)F; a.B = (int)B; a.C = (int)(V * C); a.T = T;
-    a.vids = c->anchor_tab.dev.as<VidDesc>(); a.cls = (int)C;
+    a.F = (int)vs.F; a.B = (int)B; a.C = (int)(V * C); a.T = T;
+    a.cls = a.vids ? (int)C : 0;
     a.aframes = d_anchor_frames; a.aboxes = d_anchor_boxes; a.ascores = d_anchor_scores;
     a.link_t32 = thresh_to_f32(link_thres);
-    a.reach = chain_reach(max_frames, (int)Fmax);
+    a.reach = chain_reach(max_frames, (int)vs.Fmax);
     a.tracks = d_tracks; a.anchors = d_anchors; a.ntracks = d_ntracks;
     a.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_TLINK);
-        hipLaunchKernelGGL(anchor_link_kernel<true>, dim3((unsigned)(V * C * T), 2), dim3(kAnchorLT), 0, c->stream, a);
+        const dim3 grid((unsigned)(V * C * T), 2);
+        if (a.vids) hipLaunchKernelGGL(anchor_link_kernel<true>, grid, dim3(kAnchorLT), 0, c->stream, a);
+        else hipLaunchKernelGGL(anchor_link_kernel<false>, grid, dim3(kAnchorLT), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
@@ -3744,24 +3736,42 @@ int vdet_anchor_propagate_tracks_batch(vdet_ctx *c, const float *d_tracks, const
     if (!c) return VDET_EINVAL;
     if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (B > 32767) return fail(c, VDET_EINVAL, "at most 32767 boxes per frame");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
-    if (F * B > 0x7FFFFFF0ll || C * std::max(T, 1) * F > 0x7FFFFFF0ll || V * C * std::max(T, 1) > 0x7FFFFFF0ll)
+    if (!fits_upto(0x7FFFFFF0ll, {vs.F, B}) || !fits_upto(0x7FFFFFF0ll, {C, std::max(T, 1), vs.F}) || !fits_upto(0x7FFFFFF0ll, {V, C, std::max(T, 1)}))
         return fail(c, VDET_EINVAL, "volume too large (F*B, C*T*F and V*C*T must stay below 2^31)");
     if (T == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_anchors || !d_boxes || !d_scores || !d_det_score || !d_best) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
+    const VidDesc *vids = nullptr;      // (one video travels in the kernel arguments alone)
+    if ((rc = video_table(c, c->anchor_tab, vs, &vids))) return rc;
     {
         StageTimer tm(c, ST_OTHER);
-        hipLaunchKernelGGL(anchor_propagate_kernel<true>, dim3((unsigned)(V * C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks,
-                           d_anchors, d_boxes, d_scores, (int)F, (int)B, (int)(V * C), T, d_det_score, d_best, &c->d_cnt->status,
-                           (const VidDesc *)c->anchor_tab.dev.as<VidDesc>(), (int)C);
+        const auto kernel = vids ? anchor_propagate_kernel<true> : anchor_propagate_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(V * C * T)), dim3(kAnchorLT), 0, c->stream, d_tracks, d_ntracks, d_anchors, d_boxes,
+                           d_scores, (int)vs.F, (int)B, (int)(V * C), T, d_det_score, d_best, &c->d_cnt->status, vids, vids ? (int)C : 0);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
+}
+
+int vdet_track_from_anchors(vdet_ctx *c, const float *d_boxes, int64_t F, int64_t B, const int32_t *d_anchor_frames,
+                            const float *d_anchor_boxes, const float *d_anchor_scores, int64_t C, int T, double link_thres,
+                            int max_frames, float *d_tracks, float *d_anchors, int32_t *d_ntracks)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_track_from_anchors_batch(c, d_boxes, off, 1, B, d_anchor_frames, d_anchor_boxes, d_anchor_scores, C, T, link_thres,
+                                         max_frames, d_tracks, d_anchors, d_ntracks);
+}
+
+int vdet_anchor_propagate_tracks(vdet_ctx *c, const float *d_tracks, const int32_t *d_ntracks, const float *d_anchors,
+                                 const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t C, int T,
+                                 double *d_det_score, int32_t *d_best)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_anchor_propagate_tracks_batch(c, d_tracks, d_ntracks, d_anchors, d_boxes, d_scores, off, 1, B, C, T, d_det_score, d_best);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3778,11 +3788,11 @@ int vdet_merge_tracks_batch(vdet_ctx *c, int scheme, const int64_t *h_frame_off,
     if (scheme != VDET_MERGE_COMBINE && scheme != VDET_MERGE_MAX) return fail(c, VDET_EINVAL, "scheme must be VDET_MERGE_COMBINE or VDET_MERGE_MAX");
     if (n_series < 1 || n_series > kMergeMaxSeries) return fail(c, VDET_EINVAL, "1 to %d series (series 0 is det_score)", kMergeMaxSeries);
     if (C < 1 || Ta < 0 || Tb < 0) return fail(c, VDET_EINVAL, "bad shape");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
     const int64_t To = scheme == VDET_MERGE_COMBINE ? (int64_t)Ta + Tb : Ta, Tmax = std::max<int64_t>(std::max<int64_t>(To, Tb), 1);
-    if (C * Tmax >= 0x7FFFFFF0ll || C * Tmax * F >= 0x7FFFFFF0ll || V * C * Tmax >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, Tmax, vs.F}) || !fits_below(0x7FFFFFF0ll, {V, C, Tmax}))
         return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16 for Ta, Tb and the output's T)");
     if (!d_ntracks_a || !d_ntracks_b || !d_ntracks_out) return fail(c, VDET_EINVAL, "null buffer");
     const bool tbx = d_tboxes_out != nullptr;
@@ -3803,16 +3813,12 @@ int vdet_merge_tracks_batch(vdet_ctx *c, int scheme, const int64_t *h_frame_off,
         HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
         return VDET_OK;
     }
-    // one video travels in the kernel arguments alone; more share the anchor route's per-video table, keyed by the offsets
-    if (V > 1) {
-        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
-        g.vids = c->anchor_tab.dev.as<VidDesc>();
-    }
+    if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
     g.a.tracks = d_tracks_a; g.a.ntracks = d_ntracks_a; g.a.anchors = d_anchors_a; g.a.tboxes = d_tboxes_a; g.a.T = Ta;
     g.b.tracks = d_tracks_b; g.b.ntracks = d_ntracks_b; g.b.anchors = d_anchors_b; g.b.tboxes = d_tboxes_b; g.b.T = Tb;
-    g.F = (int)F; g.C = (int)C; g.nser = n_series; g.To = (int)To;
+    g.F = (int)vs.F; g.C = (int)C; g.nser = n_series; g.To = (int)To;
     g.otracks = d_tracks_out; g.ontracks = d_ntracks_out; g.oanchors = d_anchors_out; g.otboxes = d_tboxes_out;
-    g.oseries = d_series_out; g.oN = C * To * F; g.from_b = d_from_b; g.status = &c->d_cnt->status;
+    g.oseries = d_series_out; g.oN = C * To * vs.F; g.from_b = d_from_b; g.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_OTHER);
         const dim3 grid((unsigned)((C * To + kMergeWaves - 1) / kMergeWaves), (unsigned)V);
@@ -3846,17 +3852,18 @@ int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, in
 {
     if (!c) return VDET_EINVAL;
     if (C < 1 || T < 0 || top_still < 0) return fail(c, VDET_EINVAL, "bad shape");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
+    const int64_t F = vs.F, Fmax = vs.Fmax;
     if ((int64_t)top_still + T > kTnMaxList)
         return fail(c, VDET_EINVAL, "top_still + T = %lld candidates per (frame, class); the limit is %d", (long long)top_still + T, kTnMaxList);
     if (R < 1 || R > kTnMaxList) return fail(c, VDET_EINVAL, "R = %d output rows per (frame, class); 1 .. %d", R, kTnMaxList);
-    if (C * (int64_t)R * F >= 0x7FFFFFF0ll || C * (int64_t)T * F >= 0x7FFFFFF0ll || V * C >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, R, F}) || !fits_below(0x7FFFFFF0ll, {C, T, F}) || !fits_below(0x7FFFFFF0ll, {V, C}))
         return fail(c, VDET_EINVAL, "too many tubelet boxes (C*R*F and C*T*F must stay below 2^31 - 16)");
     if (top_still > 0) {
         if (B < 1 || B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; 1 .. 32767", (long long)B);
-        if (cap < 1 || cap > 0x7FFFFFF0ll || F * C * cap >= (1ll << 40)) return fail(c, VDET_EINVAL, "bad keep-list capacity");
+        if (cap < 1 || cap > 0x7FFFFFF0ll || !fits_below(1ll << 40, {F, C, cap})) return fail(c, VDET_EINVAL, "bad keep-list capacity");
         if (!d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt) return fail(c, VDET_EINVAL, "null buffer (top_still > 0 needs the still-image source)");
         if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
     }
@@ -3866,10 +3873,7 @@ int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, in
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     TrackNmsArgs g{};
-    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_merge_tracks_batch)
-        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
-        g.vids = c->anchor_tab.dev.as<VidDesc>();
-    }
+    if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
     g.tracks = d_tracks; g.ntracks = d_ntracks; g.score = d_score; g.tboxes = T > 0 ? reinterpret_cast<const float4 *>(d_tboxes) : nullptr;
     g.boxes = reinterpret_cast<const float4 *>(d_boxes); g.scores = d_scores; g.keep_idx = d_keep_idx; g.keep_cnt = d_keep_cnt;
     g.F = (int)F; g.Ftot = (int)F; g.C = (int)C; g.T = T; g.B = (int)B; g.cap = (int)cap; g.top_still = top_still; g.R = R;
@@ -3912,10 +3916,11 @@ int vdet_rescore_tubelets_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t
     if (B <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (window < 1 || window % 2 != 1) return fail(c, VDET_EINVAL, "Window size must be odd!");
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
-    if (F * B > 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || V * C >= 0x7FFFFFF0ll)
+    const int64_t F = vs.F, Fmax = vs.Fmax;
+    if (!fits_upto(0x7FFFFFF0ll, {F, B}) || !fits_below(0x7FFFFFF0ll, {C, std::max(T, 1), F}) || !fits_below(0x7FFFFFF0ll, {V, C}))
         return fail(c, VDET_EINVAL, "volume too large (F*B and C*T*F must stay below 2^31 - 16)");
     if (T == 0) return VDET_OK;
     if (!d_tracks || !d_ntracks || !d_boxes || !d_scores || !d_det || !d_pooled || !d_tboxes || !d_src) return fail(c, VDET_EINVAL, "null buffer");
@@ -3939,10 +3944,7 @@ int vdet_rescore_tubelets_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t
         g.ix = frame_index_of(c);
         g.group_flags = c->gflags.as<uint32_t>();
     }
-    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_merge_tracks_batch)
-        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
-        g.vids = c->anchor_tab.dev.as<VidDesc>();
-    }
+    if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
     g.tracks = d_tracks; g.ntracks = d_ntracks; g.boxes = reinterpret_cast<const float4 *>(d_boxes); g.scores = d_scores;
     g.floor = d_floor; g.floor_f64 = floor_f64 ? 1 : 0;
     g.F = (int)F; g.B = (int)B; g.C = (int)C; g.T = T;
@@ -4061,7 +4063,7 @@ int vdet_tubelet_patches(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64
     if (C < 1 || T < 0 || F < 1 || ld < 4) return fail(c, VDET_EINVAL, "bad shape (tracks must be [C,T,F,>=4])");
     if (f0 < 0 || f1 <= f0 || f1 > F) return fail(c, VDET_EINVAL, "frames must be a range 0 <= f0 < f1 <= F");
     if (Fi != f1 - f0) return fail(c, VDET_EINVAL, "images must hold the f1 - f0 = %lld frames of the range", (long long)(f1 - f0));
-    if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16)");
+    if (!fits_below(0x7FFFFFF0ll, {C, std::max(T, 1), F})) return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16)");
     if (cap < 0) return fail(c, VDET_EINVAL, "cap must not be negative");
     int rc = patch_check(c, d_images, Fi, H, W, S, padding, mode, out_dtype, cap, d_patches);
     if (rc) return rc;
@@ -4158,9 +4160,9 @@ int vdet_svm_head(vdet_ctx *c, const void *d_feat, int feat_dtype, int64_t N, in
         HIPCHK(c, hipMemsetAsync(d_nbad, 0, sizeof(int32_t), c->stream));
         return VDET_OK;
     }
-    if (d_slot ? (C < 1 || T < 1 || F < 1 || C * (int64_t)T * F >= 0x7FFFFFF0ll) : (C != 1))
+    if (d_slot ? (C < 1 || T < 1 || F < 1 || !fits_below(0x7FFFFFF0ll, {C, T, F})) : (C != 1))
         return fail(c, VDET_EINVAL, "shape must be C, T, F >= 1 with C*T*F below 2^31 - 16 (without slot: C = 1)");
-    if (K > ((int64_t)1 << 40) / M || N > ((int64_t)1 << 46) / G / K) return fail(c, VDET_EINVAL, "matrix too large");
+    if (!fits_upto(1ll << 40, {K, M}) || !fits_upto(1ll << 46, {N, G, K})) return fail(c, VDET_EINVAL, "matrix too large");
     const size_t csz = compute_f64 ? 8 : 4;
     const int gpw = G >= 32 ? 1 : (32 + G - 1) / G;
     const int64_t nwaves = (N + gpw - 1) / gpw, blocks = (nwaves + 3) / 4;
@@ -4224,7 +4226,7 @@ static int track_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_t F, in
     if (F <= 0 || H <= 0 || W <= 0 || C <= 0 || T < 0) return fail(c, VDET_EINVAL, "bad shape");
     if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
     if (box && pix_box_check(c, H, W)) return VDET_EINVAL;
-    if (C * (int64_t)std::max(T, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(T, 1) >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, std::max(T, 1), F}))
         return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
     if (!d_images || !d_ntracks || (T && (!d_anchor_frames || !d_anchor_boxes || !d_tracks || !d_anchors))) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4282,8 +4284,9 @@ int vdet_luma_integral(vdet_ctx *c, const uint8_t *d_images, int64_t F, int64_t 
     if (H > 32767 || W > 32767) return fail(c, VDET_EINVAL, "images of at most 32767 rows and columns");
     if (pix_box_check(c, H, W)) return VDET_EINVAL;
     const int64_t nbx = (W + kPixIntColLT) / kPixIntColLT;                   // blocks over the W + 1 columns of a frame's table
-    const int64_t row_blocks = (F * H + kPixIntRowWaves - 1) / kPixIntRowWaves;
-    if (F >= 0x7FFFFFF0ll || row_blocks >= 0x7FFFFFF0ll || F * nbx >= 0x7FFFFFF0ll)
+    // (F*H is formed only once F itself is known to be small)
+    const int64_t row_blocks = F >= 0x7FFFFFF0ll ? F : (F * H + kPixIntRowWaves - 1) / kPixIntRowWaves;
+    if (row_blocks >= 0x7FFFFFF0ll || !fits_below(0x7FFFFFF0ll, {F, nbx}))
         return fail(c, VDET_EINVAL, "video too large (F*H/4 and F*ceil((W+1)/128) must stay below 2^31 - 16)");
     if (!d_images || !d_integral) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -4345,7 +4348,7 @@ static int track_volume_pixels_impl(vdet_ctx *c, const uint8_t *d_images, int64_
     if (rc) return rc;
     if (pix_settings_check(c, H, W, S, R, min_conf, max_frames, step, sc)) return VDET_EINVAL;
     if (box && pix_box_check(c, H, W)) return VDET_EINVAL;
-    if (C * (int64_t)std::max(max_tracks, 1) * F >= 0x7FFFFFF0ll || C * (int64_t)std::max(max_tracks, 1) >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, std::max(max_tracks, 1), F}))
         return fail(c, VDET_EINVAL, "volume too large (C*max_tracks*F must stay below 2^31 - 16)");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
@@ -4447,7 +4450,7 @@ int motion_table_check(vdet_ctx *c, int64_t F, int64_t Hb, int64_t Wb)
 {
     if (F <= 0 || Hb <= 0 || Wb <= 0) return fail(c, VDET_EINVAL, "bad shape");
     if (Hb > kMoTabRows || Wb > kMoTabRows) return fail(c, VDET_EINVAL, "a motion field of at most %d block rows and columns", kMoTabRows);
-    if (F >= 0x7FFFFFF0ll || 4 * F * (Hb + 1) * (Wb + 1) >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {4, F, Hb + 1, Wb + 1}))
         return fail(c, VDET_EINVAL, "motion field too large (2*F*(Hb+1)*(Wb+1)*2 must stay below 2^31 - 16)");
     return VDET_OK;
 }
@@ -4533,7 +4536,7 @@ int vdet_propagate_boxes(vdet_ctx *c, const int32_t *d_fsum, int64_t F, int64_t 
     const int64_t T = 2 * (int64_t)reach * top;
     if (T > 1024) return fail(c, VDET_EINVAL, "2*reach*top = %lld slots per class; the limit is 1024", (long long)T);
     if (!(decay >= 0.0) || !std::isfinite(decay)) return fail(c, VDET_EINVAL, "decay must be finite and >= 0");
-    if (C * T * F >= 0x7FFFFFF0ll || kcap >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, T, F}) || kcap >= 0x7FFFFFF0ll)
         return fail(c, VDET_EINVAL, "volume too large (C*T*F must stay below 2^31 - 16)");
     if (!d_fsum || !d_boxes || !d_scores || !d_keep_idx || !d_keep_cnt || !d_tracks || !d_score || !d_src || !d_ntracks)
         return fail(c, VDET_EINVAL, "null buffer");
@@ -4577,20 +4580,16 @@ int ctxs_videos(vdet_ctx *c, int64_t F, int64_t B, int64_t C, const int64_t *h_f
                 int64_t *chunks, uint32_t *cap_max, int64_t *rec_total)
 {
     if (F <= 0 || B <= 0 || C <= 0) return fail(c, VDET_EINVAL, "bad shape");
-    if (F * B > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
+    if (!fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large (F*B must stay below 2^31 - 16)");
     // the class of an element is (class of the chunk's first element + offset in the chunk) % C in 32-bit arithmetic: the sum
     // (< C + kCtxChunk + 4) and the suppress kernel's running class (< 2 C) must fit 32 bits.  No other limit on C.
     if (C > 0x7FFF0000ll) return fail(c, VDET_EINVAL, "C = %lld classes; the limit is 2^31 - 65536", (long long)C);
-    int64_t Fmax = F;
-    *nv = 1;
-    if (h_frame_off) {
-        int64_t Ft = 0;
-        const int rc = check_frame_off(c, h_frame_off, V, false, 65535, &Ft, &Fmax);
-        if (rc) return rc;
-        if (Ft != F) return fail(c, VDET_EINVAL, "frame_off must end at F");
-        *nv = V;
-    }
-    if (Fmax * B > 0xFFFFFFFFll / C) return fail(c, VDET_EINVAL, "a video of 2^32 scores or more (the counters are 32 bits wide)");
+    Videos vs;
+    const int rc = read_videos_or_one(c, h_frame_off, V, F, 65535, &vs);
+    if (rc) return rc;
+    const int64_t Fmax = vs.Fmax;
+    *nv = vs.V;
+    if (!fits_upto(0xFFFFFFFFll, {Fmax, B, C})) return fail(c, VDET_EINVAL, "a video of 2^32 scores or more (the counters are 32 bits wide)");
     *chunks = (Fmax * B * C + kCtxChunk - 1) / kCtxChunk;
     *cap_max = ctxs_cap(c, Fmax * B * C);
     if (!h_frame_off) {
@@ -4708,20 +4707,21 @@ int vdet_seq_nms_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64
 {
     if (!c) return VDET_EINVAL;
     if (C < 1) return fail(c, VDET_EINVAL, "bad shape");
-    int64_t F = 0, Fmax = 0;
-    int rc = check_frame_off(c, h_frame_off, V, false, 65535, &F, &Fmax);
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
+    const int64_t F = vs.F, Fmax = vs.Fmax;
     if (R < 1 || R > kSqMaxR) return fail(c, VDET_EINVAL, "R = %d rows per (frame, class); 1 .. %d (cut wider lists with vdet_nms_tracks' R)", R, kSqMaxR);
     if (max_seqs < 1 || max_seqs > kSqMaxSeqs) return fail(c, VDET_EINVAL, "max_seqs = %d; 1 .. %d", max_seqs, kSqMaxSeqs);
     if (rescore != 0 && rescore != 1) return fail(c, VDET_EINVAL, "rescore must be 0 (average) or 1 (maximum)");
     if (!std::isfinite(link_thres) || !std::isfinite(nms_thres)) return fail(c, VDET_EINVAL, "link_thres and nms_thres must be finite");
     if (min_score != min_score) return fail(c, VDET_EINVAL, "min_score must not be NaN");
     const int64_t W = (R + 31) / 32, Rp = (R + 63) / 64 * 64;
-    if (C > 0x7FFFFFF0ll / R || C * R > 0x7FFFFFF0ll / F || C * (int64_t)R * F >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, R, F}))
         return fail(c, VDET_EINVAL, "too many boxes (C*R*F must stay below 2^31 - 16)");
-    if (C * (int64_t)R * F > 0x7FFFFFF0ll / W || C * (int64_t)R * F * W >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, R, F, W}))
         return fail(c, VDET_EINVAL, "too many link words (C*F*R*ceil(R/32) must stay below 2^31 - 16)");
-    if (C * V > 0x7FFFFFF0ll / max_seqs || C * V * max_seqs >= 0x7FFFFFF0ll)
+    if (!fits_below(0x7FFFFFF0ll, {C, V, max_seqs}))
         return fail(c, VDET_EINVAL, "too many sequences (C*max_seqs*V must stay below 2^31 - 16)");
     if (!d_tracks || !d_ntracks) return fail(c, VDET_EINVAL, "null buffer");
     if (!d_tracks_out || !d_score_out || !d_seq_out || !d_ntracks_out || !d_nseq || !d_seq_sum || !d_seq_len || !d_seq_end || !d_exhausted)
@@ -4729,10 +4729,7 @@ int vdet_seq_nms_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
     SeqNmsArgs g{};
-    if (V > 1) {        // one video travels in the kernel arguments alone (as in vdet_nms_tracks_batch)
-        if ((rc = anchor_vidtab(c, h_frame_off, V))) return rc;
-        g.vids = c->anchor_tab.dev.as<VidDesc>();
-    }
+    if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
     // the predecessor table of the longest video: in LDS while it fits the budget (and the device's LDS), else in global scratch
     const void *rounds_fn = reinterpret_cast<const void *>(seqnms_rounds_kernel);
     const size_t ptr_bytes = (size_t)(Fmax * Rp + Fmax) * 2;
