@@ -26,8 +26,12 @@
 //     L2 until the frame is done (spread over all XCDs: 4.3 x write amplification, PMC WRITE_SIZE).
 // adj_finish_kernel (adjrows_kernels.hpp) pads the lists and writes the walk's records.  A row with more neighbours than a slot
 // holds latches over_bits (its surplus entries are dropped): the host rebuilds the graph through the bit matrix.  Entry order
-// inside a list depends on the order of the atomics; lists are sets to every consumer.  Predicate: pred_margins, the same two
-// signed margins as iou_bits_sym_kernel (utils/nms.pyx:57-65 without the division; the half-ulp band redone with the IEEE quotient).
+// inside a list depends on the order of the atomics; lists are sets to every consumer.  Predicate: pred_sign, the same one
+// signed margin as iou_bits_sym_kernel (utils/nms.pyx:57-65 without the division; the quotient's rounding band is folded into the
+// margin, so one sign bit per pair decides and no block is ever redone).
+// (Columns from scalar registers -- the block's boxes as 32-byte records read through the constant address space, no LDS and no
+//  VGPR per column -- were built and measured: 2.31 ms per video, 2.12 with the next four columns' loads in flight, against 1.67
+//  from LDS: 2 GB of records per video, hardly any reuse in the scalar cache.  LABNOTES "Graph build: one sign per pair".)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,7 +82,7 @@ struct GraphListsParams {
     const uint32_t *group_flags;
     const ListItem *items;
     int nitems;
-    float t32, one_minus_t;
+    float t32, hg, one_minus_t;      // hg: half the gap below t32 (pred_sign)
     uint32_t *row_deg;               // per rank-row: degree = cursor of its slot (zero when the kernel starts)
     const float2 *reach_table;       // .y = x1 of the first box of every 64-column block
     const uint16_t *rowperm;
@@ -103,7 +107,7 @@ __device__ __forceinline__ void emit_half(uint16_t *__restrict__ adj, uint32_t h
     uint16_t ek[kSlots];
     int bk[kSlots];
 #pragma unroll
-    for (int k = 0; k < kSlots; ++k) { hk[k] = h; bk[k] = __builtin_ctz(h) & 31; h &= h - 1u; }      // (an empty slot: bit 31, unused)
+    for (int k = 0; k < kSlots; ++k) { hk[k] = h; bk[k] = __builtin_ctz(h | 0x80000000u); h &= h - 1u; }      // (an empty slot: bit 31, unused)
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) ek[k] = ids[bk[k]];
 #pragma unroll
@@ -146,20 +150,18 @@ __device__ __forceinline__ void emit_block(const uint32_t slot_cap, uint16_t *__
     emit_half(adj, (uint32_t)(m >> 32), boff + 2u * (uint32_t)__popc((uint32_t)m), cids + 32, lpos + 32, myid);
 }
 
-// the 64 margins pairs of one block: complement of the sign words = predicate bits, anyb = some pair in the half-ulp band
+// the 64 pairs of one block, ONE sign word per half (pred_sign: exact, band included): complement = predicate bits
 template <bool XS, bool INTS>
-__device__ __forceinline__ void margin_block(const float4 brx, const float rarea, const float4 *sb, const float *sa, float t32, float t_lo,
-                                             uint32_t &lo, uint32_t &hi, bool &anyb)
+__device__ __forceinline__ void margin_block(const float4 brx, const float rarea, const float4 *sb, const float *sa, float t32, float hg,
+                                             uint32_t &lo, uint32_t &hi)
 {
-    uint32_t nr0 = 0, nq0 = 0, nr1 = 0, nq1 = 0;
+    uint32_t nr0 = 0, nr1 = 0;
 #pragma unroll 1
     for (int g = 0; g < 4; ++g) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = 31 - 8 * g - j;
-            float mr, mq;
-            pred_margins<XS, INTS>(brx, rarea, sb[k], sa[k], t32, t_lo, mr, mq);
-            shl1_or_sign(nr0, mr); shl1_or_sign(nq0, mq);
+            shl1_or_sign(nr0, pred_sign<XS, INTS>(brx, rarea, sb[k], sa[k], t32, hg));
         }
     }
 #pragma unroll 1
@@ -167,16 +169,14 @@ __device__ __forceinline__ void margin_block(const float4 brx, const float rarea
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = 31 - 8 * g - j;
-            float mr, mq;
-            pred_margins<XS, INTS>(brx, rarea, sb[32 + k], sa[32 + k], t32, t_lo, mr, mq);
-            shl1_or_sign(nr1, mr); shl1_or_sign(nq1, mq);
+            shl1_or_sign(nr1, pred_sign<XS, INTS>(brx, rarea, sb[32 + k], sa[32 + k], t32, hg));
         }
     }
     lo = ~nr0; hi = ~nr1;
-    anyb = (nr0 != nq0) | (nr1 != nq1);
 }
 
-__global__ __launch_bounds__(64, 6) void graph_lists_kernel(const GraphListsParams prm)
+// (7 waves per SIMD: 70 VGPRs since the second margin went; the bound keeps a later edit from drifting back to 6 unnoticed)
+__global__ __launch_bounds__(64, 7) void graph_lists_kernel(const GraphListsParams prm)
 {
     __shared__ float4 sbox[2][64];
     __shared__ float sarea[2][64];
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(64, 6) void graph_lists_kernel(const GraphListsPara
     const float4 *xb = prm.xbox + gd.box_off;
     const uint16_t *xo = prm.xord + gd.box_off;
     const float t32 = prm.t32;
-    const float t_lo = t32 * (1.0f - 4.76837158203125e-7f);
+    const float hg = prm.hg;
     const TransposeConsts tcs = transpose_consts(lane);
     const bool ints = (gf & kFlagU16) != 0u;      // integer pixel coordinates: x2 + 1 / y2 + 1 formed once per box
     const uint32_t slot_cap = prm.slot_cap;
@@ -250,21 +250,10 @@ __global__ __launch_bounds__(64, 6) void graph_lists_kernel(const GraphListsPara
         const int cols_left = B - c * 64;
         const unsigned long long colvalid = cols_left >= 64 ? ~0ull : ((1ull << cols_left) - 1ull);
         uint32_t lo, hi;
-        bool anyb;
-        if (ints) { if (!dtile) margin_block<true, true>(brx, rarea, sbox[buf], sarea[buf], t32, t_lo, lo, hi, anyb);
-                    else margin_block<false, true>(brx, rarea, sbox[buf], sarea[buf], t32, t_lo, lo, hi, anyb); }
-        else { if (!dtile) margin_block<true, false>(brx, rarea, sbox[buf], sarea[buf], t32, t_lo, lo, hi, anyb);
-               else margin_block<false, false>(brx, rarea, sbox[buf], sarea[buf], t32, t_lo, lo, hi, anyb); }
-        if (__builtin_expect(__ballot(anyb) != 0ull, 0)) {
-            // rare (~1e-6 of the pairs sit in the half-ulp band, e.g. IoU exactly 3/10): redo the block with the IEEE quotient
-            lo = hi = 0u;
-            for (int k = 0; k < 64; ++k) {
-                float4 bk = sbox[buf][k];
-                if (ints) { bk.z -= 1.0f; bk.w -= 1.0f; }        // (exact: integers)
-                const bool p = pair_pred_exact_slow(br, rarea, bk, sarea[buf][k], t32);
-                if (k < 32) lo |= p ? (1u << k) : 0u; else hi |= p ? (1u << (k - 32)) : 0u;
-            }
-        }
+        if (ints) { if (!dtile) margin_block<true, true>(brx, rarea, sbox[buf], sarea[buf], t32, hg, lo, hi);
+                    else margin_block<false, true>(brx, rarea, sbox[buf], sarea[buf], t32, hg, lo, hi); }
+        else { if (!dtile) margin_block<true, false>(brx, rarea, sbox[buf], sarea[buf], t32, hg, lo, hi);
+               else margin_block<false, false>(brx, rarea, sbox[buf], sarea[buf], t32, hg, lo, hi); }
         unsigned long long m = (((unsigned long long)hi << 32) | lo) & colvalid;
         if (dtile) {     // column k of block c is rank c * 64 + k; mine are the ones of higher rank (every pair once, no self edge)
             const int d = v - c * 64;

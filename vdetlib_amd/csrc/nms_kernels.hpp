@@ -319,7 +319,12 @@ __device__ __forceinline__ void xwindow(const FrameIndex &ix, int f, float x1c, 
 // width/height (+1 convention) and a finite area: then the predicate is symmetric in (i, j) (no NaN
 // for the asymmetric max/min to see), unions are > 0 (no ZeroDivisionError) and the fast kernel
 // below is exact.  Irregular frames take the general iou_bits_kernel.
+// Every coordinate of a regular frame is also at most kRegularCoordMax = 2^60 in magnitude: then for EVERY pair of the
+// frame -- far apart, unclamped negative h included -- |w|, |h| <= 2^61 + 1, |inter| and both areas < 2^123 and
+// 0 < uni < 2^125 are finite, and no margin of the divide-free tests is ever inf - inf (pred_sign relies on it; finite
+// coordinates alone let rarea + carea or w * h overflow).
 // ------------------------------------------------------------------------------------------------
+constexpr float kRegularCoordMax = 1152921504606846976.0f;      // 2^60
 __global__ __launch_bounds__(256) void frame_flags_kernel(const float4 *__restrict__ boxes,
                                                           const GroupDesc *__restrict__ groups,
                                                           uint32_t *__restrict__ group_flags,
@@ -332,8 +337,8 @@ __global__ __launch_bounds__(256) void frame_flags_kernel(const float4 *__restri
         const float4 b = boxes[gd.box_off + v];
         const float w = (b.z - b.x) + 1.0f, h = (b.w - b.y) + 1.0f;
         const float a = w * h;
-        const bool ok = fabsf(b.x) < inf && fabsf(b.y) < inf && fabsf(b.z) < inf && fabsf(b.w) < inf &&
-                        w > 0.0f && h > 0.0f && a < inf;
+        const bool ok = fabsf(b.x) <= kRegularCoordMax && fabsf(b.y) <= kRegularCoordMax && fabsf(b.z) <= kRegularCoordMax &&
+                        fabsf(b.w) <= kRegularCoordMax && w > 0.0f && h > 0.0f && a < inf;
         bad |= ok ? 0 : 1;
         // pixel coordinates that four u16 hold exactly (NaN fails the compares, -0.0 the sign test)
         const bool small = b.x == truncf(b.x) && b.y == truncf(b.y) && b.z == truncf(b.z) && b.w == truncf(b.w) &&
@@ -360,7 +365,9 @@ __global__ __launch_bounds__(256) void frame_flags_kernel(const float4 *__restri
 //   r >= 0            =>  inter/uni >= t32            =>  RN(inter/uni) >= t32   (true)
 //   r <  -2^-22*t32*uni => inter/uni < pred(t32)-ish  =>  RN(inter/uni) <  t32   (false)
 //   otherwise (|r| tiny, e.g. IoU exactly 3/10): the wave falls back to the IEEE division.
-// Requires 0 < t32 < inf (the host routes other thresholds to the general kernel).
+// (that is pred_regular, still the ballot form's and the walk's test; the lane-exchange form folds the band into the
+//  margin and needs no fallback: pred_sign.)
+// Requires a supported threshold (the host's sym_threshold_ok routes the others to the general kernel).
 // ------------------------------------------------------------------------------------------------
 // The exact (IEEE divide) predicate as an out-of-line call: it is needed for ~1e-6 of the pairs, and
 // when it is inlined hipcc if-converts the rare branch and computes the divide for EVERY pair
@@ -402,18 +409,30 @@ __device__ __forceinline__ bool pred_regular(float4 br, float rarea, float4 bc, 
     return p;
 }
 
-// The same test as two SIGNED margins (K1s, round 3): r = inter - t32 * uni and q = inter - t_lo * uni, each one fma
-// (sign exact), t_lo = t32 * (1 - 2^-21) rounded.  sign(r) clear <=> the predicate holds; sign(q) clear while sign(r) is
-// set <=> the pair sits in the band just below the threshold where only the IEEE quotient decides (q >= r always, the
-// band is >= 0.875 * 2^-21 * t32 * uni wide, the test above needs 2^-22).  The caller shifts BOTH sign bits into
-// accumulators with one v_alignbit_b32 each -- no compare, no add-with-carry, no per-pair border flag: after 32 pairs the
-// two words differ iff some pair was borderline.  (v_alignbit_b32 turned out to issue at half rate like v_cmp,
-// profiles/r03_valu_bench.csv: 2 fma + 2 alignbit ~ 6 issue slots against fma + mul + 2 v_cmp + v_addc ~ 7.)
-// (r is never -0.0: an exact zero rounds to +0.0, and the product -t32 * uni is never zero on a regular frame)
-// INTS: the frame's coordinates are integers (kFlagU16) and x2 / y2 arrive with the +1 already added -- every sum below
-// is an exact integer whatever the order, so the two "+ 1" of the reference's formula cost nothing.
+// (rounds 3-6 shifted in TWO signed margins per pair, pred_margins -- r = inter - t32 * uni and q = inter - t_lo * uni,
+//  t_lo = t32 * (1 - 2^-21): the words differed iff some pair sat in the band just below the threshold, and that block was
+//  redone with the IEEE quotient; tests/knife_spec.py still models that form.  pred_sign below replaced it.
+//  v_alignbit_b32 issues at half rate like v_cmp, profiles/r03_valu_bench.csv.)
+// acc = (acc << 1) | sign bit of v, one full-rate VALU instruction
+__device__ __forceinline__ void shl1_or_sign(uint32_t &acc, float v)
+{
+    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(v), 31);
+}
+
+// The same test as ONE signed margin: with hg = (t32 - nextafter(t32, 0)) / 2 (half the gap below the threshold, a power
+// of two: half_gap() on the host), RN(inter / uni) >= t32  <=>  inter / uni >= t32 - hg (the midpoint, where the rounding
+// turns)  <=>  inter - t32 * uni + hg * uni >= 0.  r = fma(-t32, uni, inter) is EXACT wherever it lies within a few
+// hg * uni of zero (the product cancels against inter down to a few bits), and the second fma has the sign of its real
+// value; a quotient exactly ON the midpoint would need a float32 uni times a 25-bit odd significand to be a float32.
+// So the sign of the result alone decides, band included: no second margin, no redo with the IEEE quotient.
+// (never -0.0: an exact zero rounds to +0.0.)  Never NaN either: on a regular frame inter and uni are finite for every
+// pair (frame_flags_kernel bounds the coordinates by 2^60), and with hg <= 1 (the host's sym_threshold_ok: hg a normal
+// float, t32 <= 2^24) hg * uni is finite -- where -t32 * uni overflows, r is -inf, the result -inf and the answer "no",
+// which is right: t32 > 1 there.
+// XSORTED / INTS as in pred_regular: bc.x >= br.x is known / integer coordinates, x2 and y2 arrive with the + 1 added and
+// every sum below is an exact integer whatever the order, so the two "+ 1" of the reference's formula cost nothing.
 template <bool XSORTED, bool INTS>
-__device__ __forceinline__ void pred_margins(float4 br, float rarea, float4 bc, float carea, float t32, float t_lo, float &r, float &q)
+__device__ __forceinline__ float pred_sign(float4 br, float rarea, float4 bc, float carea, float t32, float hg)
 {
     const float xx1 = XSORTED ? bc.x : amax(br.x, bc.x);
     const float yy1 = amax(br.y, bc.y);
@@ -423,14 +442,7 @@ __device__ __forceinline__ void pred_margins(float4 br, float rarea, float4 bc, 
     const float h = INTS ? yy2 - yy1 : (yy2 - yy1) + 1.0f;       // (not clamped: see pred_regular)
     const float inter = w * h;
     const float uni = (rarea + carea) - inter;
-    r = __builtin_fmaf(-t32, uni, inter);
-    q = __builtin_fmaf(-t_lo, uni, inter);
-}
-
-// acc = (acc << 1) | sign bit of v, one full-rate VALU instruction
-__device__ __forceinline__ void shl1_or_sign(uint32_t &acc, float v)
-{
-    acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(v), 31);
+    return __builtin_fmaf(hg, uni, __builtin_fmaf(-t32, uni, inter));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -571,7 +583,7 @@ template <bool WT>
 __global__ __launch_bounds__(256) void iou_bits_sym_kernel(const float4 *__restrict__ xbox,
                                                            const GroupDesc *__restrict__ groups,
                                                            const uint32_t *__restrict__ group_flags,
-                                                           const TilePair *__restrict__ pairs, float t32, float one_minus_t,
+                                                           const TilePair *__restrict__ pairs, float t32, float hg, float one_minus_t,
                                                            uint64_t *__restrict__ bits, uint32_t *__restrict__ row_deg,
                                                            const float2 *__restrict__ reach_table)
 {
@@ -594,7 +606,6 @@ __global__ __launch_bounds__(256) void iou_bits_sym_kernel(const float4 *__restr
         if (tp.ct * 4 >= W || rtab[tp.ct * 4].y > tr) return;       // (block-uniform)
     }
     const float t32e = t32 * 4.76837158203125e-7f;   // 2^-21
-    const float t_lo = t32 * (1.0f - 4.76837158203125e-7f);
     const TransposeConsts tcs = transpose_consts(lane);
     // integer pixel coordinates (kFlagU16): x2 + 1 / y2 + 1 are formed once per box instead of once per pair
     const bool ints = WT && (group_flags[tp.group] & kFlagU16) != 0u;
@@ -628,34 +639,31 @@ __global__ __launch_bounds__(256) void iou_bits_sym_kernel(const float4 *__restr
         // evaluated nor written -- K2 applies the same test before it reads
         if (rows_left <= 0 || (c > r && rtab[c].y > my_reach)) continue;
         {
-            bool anyb = false;
             if (WT) {
-                // sign bits of the two margins, shifted in (descending k leaves column k in bit k); lo / hi = the complement
-                uint32_t nr0 = 0, nq0 = 0, nr1 = 0, nq1 = 0;
+                // sign bit of the margin (pred_sign), shifted in (descending k leaves column k in bit k); lo / hi = the complement
+                uint32_t nr0 = 0, nr1 = 0;
 #define VDET_MARGIN_BLOCK(XS, IN) \
                 _Pragma("unroll 1") for (int g = 0; g < 4; ++g) { \
                     _Pragma("unroll") for (int j = 0; j < 8; ++j) { \
                         const int k = 31 - 8 * g - j; \
-                        float mr, mq; \
-                        pred_margins<XS, IN>(brx, rarea, sbox[q * 64 + k], sarea[q * 64 + k], t32, t_lo, mr, mq); \
-                        shl1_or_sign(nr0, mr); shl1_or_sign(nq0, mq); \
+                        shl1_or_sign(nr0, pred_sign<XS, IN>(brx, rarea, sbox[q * 64 + k], sarea[q * 64 + k], t32, hg)); \
                     } \
                 } \
                 _Pragma("unroll 1") for (int g = 0; g < 4; ++g) { \
                     _Pragma("unroll") for (int j = 0; j < 8; ++j) { \
                         const int k = 31 - 8 * g - j; \
-                        float mr, mq; \
-                        pred_margins<XS, IN>(brx, rarea, sbox[q * 64 + 32 + k], sarea[q * 64 + 32 + k], t32, t_lo, mr, mq); \
-                        shl1_or_sign(nr1, mr); shl1_or_sign(nq1, mq); \
+                        shl1_or_sign(nr1, pred_sign<XS, IN>(brx, rarea, sbox[q * 64 + 32 + k], sarea[q * 64 + 32 + k], t32, hg)); \
                     } \
                 }
                 // (off-diagonal block: every column starts at or to the right of every row in the x1 order)
                 if (ints) { if (c > r) { VDET_MARGIN_BLOCK(true, true) } else { VDET_MARGIN_BLOCK(false, true) } }
                 else { if (c > r) { VDET_MARGIN_BLOCK(true, false) } else { VDET_MARGIN_BLOCK(false, false) } }
 #undef VDET_MARGIN_BLOCK
-                lo = ~nr0; hi = ~nr1;
-                anyb = (nr0 != nq0) | (nr1 != nq1);
+                lo = ~nr0; hi = ~nr1;         // (exact as it stands: nothing to redo)
             } else {
+            // the ballot form (the lane-exchange self-test failed): pred_regular, and the block redone with the IEEE quotient
+            // when some pair sits in the band below the threshold (ints is never set here)
+            bool anyb = false;
 #pragma unroll
             for (int kk = 0; kk < 32; ++kk) {
                 const int k = 31 - kk;      // descending: acc = 2*acc + p (one v_addc) leaves column k in bit k
@@ -682,21 +690,16 @@ __global__ __launch_bounds__(256) void iou_bits_sym_kernel(const float4 *__restr
                     thi = (lane == 32 + k) ? (uint32_t)(b >> 32) : thi;
                 }
             }
-            }
             if (__builtin_expect(__ballot(anyb) != 0ull, 0)) {
-                // rare (~1e-6 of the pairs sit in the half-ulp band, e.g. IoU exactly 3/10):
-                // redo this 64 x 64 block with the IEEE quotient
+                // rare (~1e-6 of the pairs sit in the half-ulp band, e.g. IoU exactly 3/10)
                 lo = hi = tlo = thi = 0;
                 for (int k = 0; k < 64; ++k) {
-                    float4 bk = sbox[q * 64 + k];
-                    if (ints) { bk.z -= 1.0f; bk.w -= 1.0f; }        // (exact: integers)
-                    const bool p = pair_pred_exact_slow(br, rarea, bk, sarea[q * 64 + k], t32);
+                    const bool p = pair_pred_exact_slow(br, rarea, sbox[q * 64 + k], sarea[q * 64 + k], t32);
                     if (k < 32) lo |= p ? (1u << k) : 0u; else hi |= p ? (1u << (k - 32)) : 0u;
-                    if (!WT) {
-                        const unsigned long long b = __ballot(p);
-                        if (lane == k) { tlo = (uint32_t)b; thi = (uint32_t)(b >> 32); }
-                    }
+                    const unsigned long long b = __ballot(p);
+                    if (lane == k) { tlo = (uint32_t)b; thi = (uint32_t)(b >> 32); }
                 }
+            }
             }
             if (WT && c > r) {   // the transposed block from the row-major words, on the lane-exchange network
                 tlo = lo; thi = hi;

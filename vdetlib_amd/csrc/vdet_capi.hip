@@ -413,6 +413,14 @@ float thresh_to_f32(double thresh)
     return f;
 }
 
+// half the gap between t32 and the float32 below it: where RN(inter / uni) turns from < t32 to >= t32 (pred_sign)
+float half_gap(float t32) { return (t32 - nextafterf(t32, 0.0f)) * 0.5f; }
+
+// thresholds the divide-free test of the regular-frame kernels is exact for: hg must be a normal float (so t32 is no
+// subnormal) and at most 1 (t32 <= 2^24), so that hg * uni is finite for the unions of a regular frame, which
+// frame_flags_kernel keeps finite by bounding the coordinates (an infinite uni would make the margin inf - inf)
+bool sym_threshold_ok(float t32) { return t32 > 1e-30f && t32 <= 16777216.0f && std::isnormal(half_gap(t32)); }
+
 uint32_t pow2ceil(uint32_t x)
 {
     uint32_t p = 1;
@@ -721,7 +729,7 @@ int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, doub
     // direct lists (iou_bits_sym_kernel<true, true>): regular frames of large volumes get a fixed slot per row at the start of
     // the pool, the dynamic part (irregular frames) follows
     auto direct_now = [&]() {
-        return c->direct_lists && c->adj_rows && c->wave_transpose && pl.nmax > 384 && t32 > 1e-30f && t32 < INFINITY && !c->force_general &&
+        return c->direct_lists && c->adj_rows && c->wave_transpose && pl.nmax > 384 && sym_threshold_ok(t32) && !c->force_general &&
                (size_t)8 * pl.nmax + 24 * 1024 <= c->max_lds && ((unsigned long long)pl.ntot + 1ull) * c->direct_cap * 2ull + 512ull <= 0xFFFFFFFFull;     // (byte offsets of the entries in 32 bits)
     };
     // (one slot more than rows: where the entries of a column that outgrew its slot are dumped)
@@ -760,9 +768,9 @@ int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, doub
         if (direct) hipLaunchKernelGGL(pool_start_kernel, dim3(1), dim3(1), 0, c->stream, &c->d_cnt->pool_used, fixed_pool());
         const int pool_bits = async ? (kStPool | kStPoolAsync) : kStPool;
         const unsigned long long pool_cap = (c->adj.cap - 2048) / 2;     // (the packed walk reads up to 256 B past a list)
-        // fast symmetric kernel for regular frames needs 0 < t32 < inf (exact divide-free test)
+        // fast symmetric kernel for regular frames needs a threshold its divide-free test is exact for (sym_threshold_ok)
         // ... and the x1 index, whose sort must fit the LDS (8 B per box + tables)
-        const bool use_sym = t32 > 1e-30f && t32 < INFINITY && !c->force_general &&
+        const bool use_sym = sym_threshold_ok(t32) && !c->force_general &&
                              (size_t)8 * pl.nmax + 24 * 1024 <= c->max_lds;
         c->sym_built = use_sym;
         c->wmeta_built = use_sym;
@@ -802,7 +810,7 @@ int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, doub
             GraphListsParams gp;
             gp.xbox = c->xbox.as<float4>(); gp.xord = c->xord.as<uint16_t>(); gp.groups = c->groups.as<GroupDesc>();
             gp.group_flags = c->gflags.as<uint32_t>(); gp.items = c->ditems.as<ListItem>(); gp.nitems = (int)pl.ditems.size();
-            gp.t32 = t32; gp.one_minus_t = one_minus_t; gp.row_deg = c->rowz.as<uint32_t>(); gp.reach_table = c->reachtab.as<float2>();
+            gp.t32 = t32; gp.hg = half_gap(t32); gp.one_minus_t = one_minus_t; gp.row_deg = c->rowz.as<uint32_t>(); gp.reach_table = c->reachtab.as<float2>();
             gp.rowperm = c->rowperm.as<uint16_t>(); gp.qreach = c->qreach.as<float>(); gp.adj = c->adj.as<uint16_t>();
             gp.slot_cap = c->direct_cap; gp.status = &c->d_cnt->status; gp.over_bits = pool_bits | kStDirect;
             gp.trash_off = (uint32_t)((unsigned long long)pl.ntot * c->direct_cap * 2ull);      // (the spare slot behind the rows')
@@ -819,12 +827,12 @@ int build_graph(vdet_ctx *c, const float4 *d_boxes, NmsPlan &pl, float t32, doub
                 if (c->wave_transpose)
                     hipLaunchKernelGGL(iou_bits_sym_kernel<true>, dim3(bp.second - bp.first), dim3(256), 0, c->stream,
                                        c->xbox.as<float4>(), c->groups.as<GroupDesc>(), c->gflags.as<uint32_t>(),
-                                       c->pairs.as<TilePair>() + bp.first, t32, one_minus_t, bits_b, c->rowz.as<uint32_t>(),
+                                       c->pairs.as<TilePair>() + bp.first, t32, half_gap(t32), one_minus_t, bits_b, c->rowz.as<uint32_t>(),
                                        c->reachtab.as<float2>());
                 else
                     hipLaunchKernelGGL(iou_bits_sym_kernel<false>, dim3(bp.second - bp.first), dim3(256), 0, c->stream,
                                        c->xbox.as<float4>(), c->groups.as<GroupDesc>(), c->gflags.as<uint32_t>(),
-                                       c->pairs.as<TilePair>() + bp.first, t32, one_minus_t, bits_b, c->rowz.as<uint32_t>(),
+                                       c->pairs.as<TilePair>() + bp.first, t32, half_gap(t32), one_minus_t, bits_b, c->rowz.as<uint32_t>(),
                                        c->reachtab.as<float2>());
             }
             // enough column splits to fill the chip when there are few row tiles
@@ -1700,6 +1708,7 @@ int vdet_query(vdet_ctx *c, int what)
     if (what == 1) return c->n_cu;
     if (what == 2) return c->all_regular ? 1 : 0;
     if (what == 3) return c->wave_transpose ? 1 : 0;
+    if (what == 15) return c->direct_ntot > 0 ? 1 : 0;    // the last graph build took the direct lists (graph_lists_kernel)
     if (what == 8) return (int)std::min<long long>(c->n_host_syncs, 0x7FFFFFFF);
     if (what == 10) return (int)std::min<long long>(c->tcn_params.uploads, 0x7FFFFFFF);   // TCN parameter uploads so far
     if (what == 11) return (int)std::min<long long>(c->anchor_tab.uploads, 0x7FFFFFFF);   // per-video tables of the anchor route's batch forms staged so far
