@@ -219,6 +219,11 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * the first call (synchronises the stream).
  * what = 14 -> where the last vdet_seq_nms[_batch] kept the predecessor table: 1 in LDS, 2 in global scratch (the longest video's
  * table outgrew the LDS budget, or VDET_SEQNMS_LDS=0); -1 before the first call.
+ * what = 15 -> 1 if the last suppression-graph build took the direct lists.
+ * what = 16 -> (frame, class) columns of the last volume sort that the counting sort ordered with the key -> bin map INHERITED
+ * from the column its workgroup sorted before (no histogram of their own; the order does not depend on the map);
+ * what = 17 -> columns whose inherited map overflowed a bin and that were sorted AGAIN with their own map (they do not go to the
+ * LSD kernel and are not counted by 16).  Both synchronise the stream; -1 if that sort did not use the counting sort.
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant -- the one switch that does, VDET_VPASS_FORM,
@@ -228,6 +233,9 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  *   VDET_NO_LAZY=1        eager track_det_nms of every crossed list (what irregular frames take)
  *   VDET_NO_FUSED=1       h_* calls of <= 640 rows through the general kernel chain (what larger inputs take)
  *   VDET_BINSORT=0        the LSD radix sort for every column (what tied / thresholded columns take)
+ *   VDET_BINSORT_INHERIT=0  every column of the counting sort builds its own key -> bin map (what a column takes whose
+ *                         predecessor's map does not fit its scores)
+ *   VDET_BINSORT_GRID=n   at most n workgroups for the counting sort (1: one workgroup sorts the columns in order)
  *   VDET_SMALL_LISTS=0    frames of <= 384 boxes through the large-list sort and walk
  *   VDET_DIRECT_LISTS=0   the suppression graph of regular frames of > 384 boxes through the bit matrix (what a context takes for
  *                         good once a row had more neighbours than a direct list slot holds); VDET_DIRECT_CAP=n entries per slot

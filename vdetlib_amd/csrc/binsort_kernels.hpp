@@ -8,7 +8,7 @@
 //
 //   1. level 1: histogram of the keys' top 9 bits (sign + exponent of the inverted sortable key), 8 copies per value
 //      spread over the lanes (scores concentrate on a handful of exponents; same-address LDS atomics serialise);
-//   2. every exponent value e that occurs gets m_e = ceil(count_e * S / N) sub-bins of EQUAL mantissa width,
+//   2. every exponent value e gets m_e = max(1, ceil(count_e * S / N)) sub-bins of EQUAL mantissa width,
 //      S = 32 256: a piecewise-linear, monotone map key -> bin in [0, 32 768) that follows the key distribution octave
 //      by octave (uniform, normal, exponential / softmax-like scores all end with ~0.3 keys per bin);
 //   3. one returning byte-wide LDS atomic per key counts the bin and hands the key its arrival rank r inside it;
@@ -24,6 +24,21 @@
 // afterwards (sort_list_kernel) -- the decision is made per problem, on the device, from the counts alone.
 // Workgroups are persistent and claim problems from a global counter; the next problem's keys are in flight while
 // the current one is scanned, scattered and fixed up.
+//
+// The map of step 2 is INHERITED.  It carries no part of the result: phase 6 orders every bin exactly, a bin that is too full is
+// detected in phase 3, and the output is defined by the keys alone -- any monotone map that keeps the exponent values in bins of
+// their own ends in the same order.  So step 2 gives EVERY exponent value at least one sub-bin (an absent value would share the
+// next one's bin under another list's keys, and fractions of different exponents do not compare), and a workgroup sorts a list
+// with the map of the list it sorted before: no phase 1, no phase 2, three barriers fewer.  A detector's per-class score columns
+// look alike from one list to the next; where they do not, the kernel notices from the ranks of phase 3:
+//   - a rank >= kBinMax under an inherited map: the list is sorted AGAIN with its own map (counters cleared, keys reloaded from
+//     L2, phases 1-2-3), and the next 1, 2, 4 ... kBinBackoffMax lists build their own maps without trying (doubling with
+//     consecutive redos, back to none after a cleanly inherited list): alternating distributions do not pay twice per list;
+//   - a rank >= kBinMax under the list's OWN map, or an excluded key: the fail list, as before;
+//   - more than N / 32 keys at rank >= kBinCrowdRank (where phase 6's slower paths start; a list's own map on random scores
+//     gives ~0.5 %): the list finishes as it is, but its map is not passed on.
+// BinSortCtl counts the lists sorted with an inherited map and the lists redone (vdet_query 16 / 17); BinSortParams::inherit = 0
+// (VDET_BINSORT_INHERIT=0) makes every list build its own map.  Measured: LABNOTES "Counting sort: inherited bin map".
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,9 +54,14 @@ namespace vdet {
 __host__ __device__ constexpr int binsort_words(int cpw) { return cpw <= 20 ? 4096 : 8192; }
 constexpr int kBinMax = 10;              // keys per bin (three of them must fit a 5-bit field of the scanned counter word)
 
+constexpr int kBinCrowdRank = 3;         // arrival ranks from here on take phase 6's slower paths: counted per list (crowding rule)
+constexpr int kBinBackoffMax = 64;       // own maps after a redo: 1, 2, 4 ... lists with consecutive redos
+
 struct BinSortCtl {
     int next;            // next problem to claim
     int nfail;           // problems handed to the LSD kernel
+    int ninherit;        // problems sorted with the map of their block's previous problem (vdet_query 16)
+    int nredo;           // problems whose inherited map overflowed a bin: sorted again with their own map (vdet_query 17)
 };
 
 struct BinSortParams {
@@ -51,6 +71,7 @@ struct BinSortParams {
     int32_t *ncand;      // [P]
     BinSortCtl *ctl;
     int32_t *fail_list;  // [P]
+    int inherit;         // 0: every problem builds its own key -> bin map (VDET_BINSORT_INHERIT=0)
 };
 
 // dynamic LDS: [counter words: 32 KB][16 B][entries: N + kBinTail words]
@@ -99,7 +120,10 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
     __shared__ uint32_t tab[512];        // per exponent value: first bin << 16 | number of sub-bins
     __shared__ uint32_t wsum[NW];
     __shared__ int snext;
-    __shared__ int sbad;
+    // verdict on a list, one word per list PARITY: crowded keys (bits 0-19, summed) | threads that saw a rank >= kBinMax
+    // (bits 20-30, summed) | an excluded key (bit 31).  Two words because the inheriting path has no barrier between the top of
+    // the loop and phase 3: the word of the NEXT list is zeroed right after this list's is read (see the loop for the order)
+    __shared__ uint32_t sflag[2];
 
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int P = prm.P, N = prm.N;
@@ -128,6 +152,7 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
     };
 
     if (tid == 0) snext = atomicAdd(&prm.ctl->next, 1);
+    if (tid < 2) sflag[tid] = 0u;
     for (int i = tid; i < kBinWords / 4; i += BLOCK) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < kBinTail) ent[N + tid] = 0x8000u;                  // sentinels: "a new bin starts here" closes every walk to the right
     __syncthreads();
@@ -139,24 +164,38 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
     // (every phase re-derives what it needs from an OPAQUE copy of the thread index: left alone, hipcc hoists each
     //  phase's addresses and predicates out of the problem loop and then spills them -- seen in the ISA)
     auto fresh_tid = [&]() -> int { int t = tid; asm volatile("" : "+v"(t)); return t; };
+    // The key -> bin map `tab` carries no part of the result (any monotone map that keeps exponent values apart ends in the same
+    // order: phase 6 orders every bin exactly), so a block passes it from one list to the next and skips phases 1-2 for as long as
+    // it spreads the keys.  All of this state is the same in every thread (it is derived from sflag and snext after barriers).
+    int have_map = 0;                // tab holds a map worth passing on
+    int own_left = 0, backoff = 0;   // lists still to build their own map after a redo; the length of the last such run
+    int par = 0;                     // which sflag word this list uses
+    int n_inherit = 0, n_redo = 0;
     while (p < P) {
-        int bad = 0;
         finish_keys(ik);
-        if (tid == 0) sbad = 0;
+        int claimed = 0;
+        if (tid == 0) claimed = atomicAdd(&prm.ctl->next, 1);                   // (handed to snext in front of phase 3's barrier)
+        bool inherit = have_map && own_left == 0, redone = false;
+        uint32_t cs[CPW];            // bin << 16 | fraction
+        uint32_t rr[(CPW + 3) / 4];  // ranks, one byte each
+        unsigned long long have;     // which of my slots hold keys: a bit per slot (ik is reused for the next list)
+        uint32_t flags;
+        static_assert(CPW % 4 == 0, "whole words of ranks");
+        for (;;) {
+        if (!inherit) {
         // ---- 1. level 1: exponent histogram, 8 copies per value (lane & 7)
         {
             const int t = fresh_tid();
             const uint32_t copy = (uint32_t)(t & 7);
 #pragma unroll
             for (int k = 0; k < CPW; ++k) {
-                const bool none = ik[k] == 0xFFFFFFFFu;                          // (slots past N hold 0xFFFFFFFF too)
-                bad |= (int)(none & (t + k * BLOCK < N));                        // excluded keys: the LSD kernel's business
-                if (!none) atomicAdd(&hist[((ik[k] >> 23) << 3) | copy], 1u);
+                if (ik[k] != 0xFFFFFFFFu) atomicAdd(&hist[((ik[k] >> 23) << 3) | copy], 1u);      // (slots past N hold 0xFFFFFFFF too)
             }
         }
-        if (tid == 0) snext = atomicAdd(&prm.ctl->next, 1);                     // (read after the barriers below)
         lds_only_barrier();
-        // ---- 2. sub-bins per exponent value: thread e owns value e (BLOCK == 512 values); its level-1 words are zeroed again
+        // ---- 2. sub-bins per exponent value: thread e owns value e (BLOCK == 512 values); its level-1 words are zeroed again.
+        //         EVERY value gets at least one sub-bin (kBinSub leaves one per value): under a map inherited from another list a
+        //         value without one would share the next value's bin, and fractions of different exponents do not compare
         {
             static_assert(BLOCK == 512, "one thread per exponent value");
             const int e = fresh_tid();
@@ -164,7 +203,9 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
             const uint4 a = src[0], b = src[1];
             src[0] = make_uint4(0u, 0u, 0u, 0u); src[1] = make_uint4(0u, 0u, 0u, 0u);
             const uint32_t cnt = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
-            const uint32_t m = cnt ? (cnt * (uint32_t)kBinSub + (uint32_t)N - 1u) / (uint32_t)N : 0u;      // (cnt <= N < 2^15, kBinSub < 2^15)
+            uint32_t n2 = (uint32_t)N;
+            asm volatile("" : "+s"(n2));                  // (the division's reciprocal is not kept in a register across the lists)
+            const uint32_t m = max(1u, (cnt * (uint32_t)kBinSub + n2 - 1u) / n2);                            // (cnt <= N < 2^15, kBinSub < 2^15)
             const uint32_t incl = wave_incl_scan_u32(m);
             if ((e & 63) == 63) wsum[w] = incl;
             lds_only_barrier();
@@ -173,12 +214,10 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
             tab[e] = (run << 16) | m;
         }
         lds_only_barrier();
-        const int pnext = __builtin_amdgcn_readfirstlane(snext);
+        }
         // ---- 3. bin + arrival rank of every key.  Each stage of the phase runs over ALL the thread's keys before the next
         //         one starts (table reads, then atomics, then their returns): 16 waves per CU hide no LDS latency, the
         //         20 independent operations per thread do
-        uint32_t cs[CPW];            // bin << 16 | fraction
-        uint32_t rr[(CPW + 3) / 4];  // ranks, one byte each
         {
 #pragma unroll
             for (int k = 0; k < CPW; ++k) cs[k] = tab[ik[k] >> 23];
@@ -204,26 +243,71 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
 #pragma unroll
             for (int k = 0; k < CPW; ++k) {
                 const uint32_t r = (old[k] >> ((cs[k] >> 13) & 24u)) & 0xFFu;
-                if (r >= (uint32_t)kBinMax) bad = 1;
                 rr[k >> 2] |= r << ((k & 3) * 8);
             }
         }
-        // which of my slots hold keys: remembered as a bit per slot (ik is about to be reused)
-        unsigned long long have = 0ull;
+        // the verdict, four ranks at a time: bit 7 of a byte <- rank >= T is ((b & 0x7F) + (0x80 - T)) | b
+        uint32_t verdict = 0u;
+        {
+            uint32_t over = 0u;
+#pragma unroll
+            for (int k = 0; k < CPW / 4; ++k) {
+                const uint32_t x = rr[k], x7 = x & 0x7F7F7F7Fu;
+                over |= (x7 + 0x01010101u * (uint32_t)(0x80 - kBinMax)) | x;
+                verdict += (uint32_t)__popc(((x7 + 0x01010101u * (uint32_t)(0x80 - kBinCrowdRank)) | x) & 0x80808080u);
+            }
+            if (over & 0x80808080u) verdict |= 1u << 20;
+        }
+        have = 0ull;
 #pragma unroll
         for (int k = 0; k < CPW; ++k) have |= (unsigned long long)(ik[k] != 0xFFFFFFFFu ? 1u : 0u) << k;
+        {
+            // fewer keys than slots below N: an excluded key, the LSD kernel's business
+            const int t = fresh_tid();
+            const int my_slots = t < N ? min(CPW, (N - t + BLOCK - 1) / BLOCK) : 0;
+            if (__popcll(have) != my_slots) atomicOr(&sflag[par], 0x80000000u);
+        }
+        // one LDS atomic per wave that has something to report (on random scores ~50 threads of a list have a crowded key: one
+        // same-address atomic each cost 0.1 ms per video); <= 512 threads x 2^20, <= 18 432 crowded keys: no carry between the fields
+        if (__builtin_amdgcn_ballot_w64(verdict != 0u)) {
+            const uint32_t sum = wave_incl_scan_u32(verdict);
+            if ((fresh_tid() & 63) == 63) atomicAdd(&sflag[par], sum);
+        }
+        if (tid == 0) snext = claimed;
+        lds_only_barrier();
+        flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)sflag[par]);
+        if (!inherit || (flags >> 20) == 0u || (flags >> 31)) break;
+        // A bin overflowed under the INHERITED map: this list's keys lie elsewhere.  Not the LSD kernel's business: once more with
+        // the list's own map.  (Its keys come from L2 again; sflag is zeroed between two barriers that no access to it crosses.)
+        for (int i = fresh_tid(); i < kBinWords / 4; i += BLOCK) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+        load_keys(p, ik);
+        lds_only_barrier();
+        if (tid == 0) sflag[par] = 0u;
+        finish_keys(ik);
+        inherit = false; redone = true;
+        }
+        const int pnext = __builtin_amdgcn_readfirstlane(snext);
+        // (the NEXT list's word: last read a list ago, first written behind at least one more barrier -- phase 4's, or the one below)
+        if (tid == 0) sflag[par ^ 1] = 0u;
+        par ^= 1;
         // the next problem's keys travel while this one is scanned, scattered and fixed up
         if (pnext < P) load_keys(pnext, ik);
-        if (bad) sbad = 1;
-        lds_only_barrier();
-        if (sbad) {
-            // not spreadable (ties / quantised scores / exclusions): hand the problem to the LSD kernel
+        if (flags >> 20) {
+            // not spreadable with its own map (ties / quantised scores), or exclusions: hand the problem to the LSD kernel
             if (tid == 0) prm.fail_list[atomicAdd(&prm.ctl->nfail, 1)] = p;
             for (int i = tid; i < kBinWords / 4; i += BLOCK) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
             lds_only_barrier();
+            have_map = 0;
             p = pnext;
             continue;
         }
+        // Back-off: after a redo the next 1, 2, 4 ... kBinBackoffMax lists build their own maps (doubling with consecutive redos,
+        // so alternating distributions do not pay twice per list); a cleanly inherited list ends it.  Crowding: a map that sent
+        // more than N / 32 keys to ranks where phase 6's slow paths start (own map on random scores: ~0.5 %) is not passed on.
+        if (redone) { backoff = backoff ? min(2 * backoff, kBinBackoffMax) : 1; own_left = backoff; ++n_redo; }
+        else if (inherit) { backoff = 0; ++n_inherit; }
+        else if (own_left) --own_left;
+        have_map = prm.inherit && (int)(flags & 0xFFFFFu) * 32 <= N;
         // ---- 4. exclusive scan of the byte counters; word <- start | s1 << 17 | s2 << 22 | s3 << 27, s_j = keys in the
         //         word's first j bins (<= 3 * kBinMax = 30: five bits)
         //         (two reads of the thread's 16 words instead of 16 live registers + their shifted copies across the barrier)
@@ -359,13 +443,17 @@ __global__ __launch_bounds__(512, CPW <= 20 ? 4 : 2) void binsort_kernel(const B
                 const int q = (w * CPW + ch) * 64 + lane6;
                 if (q < N) out[q] = (uint16_t)(ent[q] & 0x7FFFu);
             }
-            // every key of the list is a candidate HERE: a list with an excluded key (NaN score, key 0xFFFFFFFF -- `bad` in
-            // phase 1, decided on the device, not by the host's gating) was handed to the LSD kernel, which counts its own
-            if (tid == 0) prm.ncand[p] = N;
+            // every key of the list is a candidate HERE: a list with an excluded key (NaN score, key 0xFFFFFFFF -- bit 31 of the
+            // verdict in phase 3, decided on the device, not by the host's gating) was handed to the LSD kernel, which counts its own
+            int nn = N;
+            asm volatile("" : "+s"(nn));                  // (not a vector copy of N held across the lists)
+            if (tid == 0) prm.ncand[p] = nn;
         }
         lds_only_barrier();
         p = pnext;
     }
+    if (tid == 0 && n_inherit) atomicAdd(&prm.ctl->ninherit, n_inherit);
+    if (tid == 0 && n_redo) atomicAdd(&prm.ctl->nredo, n_redo);
 }
 
 }  // namespace vdet

@@ -185,6 +185,8 @@ struct vdet_ctx {
     unsigned long long direct_fixed = 0;
     bool no_fused = false;        // VDET_NO_FUSED=1: the host-buffer calls of <= 640 rows through the general kernel chain too (the path of larger inputs)
     bool binsort = true;          // VDET_BINSORT=0: the LSD radix kernel (the fallback of tied / thresholded columns) for every column
+    bool binsort_inherit = true;  // VDET_BINSORT_INHERIT=0: every column of the counting sort builds its own key -> bin map
+    int binsort_grid = 0;         // VDET_BINSORT_GRID=n: at most n workgroups for the counting sort (0: as many as fit the chip)
     const std::vector<GroupDesc> *host_groups = nullptr;   // group table of the call in flight (mode 2)
     bool sym_built = false;       // the last graph build ran K0 + frame index + K1s (regular-frame fast path)
     // volume geometry whose group / tile / pair tables are resident in c->groups / c->tiles / c->pairs
@@ -1067,7 +1069,7 @@ int launch_sort_walk(vdet_ctx *c, const SortWalkArgs &a, int nmax, int64_t order
         const int bin_cpw = nmax <= 4096 ? 8 : nmax <= 10240 ? 20 : 36;      // keys per thread, 512 threads
         const size_t bin_lds = binsort_lds_bytes(std::max(nmax, 1), bin_cpw);
         // (threshold / top-k / exclusion lists change ncand: those go to the LSD kernel; a NaN inside an otherwise plain list is
-        //  caught per list on the device, binsort_kernels.hpp phase 1)
+        //  caught per list on the device, binsort_kernels.hpp phase 3)
         const bool use_bin = c->binsort && (sp.mode == 1 || sp.mode == 3) && a.topk == 0 && !a.use_thr && !a.excl && block == 1024 &&
                              nmax <= 512 * bin_cpw && bin_lds + 4096 <= c->dyn_lds_max;
         // frames of at most 384 boxes: one WAVE per list (small_kernels.hpp: the same stable LSD passes without a workgroup)
@@ -1093,7 +1095,9 @@ int launch_sort_walk(vdet_ctx *c, const SortWalkArgs &a, int nmax, int64_t order
             bp.ctl = c->sortctl.as<BinSortCtl>();
             bp.fail_list = reinterpret_cast<int32_t *>(c->sortctl.as<char>() + sizeof(BinSortCtl));
             const int per_cu = std::max<int>(1, (int)(c->max_lds / (bin_lds + 4096)));
-            const int grid = std::min(a.P, per_cu * c->n_cu);
+            bp.inherit = c->binsort_inherit ? 1 : 0;
+            const int full = std::min(a.P, per_cu * c->n_cu);
+            const int grid = c->binsort_grid > 0 ? std::min(full, c->binsort_grid) : full;
 #define VDET_BSK(CP) (floats ? reinterpret_cast<const void *>(binsort_kernel<CP, true>) : reinterpret_cast<const void *>(binsort_kernel<CP, false>))
             const void *bfn = bin_cpw == 8 ? VDET_BSK(8) : bin_cpw == 20 ? VDET_BSK(20) : VDET_BSK(36);
 #undef VDET_BSK
@@ -1575,6 +1579,8 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_DIRECT_LISTS")) c->direct_lists = atoi(e) != 0;
     if (const char *e = getenv("VDET_DIRECT_CAP")) { const int v = atoi(e); if (v >= 8 && v <= 32760) c->direct_cap = (uint32_t)(v & ~7); }
     if (const char *e = getenv("VDET_BINSORT")) c->binsort = atoi(e) != 0;
+    if (const char *e = getenv("VDET_BINSORT_INHERIT")) c->binsort_inherit = atoi(e) != 0;
+    if (const char *e = getenv("VDET_BINSORT_GRID")) { const int v = atoi(e); if (v >= 1) c->binsort_grid = v; }
     if (const char *e = getenv("VDET_SMALL_LISTS")) c->small_lists = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_GLOBAL")) c->tcn_global = atoi(e) != 0;
@@ -1723,11 +1729,12 @@ int vdet_query(vdet_ctx *c, int what)
         return reads;
     }
     if (what == 14) return c->sq_last_path;   // the last vdet_seq_nms[_batch]: 1 predecessor table in LDS, 2 in global scratch (-1: no call yet)
-    if (what == 9) {   // problems the last volume sort's counting kernel handed to the LSD kernel (-1: it did not run)
+    if (what == 9 || what == 16 || what == 17) {   // the last volume sort's counting kernel (-1: it did not run): problems handed to
+        // the LSD kernel (9), sorted with an inherited key -> bin map (16), sorted again with their own map (17)
         if (!c->last_sort_binned || !c->sortctl.p) return -1;
         BinSortCtl h{};
         if (hipMemcpyAsync(&h, c->sortctl.p, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess || host_sync(c) != hipSuccess) return VDET_EHIP;
-        return h.nfail;
+        return what == 9 ? h.nfail : what == 16 ? h.ninherit : h.nredo;
     }
     if (what >= 4 && what <= 7) {     // link steps of the last tracking call served by the memo (4) / scanned (5); 6 / 7: the warm-up's
         unsigned int h[4] = {0, 0, 0, 0};
