@@ -224,6 +224,10 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  * from the column its workgroup sorted before (no histogram of their own; the order does not depend on the map);
  * what = 17 -> columns whose inherited map overflowed a bin and that were sorted AGAIN with their own map (they do not go to the
  * LSD kernel and are not counted by 16).  Both synchronise the stream; -1 if that sort did not use the counting sort.
+ * what = 18 -> (frame, class) lists of the last volume walk that entered the WIDE filter of the packed walk (four chunks of 64
+ * candidates tested per pass once a pass queued fewer than 12; the keep lists do not depend on it);
+ * what = 19 -> wide passes of that walk that wanted more than 64 candidates and were queued chunk by chunk instead.  Both
+ * synchronise the stream; -1 if the last walk could not take the wide filter (VDET_WALK_WIDE=0, no regular frame).
  *
  * Environment switches, read once by vdet_create (diagnostics: each FORCES a fallback path the library takes anyway on some
  * inputs or devices, with identical results; none selects a tuning variant -- the one switch that does, VDET_VPASS_FORM,
@@ -236,6 +240,8 @@ int vdet_set_async(vdet_ctx *ctx, int enable);
  *   VDET_BINSORT_INHERIT=0  every column of the counting sort builds its own key -> bin map (what a column takes whose
  *                         predecessor's map does not fit its scores)
  *   VDET_BINSORT_GRID=n   at most n workgroups for the counting sort (1: one workgroup sorts the columns in order)
+ *   VDET_WALK_WIDE=0      the packed walk filters every list 64 candidates per pass to its end (what a list takes until a pass
+ *                         queues fewer than 12 candidates); VDET_WALK_WIDE_NSW=n (1..63) moves that switch point
  *   VDET_SMALL_LISTS=0    frames of <= 384 boxes through the large-list sort and walk
  *   VDET_DIRECT_LISTS=0   the suppression graph of regular frames of > 384 boxes through the bit matrix (what a context takes for
  *                         good once a row had more neighbours than a direct list slot holds); VDET_DIRECT_CAP=n entries per slot

@@ -1407,6 +1407,9 @@ struct WalkParams {
     int adj32;                // the adjacency pool is smaller than 4 GB (byte offsets of its lists fit 32 bits)
     const uint4 *wmeta16;     // frames of integer coordinates (kFlagU16) whose records adj_rows_kernel wrote: the same record in 16
                               // bytes {x1 | y1 << 16, x2 | y2 << 16, list offset, degree} (null: none)
+    int wide_nsw;             // the packed walk filters kWideW chunks per pass after a narrow pass that queued fewer than this many
+                              // candidates (0: never, the narrow-only walk)
+    uint32_t *wide_stats;     // [2][kWideStatSlots]: lists that went wide / wide passes that overflowed, spread over slots by list
 };
 
 // LDS words through which the lanes of one wave talk to each other (the walks' dead masks): every
@@ -1627,6 +1630,62 @@ __device__ __forceinline__ void walk_ring_drain(const WalkParams &prm, lds_mask_
     }
 }
 
+// The WIDE filter of a list's sparse tail.  Past the first few hundred candidates a chunk of 64 holds a handful of alive ones
+// (6.3 on the bench's frames, devtools/walk_filter_sim.py), so the narrow pass below -- an order load, two mask reads, a 64-lane
+// record gather, ballot and ring writes, one more step of the list's sequential chain -- runs more often than the groups it
+// feeds.  After a narrow pass that queued fewer than prm.wide_nsw candidates (wave-uniform, one-way) the list is taken kWideW chunks
+// per pass, in the same two stages that keep the records' round trip off the chain:
+//   stage 1, one pass ahead: the kWideW x 64 ids of the NEXT block are tested against the dead mask (a superset of what will be
+//            needed), the wanted ones compacted in list order (ballot + mbcnt per slice) through 64 words of LDS staging, and
+//            ONE record load is issued for the at most 64 compacted candidates;
+//   stage 2, the block's own pass: those candidates are tested again (one mask read), the alive ones queued with their records,
+//            the ring drained.
+// A block with more than 64 wanted candidates (the density rose again) is queued slice by slice instead, with a fresh test, its
+// records loaded on the spot and a drain after every slice: the narrow rule without its pipeline.  Candidates enter the ring in
+// list order on both paths, and a candidate that died between its test and its group is found dead when the group starts -- the
+// rule the narrow pass already relies on -- so the keep lists are the narrow walk's.
+#ifndef VDET_WALK_W
+#define VDET_WALK_W 4
+#endif
+constexpr int kWideW = VDET_WALK_W;            // chunks per wide pass (a constant: the slices are unrolled)
+constexpr int kWideSpan = 64 * kWideW;
+constexpr int kWideStage = 64;                 // LDS words per wave behind the ring: the compacted ids of one block
+constexpr int kWideStatSlots = 64;
+
+template <bool U16>
+__device__ __forceinline__ void walk_rec_load(const WalkMeta *__restrict__ wmeta, const uint4 *__restrict__ wm16, const uint32_t id,
+                                              uint4 &r, float4 &b, uint2 &m)
+{
+    if (U16) r = wm16[id];
+    else { const WalkMeta *wm = wmeta + id; b = wm->box; const uint4 rw = wm->row; m = make_uint2(rw.x, rw.y); }
+}
+
+// the lanes with `alive` set enter the ring behind its qn queued candidates, in lane order, with their records
+template <bool U16>
+__device__ __forceinline__ void walk_ring_push(lds_mask_t ring, lds_f4_t ringb, const int qh, int &qn, const bool alive, const int c,
+                                               const uint4 &r, const float4 &b, const uint2 &m)
+{
+    const unsigned long long am = __ballot(alive);
+    if (alive) {
+        const int s = ring_wrap(qh + qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u)));
+        ring[8 * s] = (uint32_t)c;
+        lds_f4v bv;
+        if (U16) {
+            ring[8 * s + 1] = r.z;
+            ring[8 * s + 2] = r.w;
+            bv.x = (float)(r.x & 0xFFFFu); bv.y = (float)(r.x >> 16);
+            bv.z = (float)(r.y & 0xFFFFu); bv.w = (float)(r.y >> 16);
+        } else {
+            ring[8 * s + 1] = m.x;
+            ring[8 * s + 2] = m.y;
+            bv.x = b.x; bv.y = b.y; bv.z = b.z; bv.w = b.w;
+        }
+        ringb[2 * s + 1] = bv;
+        ring[8 * s + 3] = __float_as_uint(box_area(make_float4(bv.x, bv.y, bv.z, bv.w)));
+    }
+    qn += __popcll(am);
+}
+
 // U16: the records come from wmeta16 -- ONE 16-byte load per candidate and chunk instead of two.  The walk's busiest unit is the
 // address unit of the L1 (TA_BUSY 71 % of the kernel's cycles, profiles/r06_pmc_tcp.csv), and the record prefetch -- issued for all
 // 64 lanes of every one of the 157 chunks -- is ~40 % of the bytes it generates addresses for.  The raw words stay in registers
@@ -1634,7 +1693,7 @@ __device__ __forceinline__ void walk_ring_drain(const WalkParams &prm, lds_mask_
 template <bool U16>
 __device__ __forceinline__ void walk_list_packed(const WalkParams &prm, lds_mask_t mask, const int lane, const int rb,
                                                  const uint16_t *__restrict__ order, const int ncand,
-                                                 int32_t *__restrict__ out, const int64_t cap, int &nk_out)
+                                                 int32_t *__restrict__ out, const int64_t cap, int &nk_out, int &wide_in, int &wide_ovf)
 {
     lds_mask_t ring = mask + prm.mask_words;
     lds_f4_t ringb = (lds_f4_t)ring;                              // slot s: words 8s .. 8s+3 = meta, float4 2s+1 = box
@@ -1696,17 +1755,100 @@ __device__ __forceinline__ void walk_list_packed(const WalkParams &prm, lds_mask
             ringb[2 * s + 1] = bv;                                                                                                   \
             ring[8 * s + 3] = __float_as_uint(box_area(make_float4(bv.x, bv.y, bv.z, bv.w)));                                        \
         }                                                                                                                            \
-        qn += __popcll(am);                                                                                                          \
+        nq_last = __popcll(am);                                                                                                      \
+        qn += nq_last;                                                                                                               \
         walk_ring_drain(prm, mask, ring, ringb, lane, t32, q0_ + 64 >= ncand, qh, qn, nk, out, cap);                                 \
     }
+    // (a list's first pass queues 64 candidates, more than any wide_nsw the host passes: the switch is never taken there)
+    const int nsw = prm.wide_nsw;
+    int nq_last = 0, qw = ncand;                                  // qw: where the wide filter takes over (ncand: nowhere)
     for (int q0 = 0; q0 < ncand; q0 += 192) {
         VDET_WALK_PASS(q0, 0, 1, 2)
         if (q0 + 64 >= ncand) break;
+        if (nq_last < nsw) { qw = q0 + 64; break; }
         VDET_WALK_PASS(q0 + 64, 1, 2, 0)
         if (q0 + 128 >= ncand) break;
+        if (nq_last < nsw) { qw = q0 + 128; break; }
         VDET_WALK_PASS(q0 + 128, 2, 0, 1)
+        if (q0 + 192 < ncand && nq_last < nsw) { qw = q0 + 192; break; }
     }
 #undef VDET_WALK_PASS
+    if (qw < ncand) wide_in = 1;
+    while (qw < ncand) {
+        // Two register sets taken in turn (the loop is unrolled by two; no copies at its bottom, see above): while block k is
+        // queued from set k % 2, the ids of block k + 1 (requested one pass earlier) are compacted and their records requested
+        // into set (k + 1) % 2, and the ids of block k + 2 are requested into the registers block k's ids came from.  The mask
+        // words are read for every lane (an id is a valid box whatever its position; no branch around an LDS read), all
+        // kWideW of them before the first is looked at.
+        lds_mask_t stage = ring + 8 * kPackRing;
+        int id0[kWideW], id1[kWideW];
+        int c0 = 0, c1 = 0, n0 = 0, n1 = 0;                       // compacted candidates, and how many the block wanted (wave-uniform)
+        uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
+        float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+        uint2 m0 = make_uint2(0u, 0u), m1 = m0;
+#define VDET_WIDE_IDS(QB, ID)                                                                                                        \
+        _Pragma("unroll") for (int j = 0; j < kWideW; ++j) ID[j] = (int)order[(uint32_t)min((QB) + 64 * j + lane, last)];
+        /* stage 1 (a block behind the list's end wants nothing and reads record 0, as the lanes past a block's count do) */
+#define VDET_WIDE_STAGE1(QB, ID, CC, NC, R, BX, M)                                                                                   \
+        {                                                                                                                            \
+            uint32_t mw[kWideW];                                                                                                     \
+            _Pragma("unroll") for (int j = 0; j < kWideW; ++j) mw[j] = mask[ID[j] >> 5];                                              \
+            int tot = 0;                                                                                                             \
+            _Pragma("unroll") for (int j = 0; j < kWideW; ++j) {                                                                     \
+                const bool want = ((QB) + 64 * j + lane) < ncand && !((mw[j] >> (ID[j] & 31)) & 1u);                                 \
+                const unsigned long long wm = __ballot(want);                                                                        \
+                const int at = tot + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u)); \
+                if (want && at < kWideStage) stage[at] = (uint32_t)ID[j];                                                            \
+                tot += __popcll(wm);                                                                                                 \
+            }                                                                                                                        \
+            NC = tot;                                                                                                                \
+            const uint32_t sid = stage[lane];                                                                                        \
+            CC = lane < tot ? (int)sid : 0;                                                                                          \
+            walk_rec_load<U16>(wmeta, wm16, (uint32_t)CC, R, BX, M);                                                                 \
+        }
+#define VDET_WIDE_STAGE2(QB, CC, NC, R, BX, M)                                                                                       \
+        {                                                                                                                            \
+            const uint32_t mc = mask[CC >> 5];                                                                                       \
+            const bool alive = lane < NC && !((mc >> (CC & 31)) & 1u);                                                               \
+            walk_ring_push<U16>(ring, ringb, qh, qn, alive, CC, R, BX, M);                                                           \
+            walk_ring_drain(prm, mask, ring, ringb, lane, t32, (QB) + kWideSpan >= ncand, qh, qn, nk, out, cap);                     \
+        }
+        VDET_WIDE_IDS(qw, id0)
+        VDET_WIDE_IDS(qw + kWideSpan, id1)
+        VDET_WIDE_STAGE1(qw, id0, c0, n0, r0, b0, m0)
+        // (a block that wanted more than the staging holds ends the pipelined loop: a branch with loads of its own inside the loop
+        //  would make the number of loads in flight depend on the path)
+        bool over = false;
+        for (;; qw += 2 * kWideSpan) {
+            VDET_WIDE_IDS(qw + 2 * kWideSpan, id0)
+            VDET_WIDE_STAGE1(qw + kWideSpan, id1, c1, n1, r1, b1, m1)
+            if (n0 > kWideStage) { over = true; break; }
+            VDET_WIDE_STAGE2(qw, c0, n0, r0, b0, m0)
+            if (qw + kWideSpan >= ncand) { qw = ncand; break; }
+            VDET_WIDE_IDS(qw + 3 * kWideSpan, id1)
+            VDET_WIDE_STAGE1(qw + 2 * kWideSpan, id0, c0, n0, r0, b0, m0)
+            if (n1 > kWideStage) { over = true; qw += kWideSpan; break; }
+            VDET_WIDE_STAGE2(qw + kWideSpan, c1, n1, r1, b1, m1)
+            if (qw + 2 * kWideSpan >= ncand) { qw = ncand; break; }
+        }
+#undef VDET_WIDE_IDS
+#undef VDET_WIDE_STAGE1
+#undef VDET_WIDE_STAGE2
+        if (!over) break;
+        // the block at qw slice by slice: the narrow rule without its pipeline (fresh test, records loaded on the spot, a drain per
+        // slice), then the wide filter starts again behind it
+        ++wide_ovf;
+        const int qe = min(qw + kWideSpan, ncand);
+        for (int qs = qw; qs < qe; qs += 64) {
+            const int id = (int)order[(uint32_t)min(qs + lane, last)];
+            const bool alive = (qs + lane) < ncand && !((mask[id >> 5] >> (id & 31)) & 1u);
+            uint4 rs = make_uint4(0u, 0u, 0u, 0u); float4 bs = make_float4(0.f, 0.f, 0.f, 0.f); uint2 ms = make_uint2(0u, 0u);
+            walk_rec_load<U16>(wmeta, wm16, alive ? (uint32_t)id : 0u, rs, bs, ms);
+            walk_ring_push<U16>(ring, ringb, qh, qn, alive, id, rs, bs, ms);
+            walk_ring_drain(prm, mask, ring, ringb, lane, t32, qs + 64 >= ncand, qh, qn, nk, out, cap);
+        }
+        qw = qe;
+    }
     nk_out = nk;
 }
 
@@ -1737,8 +1879,13 @@ __device__ __forceinline__ void walk_one(const WalkParams &prm, const int p, uns
     int bad = 0;
     if (regular && prm.packed && N >= 2) {     // (singleton groups have no graph: adj_build_kernel never saw them)
         // (wave-uniform) integer frames whose records exist in 16 bytes take them
-        if (prm.wmeta16 && (prm.group_flags[pr.g] & kFlagU16)) walk_list_packed<true>(prm, mask, lane, rb, order, ncand, out, cap, nk);
-        else walk_list_packed<false>(prm, mask, lane, rb, order, ncand, out, cap, nk);
+        int wide_in = 0, wide_ovf = 0;         // (wave-uniform, in registers: at most one atomic each at the end of the list)
+        if (prm.wmeta16 && (prm.group_flags[pr.g] & kFlagU16)) walk_list_packed<true>(prm, mask, lane, rb, order, ncand, out, cap, nk, wide_in, wide_ovf);
+        else walk_list_packed<false>(prm, mask, lane, rb, order, ncand, out, cap, nk, wide_in, wide_ovf);
+        if (wide_in && lane == 0) {
+            atomicAdd(prm.wide_stats + (p & (kWideStatSlots - 1)), 1u);
+            if (wide_ovf) atomicAdd(prm.wide_stats + kWideStatSlots + (p & (kWideStatSlots - 1)), (uint32_t)wide_ovf);
+        }
         if (lane == 0) prm.keep_cnt[p] = nk;
         if ((int64_t)nk > cap && lane == 0) atomicOr(prm.status, kStCap);
         return;
@@ -1804,7 +1951,8 @@ __device__ __forceinline__ void walk_one(const WalkParams &prm, const int p, uns
     if (__ballot(bad != 0) && lane == 0) atomicOr(prm.status, kStDivZero);
 }
 
-__global__ __launch_bounds__(256) void walk_kernel(const WalkParams prm)
+// (8 waves per SIMD is the walk's latency hiding: pinned, so that a register too many is a build-time spill report, not a silent wave less)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void walk_kernel(const WalkParams prm)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // (the wave index through readfirstlane: hipcc then knows that the problem, its list / frame pointers and every

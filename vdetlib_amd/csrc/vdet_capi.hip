@@ -206,6 +206,10 @@ struct vdet_ctx {
     bool last_sort_binned = false;   // the last per-(frame, class) sort went through binsort_kernel (vdet_query 9)
     StagedTab vidtab, segtab;     // batched videos, keyed by the frame offsets: {first frame, frames} per video / per frame {first, one past last} of its video
     DevBuf sortctl;               // binsort_kernel's work counter + the list of problems it handed to the LSD kernel
+    int walk_wide_nsw = 12;       // the packed walk filters its lists' sparse tails kWideW chunks per pass once a pass queued fewer
+                                  // candidates than this (VDET_WALK_WIDE=0: never; VDET_WALK_WIDE_NSW: 1..63)
+    bool last_walk_wide = false;  // the last walk could take the wide filter (vdet_query 18 / 19)
+    DevBuf walkstats;             // [2][kWideStatSlots] u32: lists that went wide / wide passes that overflowed in the last walk
     DevBuf nover;                 // vdet_det_nms_volume: candidates per list before the topk cut
     DevBuf ordncand;              // vdet_nms_volume_ordered: the caller's counts after check_order_kernel
     DevBuf linkmemo, linkstats, linkwarm, linkorder, linkchains, linknodes, tracknode, rtodo;
@@ -1136,6 +1140,14 @@ int launch_sort_walk(vdet_ctx *c, const SortWalkArgs &a, int nmax, int64_t order
     wp.t32 = c->gt32;
     wp.wmeta16 = (wp.packed && c->wmeta16_built) ? c->wmeta16.as<uint4>() : nullptr;
     wp.adj32 = c->adj.cap <= 0xFFFFFF00ull ? 1 : 0;
+    wp.wide_nsw = wp.packed ? c->walk_wide_nsw : 0;
+    if (wp.packed) wp.wave_words += kWideStage;                           // + the wide filter's staging behind the ring
+    c->last_walk_wide = wp.wide_nsw > 0;
+    if (wp.wide_nsw > 0) {
+        HIPCHK(c, c->walkstats.reserve(sizeof(uint32_t) * 2 * kWideStatSlots));
+        HIPCHK(c, hipMemsetAsync(c->walkstats.p, 0, sizeof(uint32_t) * 2 * kWideStatSlots, c->stream));
+        wp.wide_stats = c->walkstats.as<uint32_t>();
+    }
     // frames of at most 384 boxes: one LANE per list, the frames' rows in LDS (small_kernels.hpp); the lists of irregular frames
     // are left to the general walk (walk_rest_kernel: normally nothing)
     const bool small_walk = c->small_lists && a.mode != 2 && nmax <= kSmallMax && wp.group_flags && a.C > 0 && a.P % a.C == 0;
@@ -1580,6 +1592,8 @@ int vdet_create(vdet_ctx **out, int device)
     if (const char *e = getenv("VDET_DIRECT_CAP")) { const int v = atoi(e); if (v >= 8 && v <= 32760) c->direct_cap = (uint32_t)(v & ~7); }
     if (const char *e = getenv("VDET_BINSORT")) c->binsort = atoi(e) != 0;
     if (const char *e = getenv("VDET_BINSORT_INHERIT")) c->binsort_inherit = atoi(e) != 0;
+    if (const char *e = getenv("VDET_WALK_WIDE")) { if (atoi(e) == 0) c->walk_wide_nsw = 0; }
+    if (const char *e = getenv("VDET_WALK_WIDE_NSW")) { const int v = atoi(e); if (v >= 1 && v <= 63 && c->walk_wide_nsw > 0) c->walk_wide_nsw = v; }
     if (const char *e = getenv("VDET_BINSORT_GRID")) { const int v = atoi(e); if (v >= 1) c->binsort_grid = v; }
     if (const char *e = getenv("VDET_SMALL_LISTS")) c->small_lists = atoi(e) != 0;
     if (const char *e = getenv("VDET_TCN_TILED")) c->tcn_tiled = atoi(e) != 0;
@@ -1658,7 +1672,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->rowz, &c->rowmeta, &c->groupz, &c->adj, &c->comp, &c->origidx, &c->out64,
                       &c->trk_frames, &c->trk_boxes, &c->b1, &c->b2, &c->iou_out, &c->order, &c->ncand, &c->keepidx,
                       &c->keepcnt, &c->gflags, &c->pairs, &c->tkeys, &c->tstate, &c->visited, &c->heads, &c->xkeys, &c->xord, &c->xncand, &c->linkmemo, &c->linkstats, &c->linkwarm, &c->linkorder, &c->linkchains, &c->linknodes, &c->tracknode, &c->rtodo,
-                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
+                      &c->xbox, &c->xbox16, &c->xord16, &c->xcum, &c->xinfo, &c->wmeta, &c->wmeta16, &c->reachtab, &c->rowperm, &c->qreach, &c->ditems, &c->striptot, &c->stripoff, &c->sortctl, &c->walkstats, &c->segtab.dev, &c->vidtab.dev, &c->nover, &c->ordncand, &c->ev_tab, &c->ev_dtp, &c->ev_dsc,
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
                       &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad,
@@ -1735,6 +1749,15 @@ int vdet_query(vdet_ctx *c, int what)
         BinSortCtl h{};
         if (hipMemcpyAsync(&h, c->sortctl.p, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess || host_sync(c) != hipSuccess) return VDET_EHIP;
         return what == 9 ? h.nfail : what == 16 ? h.ninherit : h.nredo;
+    }
+    if (what == 18 || what == 19) {   // the last volume walk's wide filter (-1: it could not run): lists that entered it (18), wide
+        // passes that wanted more candidates than the staging holds and were queued slice by slice (19)
+        if (!c->last_walk_wide || !c->walkstats.p) return -1;
+        uint32_t h[2 * kWideStatSlots];
+        if (hipMemcpyAsync(h, c->walkstats.p, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess || host_sync(c) != hipSuccess) return VDET_EHIP;
+        unsigned long long n = 0;
+        for (int i = 0; i < kWideStatSlots; ++i) n += h[(what - 18) * kWideStatSlots + i];
+        return (int)std::min<unsigned long long>(n, 0x7FFFFFFFull);
     }
     if (what >= 4 && what <= 7) {     // link steps of the last tracking call served by the memo (4) / scanned (5); 6 / 7: the warm-up's
         unsigned int h[4] = {0, 0, 0, 0};
