@@ -133,6 +133,12 @@
  *                                                                     A video whose predecessor table ((F_v*Rp + F_v) int16,
  *                                                                     Rp = R rounded up to 64) outgrows 128 KiB of LDS keeps
  *                                                                     it in global scratch: same results
+ *   Soft-NMS of the per-frame lists        (vdet_soft_nms_tracks, vdet_soft_nms_tracks_batch) the row of vdet_nms_tracks
+ *                                          (top_still + T <= 1024, 1 <= R <= 1024, B <= 32767, C*R*F and C*T*F < 2^31 - 16, at
+ *                                          most 65535 videos), and method 0 or 1, sigma finite and >= 1/64, thresh and
+ *                                          min_score not NaN                                                     VDET_EINVAL; bad
+ *                                                                     keep data, a zero union and R below a list's count as
+ *                                                                     in vdet_nms_tracks.  One path for every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -950,6 +956,62 @@ int vdet_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, 
                           const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
                           int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
                           int32_t *d_cnt_out, int32_t *d_ntracks_out);
+
+/* ---- device Soft-NMS of the same lists: scores decayed, nothing deleted (Bodla et al., ICCV 2017) ---------------------------
+ *
+ * The reference has no such step; the rule is this file's, stated again in numpy float32 by tests/softnms_spec.py, which the
+ * device equals on bits.  ROWS: vdet_nms_tracks' rows, in its order and with its row indices (still-image rows
+ * k < min(d_keep_cnt, top_still), then tubelet rows by slot; a NaN f32 score is no row; a d_keep_cnt / d_keep_idx out of range
+ * latches VDET_EINVAL and the entry is skipped).  Every row carries a CURRENT f32 score, at first the f32 rounding of its
+ * source score.  With min32 = (float)min_score and sigma32 = (float)sigma:
+ *   1. every row whose current score is < min32 is removed (min_score = -inf removes nothing);
+ *   2. while a row is alive:
+ *      - the alive row with the largest current score is taken: -0.0 == +0.0, equal scores by DESCENDING row index -- the order
+ *        at the top of this file applied to the current scores;
+ *      - it is EMITTED as the next rank: its box, its current score bit for bit (a -0.0 stays -0.0), its src; it is no longer
+ *        alive;
+ *      - for every other alive row j: ovr as utils/nms.pyx:57-64 computes it in f32 with the emitted box as box i ('/' is the
+ *        correctly rounded division).  Every alive row is an EVALUATED pair: a zero union latches VDET_EDIVZERO (vdet_sync), as
+ *        in vdet_nms_tracks.  A NaN ovr changes nothing.  Otherwise
+ *          method 0 'linear':  iff (double)ovr >= thresh:  s_j = s_j * (1.0f - ovr)       two f32 operations
+ *          method 1 'gauss':   s_j = s_j * g(-(ovr * ovr) / sigma32)   for every pair; thresh is not used
+ *      - a score that became NaN (inf * 0) or fell below min32 removes the row.
+ * '>=' is this project's convention for every threshold; Bodla's code tests ovr > thresh, so the two differ exactly where
+ * ovr == thresh.
+ * g is an exponential written as a fixed sequence of single, correctly rounded f32 operations (csrc/softnms_kernels.hpp sn_exp,
+ * tests/softnms_spec.py g; the library is built with -ffp-contract=off): x < -87 gives +0.0; else x is rounded to a multiple
+ * of 2^-20, k = rint(x * log2 e), r = x - k * ln2_hi - k * ln2_lo, a degree-6 polynomial in r by Horner's scheme, ldexp(p, k).
+ * g(0) = 1 exactly, 0 <= g <= 1, g never increases as its argument falls (that is what the 2^-20 grid is for), and its
+ * largest relative distance from exp over [-64, 0] is 6e-7.
+ * The multiplicative rule is the published one and is meant for scores >= 0: a NEGATIVE score moves towards zero -- it RISES --
+ * when it is decayed, and an infinite one stays infinite or, times 0, becomes NaN and is removed.  Nothing here "repairs" that:
+ * mapping SVM margins into [0, 1] first is the caller's elementwise operation.
+ *
+ * Outputs: vdet_nms_tracks' rank layout.  d_tracks_out [C,R,F,5] holds the box and the DECAYED f32 score, d_score_out [C,R,F]
+ * that score widened to f64, d_score0_out [C,R,F] f64 the source's own unrounded score (what vdet_nms_tracks writes to
+ * d_score_out), d_src_out / d_cnt_out / d_ntracks_out as there, cnt = rows emitted.  More emitted rows than R latch VDET_ECAP:
+ * the count is still written, nothing past R.  NaN / INT32_MIN behind the counts.  One round per emitted row, each
+ * ceil(n / 64) f32 divisions per lane.
+ * VDET_EINVAL before any launch, with nothing written: method other than 0 / 1; sigma not finite or below 1/64 (with
+ * ovr <= 1 the argument of g then stays in [-64, 0], the range its accuracy is stated for); a NaN thresh or min_score; a NULL
+ * d_score0_out; everything vdet_nms_tracks rejects.  Inputs are never modified.  Every output element is written by the ONE
+ * launch of the call; asynchronous, no host wait, no scratch; reads and writes nothing of the context's cached graph, lists,
+ * index or link memo.  Timed under "other".
+ */
+int vdet_soft_nms_tracks(vdet_ctx *ctx, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                         const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores,
+                         int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh,
+                         int R, int method, double sigma, double min_score, float *d_tracks_out, double *d_score_out,
+                         int32_t *d_src_out, int32_t *d_cnt_out, int32_t *d_ntracks_out, double *d_score0_out);
+
+/* The same for V videos, laid out and staged as in vdet_nms_tracks_batch (d_score0_out like d_score_out); per video the bits
+ * are vdet_soft_nms_tracks' on that video alone. */
+int vdet_soft_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                               const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes,
+                               const float *d_boxes, const float *d_scores, int64_t B, const int32_t *d_keep_idx,
+                               const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R, int method, double sigma,
+                               double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out,
+                               int32_t *d_ntracks_out, double *d_score0_out);
 
 /* ---- device re-scoring of ANY tubelet set against the detections -----------------------------------------------------------
  *

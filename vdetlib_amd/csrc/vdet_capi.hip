@@ -37,6 +37,7 @@
 #include "context_kernels.hpp"
 #include "merge_kernels.hpp"
 #include "tracknms_kernels.hpp"
+#include "softnms_kernels.hpp"
 #include "rescore_kernels.hpp"
 #include "patch_kernels.hpp"
 #include "svmhead_kernels.hpp"
@@ -3883,18 +3884,18 @@ int vdet_merge_tracks(vdet_ctx *c, int scheme, int64_t F, int64_t C, int Ta, int
 // ---------------------------------------------------------------------------------------------
 // Per-frame NMS of tubelets with still-image detections (tracknms_kernels.hpp)
 // ---------------------------------------------------------------------------------------------
-int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
-                          const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
-                          const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
-                          int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
-                          int32_t *d_cnt_out, int32_t *d_ntracks_out)
+// the checks of vdet_nms_tracks[_batch] and its kernel arguments, shared with vdet_soft_nms_tracks[_batch]: nothing is launched,
+// nothing written; vs = the videos as read
+static int tracknms_args(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                         const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
+                         const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
+                         int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                         int32_t *d_cnt_out, int32_t *d_ntracks_out, Videos &vs, TrackNmsArgs &g)
 {
-    if (!c) return VDET_EINVAL;
     if (C < 1 || T < 0 || top_still < 0) return fail(c, VDET_EINVAL, "bad shape");
-    Videos vs;
     int rc = read_videos(c, h_frame_off, V, 65535, &vs);
     if (rc) return rc;
-    const int64_t F = vs.F, Fmax = vs.Fmax;
+    const int64_t F = vs.F;
     if ((int64_t)top_still + T > kTnMaxList)
         return fail(c, VDET_EINVAL, "top_still + T = %lld candidates per (frame, class); the limit is %d", (long long)top_still + T, kTnMaxList);
     if (R < 1 || R > kTnMaxList) return fail(c, VDET_EINVAL, "R = %d output rows per (frame, class); 1 .. %d", R, kTnMaxList);
@@ -3911,7 +3912,6 @@ int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, in
     if (!d_tracks_out || !d_score_out || !d_src_out || !d_cnt_out || !d_ntracks_out) return fail(c, VDET_EINVAL, "null buffer");
     HIPCHK(c, hipSetDevice(c->device));
     timing_reset(c);
-    TrackNmsArgs g{};
     if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
     g.tracks = d_tracks; g.ntracks = d_ntracks; g.score = d_score; g.tboxes = T > 0 ? reinterpret_cast<const float4 *>(d_tboxes) : nullptr;
     g.boxes = reinterpret_cast<const float4 *>(d_boxes); g.scores = d_scores; g.keep_idx = d_keep_idx; g.keep_cnt = d_keep_cnt;
@@ -3919,6 +3919,23 @@ int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, in
     g.nmax = top_still + T; g.score_f64 = score_f64 ? 1 : 0; g.t32 = thresh_to_f32(thresh);
     g.otracks = d_tracks_out; g.oscore = d_score_out; g.osrc = d_src_out; g.ocnt = d_cnt_out; g.ontracks = d_ntracks_out;
     g.status = &c->d_cnt->status;
+    return VDET_OK;
+}
+
+int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                          const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
+                          const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
+                          int top_still, double thresh, int R, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                          int32_t *d_cnt_out, int32_t *d_ntracks_out)
+{
+    if (!c) return VDET_EINVAL;
+    Videos vs;
+    TrackNmsArgs g{};
+    const int rc = tracknms_args(c, h_frame_off, V, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
+                                 d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
+                                 d_ntracks_out, vs, g);
+    if (rc) return rc;
+    const int64_t Fmax = vs.Fmax;
     // the LDS of a wave follows the call's own top_still + T; as many waves per workgroup (4, 2, 1) as 64 KiB hold
     int waves = 4;
     while (waves > 1 && (size_t)waves * g.nmax * kTnBytesPerCand > 65536) waves >>= 1;
@@ -3941,6 +3958,54 @@ int vdet_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tra
     return vdet_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B, d_keep_idx,
                                  d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
                                  d_ntracks_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Soft-NMS of the same lists (softnms_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_soft_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                               const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes,
+                               const float *d_boxes, const float *d_scores, int64_t B, const int32_t *d_keep_idx,
+                               const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R, int method, double sigma,
+                               double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out,
+                               int32_t *d_ntracks_out, double *d_score0_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (method != kSnLinear && method != kSnGauss) return fail(c, VDET_EINVAL, "method = %d; 0 (linear) or 1 (gauss)", method);
+    if (!std::isfinite(sigma) || !(sigma >= kSnSigmaMin))
+        return fail(c, VDET_EINVAL, "sigma = %g; finite and at least 1/64 (the Gaussian weight's argument stays in [-64, 0])", sigma);
+    if (thresh != thresh || min_score != min_score) return fail(c, VDET_EINVAL, "thresh and min_score must not be NaN");
+    if (!d_score0_out) return fail(c, VDET_EINVAL, "null buffer");
+    Videos vs;
+    SoftNmsArgs a{};
+    const int rc = tracknms_args(c, h_frame_off, V, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
+                                 d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
+                                 d_ntracks_out, vs, a.tn);
+    if (rc) return rc;
+    a.oscore0 = d_score0_out; a.method = method; a.sigma32 = (float)sigma; a.min32 = (float)min_score;
+    // as many waves per workgroup (4, 2, 1) as stay BELOW 64 KiB of LDS: 1 only at the limit of 1024 candidates
+    int waves = 4;
+    while (waves > 1 && (size_t)waves * a.tn.nmax * kSnBytesPerCand >= 65536) waves >>= 1;
+    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)((C * vs.Fmax + waves - 1) / waves), (unsigned)V);
+        hipLaunchKernelGGL(softnms_kernel, grid, dim3(64 * waves), (size_t)waves * a.tn.nmax * kSnBytesPerCand, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_soft_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                         const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores,
+                         int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh,
+                         int R, int method, double sigma, double min_score, float *d_tracks_out, double *d_score_out,
+                         int32_t *d_src_out, int32_t *d_cnt_out, int32_t *d_ntracks_out, double *d_score0_out)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_soft_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
+                                      d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, method, sigma, min_score, d_tracks_out,
+                                      d_score_out, d_src_out, d_cnt_out, d_ntracks_out, d_score0_out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1585,8 +1585,9 @@ def _tn_still(still, Ft, C, T, top_still):
     return (boxes, scores, keep_idx, keep_cnt), B, kcap, top_still
 
 
-def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync):
-    """Allocate the outputs (flat, batch layout) and enqueue the one launch; every tensor contiguous and on one device."""
+def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync, soft=None):
+    """Allocate the outputs (flat, batch layout) and enqueue the one launch; every tensor contiguous and on one device.
+    ``soft`` = (method code, sigma, min_score): soft_nms_tracks' launch, which returns the source scores as a sixth tensor."""
     V, Ft = len(off) - 1, int(off[-1])
     dev = ntracks.device
     N = C * R * Ft
@@ -1600,13 +1601,19 @@ def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top
     tail = (C, T, ptr(tracks), ntracks.data_ptr(), ptr(score), int(score.dtype == torch.float64), ptr(tboxes), sp[0], sp[1], B, sp[2],
             sp[3], kcap, top_still if still is not None else 0, float(thresh), R, otracks.data_ptr(), oscore.data_ptr(),
             osrc.data_ptr(), ocnt.data_ptr(), ont.data_ptr())
+    one, many = (ctx.lib.vdet_nms_tracks, ctx.lib.vdet_nms_tracks_batch)
+    oscore0 = None
+    if soft is not None:
+        oscore0 = torch.empty((N,), dtype=torch.float64, device=dev)
+        tail = tail[:16] + (int(soft[0]), float(soft[1]), float(soft[2])) + tail[16:] + (oscore0.data_ptr(),)
+        one, many = (ctx.lib.vdet_soft_nms_tracks, ctx.lib.vdet_soft_nms_tracks_batch)
     if V == 1:
-        ctx.check(ctx.lib.vdet_nms_tracks(ctx.h, Ft, *tail))
+        ctx.check(one(ctx.h, Ft, *tail))
     else:
-        ctx.check(ctx.lib.vdet_nms_tracks_batch(ctx.h, off.ctypes.data, V, *tail))
+        ctx.check(many(ctx.h, off.ctypes.data, V, *tail))
     if sync:
         ctx.sync()
-    return otracks, oscore, osrc, ocnt, ont
+    return (otracks, oscore, osrc, ocnt, ont) if soft is None else (otracks, oscore, osrc, ocnt, ont, oscore0)
 
 
 def _tn_limits(C, T, Ft, top_still, cap):
@@ -1620,26 +1627,9 @@ def _tn_limits(C, T, Ft, top_still, cap):
     return R
 
 
-def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None, sync=True, ctx=None):
-    """Per-frame NMS of tubelet boxes together with still-image detections (``apply_vid_nms`` / ``vid_nms``, utils/nms.pyx:71-125,
-    as arrays): one list of detections per frame and class, one launch, no host wait.
-
-    tracks [C,T,F,5] f32, ntracks [C] int32, score [C,T,F] f32 / f64 (``pooled``, ``det``, a TCN output: the series that scores
-    the tubelet boxes), tboxes [C,T,F,4] f32 (the boxes to use instead of the track rows).  A ``merge_tracks`` /
-    ``interpolate_tracks`` dict goes in as ``tracks`` (then ``ntracks`` stays None, ``score`` is the index of the series,
-    default 0, or a tensor; the dict's tboxes are used unless ``tboxes`` is given).  ``still`` = (boxes [F,B,4] f32, scores
-    [F,B,C] f32, keep_idx [F,C,k] int32, keep_cnt [F,C] int32): NMS survivors as ``DetEvaluator.add_keep_lists`` takes them
-    ('FBC'); the first ``top_still`` of every list take part (default min(k, 1024 - T)).  T = 0 is the still-image source alone.
-    The rows of a list are the still-image rows, then the tubelet rows by slot; a NaN score is no row.  Result: nms of the
-    reference (f32, +1 areas, suppression iff ovr >= thresh, descending score, ties by descending row) -- semantics in full:
-    include/vdet_hip.h (vdet_nms_tracks).  ``cap``: output rows per list (default top_still + T, which cannot overflow; fewer
-    than a list keeps raises ValueError at the wait).  An evaluated zero-union pair raises ZeroDivisionError, a keep count or
-    index out of range ValueError, when the call -- or with ``sync=False`` a later ``ctx.sync()`` -- waits.
-
-    Returns a dict in the tubelet layout with the RANK as the slot axis: ``tracks`` [C,R,F,5] f32 (x1,y1,x2,y2,f32 score),
-    ``score`` [C,R,F] f64 (the source's own score), ``src`` [C,R,F] int32 (b >= 0: still-image box b; -(t+1): tubelet slot t;
-    INT32_MIN behind the count), ``cnt`` [C,F] int32, ``ntracks`` [C] int32 -- NaN behind the counts.  ``tracks`` / ``ntracks`` /
-    ``score`` feed every consumer of tubelets; ``DetEvaluator.add_detections`` takes the dict."""
+def _tn_tubelets(tracks, ntracks, score, tboxes):
+    """The tubelet source of nms_tracks / soft_nms_tracks, checked -- tensors, or a ``merge_tracks`` / ``interpolate_tracks`` dict
+    as ``tracks``: (tracks, ntracks, score, tboxes, C, T, F)."""
     if isinstance(tracks, dict):
         d = tracks
         if ntracks is not None or any(k not in d for k in ('tracks', 'ntracks')):
@@ -1663,6 +1653,30 @@ def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh
         raise ValueError("score must be float32 / float64 [C,T,F]")
     if tboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float32 or tuple(tboxes.shape) != (C, T, F, 4)):
         raise ValueError("tboxes must be float32 [C,T,F,4]")
+    return tracks, ntracks, score, tboxes, C, T, F
+
+
+def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None, sync=True, ctx=None):
+    """Per-frame NMS of tubelet boxes together with still-image detections (``apply_vid_nms`` / ``vid_nms``, utils/nms.pyx:71-125,
+    as arrays): one list of detections per frame and class, one launch, no host wait.
+
+    tracks [C,T,F,5] f32, ntracks [C] int32, score [C,T,F] f32 / f64 (``pooled``, ``det``, a TCN output: the series that scores
+    the tubelet boxes), tboxes [C,T,F,4] f32 (the boxes to use instead of the track rows).  A ``merge_tracks`` /
+    ``interpolate_tracks`` dict goes in as ``tracks`` (then ``ntracks`` stays None, ``score`` is the index of the series,
+    default 0, or a tensor; the dict's tboxes are used unless ``tboxes`` is given).  ``still`` = (boxes [F,B,4] f32, scores
+    [F,B,C] f32, keep_idx [F,C,k] int32, keep_cnt [F,C] int32): NMS survivors as ``DetEvaluator.add_keep_lists`` takes them
+    ('FBC'); the first ``top_still`` of every list take part (default min(k, 1024 - T)).  T = 0 is the still-image source alone.
+    The rows of a list are the still-image rows, then the tubelet rows by slot; a NaN score is no row.  Result: nms of the
+    reference (f32, +1 areas, suppression iff ovr >= thresh, descending score, ties by descending row) -- semantics in full:
+    include/vdet_hip.h (vdet_nms_tracks).  ``cap``: output rows per list (default top_still + T, which cannot overflow; fewer
+    than a list keeps raises ValueError at the wait).  An evaluated zero-union pair raises ZeroDivisionError, a keep count or
+    index out of range ValueError, when the call -- or with ``sync=False`` a later ``ctx.sync()`` -- waits.
+
+    Returns a dict in the tubelet layout with the RANK as the slot axis: ``tracks`` [C,R,F,5] f32 (x1,y1,x2,y2,f32 score),
+    ``score`` [C,R,F] f64 (the source's own score), ``src`` [C,R,F] int32 (b >= 0: still-image box b; -(t+1): tubelet slot t;
+    INT32_MIN behind the count), ``cnt`` [C,F] int32, ``ntracks`` [C] int32 -- NaN behind the counts.  ``tracks`` / ``ntracks`` /
+    ``score`` feed every consumer of tubelets; ``DetEvaluator.add_detections`` takes the dict."""
+    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
     still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
     R = _tn_limits(C, T, F, top_still, cap)
     _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
@@ -1699,6 +1713,92 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
     views = lambda flat, per: _batch_views(flat, off, C, R, per)
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
+
+
+_SN_METHODS = ('linear', 'gauss')       # include/vdet_hip.h: vdet_soft_nms_tracks
+_SN_SIGMA_MIN = 1.0 / 64
+
+
+def _sn_settings(method, thresh, sigma, min_score):
+    """The scalar arguments of soft_nms_tracks, checked against the limits of include/vdet_hip.h: (method code, sigma, min_score)."""
+    if method not in _SN_METHODS:
+        raise ValueError("method must be 'linear' or 'gauss'")
+    try:
+        thresh, sigma, min_score = float(thresh), float(sigma), float(min_score)
+    except (TypeError, ValueError):
+        raise ValueError("thresh, sigma and min_score must be numbers")
+    if not math.isfinite(sigma) or sigma < _SN_SIGMA_MIN:
+        raise ValueError("sigma = %r; finite and at least 1/64" % sigma)
+    if math.isnan(thresh) or math.isnan(min_score):
+        raise ValueError("thresh and min_score must not be NaN")
+    return _SN_METHODS.index(method), sigma, min_score
+
+
+def soft_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, method='linear', thresh=0.3, sigma=0.5,
+                    min_score=0.001, top_still=None, cap=None, sync=True, ctx=None):
+    """Soft-NMS (Bodla et al., ICCV 2017) of the per-frame detection lists ``nms_tracks`` builds: a row that overlaps a better
+    one keeps its place in the list with a DECAYED score instead of being deleted.  One launch, no host wait.  The reference
+    library has no function for it; the rule in full: include/vdet_hip.h (vdet_soft_nms_tracks); tests/softnms_spec.py states it
+    in numpy float32 and the device matches it on bits.
+
+    Every argument up to ``still``, ``top_still`` and ``cap`` as in ``nms_tracks`` (a ``merge_tracks`` / ``interpolate_tracks``
+    dict goes in as ``tracks``); the rows of a list and their order are its rows.  Rows below ``min_score`` are removed; then,
+    round after round, the alive row with the largest current f32 score (ties by descending row) is emitted and every other
+    alive row j is decayed by its overlap ovr with it: ``'linear'`` s_j *= 1 - ovr iff ovr >= ``thresh`` (the project's ``>=``;
+    the paper's code tests ``>``), ``'gauss'`` s_j *= exp(-ovr^2 / ``sigma``) for every pair (``thresh`` unused; ``sigma`` >=
+    1/64).  A score that falls below ``min_score`` (or becomes NaN) removes the row; ``min_score=-inf`` keeps every row.  The
+    rule is multiplicative and meant for scores >= 0: a negative score RISES towards zero when decayed -- map margins into
+    [0, 1] first where that matters.
+
+    The defaults -- ``method='linear'``, ``thresh=0.3``, ``sigma=0.5``, ``min_score=0.001`` -- are recalled from the paper's
+    public code and could not be checked here.
+
+    Returns a dict in ``nms_tracks``' rank layout: ``tracks`` [C,R,F,5] f32 (box, decayed f32 score), ``score`` [C,R,F] f64 (the
+    decayed score widened), ``score0`` [C,R,F] f64 (the source's own unrounded score: what ``nms_tracks`` calls ``score``),
+    ``src`` [C,R,F] int32, ``cnt`` [C,F] int32 (rows emitted), ``ntracks`` [C] int32 -- NaN / INT32_MIN behind the counts.
+    ``DetEvaluator.add_detections`` takes the dict; ``seq_nms`` / ``top_anchors`` / ``nms_tracks`` take its tracks / ntracks /
+    score.  ``cap`` below a list's count raises ValueError at the wait (the counts are written), an evaluated zero-union pair
+    ZeroDivisionError, a keep count or index out of range ValueError."""
+    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
+    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
+    R = _tn_limits(C, T, F, top_still, cap)
+    soft = _sn_settings(method, thresh, sigma, min_score)
+    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
+    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
+    tboxes = None if tboxes is None else tboxes.contiguous()
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont, os0 = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still, B,
+                                             kcap, top_still, thresh, R, sync, soft)
+    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), score0=os0.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt,
+                ntracks=ont.view(C))
+
+
+def soft_nms_tracks_batch(batch_out, score='pooled', still=None, method='linear', thresh=0.3, sigma=0.5, min_score=0.001,
+                          top_still=None, cap=None, use_tboxes=True, sync=True, ctx=None):
+    """``soft_nms_tracks`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in ONE launch; the inputs as in
+    ``nms_tracks_batch``.  Per video the bits are ``soft_nms_tracks``' on that video alone.  Returns ``tracks`` / ``score`` /
+    ``score0`` / ``src`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot], ``ntracks`` [V,C]
+    and ``frame_off``."""
+    b = _batch_read(batch_out)
+    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
+    sv = batch_out.get(score) if isinstance(score, str) else None
+    if not sv:
+        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
+    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
+    bv = batch_out.get('tboxes') if use_tboxes else None
+    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
+    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
+    R = _tn_limits(C, T, Ft, top_still, cap)
+    soft = _sn_settings(method, thresh, sigma, min_score)
+    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont, os0 = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync,
+                                             soft)
+    views = lambda flat, per: _batch_views(flat, off, C, R, per)
+    return dict(tracks=views(ot, 5), score=views(osc, 1), score0=views(os0, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont,
+                frame_off=off)
 
 
 _SQ_MAX_R, _SQ_MAX_SEQS = 256, 4096     # include/vdet_hip.h: vdet_seq_nms
