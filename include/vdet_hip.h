@@ -139,6 +139,10 @@
  *                                          min_score not NaN                                                     VDET_EINVAL; bad
  *                                                                     keep data, a zero union and R below a list's count as
  *                                                                     in vdet_nms_tracks.  One path for every size
+ *   Box voting on the per-frame lists      (vdet_vote_nms_tracks, vdet_vote_nms_tracks_batch) the row of vdet_nms_tracks, and
+ *                                          weights 0 or 1, vote_thresh not NaN                                   VDET_EINVAL; bad
+ *                                                                     keep data, a zero union OF THE NMS and R below a list's
+ *                                                                     count as in vdet_nms_tracks.  One path for every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1012,6 +1016,56 @@ int vdet_soft_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_
                                const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R, int method, double sigma,
                                double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out,
                                int32_t *d_ntracks_out, double *d_score0_out);
+
+/* ---- device box voting on the same lists: NMS survivors take their neighbours' boxes (Gidaris & Komodakis, ICCV 2015) --------
+ *
+ * The reference has no such step; the rule is this file's, stated again in numpy by tests/votenms_spec.py, which the device
+ * equals on bits.
+ *   1. KEPT ROWS.  The list's rows, row indices, order, kept rows, ranks, score, src, cnt, ntracks and status flags are exactly
+ *      vdet_nms_tracks' at thresh -- the VDET_EDIVZERO of a zero-union pair the hard NMS evaluates and the VDET_EINVAL of bad
+ *      keep data included.
+ *   2. VOTERS of the kept row i: i itself (no test), and every other PRESENT row j of the list -- not absent; suppressed rows
+ *      and other kept rows are included -- that passes the overlap test: with ovr and uni computed exactly as
+ *      utils/nms.pyx:57-64 computes them in f32 with i as box i, j votes iff uni != 0 and (double)ovr >= vote_thresh (the
+ *      threshold goes through the same rounding-up to f32 as thresh).  A NaN ovr or a zero union is no voter and latches
+ *      NOTHING: these are pairs the reference never evaluates.
+ *   3. WEIGHTS.  weights 0 'score': w_j = (double)s32_j if s32_j > 0, else 0.0, s32 = the f32 score the NMS orders by.
+ *      weights 1 'uniform': w_j = 1.0.
+ *   4. SUMS.  sw and the four sx_k in float64, sequentially over the voters in ASCENDING row index, from 0.0; each step is
+ *      sw += w_j; sx_k += w_j * (double)box_j[k] -- one correctly rounded multiply and one correctly rounded add (the library
+ *      is built with -ffp-contract=off).
+ *   5. RESULT.  If sw > 0 and all four sx_k / sw (correctly rounded f64 divisions) are finite, the row's box is
+ *      (float)(sx_k / sw); otherwise the row keeps its own box.
+ * A score <= 0 (or -0.0) makes a voter weigh nothing under 'score' -- its vote is still counted -- and a list of such rows keeps
+ * its own boxes; an infinite score makes the quotient inf / inf and the row keeps its own box.  Nothing here "repairs" that:
+ * mapping SVM margins into [0, 1] first is the caller's elementwise operation, as for vdet_soft_nms_tracks.
+ * With vote_thresh > 1 no row but i votes, w * x is exact in float64, (w * x) / w == x, and every output vdet_nms_tracks also
+ * has equals it bit for bit.  With thresh > 1 every row is kept and votes is a symmetric neighbourhood count.
+ *
+ * Outputs: vdet_nms_tracks' rank layout.  d_tracks_out [C,R,F,5] holds the VOTED box and the row's own f32 score, d_score_out
+ * / d_src_out / d_cnt_out / d_ntracks_out as there; d_box0_out [C,R,F,4] f32 the row's own box (NaN behind the count),
+ * d_votes_out [C,R,F] int32 the number of voters, the row itself included (0 behind the count).  More kept rows than R latch
+ * VDET_ECAP: the count is still written, nothing past R.
+ * VDET_EINVAL before any launch, with nothing written: weights other than 0 / 1; a NaN vote_thresh; a NULL d_box0_out or
+ * d_votes_out; everything vdet_nms_tracks rejects.  Inputs are never modified.  Every output element is written by the ONE
+ * launch of the call; asynchronous, no host wait, no scratch; reads and writes nothing of the context's cached graph, lists,
+ * index or link memo.  One lane per kept row walks the list: ceil(min(cnt, R) / 64) * n pair tests per lane on top of the
+ * selection's.  Timed under "other".
+ */
+int vdet_vote_nms_tracks(vdet_ctx *ctx, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                         const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores,
+                         int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh,
+                         int R, double vote_thresh, int weights, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                         int32_t *d_cnt_out, int32_t *d_ntracks_out, float *d_box0_out, int32_t *d_votes_out);
+
+/* The same for V videos, laid out and staged as in vdet_nms_tracks_batch (d_box0_out like d_tracks_out with 4 floats a row,
+ * d_votes_out like d_src_out); per video the bits are vdet_vote_nms_tracks' on that video alone. */
+int vdet_vote_nms_tracks_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                               const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes,
+                               const float *d_boxes, const float *d_scores, int64_t B, const int32_t *d_keep_idx,
+                               const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R, double vote_thresh,
+                               int weights, float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out,
+                               int32_t *d_ntracks_out, float *d_box0_out, int32_t *d_votes_out);
 
 /* ---- device re-scoring of ANY tubelet set against the detections -----------------------------------------------------------
  *

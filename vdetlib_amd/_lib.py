@@ -97,6 +97,10 @@ SYMBOLS = {
                                    _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_soft_nms_tracks_batch": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _ci, _f64,
                                          _ci, _ci, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vdet_vote_nms_tracks": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _ci, _f64, _ci, _f64,
+                                   _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vdet_vote_nms_tracks_batch": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _ci, _f64,
+                                         _ci, _f64, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_rescore_tubelets": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp, _vp, _vp]),
     "vdet_rescore_tubelets_batch": (_ci, [_vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp, _vp,
                                           _vp]),

@@ -38,6 +38,7 @@
 #include "merge_kernels.hpp"
 #include "tracknms_kernels.hpp"
 #include "softnms_kernels.hpp"
+#include "votenms_kernels.hpp"
 #include "rescore_kernels.hpp"
 #include "patch_kernels.hpp"
 #include "svmhead_kernels.hpp"
@@ -3884,8 +3885,8 @@ int vdet_merge_tracks(vdet_ctx *c, int scheme, int64_t F, int64_t C, int Ta, int
 // ---------------------------------------------------------------------------------------------
 // Per-frame NMS of tubelets with still-image detections (tracknms_kernels.hpp)
 // ---------------------------------------------------------------------------------------------
-// the checks of vdet_nms_tracks[_batch] and its kernel arguments, shared with vdet_soft_nms_tracks[_batch]: nothing is launched,
-// nothing written; vs = the videos as read
+// the checks of vdet_nms_tracks[_batch] and its kernel arguments, shared with vdet_soft_nms_tracks[_batch] and
+// vdet_vote_nms_tracks[_batch]: nothing is launched, nothing written; vs = the videos as read
 static int tracknms_args(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
                          const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
                          const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
@@ -4006,6 +4007,52 @@ int vdet_soft_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *
     return vdet_soft_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
                                       d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, method, sigma, min_score, d_tracks_out,
                                       d_score_out, d_src_out, d_cnt_out, d_ntracks_out, d_score0_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Box voting on the same lists (votenms_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_vote_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                               const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes,
+                               const float *d_boxes, const float *d_scores, int64_t B, const int32_t *d_keep_idx,
+                               const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh, int R, double vote_thresh,
+                               int weights, float *d_tracks_out, double *d_score_out, int32_t *d_src_out, int32_t *d_cnt_out,
+                               int32_t *d_ntracks_out, float *d_box0_out, int32_t *d_votes_out)
+{
+    if (!c) return VDET_EINVAL;
+    if (weights != kVnScore && weights != kVnUniform) return fail(c, VDET_EINVAL, "weights = %d; 0 (score) or 1 (uniform)", weights);
+    if (vote_thresh != vote_thresh) return fail(c, VDET_EINVAL, "vote_thresh must not be NaN");
+    if (!d_box0_out || !d_votes_out) return fail(c, VDET_EINVAL, "null buffer");
+    Videos vs;
+    VoteNmsArgs a{};
+    const int rc = tracknms_args(c, h_frame_off, V, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
+                                 d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
+                                 d_ntracks_out, vs, a.tn);
+    if (rc) return rc;
+    a.obox0 = d_box0_out; a.ovotes = d_votes_out; a.weights = weights; a.v32 = thresh_to_f32(vote_thresh);
+    // as many waves per workgroup (4, 2, 1) as stay BELOW 64 KiB of LDS: 1 only at the limit of 1024 candidates
+    int waves = 4;
+    while (waves > 1 && (size_t)waves * a.tn.nmax * kVnBytesPerCand >= 65536) waves >>= 1;
+    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)((C * vs.Fmax + waves - 1) / waves), (unsigned)V);
+        hipLaunchKernelGGL(votenms_kernel, grid, dim3(64 * waves), (size_t)waves * a.tn.nmax * kVnBytesPerCand, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_vote_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                         const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes, const float *d_scores,
+                         int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap, int top_still, double thresh,
+                         int R, double vote_thresh, int weights, float *d_tracks_out, double *d_score_out, int32_t *d_src_out,
+                         int32_t *d_cnt_out, int32_t *d_ntracks_out, float *d_box0_out, int32_t *d_votes_out)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_vote_nms_tracks_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_score, score_f64, d_tboxes, d_boxes, d_scores, B,
+                                      d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, vote_thresh, weights, d_tracks_out,
+                                      d_score_out, d_src_out, d_cnt_out, d_ntracks_out, d_box0_out, d_votes_out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1585,9 +1585,11 @@ def _tn_still(still, Ft, C, T, top_still):
     return (boxes, scores, keep_idx, keep_cnt), B, kcap, top_still
 
 
-def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync, soft=None):
+def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync, soft=None, vote=None):
     """Allocate the outputs (flat, batch layout) and enqueue the one launch; every tensor contiguous and on one device.
-    ``soft`` = (method code, sigma, min_score): soft_nms_tracks' launch, which returns the source scores as a sixth tensor."""
+    ``soft`` = (method code, sigma, min_score): soft_nms_tracks' launch, which returns the source scores as a sixth tensor.
+    ``vote`` = (vote_thresh, weights code): vote_nms_tracks' launch, which returns the own boxes and the vote counts as a sixth
+    and a seventh."""
     V, Ft = len(off) - 1, int(off[-1])
     dev = ntracks.device
     N = C * R * Ft
@@ -1607,13 +1609,18 @@ def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top
         oscore0 = torch.empty((N,), dtype=torch.float64, device=dev)
         tail = tail[:16] + (int(soft[0]), float(soft[1]), float(soft[2])) + tail[16:] + (oscore0.data_ptr(),)
         one, many = (ctx.lib.vdet_soft_nms_tracks, ctx.lib.vdet_soft_nms_tracks_batch)
+    extra = () if soft is None else (oscore0,)
+    if vote is not None:
+        extra = (torch.empty((N * 4,), dtype=torch.float32, device=dev), torch.empty((N,), dtype=torch.int32, device=dev))
+        tail = tail[:16] + (float(vote[0]), int(vote[1])) + tail[16:] + tuple(x.data_ptr() for x in extra)
+        one, many = (ctx.lib.vdet_vote_nms_tracks, ctx.lib.vdet_vote_nms_tracks_batch)
     if V == 1:
         ctx.check(one(ctx.h, Ft, *tail))
     else:
         ctx.check(many(ctx.h, off.ctypes.data, V, *tail))
     if sync:
         ctx.sync()
-    return (otracks, oscore, osrc, ocnt, ont) if soft is None else (otracks, oscore, osrc, ocnt, ont, oscore0)
+    return (otracks, oscore, osrc, ocnt, ont) + extra
 
 
 def _tn_limits(C, T, Ft, top_still, cap):
@@ -1799,6 +1806,86 @@ def soft_nms_tracks_batch(batch_out, score='pooled', still=None, method='linear'
     views = lambda flat, per: _batch_views(flat, off, C, R, per)
     return dict(tracks=views(ot, 5), score=views(osc, 1), score0=views(os0, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont,
                 frame_off=off)
+
+
+_VN_WEIGHTS = ('score', 'uniform')      # include/vdet_hip.h: vdet_vote_nms_tracks
+
+
+def _vn_settings(vote_thresh, weights):
+    """The scalar arguments of vote_nms_tracks, checked against the limits of include/vdet_hip.h: (vote_thresh, weights code)."""
+    if weights not in _VN_WEIGHTS:
+        raise ValueError("weights must be 'score' or 'uniform'")
+    try:
+        vote_thresh = float(vote_thresh)
+    except (TypeError, ValueError):
+        raise ValueError("vote_thresh must be a number")
+    if math.isnan(vote_thresh):
+        raise ValueError("vote_thresh must not be NaN")
+    return vote_thresh, _VN_WEIGHTS.index(weights)
+
+
+def vote_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None,
+                    vote_thresh=0.5, weights='score', sync=True, ctx=None):
+    """Bounding-box voting (Gidaris & Komodakis, ICCV 2015) on the per-frame detection lists ``nms_tracks`` builds: the hard NMS
+    at ``thresh`` decides which rows are kept, their order and their scores -- exactly ``nms_tracks``' -- and every kept row's
+    BOX becomes the weighted mean of the boxes of the list's rows that overlap it, the suppressed ones included.  One launch,
+    no host wait.  The reference library has no function for it; the rule in full: include/vdet_hip.h (vdet_vote_nms_tracks);
+    tests/votenms_spec.py states it in numpy and the device matches it on bits.
+
+    Every argument up to ``cap`` as in ``nms_tracks`` (a ``merge_tracks`` / ``interpolate_tracks`` dict goes in as ``tracks``).
+    The voters of a kept row are the row itself and every other present row whose overlap with it (the reference's f32 ovr,
+    the kept row as box i) is >= ``vote_thresh``; a zero union or a NaN overlap is no voter and raises nothing.  ``weights``:
+    ``'score'`` weighs a voter by its f32 score where that is > 0 and by nothing otherwise, ``'uniform'`` by 1.  The sums run
+    in float64 over the voters in ascending row index; a row whose weights sum to 0, or whose mean is not finite, keeps its own
+    box.  A score <= 0 therefore moves nothing under ``'score'`` -- map margins into [0, 1] first where that matters.
+    ``vote_thresh`` above 1 leaves every box as it is: the result then equals ``nms_tracks``' on bits.
+
+    Returns ``nms_tracks``' dict -- ``tracks`` [C,R,F,5] f32 now with the VOTED box beside the row's own f32 score, ``score``,
+    ``src``, ``cnt``, ``ntracks`` unchanged -- plus ``box0`` [C,R,F,4] f32 (the row's own box, NaN behind the count) and
+    ``votes`` [C,R,F] int32 (voters, the row itself included; 0 behind the count).  ``DetEvaluator.add_detections`` takes the
+    dict; ``seq_nms`` / ``soft_nms_tracks`` / ``top_anchors`` / ``nms_tracks`` take its tracks / ntracks / score.  The errors at
+    the wait are ``nms_tracks``': ``cap`` below a list's count, a zero-union pair the NMS evaluates, bad keep data."""
+    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
+    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
+    R = _tn_limits(C, T, F, top_still, cap)
+    vote = _vn_settings(vote_thresh, weights)
+    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
+    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
+    tboxes = None if tboxes is None else tboxes.contiguous()
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont, ob0, ov = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still,
+                                                 B, kcap, top_still, thresh, R, sync, vote=vote)
+    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt, ntracks=ont.view(C),
+                box0=ob0.view(C, R, F, 4), votes=ov.view(C, R, F))
+
+
+def vote_nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_still=None, cap=None, vote_thresh=0.5,
+                          weights='score', use_tboxes=True, sync=True, ctx=None):
+    """``vote_nms_tracks`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in ONE launch; the inputs as in
+    ``nms_tracks_batch``.  Per video the bits are ``vote_nms_tracks``' on that video alone.  Returns ``tracks`` / ``score`` /
+    ``src`` / ``box0`` / ``votes`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot],
+    ``ntracks`` [V,C] and ``frame_off``: a dict in ``video_batch``'s layout again, which ``DetEvaluator.add_detections``,
+    ``seq_nms_batch``, ``soft_nms_tracks_batch`` (``score='score'``), ``nms_tracks_batch`` and ``top_anchors`` take as it is."""
+    b = _batch_read(batch_out)
+    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
+    sv = batch_out.get(score) if isinstance(score, str) else None
+    if not sv:
+        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
+    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
+    bv = batch_out.get('tboxes') if use_tboxes else None
+    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
+    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
+    R = _tn_limits(C, T, Ft, top_still, cap)
+    vote = _vn_settings(vote_thresh, weights)
+    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    ot, osc, osrc, ocnt, ont, ob0, ov = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R,
+                                                 sync, vote=vote)
+    views = lambda flat, per: _batch_views(flat, off, C, R, per)
+    return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), box0=views(ob0, 4), votes=views(ov, 1), cnt=ocnt,
+                ntracks=ont, frame_off=off)
 
 
 _SQ_MAX_R, _SQ_MAX_SEQS = 256, 4096     # include/vdet_hip.h: vdet_seq_nms
