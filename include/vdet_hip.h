@@ -143,6 +143,14 @@
  *                                          weights 0 or 1, vote_thresh not NaN                                   VDET_EINVAL; bad
  *                                                                     keep data, a zero union OF THE NMS and R below a list's
  *                                                                     count as in vdet_nms_tracks.  One path for every size
+ *   NMS over whole tubelets: slots         (vdet_nms_tubelets, vdet_nms_tubelets_batch) 1 <= T <= 256 tubelet slots per class
+ *                                          (the bit rows and the order of a class live in one wave's LDS), C*T*F < 2^31 - 16,
+ *                                          at most 65535 videos, 0 .. 4 series                                  VDET_EINVAL
+ *   NMS over whole tubelets: settings      thresh not NaN, min_shared >= 1, norm 0 .. 2 (union, shared, min), score_mode 0 .. 2
+ *                                          (a score per slot [C,T], mean or max of a series [C,T,F])             VDET_EINVAL.
+ *                                                                     Nothing is an error on the device: a box that gives no
+ *                                                                     finite positive quotient contributes 0.  One path for
+ *                                                                     every size
  */
 #ifndef VDET_HIP_H
 #define VDET_HIP_H
@@ -1541,6 +1549,77 @@ int vdet_seq_nms_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int
                        int rescore, int max_seqs, double min_score, float *d_tracks_out, double *d_score_out, int32_t *d_seq_out,
                        int32_t *d_ntracks_out, int32_t *d_nseq, double *d_seq_sum, int32_t *d_seq_len, int32_t *d_seq_end,
                        uint8_t *d_exhausted);
+
+/* ---- NMS over whole tubelets by spatio-temporal overlap (tube NMS of the tubelet detectors; no counterpart in the reference) ---
+ *
+ * Drops the tubelets of a class that repeat a better-scored tubelet of the same class, judged over their whole extent -- the
+ * stage behind tracking (vdet_track_from_anchors, vdet_track_pixels) or vdet_merge_tracks and in front of the scorers.  The rule
+ * is the project's own; it is stated once more in numpy (tests/tubenms_spec.py) and the device equals that statement on bits.
+ *
+ * Inputs, per video and class c: d_tracks [C,T,F,5] f32, d_ntracks [C] i32 (clamped to 0..T), optionally d_tboxes [C,T,F,4] f32
+ * (when given they are the boxes), optionally d_anchors [C,T,3] f32 and n_series (0..4) series [C,T,F] f64 whose DEVICE pointers
+ * sit in the host array h_series.  A box exists at (c,t,f) iff t < d_ntracks[c] and d_tracks[c,t,f,0] is not NaN -- the rule of
+ * every other stage; slots at or behind d_ntracks[c] are never read.  Inputs are never modified.
+ *
+ * 1. Tubelet score ts[t] (f64).  score_mode VDET_TUBE_SCORE_SLOT: d_score is [C,T] (f32, or f64 with score_f64), the value as
+ *    given, widened.  VDET_TUBE_SCORE_MEAN: d_score is [C,T,F]; ts = the f64 sum divided by the count, the sum running in
+ *    ASCENDING frame order from 0.0 over the frames where the box exists and the value is not NaN.  VDET_TUBE_SCORE_MAX: the
+ *    maximum over the same frames (between -0.0 and +0.0 it is +0.0, whatever the order).  No such frame: ts = NaN.  A tubelet
+ *    with no box, or with a NaN ts, is ABSENT: it is not kept, suppresses nothing and cannot be suppressed.
+ * 2. Frame overlap.  For tubelets a <= b (slot numbers) and a frame where both have a box: q = the f32 overlap of the
+ *    conventions at the top of this file with a as box i (+1 areas, max / min as "x >= y ? x : y", inter / (area_a + area_b -
+ *    inter)).  Iff q > 0 and q <= FLT_MAX the frame contributes k = (uint32) rint(q * 2^24): the product in f32 (an exact
+ *    scaling), rounded to nearest even, saturated at 2^32 - 1.  A NaN, zero, negative or infinite quotient contributes 0 and
+ *    latches nothing: there is no VDET_EDIVZERO here, no reference behaviour asks for one.
+ * 3. Pair sums, all integers: S[a,b] = the sum of k over the shared frames (uint64), I[a,b] = the number of shared frames,
+ *    n[t] = the number of frames with a box.  The sum is an integer ON PURPOSE: it does not depend on the order of the frames,
+ *    so the kernels may split them over lanes, waves and workgroups however they like -- and there are no float atomics on any
+ *    result path.
+ * 4. Tube overlap.  den = n[a] + n[b] - I (VDET_TUBE_NORM_UNION: the mean IoU over the temporal union, the usual spatio-temporal
+ *    IoU), I (VDET_TUBE_NORM_SHARED), or min(n[a], n[b]) (VDET_TUBE_NORM_MIN: a short tubelet inside a long one overlaps fully).
+ *    ovr = 0.0 if den == 0 or I < min_shared, else (double)S / ((double)den * 16777216.0): one IEEE f64 division.  ovr[b,a] =
+ *    ovr[a,b]; the diagonal follows the same rule.
+ * 5. Selection.  The present tubelets in descending ts (-0.0 == +0.0, equal scores by DESCENDING slot) are walked once: a live
+ *    tubelet is kept, and every live tubelet behind it with ovr >= thresh is suppressed.  thresh > 1 suppresses nothing: the
+ *    result is the present tubelets in score order, bit for bit.
+ * 6. Outputs -- every element is written by the call's launches, no fill pass by the caller.  The kept tubelets are compacted
+ *    into rank order: slot r < d_ntracks_out[c] of d_tracks_out, d_tboxes_out, d_anchors_out and d_series_out [n_series][C*T*F]
+ *    (vdet_merge_tracks' layout) is a bit-for-bit copy of source slot d_src[c,r]; slots behind the count are NaN rows, NaN
+ *    series and zero anchors.  d_tboxes_out / d_anchors_out: given iff the input is.  d_src [C,T] i32 (INT32_MIN behind the
+ *    count), d_tscore [C,T] f64 (ts of the kept slot, NaN behind the count), d_by [C,T] i32 indexed by INPUT slot: its own index
+ *    if kept, the kept slot that suppressed it, -1 if absent or at or behind d_ntracks.  d_overlaps [C,T,T] f64 or NULL (not
+ *    computed): ovr of every pair of present tubelets, rows and columns of every other slot NaN.
+ *
+ * Four launches (tubelet scores and extents; the pair pass over tiles of 32 x 32 pairs, which leaves one bit per pair; one wave
+ * per class for the selection; the gather), no host wait, scratch of the context sized on demand (V*C*T*(20 + 4*ceil(T/32))
+ * bytes).  Timed under "other".  Nothing of the context's cached graph, lists, index or link memo is read or written.
+ *
+ * vdet_nms_tubelets_batch: V videos in vdet_video_batch's layout -- the [C,T,F,...] arrays of video v start at element
+ * C*T*h_frame_off[v] (times 5 / 4 for rows / tboxes), d_ntracks, d_ntracks_out [V,C], d_anchors [V,C,T,3], a per-slot d_score,
+ * d_src, d_tscore, d_by [V,C,T], d_overlaps [V,C,T,T].  Per video the bits are vdet_nms_tubelets' on that video alone.  More
+ * than one video reads the per-video table staged keyed by the offsets (vdet_query 11): the same offsets again neither wait
+ * nor copy.
+ *
+ * Both: argument checks before any launch, VDET_EINVAL, nothing touched; ctx NULL: VDET_EINVAL.  Limits: the table at the top.
+ */
+#define VDET_TUBE_NORM_UNION 0
+#define VDET_TUBE_NORM_SHARED 1
+#define VDET_TUBE_NORM_MIN 2
+#define VDET_TUBE_SCORE_SLOT 0
+#define VDET_TUBE_SCORE_MEAN 1
+#define VDET_TUBE_SCORE_MAX 2
+
+int vdet_nms_tubelets(vdet_ctx *ctx, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                      const float *d_tboxes, const void *d_score, int score_f64, int score_mode, const float *d_anchors,
+                      const double *const *h_series, int n_series, double thresh, int norm, int min_shared, float *d_tracks_out,
+                      int32_t *d_ntracks_out, float *d_tboxes_out, float *d_anchors_out, double *d_series_out, int32_t *d_src,
+                      double *d_tscore, int32_t *d_by, double *d_overlaps);
+
+int vdet_nms_tubelets_batch(vdet_ctx *ctx, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                            const int32_t *d_ntracks, const float *d_tboxes, const void *d_score, int score_f64, int score_mode,
+                            const float *d_anchors, const double *const *h_series, int n_series, double thresh, int norm,
+                            int min_shared, float *d_tracks_out, int32_t *d_ntracks_out, float *d_tboxes_out, float *d_anchors_out,
+                            double *d_series_out, int32_t *d_src, double *d_tscore, int32_t *d_by, double *d_overlaps);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,10 @@ SYMBOLS = {
                                 _vp, _vp, _vp]),
     "vdet_merge_tracks_batch": (_ci, [_vp, _ci, _vp, _i64, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
+    "vdet_nms_tubelets": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp]),
+    "vdet_nms_tubelets_batch": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ci, _f64, _ci, _ci, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_nms_tracks": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _ci, _f64, _ci, _vp, _vp,
                               _vp, _vp, _vp]),
     "vdet_nms_tracks_batch": (_ci, [_vp, _vp, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _ci, _f64, _ci,

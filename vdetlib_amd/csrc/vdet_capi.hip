@@ -36,6 +36,7 @@
 #include "topanchor_kernels.hpp"
 #include "context_kernels.hpp"
 #include "merge_kernels.hpp"
+#include "tubenms_kernels.hpp"
 #include "tracknms_kernels.hpp"
 #include "softnms_kernels.hpp"
 #include "votenms_kernels.hpp"
@@ -255,6 +256,7 @@ struct vdet_ctx {
     bool sq_lds = true;           // VDET_SEQNMS_LDS=0: the predecessor table in global scratch (the path of long videos)
     bool sq_attr_set = false;
     int sq_last_path = -1;        // vdet_query 14: 1 the table in LDS, 2 in global scratch
+    DevBuf tube_scratch;          // NMS over whole tubelets (tubenms_kernels.hpp): scores, counts, extents and the bit rows per (video, class)
 };
 
 namespace {
@@ -1678,7 +1680,7 @@ int vdet_destroy(vdet_ctx *c)
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
                       &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad,
-                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec, &c->sq_link, &c->sq_live, &c->sq_done, &c->sq_ptr};
+                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec, &c->sq_link, &c->sq_live, &c->sq_done, &c->sq_ptr, &c->tube_scratch};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -4928,6 +4930,80 @@ int vdet_seq_nms(vdet_ctx *c, int64_t F, int64_t C, int R, const float *d_tracks
     return vdet_seq_nms_batch(c, off, 1, C, R, d_tracks, d_ntracks, d_score, score_f64, link_thres, nms_thres, rescore, max_seqs,
                               min_score, d_tracks_out, d_score_out, d_seq_out, d_ntracks_out, d_nseq, d_seq_sum, d_seq_len,
                               d_seq_end, d_exhausted);
+}
+
+// ---------------------------------------------------------------------------------------------
+// NMS over whole tubelets by spatio-temporal overlap (tubenms_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+int vdet_nms_tubelets_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
+                            const int32_t *d_ntracks, const float *d_tboxes, const void *d_score, int score_f64, int score_mode,
+                            const float *d_anchors, const double *const *h_series, int n_series, double thresh, int norm,
+                            int min_shared, float *d_tracks_out, int32_t *d_ntracks_out, float *d_tboxes_out, float *d_anchors_out,
+                            double *d_series_out, int32_t *d_src, double *d_tscore, int32_t *d_by, double *d_overlaps)
+{
+    if (!c) return VDET_EINVAL;
+    if (C < 1) return fail(c, VDET_EINVAL, "bad shape");
+    if (T < 1 || T > kTubeMaxT) return fail(c, VDET_EINVAL, "T = %d tubelet slots per class; 1 .. %d", T, kTubeMaxT);
+    if (n_series < 0 || n_series > kMergeMaxSeries) return fail(c, VDET_EINVAL, "0 to %d series", kMergeMaxSeries);
+    if (thresh != thresh) return fail(c, VDET_EINVAL, "thresh must not be NaN");
+    if (min_shared < 1) return fail(c, VDET_EINVAL, "min_shared must be at least 1");
+    if (norm != VDET_TUBE_NORM_UNION && norm != VDET_TUBE_NORM_SHARED && norm != VDET_TUBE_NORM_MIN)
+        return fail(c, VDET_EINVAL, "norm must be VDET_TUBE_NORM_UNION, VDET_TUBE_NORM_SHARED or VDET_TUBE_NORM_MIN");
+    if (score_mode != VDET_TUBE_SCORE_SLOT && score_mode != VDET_TUBE_SCORE_MEAN && score_mode != VDET_TUBE_SCORE_MAX)
+        return fail(c, VDET_EINVAL, "score_mode must be VDET_TUBE_SCORE_SLOT, VDET_TUBE_SCORE_MEAN or VDET_TUBE_SCORE_MAX");
+    Videos vs;
+    int rc = read_videos(c, h_frame_off, V, 65535, &vs);
+    if (rc) return rc;
+    if (!fits_below(0x7FFFFFF0ll, {C, T, vs.F}) || !fits_below(0x7FFFFFF0ll, {V, C, T}))
+        return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16)");
+    if (!d_tracks || !d_ntracks || !d_score || !d_tracks_out || !d_ntracks_out || !d_src || !d_tscore || !d_by)
+        return fail(c, VDET_EINVAL, "null buffer");
+    if ((d_tboxes != nullptr) != (d_tboxes_out != nullptr)) return fail(c, VDET_EINVAL, "tboxes: the input and the output, or neither");
+    if ((d_anchors != nullptr) != (d_anchors_out != nullptr)) return fail(c, VDET_EINVAL, "anchors: the input and the output, or neither");
+    if (n_series && (!h_series || !d_series_out)) return fail(c, VDET_EINVAL, "null buffer");
+    TubeArgs g{};
+    for (int q = 0; q < n_series; ++q) {
+        if (!h_series[q]) return fail(c, VDET_EINVAL, "null buffer");
+        g.series[q] = h_series[q];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if ((rc = video_table(c, c->anchor_tab, vs, &g.vids))) return rc;
+    const int64_t W = (T + 31) / 32, slots = V * C * T;
+    HIPCHK(c, c->tube_scratch.reserve((size_t)slots * (8 + 3 * 4 + (size_t)W * 4)));
+    g.s.ts = c->tube_scratch.as<double>();
+    g.s.n = reinterpret_cast<int32_t *>(g.s.ts + slots);
+    g.s.first = g.s.n + slots;
+    g.s.last = g.s.first + slots;
+    g.s.bits = reinterpret_cast<uint32_t *>(g.s.last + slots);
+    g.tracks = d_tracks; g.ntracks = d_ntracks; g.tboxes = d_tboxes; g.score = d_score; g.anchors = d_anchors;
+    g.F = (int)vs.F; g.C = (int)C; g.T = T; g.W = (int)W; g.nser = n_series;
+    g.score_f64 = score_f64 ? 1 : 0; g.score_mode = score_mode; g.norm = norm; g.min_shared = min_shared; g.thresh = thresh;
+    g.otracks = d_tracks_out; g.ontracks = d_ntracks_out; g.oanchors = d_anchors_out; g.otboxes = d_tboxes_out;
+    g.oseries = d_series_out; g.oN = C * T * vs.F; g.src = d_src; g.tscore = d_tscore; g.by = d_by; g.overlaps = d_overlaps;
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 per_slot((unsigned)((C * T + kTubeWaves - 1) / kTubeWaves), (unsigned)V);
+        const int64_t nt1 = (T + kTubeTile - 1) / kTubeTile, ntiles = nt1 * (nt1 + 1) / 2;      // (C * ntiles <= C * T)
+        hipLaunchKernelGGL(tubenms_score_kernel, per_slot, dim3(kTubeLT), 0, c->stream, g);
+        hipLaunchKernelGGL(tubenms_pair_kernel, dim3((unsigned)(C * ntiles), (unsigned)V), dim3(kTubeLT), 0, c->stream, g);
+        hipLaunchKernelGGL(tubenms_select_kernel, dim3((unsigned)(V * C)), dim3(64), 0, c->stream, g);
+        hipLaunchKernelGGL(tubenms_gather_kernel, per_slot, dim3(kTubeLT), 0, c->stream, g);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_nms_tubelets(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
+                      const float *d_tboxes, const void *d_score, int score_f64, int score_mode, const float *d_anchors,
+                      const double *const *h_series, int n_series, double thresh, int norm, int min_shared, float *d_tracks_out,
+                      int32_t *d_ntracks_out, float *d_tboxes_out, float *d_anchors_out, double *d_series_out, int32_t *d_src,
+                      double *d_tscore, int32_t *d_by, double *d_overlaps)
+{
+    const int64_t off[2] = {0, F};
+    return vdet_nms_tubelets_batch(c, off, 1, C, T, d_tracks, d_ntracks, d_tboxes, d_score, score_f64, score_mode, d_anchors, h_series,
+                                   n_series, thresh, norm, min_shared, d_tracks_out, d_ntracks_out, d_tboxes_out, d_anchors_out,
+                                   d_series_out, d_src, d_tscore, d_by, d_overlaps);
 }
 
 }  // extern "C"

@@ -1634,9 +1634,10 @@ def _tn_limits(C, T, Ft, top_still, cap):
     return R
 
 
-def _tn_tubelets(tracks, ntracks, score, tboxes):
-    """The tubelet source of nms_tracks / soft_nms_tracks, checked -- tensors, or a ``merge_tracks`` / ``interpolate_tracks`` dict
-    as ``tracks``: (tracks, ntracks, score, tboxes, C, T, F)."""
+def _tn_tubelets(tracks, ntracks, score, tboxes, per_slot=False):
+    """The tubelet source of nms_tracks / soft_nms_tracks / nms_tubelets, checked -- tensors, or a ``merge_tracks`` /
+    ``interpolate_tracks`` dict as ``tracks``: (tracks, ntracks, score, tboxes, C, T, F).  ``per_slot``: a score [C,T] is as good
+    as one [C,T,F]."""
     if isinstance(tracks, dict):
         d = tracks
         if ntracks is not None or any(k not in d for k in ('tracks', 'ntracks')):
@@ -1656,8 +1657,9 @@ def _tn_tubelets(tracks, ntracks, score, tboxes):
         raise ValueError("at least one class and one frame")
     if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
         raise ValueError("ntracks must be int32 [C]")
-    if not torch.is_tensor(score) or score.dtype not in (torch.float32, torch.float64) or tuple(score.shape) != (C, T, F):
-        raise ValueError("score must be float32 / float64 [C,T,F]")
+    shapes = ((C, T, F), (C, T)) if per_slot else ((C, T, F),)
+    if not torch.is_tensor(score) or score.dtype not in (torch.float32, torch.float64) or tuple(score.shape) not in shapes:
+        raise ValueError("score must be float32 / float64 [C,T,F]" + (" or [C,T]" if per_slot else ""))
     if tboxes is not None and (not torch.is_tensor(tboxes) or tboxes.dtype != torch.float32 or tuple(tboxes.shape) != (C, T, F, 4)):
         raise ValueError("tboxes must be float32 [C,T,F,4]")
     return tracks, ntracks, score, tboxes, C, T, F
@@ -1720,6 +1722,162 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
     views = lambda flat, per: _batch_views(flat, off, C, R, per)
     return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
+
+
+_TUBE_NORMS = {'union': 0, 'shared': 1, 'min': 2}       # include/vdet_hip.h: VDET_TUBE_NORM_*
+_TUBE_REDUCES = {'mean': 1, 'max': 2}                   # VDET_TUBE_SCORE_MEAN / _MAX (0, VDET_TUBE_SCORE_SLOT: a score per slot)
+_TUBE_MAX_T = 256
+
+
+def _tube_settings(thresh, norm, reduce, min_shared, C, T, Ft, V=1):
+    """The scalar arguments and the shape of nms_tubelets, checked against the limits of include/vdet_hip.h: (thresh, norm code,
+    reduce code, min_shared)."""
+    if norm not in _TUBE_NORMS:
+        raise ValueError("norm must be 'union', 'shared' or 'min'")
+    if reduce not in _TUBE_REDUCES:
+        raise ValueError("reduce must be 'mean' or 'max'")
+    try:
+        thresh = float(thresh)
+    except (TypeError, ValueError):
+        raise ValueError("thresh must be a number")
+    if thresh != thresh:
+        raise ValueError("thresh must not be NaN")
+    if isinstance(min_shared, bool) or not isinstance(min_shared, (int, np.integer)) or min_shared < 1:
+        raise ValueError("min_shared must be an integer >= 1")
+    if not 1 <= T <= _TUBE_MAX_T:
+        raise ValueError("T = %d tubelet slots per class; 1 .. %d" % (T, _TUBE_MAX_T))
+    if V > 65535:
+        raise ValueError("at most 65535 videos in one call")
+    if max(C * T * Ft, V * C * T) >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16)")
+    return thresh, _TUBE_NORMS[norm], _TUBE_REDUCES[reduce], int(min_shared)
+
+
+def _tube_call(ctx, off, C, T, tracks, ntracks, tboxes, score, mode, anchors, series, thresh, norm, min_shared, return_overlaps,
+               sync):
+    """Allocate the outputs (flat, batch layout) and enqueue the launches; every tensor contiguous and on one device.  Returns
+    (tracks, ntracks [V,C], tboxes or None, anchors [V,C,T,3] or None, series [n, N], src, tscore, by [V,C,T], overlaps
+    [V,C,T,T] or None)."""
+    V, Ft = len(off) - 1, int(off[-1])
+    dev = tracks.device
+    n, N = len(series), C * T * Ft
+    otracks = torch.empty((N * 5,), dtype=torch.float32, device=dev)
+    ont = torch.empty((V, C), dtype=torch.int32, device=dev)
+    otboxes = torch.empty((N * 4,), dtype=torch.float32, device=dev) if tboxes is not None else None
+    oanchors = torch.empty((V, C, T, 3), dtype=torch.float32, device=dev) if anchors is not None else None
+    oseries = torch.empty((n, N), dtype=torch.float64, device=dev)
+    src = torch.empty((V, C, T), dtype=torch.int32, device=dev)
+    tscore = torch.empty((V, C, T), dtype=torch.float64, device=dev)
+    by = torch.empty((V, C, T), dtype=torch.int32, device=dev)
+    ov = torch.empty((V, C, T, T), dtype=torch.float64, device=dev) if return_overlaps else None
+    ps = (ctypes.c_void_p * 4)(*[x.data_ptr() for x in series])
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    tail = (C, T, tracks.data_ptr(), ntracks.data_ptr(), ptr(tboxes), score.data_ptr(), int(score.dtype == torch.float64), mode,
+            ptr(anchors), ps, n, thresh, norm, min_shared, otracks.data_ptr(), ont.data_ptr(), ptr(otboxes), ptr(oanchors),
+            oseries.data_ptr() if n else None, src.data_ptr(), tscore.data_ptr(), by.data_ptr(), ptr(ov))
+    if V == 1:
+        ctx.check(ctx.lib.vdet_nms_tubelets(ctx.h, Ft, *tail))
+    else:
+        ctx.check(ctx.lib.vdet_nms_tubelets_batch(ctx.h, off.ctypes.data, V, *tail))
+    if sync:
+        ctx.sync()
+    return otracks, ont, otboxes, oanchors, oseries, src, tscore, by, ov
+
+
+def nms_tubelets(tracks, ntracks=None, score=None, tboxes=None, anchors=None, series=None, thresh=0.5, norm='union', reduce='mean',
+                 min_shared=1, return_overlaps=False, sync=True, ctx=None):
+    """NMS over WHOLE tubelets by spatio-temporal overlap: per class, a tubelet that repeats a better-scored one is dropped, the
+    survivors are compacted into score order.  The stage behind ``track_from_anchors`` / ``track_pixels`` / ``merge_tracks`` and
+    in front of the scorers; no host wait.  The rule is the project's own -- in full: include/vdet_hip.h (vdet_nms_tubelets),
+    in numpy: tests/tubenms_spec.py.
+
+    tracks [C,T,F,5] f32, ntracks [C] int32, tboxes [C,T,F,4] f32 (the boxes to use instead of the track rows), anchors [C,T,3]
+    f32 and ``series`` (up to 4 f64 [C,T,F] tensors, or one tensor) travel with the kept tubelets.  ``score`` (f32 / f64): [C,T]
+    -- a score per tubelet -- or [C,T,F], reduced by ``reduce`` ('mean' / 'max') over the frames where the box exists and the
+    value is not NaN.  A ``merge_tracks`` / ``interpolate_tracks`` dict goes in as ``tracks`` (then ``ntracks`` stays None,
+    ``score`` is the index of a series, default 0, or a tensor; the dict's tboxes, anchors and series are used unless given).
+    A tubelet without a box or with a NaN score is absent: neither kept nor suppressing.
+      overlap of two tubelets = (sum over the shared frames of the f32 IoU, in units of 2^-24) / den, with den by ``norm``:
+        'union'  frames on which either has a box (the usual spatio-temporal IoU),
+        'shared' frames on which both have one,
+        'min'    the boxes of the shorter (a short tubelet inside a long one overlaps fully);
+      0 with fewer than ``min_shared`` shared frames.  Greedy in descending score (ties by descending slot): suppression iff
+      overlap >= thresh; thresh > 1 only sorts.
+
+    Returns a dict of ``merge_tracks``' form -- ``tracks``, ``ntracks``, and ``tboxes`` / ``anchors`` / ``series`` when given:
+    slot r is a bit-for-bit copy of source slot ``src[c,r]``, NaN rows (zero anchors) behind the count -- plus ``src`` [C,T]
+    int32 (INT32_MIN behind the count), ``tscore`` [C,T] f64, ``by`` [C,T] int32 by INPUT slot (itself if kept, the slot that
+    suppressed it, -1 if absent) and, with ``return_overlaps``, ``overlaps`` [C,T,T] f64 (NaN rows and columns for absent
+    slots).  The result feeds ``merge_tracks``, ``nms_tracks``, ``rescore_tubelets``, ``tcn_tracks``, ``DetEvaluator.add_tracks``."""
+    if isinstance(tracks, dict):
+        anchors = tracks.get('anchors') if anchors is None else anchors
+        series = tracks.get('series') if series is None else series
+    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes, per_slot=True)
+    if anchors is not None and (not torch.is_tensor(anchors) or anchors.dtype != torch.float32 or tuple(anchors.shape) != (C, T, 3)):
+        raise ValueError("anchors must be float32 [C,T,3]")
+    if series is None or (isinstance(series, (tuple, list)) and not series):
+        series = ()
+    else:
+        series = _merge_series(series, (C, T, F), 'nms_tubelets')
+    thresh, norm, mode, min_shared = _tube_settings(thresh, norm, reduce, min_shared, C, T, F)
+    _same_gpu((tracks, ntracks, score, tboxes, anchors) + series, "every tensor")
+    cont = lambda x: None if x is None else x.contiguous()
+    tracks, ntracks, score, tboxes, anchors = cont(tracks), cont(ntracks), cont(score), cont(tboxes), cont(anchors)
+    series = tuple(x.contiguous() for x in series)
+    ctx = _ctx_for(tracks, ctx)
+    ot, ont, otb, oan, oser, src, tscore, by, ov = _tube_call(
+        ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, tboxes, score, mode if score.dim() == 3 else 0, anchors, series,
+        thresh, norm, min_shared, return_overlaps, sync)
+    out = dict(tracks=ot.view(C, T, F, 5), ntracks=ont.view(C), src=src.view(C, T), tscore=tscore.view(C, T), by=by.view(C, T))
+    if otb is not None:
+        out['tboxes'] = otb.view(C, T, F, 4)
+    if oan is not None:
+        out['anchors'] = oan.view(C, T, 3)
+    if series:
+        out['series'] = tuple(oser[q].view(C, T, F) for q in range(len(series)))
+    if ov is not None:
+        out['overlaps'] = ov.view(C, T, T)
+    return out
+
+
+def nms_tubelets_batch(batch_out, score='det', thresh=0.5, norm='union', reduce='mean', min_shared=1, return_overlaps=False,
+                       sync=True, ctx=None):
+    """``nms_tubelets`` for every video of a dict in ``video_batch``'s layout (``_batch_read``) in ONE call.  ``score`` names the
+    field of the dict that scores the tubelets ('det', 'pooled', ...: per-video [C,T,F_v] views, f32 or f64, reduced by
+    ``reduce``), or is a tensor [V,C,T] with a score per tubelet.  The dict's ``tboxes`` are the boxes when it has them;
+    ``det`` / ``pooled`` (f64), ``tboxes`` and ``anchors`` travel with the kept tubelets when present.  Per
+    video the bits are ``nms_tubelets``' on that video alone.  Returns the same layout -- ``tracks``, ``det``, ``pooled``,
+    ``tboxes`` (empty lists for what the input lacks), ``anchors`` (None without), ``ntracks`` [V,C], ``frame_off`` -- plus
+    ``src`` / ``tscore`` / ``by`` [V,C,T] and, with ``return_overlaps``, ``overlaps`` [V,C,T,T]."""
+    with_anchors = isinstance(batch_out, dict) and batch_out.get('anchors') is not None
+    b = _batch_read(batch_out, need=('anchors',) if with_anchors else ())
+    off, V, Ft, C, T, tracks, ntracks, anchors = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks, b.anchors
+    if isinstance(score, str):
+        sv = batch_out.get(score)
+        if not sv:
+            raise ValueError("score must name a per-video series of batch_out (e.g. 'det', 'pooled') or be a tensor [V,C,T]")
+        sc, per_frame = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out'), True
+    else:
+        if not torch.is_tensor(score) or score.dtype not in _F32_F64 or tuple(score.shape) != (V, C, T):
+            raise ValueError("score must name a per-video series of batch_out (e.g. 'det', 'pooled') or be a tensor [V,C,T]")
+        sc, per_frame = score.contiguous(), False
+    names = [k for k in ('det', 'pooled') if batch_out.get(k)]
+    series = tuple(_batch_field(b, batch_out[k], 1, _F64, k, 'batch_out') for k in names)
+    bv = batch_out.get('tboxes')
+    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
+    thresh, norm, mode, min_shared = _tube_settings(thresh, norm, reduce, min_shared, C, T, Ft, V)
+    _same_gpu((tracks, ntracks, sc, tboxes, anchors) + series, "every tensor")
+    ctx = _ctx_for(tracks, ctx)
+    ot, ont, otb, oan, oser, src, tscore, by, ov = _tube_call(
+        ctx, off, C, T, tracks, ntracks, tboxes, sc, mode if per_frame else 0, anchors, series, thresh, norm, min_shared,
+        return_overlaps, sync)
+    views = lambda flat, per: _batch_views(flat, off, C, T, per)
+    ser = {k: views(oser[q], 1) for q, k in enumerate(names)}
+    out = dict(tracks=views(ot, 5), det=ser.get('det', []), pooled=ser.get('pooled', []), tboxes=views(otb, 4) if otb is not None else [],
+               anchors=oan, ntracks=ont, frame_off=off, src=src, tscore=tscore, by=by)
+    if ov is not None:
+        out['overlaps'] = ov
+    return out
 
 
 _SN_METHODS = ('linear', 'gauss')       # include/vdet_hip.h: vdet_soft_nms_tracks
