@@ -11,41 +11,13 @@ import numpy as np
 import pytest
 
 import synth
+from listnms_harness import ListNms, dev, wide_lists
 from test_nms_tracks_cpu import CASES, SRC_PAD, THRESH, _oracle, expected, list_rows, make_case, outputs_equal, same_bits, still_of
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ('tracks', 'score', 'src', 'cnt', 'ntracks')
-
-
-def dev(x):
-    import torch
-    return None if x is None else torch.from_numpy(np.array(x)).cuda()
-
-
-def host(out):
-    return {k: out[k].cpu().numpy() for k in KEYS}
-
-
-def run(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    """ops.nms_tracks on device copies -> numpy; the inputs must come back bit-identical"""
-    from vdetlib_amd import ops
-    ins = [tracks, ntracks, score, tboxes] + list(still or ())
-    d = [dev(x) for x in ins]
-    out = host(ops.nms_tracks(d[0], d[1], d[2], tboxes=d[3], still=tuple(d[4:]) if still is not None else None, thresh=THRESH, **kw))
-    for x, y in zip(ins, d):
-        assert x is None or same_bits(y.cpu().numpy(), np.ascontiguousarray(x))
-    return out
-
-
-def check_case(case, tboxes=True, still=True, score=None, **kw):
-    st = still_of(case) if still else None
-    bx = case['tboxes'] if tboxes else None
-    sc = case['score'] if score is None else score
-    want = expected(case['tracks'], case['ntracks'], sc, bx, st, top_still=kw.get('top_still'), R=kw.get('cap'))
-    got = run(case['tracks'], case['ntracks'], sc, bx, st, **kw)
-    assert outputs_equal(got, want)
-    return got, want
+H = ListNms('nms_tracks', expected, case_thresh=THRESH, op_kw=dict(thresh=THRESH), equal=outputs_equal)
+host, run, check, check_case = H.host, H.run, H.check, H.check_case
 
 
 def longest(case, top_still):
@@ -70,7 +42,7 @@ def unsuppressed(shape):
 
 @pytest.mark.parametrize("shape", CASES)
 def test_generated_cases(shape):
-    got, want = check_case(make_case(*shape))
+    got = check_case(make_case(*shape))
     src = got['src'][got['src'] != SRC_PAD]
     assert (src >= 0).any() and (src < 0).any() and got['tracks'].shape[1] == shape[2] + 2 * shape[4]
 
@@ -79,32 +51,39 @@ def test_generated_cases(shape):
 def test_list_lengths_across_the_chunk_edge(n):
     case = make_case(*CASES[1]) if n < 100 else unsuppressed(CASES[1])
     top = next(t for t in range(0, 131) if longest(case, t) == n)
-    got, _ = check_case(case, top_still=top)
+    got = check_case(case, top_still=top)
     assert got['cnt'].max() > 32
 
 
-@pytest.mark.parametrize("variant", ["top_still_0", "no_still", "no_tubelets", "wide_lds"])
+@pytest.mark.parametrize("variant", ["top_still_0", "no_still", "no_tubelets", "wide_lds", "wide_lds_682", "wide_lds_683"])
 def test_source_variants(variant):
     case = make_case(*CASES[2])
     if variant == "top_still_0":
-        got, _ = check_case(case, top_still=0)
+        got = check_case(case, top_still=0)
         assert (got['src'][got['src'] != SRC_PAD] < 0).all() and got['cnt'].max() > 0
         assert outputs_equal(got, run(case['tracks'], case['ntracks'], case['score'], case['tboxes'], None))
     elif variant == "no_still":
-        got, _ = check_case(case, still=False)
+        got = check_case(case, still=False)
         assert got['tracks'].shape[1] == case['tracks'].shape[1]
     elif variant == "no_tubelets":
         seed, F, B, C, _ = CASES[2]
-        got, _ = check_case(make_case(seed, F, B, C, 0))
+        got = check_case(make_case(seed, F, B, C, 0))
         assert (got['src'][got['src'] != SRC_PAD] >= 0).all() and np.array_equal(got['cnt'], make_case(seed, F, B, C, 0)['keep_cnt'].T)
-    else:           # top_still + T = 766 candidates of LDS per wave: two waves per workgroup instead of four, nine lists
+    elif variant == "wide_lds":     # top_still + T = 766 candidates of LDS per wave: two waves per workgroup instead of four, nine lists
         check_case(case, top_still=700)
+    else:           # the break itself: 4 x 682 x 24 bytes stay below 64 KiB (four waves), 4 x 683 x 24 do not (two)
+        nmax = int(variant[-3:])
+        tracks, nt, score, still = wide_lists(nmax)
+        got = check(tracks, nt, score, None, still, top_still=nmax - 11)
+        assert got['tracks'].shape[1] == nmax and (0 < got['cnt']).all() and (got['cnt'] < nmax).all()
+        live = got['src'] != SRC_PAD
+        assert all((got['src'][0, :, f][live[0, :, f]] < 0).any() for f in range(2))        # a tubelet row is kept
 
 
 @pytest.mark.parametrize("F", [1, 64, 65])
 def test_frame_counts_on_a_coherent_video(F):
     case = make_case(21, F, 24, 2, 3, synth.coherent_video)
-    got, _ = check_case(case)
+    got = check_case(case)
     assert got['cnt'].min() > 0
 
 
@@ -137,7 +116,7 @@ def test_the_1024_candidate_limit():
 def test_score_series_and_boxes(dtype, tboxes):
     case = make_case(*CASES[0])
     sc = case['score'].astype(dtype)
-    got, want = check_case(case, tboxes=tboxes, score=sc)
+    got = check_case(case, tboxes=tboxes, score=sc)
     live = got['src'] < 0
     live &= got['src'] != SRC_PAD
     assert live.any() and got['score'].dtype == np.float64

@@ -5,7 +5,6 @@ bit-identical after every call.
 The generated cases are test_nms_tracks_cpu.CASES and case 2 with every box in its keep list; their input condition (every list
 reordered by the decay, tied scores emitted, rows removed by decay alone) is checked in test_softnms_cpu.py, whose hand-made
 lists (pins) and knife-edge lists run here on the device."""
-import functools
 import math
 
 import numpy as np
@@ -13,55 +12,19 @@ import pytest
 
 import knife_spec as K
 import softnms_spec as S
-import synth
+from listnms_harness import ListNms, guards_intact, wide_lists
 from test_nms_tracks_cpu import CASES, SRC_PAD, make_case, same_bits, still_of
 from test_nms_tracks_gpu import batch_cases, dev, longest, pack_batch, unsuppressed
 from test_softnms_cpu import LINEAR_THRESH, SOFT_BAD, ZERO_UNION, case_lists, case_median, gpu_cases, knife_lists, pins
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ('tracks', 'score', 'score0', 'src', 'cnt', 'ntracks')
+H = ListNms('soft_nms_tracks', S.expected, own=(('score0', 1, np.float64),), case_thresh=LINEAR_THRESH)
+host, outputs_equal, run, want_of, check, check_case = H.host, H.outputs_equal, H.run, H.want_of, H.check, H.check_case
+c_buffers, video_of = H.c_buffers, H.video_of
+
 INF = math.inf
 F32 = np.float32
-
-
-def host(out):
-    return {k: out[k].cpu().numpy() for k in KEYS}
-
-
-def outputs_equal(got, want):
-    return all(same_bits(got[k], want[k]) for k in ('tracks', 'score', 'score0', 'src')) and \
-        np.array_equal(got['cnt'], want['cnt']) and np.array_equal(got['ntracks'], want['ntracks']) and \
-        got['cnt'].dtype == np.int32 and got['ntracks'].dtype == np.int32
-
-
-def run(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    """ops.soft_nms_tracks on device copies -> numpy; the inputs must come back bit-identical"""
-    from vdetlib_amd import ops
-    ins = [tracks, ntracks, score, tboxes] + list(still or ())
-    d = [dev(x) for x in ins]
-    out = host(ops.soft_nms_tracks(d[0], d[1], d[2], tboxes=d[3], still=tuple(d[4:]) if still is not None else None, **kw))
-    for x, y in zip(ins, d):
-        assert x is None or same_bits(y.cpu().numpy(), np.ascontiguousarray(x))
-    return out
-
-
-def want_of(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    kw = dict(kw)
-    cap = kw.pop('cap', None)
-    return S.expected(tracks, ntracks, score, tboxes, still, R=cap, **kw)
-
-
-def check(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    want = want_of(tracks, ntracks, score, tboxes, still, **kw)
-    got = run(tracks, ntracks, score, tboxes, still, **kw)
-    assert outputs_equal(got, want)
-    return got
-
-
-def check_case(case, tboxes=True, still=True, **kw):
-    kw.setdefault('thresh', LINEAR_THRESH)
-    return check(case['tracks'], case['ntracks'], case['score'], case['tboxes'] if tboxes else None, still_of(case) if still else None, **kw)
 
 
 def decayed(got):
@@ -114,21 +77,6 @@ def test_list_lengths_across_the_chunk_edge(n):
         assert got['cnt'].max() == n
 
 
-@functools.lru_cache(maxsize=None)
-def wide_lists(nmax):
-    """C = 1, F = 2: nmax - 11 still-image rows of overlapping boxes (every box of the frame, descending score) and 11 tubelet
-    rows that are jittered copies of detection boxes"""
-    rng = np.random.RandomState(nmax)
-    T, B = 11, nmax - 11
-    boxes = np.stack([synth.boxes_1(rng, B, degenerate=B // 3) for _ in range(2)])
-    scores = np.stack([synth.tie_free_scores(rng, B) for _ in range(2)])[:, :, None]
-    ki = np.stack([np.argsort(-scores[f, :, 0], kind='stable') for f in range(2)]).astype(np.int32)[:, None]
-    tracks = np.zeros((1, T, 2, 5), F32)
-    for f in range(2):
-        tracks[0, :, f, :4] = boxes[f, rng.permutation(B)[:T]] + rng.randint(-3, 4, (T, 4))
-    return tracks, np.array([T], np.int32), rng.rand(1, T, 2), (boxes, scores, ki, np.full((2, 1), B, np.int32))
-
-
 @pytest.mark.parametrize("nmax,method", [(511, 'linear'), (512, 'gauss'), (1023, 'linear'), (1024, 'gauss')])
 def test_waves_per_workgroup(nmax, method):
     """32 bytes of LDS per candidate, the workgroup below 64 KiB: 4 waves up to 511 candidates, 2 up to 1023, 1 at 1024"""
@@ -169,24 +117,11 @@ def test_score_series(dtype, method):
         assert (got['score0'][tub] != got['score0'][tub].astype(F32).astype(np.float64)).any()
 
 
-def c_buffers(C, R, Ft, V, G, fill=7.25, ifill=12345):
-    import torch
-    N = C * R * Ft
-    f = lambda n, dt, v: torch.full((n + G,), v, dtype=dt).cuda()
-    return dict(tracks=f(N * 5, torch.float32, fill), score=f(N, torch.float64, fill), src=f(N, torch.int32, ifill),
-                cnt=f(C * Ft, torch.int32, ifill), ntracks=f(V * C, torch.int32, ifill), score0=f(N, torch.float64, fill))
-
-
 def c_tail(d, T, B, kcap, top, thresh, R, method, sigma, floor, o, f64=1):
     p = lambda x: None if x is None else (x if isinstance(x, int) else x.data_ptr())
     return (T, p(d['tracks']), p(d['ntracks']), p(d['score']), f64, p(d.get('tboxes')), p(d.get('boxes')), p(d.get('scores')), B,
             p(d.get('keep_idx')), p(d.get('keep_cnt')), kcap, top, thresh, R, method, sigma, floor, p(o['tracks']), p(o['score']),
             p(o['src']), p(o['cnt']), p(o['ntracks']), p(o['score0']))
-
-
-def guards_intact(o, sizes, G, fill=7.25, ifill=12345):
-    return all(bool((o[k][n:] == (fill if o[k].dtype.is_floating_point else ifill)).all()) and o[k].numel() == n + G
-               for k, n in sizes.items())
 
 
 def test_capacity_below_a_lists_count():
@@ -264,12 +199,6 @@ def test_zero_union_raises_at_the_wait():
 
 
 # ---- batch form -------------------------------------------------------------------------------------------------------------
-def video_of(out, v, off):
-    return dict(tracks=out['tracks'][v].cpu().numpy(), score=out['score'][v].cpu().numpy(), score0=out['score0'][v].cpu().numpy(),
-                src=out['src'][v].cpu().numpy(), cnt=out['cnt'][:, int(off[v]):int(off[v + 1])].cpu().numpy(),
-                ntracks=out['ntracks'][v].cpu().numpy())
-
-
 @pytest.mark.parametrize("method", S.METHODS)
 def test_batch_equals_single_video_calls(method):
     import torch

@@ -12,6 +12,7 @@ import pytest
 
 import knife_spec as K
 import votenms_spec as V
+from listnms_harness import ListNms, guards_intact
 from test_nms_tracks_cpu import CASES, SRC_PAD, expected as hard_expected, make_case, same_bits, still_of
 from test_nms_tracks_gpu import batch_cases, dev, pack_batch, unsuppressed
 from test_softnms_cpu import ZERO_UNION, knife_lists
@@ -20,42 +21,13 @@ from test_votenms_cpu import (CASE_THRESH, CASE_VOTE, KEYS, VOTE_BAD, case_args,
 
 pytestmark = pytest.mark.gpu
 
-ALL = KEYS + ('cnt', 'ntracks')
+H = ListNms('vote_nms_tracks', V.expected, own=(('box0', 4, np.float32), ('votes', 1, np.int32)), case_thresh=CASE_THRESH,
+            equal=outputs_equal)
+host, run, want_of, check, check_case = H.host, H.run, H.want_of, H.check, H.check_case
+c_buffers, sizes_of, video_of = H.c_buffers, H.sizes_of, H.video_of
+
 F32 = np.float32
 SETTINGS = ((0.3, 0.5), (0.5, 0.5), (0.5, 0.7), (1.5, 0.5), (0.3, 1.5))          # (thresh, vote_thresh)
-
-
-def host(out):
-    return {k: out[k].cpu().numpy() for k in ALL}
-
-
-def run(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    """ops.vote_nms_tracks on device copies -> numpy; the inputs must come back bit-identical"""
-    from vdetlib_amd import ops
-    ins = [tracks, ntracks, score, tboxes] + list(still or ())
-    d = [dev(x) for x in ins]
-    out = host(ops.vote_nms_tracks(d[0], d[1], d[2], tboxes=d[3], still=tuple(d[4:]) if still is not None else None, **kw))
-    for x, y in zip(ins, d):
-        assert x is None or same_bits(y.cpu().numpy(), np.ascontiguousarray(x))
-    return out
-
-
-def want_of(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    kw = dict(kw)
-    cap = kw.pop('cap', None)
-    return V.expected(tracks, ntracks, score, tboxes, still, R=cap, **kw)
-
-
-def check(tracks, ntracks, score, tboxes=None, still=None, **kw):
-    want = want_of(tracks, ntracks, score, tboxes, still, **kw)
-    got = run(tracks, ntracks, score, tboxes, still, **kw)
-    assert outputs_equal(got, want)
-    return got
-
-
-def check_case(case, tboxes=True, still=True, **kw):
-    kw.setdefault('thresh', CASE_THRESH)
-    return check(case['tracks'], case['ntracks'], case['score'], case['tboxes'] if tboxes else None, still_of(case) if still else None, **kw)
 
 
 # ---- generated cases ----------------------------------------------------------------------------------------------------------
@@ -181,30 +153,11 @@ def test_score_series(dtype, weights):
 
 
 # ---- error and status paths -------------------------------------------------------------------------------------------------
-def c_buffers(C, R, Ft, V_, G, fill=7.25, ifill=12345):
-    import torch
-    N = C * R * Ft
-    f = lambda n, dt, v: torch.full((n + G,), v, dtype=dt).cuda()
-    return dict(tracks=f(N * 5, torch.float32, fill), score=f(N, torch.float64, fill), src=f(N, torch.int32, ifill),
-                cnt=f(C * Ft, torch.int32, ifill), ntracks=f(V_ * C, torch.int32, ifill), box0=f(N * 4, torch.float32, fill),
-                votes=f(N, torch.int32, ifill))
-
-
 def c_tail(d, T, B, kcap, top, thresh, R, vote_thresh, weights, o, f64=1):
     p = lambda x: None if x is None else (x if isinstance(x, int) else x.data_ptr())
     return (T, p(d['tracks']), p(d['ntracks']), p(d['score']), f64, p(d.get('tboxes')), p(d.get('boxes')), p(d.get('scores')), B,
             p(d.get('keep_idx')), p(d.get('keep_cnt')), kcap, top, thresh, R, vote_thresh, weights, p(o['tracks']), p(o['score']),
             p(o['src']), p(o['cnt']), p(o['ntracks']), p(o['box0']), p(o['votes']))
-
-
-def guards_intact(o, sizes, G, fill=7.25, ifill=12345):
-    return all(bool((o[k][n:] == (fill if o[k].dtype.is_floating_point else ifill)).all()) and o[k].numel() == n + G
-               for k, n in sizes.items())
-
-
-def sizes_of(C, R, Ft, V_):
-    N = C * R * Ft
-    return dict(tracks=N * 5, score=N, src=N, cnt=C * Ft, ntracks=V_ * C, box0=N * 4, votes=N)
 
 
 def test_capacity_below_a_lists_count():
@@ -286,12 +239,6 @@ def test_zero_union_of_the_nms_raises_at_the_wait():
 
 
 # ---- batch form -------------------------------------------------------------------------------------------------------------
-def video_of(out, v, off):
-    one = {k: out[k][v].cpu().numpy() for k in KEYS}
-    one.update(cnt=out['cnt'][:, int(off[v]):int(off[v + 1])].cpu().numpy(), ntracks=out['ntracks'][v].cpu().numpy())
-    return one
-
-
 @pytest.mark.parametrize("weights", V.WEIGHTS)
 def test_batch_equals_single_video_calls(weights):
     import torch

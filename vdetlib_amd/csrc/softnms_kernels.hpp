@@ -3,10 +3,11 @@
 // for every pair -- and the list is emitted in the order of the CURRENT scores.  Semantics in full: include/vdet_hip.h
 // (vdet_soft_nms_tracks); the rule in numpy float32: tests/softnms_spec.py, which the kernel equals on bits.
 //
-// The LIST, its row order and row indices, the row loader (tn_load_row) and the launch shape are tracknms_kernel's: ONE launch,
-// one WAVE per list, list s of a video is (c, f) = (s / F, s % F), 1 / 2 / 4 waves per workgroup (the most that keeps the
-// workgroup's LDS BELOW 64 KiB), grid (ceil(C*Fmax / waves), V), batch offsets from the staged VidDesc table, ntracks by an
-// integer atomicMax on a host-zeroed buffer, nothing of the prep cache read or written.
+// The LIST and the launch shape are tracknms_kernels.hpp's, through its shared pieces tn_load_row, tn_store_row / tn_store_pad
+// and tn_close.  The round below is this rule's own loop, not tn_select.  The prologue is still written out here and is
+// tn_open + TnLds statement for statement: with the two calls the round loop is the same instructions, but its head moves off
+// the 64-byte line it starts on (0x..340 -> 0x..39c in the code object) and every leg of devtools/bench_softnms.py measured
+// 1.0 - 2.0 % slower on the MI355X; with the prologue here the kernel's code up to the loop is the old one.
 //
 // Per wave, LDS: box [n] float4, COMPOSITE [n] 64-bit, current score [n] f32, area [n] f32, n = top_still + T of THE CALL
 // (32 bytes per candidate: 4 waves up to 511 candidates, 2 up to 1023, 1 at the limit of 1024).
@@ -25,7 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "tracknms_kernels.hpp"  // TrackNmsArgs, TnList, TnRow, tn_load_row, tn_wave_max, kStBadKeep, kTnMaxList
+#include "tracknms_kernels.hpp"  // TrackNmsArgs, TnList, TnRow, the shared pieces, tn_wave_max, kTnMaxList
 
 namespace vdet {
 
@@ -167,8 +168,6 @@ __global__ __launch_bounds__(256) void softnms_kernel(const SoftNmsArgs a)
     }
 
     // output: the emitted rows at their ranks with their final scores, the fill behind the count
-    const float qnan = __uint_as_float(0x7FC00000u);
-    const double qnan64 = __longlong_as_double(0x7FF8000000000000ll);
     for (int j = lane; j < m.n; j += 64) {
         const unsigned long long k = scomp[j];
         if ((k >> 32) != 0ull || k == 0ull) continue;
@@ -179,28 +178,16 @@ __global__ __launch_bounds__(256) void softnms_kernel(const SoftNmsArgs a)
         tn_load_row(g, m, j, row, dummy);
         const float sj = sscore[j];
         const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = row.box.x; o[1] = row.box.y; o[2] = row.box.z; o[3] = row.box.w; o[4] = sj;
-        g.oscore[e] = (double)sj;
+        tn_store_row(g, e, row.box, sj, (double)sj, row.src);
         a.oscore0[e] = row.s64;
-        g.osrc[e] = row.src;
     }
     for (int r = (emitted < g.R ? emitted : g.R) + lane; r < g.R; r += 64) {
         const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = qnan; o[1] = qnan; o[2] = qnan; o[3] = qnan; o[4] = qnan;
-        g.oscore[e] = qnan64;
-        a.oscore0[e] = qnan64;
-        g.osrc[e] = kTnSrcPad;
+        tn_store_pad(g, e);
+        a.oscore0[e] = __longlong_as_double(0x7FF8000000000000ll);
     }
-    const unsigned long long anybad = __ballot(badkeep), anyzero = __ballot(zero);
-    if (lane == 0) {
-        g.ocnt[(int64_t)m.c * g.Ftot + m.fg] = emitted;
-        const int live = emitted < g.R ? emitted : g.R;
-        if (live > 0) atomicMax(g.ontracks + (int64_t)v * g.C + m.c, live);
-        const int st = (anybad ? kStBadKeep : 0) | (anyzero ? kStDivZero : 0) | (emitted > g.R ? kStCap : 0);
-        if (st) atomicOr(g.status, st);
-    }
+    tn_close(g, m, lane, emitted, badkeep, zero);
 }
 
 }  // namespace vdet
+

@@ -106,31 +106,27 @@ __device__ __forceinline__ bool tn_load_row(const TrackNmsArgs &g, const TnList 
     return !(r.s32 != r.s32);
 }
 
-__global__ __launch_bounds__(256) void tracknms_kernel(const TrackNmsArgs g)
+// ---- the pieces every rule on these lists calls (softnms_kernels.hpp, votenms_kernels.hpp) ----
+
+// OPEN: the list of wave w of the nw in this workgroup.  false: the wave is past the C * F_v lists of its video.  bad is set where
+// keep_cnt is outside 0..cap (the list then has no still-image rows)
+__device__ __forceinline__ bool tn_open(const TrackNmsArgs &g, int nw, int w, TnList &m, bool &bad)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tn_smem[];
-    const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    TnList m;
     const int v = blockIdx.y;
     int64_t f0 = 0;
     m.F = g.F;
     if (g.vids) { const VidDesc vd = g.vids[v]; f0 = vd.f0; m.F = vd.F; }
     const int64_t s = (int64_t)blockIdx.x * nw + w;
-    if (s >= (int64_t)g.C * m.F) return;
+    if (s >= (int64_t)g.C * m.F) return false;
     m.c = (int)(s / m.F);
     m.f = (int)(s - (int64_t)m.c * m.F);
     m.fg = f0 + m.f;
     m.tbase = (int64_t)g.C * g.T * f0 + (int64_t)m.c * g.T * m.F + m.f;
     m.obase = (int64_t)g.C * g.R * f0 + (int64_t)m.c * g.R * m.F + m.f;
-    float4 *sbox = reinterpret_cast<float4 *>(tn_smem) + (size_t)w * g.nmax;
-    unsigned long long *scomp = reinterpret_cast<unsigned long long *>(tn_smem + (size_t)nw * g.nmax * 16) + (size_t)w * g.nmax;
-
-    bool badkeep = false;
     m.ns = 0;
     if (g.top_still > 0) {
         const int kc = g.keep_cnt[m.fg * g.C + m.c];
-        if (kc < 0 || kc > g.cap) badkeep = true;
+        if (kc < 0 || kc > g.cap) bad = true;
         else m.ns = kc < g.top_still ? kc : g.top_still;
     }
     int nt = 0;
@@ -139,6 +135,97 @@ __global__ __launch_bounds__(256) void tracknms_kernel(const TrackNmsArgs g)
         nt = nt < 0 ? 0 : (nt > g.T ? g.T : nt);
     }
     m.n = m.ns + nt;                                     // (<= top_still + T = nmax)
+    return true;
+}
+
+// LDS carve: [nw][nmax] of each plane -- boxes (16 B per candidate), composites (8 B), then the 4-byte planes k = 0, 1, ...
+struct TnLds {
+    unsigned char *smem;
+    size_t all, mine;                                    // nw * nmax, w * nmax
+    __device__ __forceinline__ TnLds(unsigned char *base, int nw, int w, int nmax) : smem(base), all((size_t)nw * nmax), mine((size_t)w * nmax) {}
+    __device__ __forceinline__ float4 *box() const { return reinterpret_cast<float4 *>(smem) + mine; }
+    __device__ __forceinline__ unsigned long long *comp() const { return reinterpret_cast<unsigned long long *>(smem + all * 16) + mine; }
+    template <typename T> __device__ __forceinline__ T *plane(int k) const
+    {
+        static_assert(sizeof(T) == 4, "a 4-byte plane");
+        return reinterpret_cast<T *>(smem + all * (24 + 4 * k)) + mine;
+    }
+};
+
+// HARD SELECTION (the header's SELECTION paragraph): best = the lane's maximum of the gathered composites.  on_keep(rank, j)
+// runs in the lane that marks row j kept.  Returns the rows kept; zero is set by an evaluated zero-union pair.
+template <typename OnKeep>
+__device__ __forceinline__ int tn_select(const TrackNmsArgs &g, const TnList &m, int lane, const float4 *sbox,
+                                         unsigned long long *scomp, unsigned long long best, bool &zero, OnKeep on_keep)
+{
+    int kept = 0;
+    for (;;) {
+        const unsigned long long top = tn_wave_max(best);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(top >> 32));
+        if (hi == 0u) break;
+        const int i = __builtin_amdgcn_readfirstlane((int)(unsigned)top);
+        const float4 bi = sbox[i];
+        const float ai = box_area(bi);
+        best = 0ull;
+        for (int j = lane; j < m.n; j += 64) {
+            const unsigned long long k = scomp[j];
+            if ((k >> 32) == 0ull) continue;
+            if (j == i) { scomp[j] = (unsigned long long)(kept + 1); on_keep(kept, j); continue; }
+            const float4 bj = sbox[j];
+            const uint32_t p = pair_pred(bi, ai, bj, box_area(bj), g.t32);
+            if (p & 2u) zero = true;
+            if (p & 1u) scomp[j] = 0ull;
+            else best = k > best ? k : best;
+        }
+        ++kept;
+    }
+    return kept;
+}
+
+// rank row e of the common outputs
+__device__ __forceinline__ void tn_store_row(const TrackNmsArgs &g, int64_t e, float4 box, float s32, double s64, int32_t src)
+{
+    float *o = g.otracks + e * 5;
+    o[0] = box.x; o[1] = box.y; o[2] = box.z; o[3] = box.w; o[4] = s32;
+    g.oscore[e] = s64;
+    g.osrc[e] = src;
+}
+
+// the fill of a rank row behind the count
+__device__ __forceinline__ void tn_store_pad(const TrackNmsArgs &g, int64_t e)
+{
+    const float qnan = __uint_as_float(0x7FC00000u);
+    float *o = g.otracks + e * 5;
+    o[0] = qnan; o[1] = qnan; o[2] = qnan; o[3] = qnan; o[4] = qnan;
+    g.oscore[e] = __longlong_as_double(0x7FF8000000000000ll);
+    g.osrc[e] = kTnSrcPad;
+}
+
+// CLOSE: cnt of the list, ntracks of its (video, class), the status bits of the wave.  The two flags come by reference: copied
+// into parameters they stay SGPR lane masks through every loop, which took softnms_kernel to 105 SGPRs (7 waves per SIMD, not 8)
+__device__ __forceinline__ void tn_close(const TrackNmsArgs &g, const TnList &m, int lane, int count, const bool &bad, const bool &zero)
+{
+    const unsigned long long anybad = __ballot(bad), anyzero = __ballot(zero);
+    if (lane == 0) {
+        g.ocnt[(int64_t)m.c * g.Ftot + m.fg] = count;
+        const int live = count < g.R ? count : g.R;
+        if (live > 0) atomicMax(g.ontracks + (int64_t)blockIdx.y * g.C + m.c, live);
+        const int st = (anybad ? kStBadKeep : 0) | (anyzero ? kStDivZero : 0) | (count > g.R ? kStCap : 0);
+        if (st) atomicOr(g.status, st);
+    }
+}
+
+__global__ __launch_bounds__(256) void tracknms_kernel(const TrackNmsArgs g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char tn_smem[];
+    const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    TnList m;
+    bool badkeep = false;
+    if (!tn_open(g, nw, w, m, badkeep)) return;
+    const TnLds lds(tn_smem, nw, w, g.nmax);
+    float4 *sbox = lds.box();
+    unsigned long long *scomp = lds.comp();
 
     // gather
     unsigned long long best = 0ull;
@@ -155,32 +242,10 @@ __global__ __launch_bounds__(256) void tracknms_kernel(const TrackNmsArgs g)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
 
-    // selection
-    int kept = 0;
     bool zero = false;
-    for (;;) {
-        const unsigned long long top = tn_wave_max(best);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(top >> 32));
-        if (hi == 0u) break;
-        const int i = __builtin_amdgcn_readfirstlane((int)(unsigned)top);
-        const float4 bi = sbox[i];
-        const float ai = box_area(bi);
-        best = 0ull;
-        for (int j = lane; j < m.n; j += 64) {
-            const unsigned long long k = scomp[j];
-            if ((k >> 32) == 0ull) continue;
-            if (j == i) { scomp[j] = (unsigned long long)(kept + 1); continue; }
-            const float4 bj = sbox[j];
-            const uint32_t p = pair_pred(bi, ai, bj, box_area(bj), g.t32);
-            if (p & 2u) zero = true;
-            if (p & 1u) scomp[j] = 0ull;
-            else best = k > best ? k : best;
-        }
-        ++kept;
-    }
+    const int kept = tn_select(g, m, lane, sbox, scomp, best, zero, [](int, int) {});
 
     // output: the kept rows at their ranks, the fill behind the count
-    const float qnan = __uint_as_float(0x7FC00000u);
     for (int j = lane; j < m.n; j += 64) {
         const unsigned long long k = scomp[j];
         if ((k >> 32) != 0ull || k == 0ull) continue;
@@ -189,27 +254,11 @@ __global__ __launch_bounds__(256) void tracknms_kernel(const TrackNmsArgs g)
         TnRow row;
         bool dummy = false;
         tn_load_row(g, m, j, row, dummy);
-        const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = row.box.x; o[1] = row.box.y; o[2] = row.box.z; o[3] = row.box.w; o[4] = row.s32;
-        g.oscore[e] = row.s64;
-        g.osrc[e] = row.src;
+        tn_store_row(g, m.obase + (int64_t)r * m.F, row.box, row.s32, row.s64, row.src);
     }
-    for (int r = (kept < g.R ? kept : g.R) + lane; r < g.R; r += 64) {
-        const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = qnan; o[1] = qnan; o[2] = qnan; o[3] = qnan; o[4] = qnan;
-        g.oscore[e] = __longlong_as_double(0x7FF8000000000000ll);
-        g.osrc[e] = kTnSrcPad;
-    }
-    const unsigned long long anybad = __ballot(badkeep), anyzero = __ballot(zero);
-    if (lane == 0) {
-        g.ocnt[(int64_t)m.c * g.Ftot + m.fg] = kept;
-        const int live = kept < g.R ? kept : g.R;
-        if (live > 0) atomicMax(g.ontracks + (int64_t)v * g.C + m.c, live);
-        const int st = (anybad ? kStBadKeep : 0) | (anyzero ? kStDivZero : 0) | (kept > g.R ? kStCap : 0);
-        if (st) atomicOr(g.status, st);
-    }
+    for (int r = (kept < g.R ? kept : g.R) + lane; r < g.R; r += 64) tn_store_pad(g, m.obase + (int64_t)r * m.F);
+    tn_close(g, m, lane, kept, badkeep, zero);
 }
 
 }  // namespace vdet
+

@@ -3925,6 +3925,26 @@ static int tracknms_args(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int
     return VDET_OK;
 }
 
+extern "C++" {
+// the launch tail of the three rules: args = what the kernel takes, g = its list part.  The LDS of a wave follows the call's own
+// top_still + T; as many waves per workgroup (4, 2, 1) as stay BELOW 64 KiB
+template <typename Args>
+static int tracknms_launch(vdet_ctx *c, const Args &args, const TrackNmsArgs &g, const Videos &vs, void (*kernel)(Args), int bytes_per_cand)
+{
+    int waves = 4;
+    // (the hard NMS never meets the bound itself: 65536 is divisible by neither 4 * 24 nor 2 * 24)
+    while (waves > 1 && (size_t)waves * g.nmax * bytes_per_cand >= 65536) waves >>= 1;
+    HIPCHK(c, hipMemsetAsync(g.ontracks, 0, (size_t)(vs.V * g.C) * 4, c->stream));
+    {
+        StageTimer tm(c, ST_OTHER);
+        const dim3 grid((unsigned)(((int64_t)g.C * vs.Fmax + waves - 1) / waves), (unsigned)vs.V);
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), (size_t)waves * g.nmax * bytes_per_cand, c->stream, args);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+}  // extern "C++"
+
 int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, int64_t C, int T, const float *d_tracks,
                           const int32_t *d_ntracks, const void *d_score, int score_f64, const float *d_tboxes, const float *d_boxes,
                           const float *d_scores, int64_t B, const int32_t *d_keep_idx, const int32_t *d_keep_cnt, int64_t cap,
@@ -3938,18 +3958,7 @@ int vdet_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t V, in
                                  d_keep_idx, d_keep_cnt, cap, top_still, thresh, R, d_tracks_out, d_score_out, d_src_out, d_cnt_out,
                                  d_ntracks_out, vs, g);
     if (rc) return rc;
-    const int64_t Fmax = vs.Fmax;
-    // the LDS of a wave follows the call's own top_still + T; as many waves per workgroup (4, 2, 1) as 64 KiB hold
-    int waves = 4;
-    while (waves > 1 && (size_t)waves * g.nmax * kTnBytesPerCand > 65536) waves >>= 1;
-    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
-    {
-        StageTimer tm(c, ST_OTHER);
-        const dim3 grid((unsigned)((C * Fmax + waves - 1) / waves), (unsigned)V);
-        hipLaunchKernelGGL(tracknms_kernel, grid, dim3(64 * waves), (size_t)waves * g.nmax * kTnBytesPerCand, c->stream, g);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VDET_OK;
+    return tracknms_launch(c, g, g, vs, tracknms_kernel, kTnBytesPerCand);
 }
 
 int vdet_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks, const void *d_score,
@@ -3986,17 +3995,7 @@ int vdet_soft_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t 
                                  d_ntracks_out, vs, a.tn);
     if (rc) return rc;
     a.oscore0 = d_score0_out; a.method = method; a.sigma32 = (float)sigma; a.min32 = (float)min_score;
-    // as many waves per workgroup (4, 2, 1) as stay BELOW 64 KiB of LDS: 1 only at the limit of 1024 candidates
-    int waves = 4;
-    while (waves > 1 && (size_t)waves * a.tn.nmax * kSnBytesPerCand >= 65536) waves >>= 1;
-    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
-    {
-        StageTimer tm(c, ST_OTHER);
-        const dim3 grid((unsigned)((C * vs.Fmax + waves - 1) / waves), (unsigned)V);
-        hipLaunchKernelGGL(softnms_kernel, grid, dim3(64 * waves), (size_t)waves * a.tn.nmax * kSnBytesPerCand, c->stream, a);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VDET_OK;
+    return tracknms_launch(c, a, a.tn, vs, softnms_kernel, kSnBytesPerCand);
 }
 
 int vdet_soft_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,
@@ -4032,17 +4031,7 @@ int vdet_vote_nms_tracks_batch(vdet_ctx *c, const int64_t *h_frame_off, int64_t 
                                  d_ntracks_out, vs, a.tn);
     if (rc) return rc;
     a.obox0 = d_box0_out; a.ovotes = d_votes_out; a.weights = weights; a.v32 = thresh_to_f32(vote_thresh);
-    // as many waves per workgroup (4, 2, 1) as stay BELOW 64 KiB of LDS: 1 only at the limit of 1024 candidates
-    int waves = 4;
-    while (waves > 1 && (size_t)waves * a.tn.nmax * kVnBytesPerCand >= 65536) waves >>= 1;
-    HIPCHK(c, hipMemsetAsync(d_ntracks_out, 0, (size_t)(V * C) * 4, c->stream));
-    {
-        StageTimer tm(c, ST_OTHER);
-        const dim3 grid((unsigned)((C * vs.Fmax + waves - 1) / waves), (unsigned)V);
-        hipLaunchKernelGGL(votenms_kernel, grid, dim3(64 * waves), (size_t)waves * a.tn.nmax * kVnBytesPerCand, c->stream, a);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VDET_OK;
+    return tracknms_launch(c, a, a.tn, vs, votenms_kernel, kVnBytesPerCand);
 }
 
 int vdet_vote_nms_tracks(vdet_ctx *c, int64_t F, int64_t C, int T, const float *d_tracks, const int32_t *d_ntracks,

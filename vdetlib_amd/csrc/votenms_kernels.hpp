@@ -3,10 +3,8 @@
 // weighted mean of the boxes of the list's present rows that overlap it -- the rows the NMS threw away included.  Semantics in
 // full: include/vdet_hip.h (vdet_vote_nms_tracks); the rule in numpy: tests/votenms_spec.py, which the kernel equals on bits.
 //
-// The LIST, its row order and row indices, the row loader (tn_load_row), the gather, the selection loop and the launch shape are
-// tracknms_kernel's: ONE launch, one WAVE per list, list s of a video is (c, f) = (s / F, s % F), 1 / 2 / 4 waves per workgroup
-// (the most that keeps the workgroup's LDS BELOW 64 KiB), grid (ceil(C*Fmax / waves), V), batch offsets from the staged VidDesc
-// table, ntracks by an integer atomicMax on a host-zeroed buffer, nothing of the prep cache read or written.
+// The LIST, the hard selection and the launch shape are tracknms_kernels.hpp's, through its shared pieces: tn_open, TnLds,
+// tn_load_row, tn_select, tn_store_row / tn_store_pad, tn_close.
 //
 // Per wave, LDS: box [n] float4, COMPOSITE [n] 64-bit, f32 score [n], rank -> row index [n] int32, n = top_still + T of THE CALL
 // (32 bytes per candidate, softnms_kernel's: 4 waves up to 511 candidates, 2 up to 1023, 1 at the limit of 1024).
@@ -16,8 +14,8 @@
 //   rank -> row: written by the lane that marks a row kept; there are never more kept rows than candidates.
 // The areas are not stored: box_area of the stored box, as the selection of tracknms_kernel computes them, so the table above
 // takes the four bytes and the waves-per-workgroup breaks stay where softnms_kernel has them.
-// SELECTION: tracknms_kernel's loop, statement for statement, plus the table entry.  The kept set, its order and the zero-union
-// flag of the pairs it evaluates are that kernel's.
+// SELECTION: tn_select, the one loop tracknms_kernel runs, with the table entry as its on_keep.  The kept set, its order and the
+// zero-union flag of the pairs it evaluates are that kernel's.
 // VOTING pass, after it: LANE l takes the ranks l, l + 64, ... below min(kept, R), holds that row's box in registers and walks
 // the rows 0 .. n-1 of the list from LDS -- every lane reads the same address: a broadcast -- testing each present row with
 // pair_pred at the vote threshold (the row itself votes untested) and adding w and w * x1, y1, x2, y2 to five float64 registers.
@@ -31,7 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "tracknms_kernels.hpp"  // TrackNmsArgs, TnList, TnRow, tn_load_row, tn_wave_max, kStBadKeep, kTnMaxList
+#include "tracknms_kernels.hpp"  // TrackNmsArgs, TnList, TnRow, the shared pieces, kTnMaxList
 
 namespace vdet {
 
@@ -55,37 +53,13 @@ __global__ __launch_bounds__(256) void votenms_kernel(const VoteNmsArgs a)
     const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     TnList m;
-    const int v = blockIdx.y;
-    int64_t f0 = 0;
-    m.F = g.F;
-    if (g.vids) { const VidDesc vd = g.vids[v]; f0 = vd.f0; m.F = vd.F; }
-    const int64_t s = (int64_t)blockIdx.x * nw + w;
-    if (s >= (int64_t)g.C * m.F) return;
-    m.c = (int)(s / m.F);
-    m.f = (int)(s - (int64_t)m.c * m.F);
-    m.fg = f0 + m.f;
-    m.tbase = (int64_t)g.C * g.T * f0 + (int64_t)m.c * g.T * m.F + m.f;
-    m.obase = (int64_t)g.C * g.R * f0 + (int64_t)m.c * g.R * m.F + m.f;
-    // [nw][nmax] of each: boxes (16 B), composites (8 B), scores (4 B), rank -> row (4 B)
-    const size_t all = (size_t)nw * g.nmax, mine = (size_t)w * g.nmax;
-    float4 *sbox = reinterpret_cast<float4 *>(vn_smem) + mine;
-    unsigned long long *scomp = reinterpret_cast<unsigned long long *>(vn_smem + all * 16) + mine;
-    float *sscore = reinterpret_cast<float *>(vn_smem + all * 24) + mine;
-    int *srow = reinterpret_cast<int *>(vn_smem + all * 28) + mine;
-
     bool badkeep = false;
-    m.ns = 0;
-    if (g.top_still > 0) {
-        const int kc = g.keep_cnt[m.fg * g.C + m.c];
-        if (kc < 0 || kc > g.cap) badkeep = true;
-        else m.ns = kc < g.top_still ? kc : g.top_still;
-    }
-    int nt = 0;
-    if (g.T > 0) {
-        nt = g.ntracks[(int64_t)v * g.C + m.c];
-        nt = nt < 0 ? 0 : (nt > g.T ? g.T : nt);
-    }
-    m.n = m.ns + nt;                                     // (<= top_still + T = nmax)
+    if (!tn_open(g, nw, w, m, badkeep)) return;
+    const TnLds lds(vn_smem, nw, w, g.nmax);
+    float4 *sbox = lds.box();
+    unsigned long long *scomp = lds.comp();
+    float *sscore = lds.plane<float>(0);
+    int *srow = lds.plane<int>(1);
 
     const float qnan = __uint_as_float(0x7FC00000u);
     // gather (tracknms_kernel's, plus the score: NaN marks an absent row, whose box is never read)
@@ -106,29 +80,8 @@ __global__ __launch_bounds__(256) void votenms_kernel(const VoteNmsArgs a)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
 
-    // selection (tracknms_kernel's, plus the rank -> row entry)
-    int kept = 0;
     bool zero = false;
-    for (;;) {
-        const unsigned long long top = tn_wave_max(best);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(top >> 32));
-        if (hi == 0u) break;
-        const int i = __builtin_amdgcn_readfirstlane((int)(unsigned)top);
-        const float4 bi = sbox[i];
-        const float ai = box_area(bi);
-        best = 0ull;
-        for (int j = lane; j < m.n; j += 64) {
-            const unsigned long long k = scomp[j];
-            if ((k >> 32) == 0ull) continue;
-            if (j == i) { scomp[j] = (unsigned long long)(kept + 1); srow[kept] = j; continue; }
-            const float4 bj = sbox[j];
-            const uint32_t p = pair_pred(bi, ai, bj, box_area(bj), g.t32);
-            if (p & 2u) zero = true;
-            if (p & 1u) scomp[j] = 0ull;
-            else best = k > best ? k : best;
-        }
-        ++kept;
-    }
+    const int kept = tn_select(g, m, lane, sbox, scomp, best, zero, [srow](int rank, int j) { srow[rank] = j; });
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
 
@@ -164,31 +117,20 @@ __global__ __launch_bounds__(256) void votenms_kernel(const VoteNmsArgs a)
         bool dummy = false;
         tn_load_row(g, m, i, row, dummy);                // the source's own score and src (the lines are in cache)
         const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = bv.x; o[1] = bv.y; o[2] = bv.z; o[3] = bv.w; o[4] = row.s32;
-        g.oscore[e] = row.s64;
-        g.osrc[e] = row.src;
+        tn_store_row(g, e, bv, row.s32, row.s64, row.src);
         float *o0 = a.obox0 + e * 4;
         o0[0] = bi.x; o0[1] = bi.y; o0[2] = bi.z; o0[3] = bi.w;
         a.ovotes[e] = votes;
     }
     for (int r = live + lane; r < g.R; r += 64) {
         const int64_t e = m.obase + (int64_t)r * m.F;
-        float *o = g.otracks + e * 5;
-        o[0] = qnan; o[1] = qnan; o[2] = qnan; o[3] = qnan; o[4] = qnan;
-        g.oscore[e] = __longlong_as_double(0x7FF8000000000000ll);
-        g.osrc[e] = kTnSrcPad;
+        tn_store_pad(g, e);
         float *o0 = a.obox0 + e * 4;
         o0[0] = qnan; o0[1] = qnan; o0[2] = qnan; o0[3] = qnan;
         a.ovotes[e] = 0;
     }
-    const unsigned long long anybad = __ballot(badkeep), anyzero = __ballot(zero);
-    if (lane == 0) {
-        g.ocnt[(int64_t)m.c * g.Ftot + m.fg] = kept;
-        if (live > 0) atomicMax(g.ontracks + (int64_t)v * g.C + m.c, live);
-        const int stt = (anybad ? kStBadKeep : 0) | (anyzero ? kStDivZero : 0) | (kept > g.R ? kStCap : 0);
-        if (stt) atomicOr(g.status, stt);
-    }
+    tn_close(g, m, lane, kept, badkeep, zero);
 }
 
 }  // namespace vdet
+

@@ -1585,44 +1585,6 @@ def _tn_still(still, Ft, C, T, top_still):
     return (boxes, scores, keep_idx, keep_cnt), B, kcap, top_still
 
 
-def _tn_call(ctx, off, C, T, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, R, sync, soft=None, vote=None):
-    """Allocate the outputs (flat, batch layout) and enqueue the one launch; every tensor contiguous and on one device.
-    ``soft`` = (method code, sigma, min_score): soft_nms_tracks' launch, which returns the source scores as a sixth tensor.
-    ``vote`` = (vote_thresh, weights code): vote_nms_tracks' launch, which returns the own boxes and the vote counts as a sixth
-    and a seventh."""
-    V, Ft = len(off) - 1, int(off[-1])
-    dev = ntracks.device
-    N = C * R * Ft
-    otracks = torch.empty((N * 5,), dtype=torch.float32, device=dev)
-    oscore = torch.empty((N,), dtype=torch.float64, device=dev)
-    osrc = torch.empty((N,), dtype=torch.int32, device=dev)
-    ocnt = torch.empty((C, Ft), dtype=torch.int32, device=dev)
-    ont = torch.empty((V, C), dtype=torch.int32, device=dev)
-    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
-    sp = [ptr(x) for x in still] if still is not None and top_still > 0 else [None] * 4
-    tail = (C, T, ptr(tracks), ntracks.data_ptr(), ptr(score), int(score.dtype == torch.float64), ptr(tboxes), sp[0], sp[1], B, sp[2],
-            sp[3], kcap, top_still if still is not None else 0, float(thresh), R, otracks.data_ptr(), oscore.data_ptr(),
-            osrc.data_ptr(), ocnt.data_ptr(), ont.data_ptr())
-    one, many = (ctx.lib.vdet_nms_tracks, ctx.lib.vdet_nms_tracks_batch)
-    oscore0 = None
-    if soft is not None:
-        oscore0 = torch.empty((N,), dtype=torch.float64, device=dev)
-        tail = tail[:16] + (int(soft[0]), float(soft[1]), float(soft[2])) + tail[16:] + (oscore0.data_ptr(),)
-        one, many = (ctx.lib.vdet_soft_nms_tracks, ctx.lib.vdet_soft_nms_tracks_batch)
-    extra = () if soft is None else (oscore0,)
-    if vote is not None:
-        extra = (torch.empty((N * 4,), dtype=torch.float32, device=dev), torch.empty((N,), dtype=torch.int32, device=dev))
-        tail = tail[:16] + (float(vote[0]), int(vote[1])) + tail[16:] + tuple(x.data_ptr() for x in extra)
-        one, many = (ctx.lib.vdet_vote_nms_tracks, ctx.lib.vdet_vote_nms_tracks_batch)
-    if V == 1:
-        ctx.check(one(ctx.h, Ft, *tail))
-    else:
-        ctx.check(many(ctx.h, off.ctypes.data, V, *tail))
-    if sync:
-        ctx.sync()
-    return (otracks, oscore, osrc, ocnt, ont) + extra
-
-
 def _tn_limits(C, T, Ft, top_still, cap):
     if top_still + T > _TN_MAX:
         raise ValueError("top_still + T = %d candidates per (frame, class); the limit is %d" % (top_still + T, _TN_MAX))
@@ -1665,6 +1627,119 @@ def _tn_tubelets(tracks, ntracks, score, tboxes, per_slot=False):
     return tracks, ntracks, score, tboxes, C, T, F
 
 
+_SN_METHODS = ('linear', 'gauss')       # include/vdet_hip.h: vdet_soft_nms_tracks
+_SN_SIGMA_MIN = 1.0 / 64
+
+
+def _sn_settings(method, thresh, sigma, min_score):
+    """The scalar arguments of soft_nms_tracks, checked against the limits of include/vdet_hip.h: (method code, sigma, min_score)."""
+    if method not in _SN_METHODS:
+        raise ValueError("method must be 'linear' or 'gauss'")
+    try:
+        thresh, sigma, min_score = float(thresh), float(sigma), float(min_score)
+    except (TypeError, ValueError):
+        raise ValueError("thresh, sigma and min_score must be numbers")
+    if not math.isfinite(sigma) or sigma < _SN_SIGMA_MIN:
+        raise ValueError("sigma = %r; finite and at least 1/64" % sigma)
+    if math.isnan(thresh) or math.isnan(min_score):
+        raise ValueError("thresh and min_score must not be NaN")
+    return _SN_METHODS.index(method), sigma, min_score
+
+
+_VN_WEIGHTS = ('score', 'uniform')      # include/vdet_hip.h: vdet_vote_nms_tracks
+
+
+def _vn_settings(vote_thresh, weights):
+    """The scalar arguments of vote_nms_tracks, checked against the limits of include/vdet_hip.h: (vote_thresh, weights code)."""
+    if weights not in _VN_WEIGHTS:
+        raise ValueError("weights must be 'score' or 'uniform'")
+    try:
+        vote_thresh = float(vote_thresh)
+    except (TypeError, ValueError):
+        raise ValueError("vote_thresh must be a number")
+    if math.isnan(vote_thresh):
+        raise ValueError("vote_thresh must not be NaN")
+    return vote_thresh, _VN_WEIGHTS.index(weights)
+
+
+# The per-row outputs every rule on the per-frame lists writes: (key, elements per row, dtype), in the header's order.
+_TN_ROWS = (('tracks', 5, torch.float32), ('score', 1, torch.float64), ('src', 1, torch.int32))
+
+# A rule, described once: its C function (the batch form is NAME_batch), the check of its own arguments -- which returns the
+# scalars that follow R in include/vdet_hip.h -- and its own per-row outputs, which follow the common ones there.
+_TN_RULES = {
+    'hard': ('vdet_nms_tracks', lambda: (), ()),
+    'soft': ('vdet_soft_nms_tracks', _sn_settings, (('score0', 1, torch.float64),)),
+    'vote': ('vdet_vote_nms_tracks', _vn_settings, (('box0', 4, torch.float32), ('votes', 1, torch.int32))),
+}
+
+
+def _tn_run(rule, own, off, C, T, tracks, ntracks, score, tboxes, still, thresh, top_still, cap, sync, ctx):
+    """What the two forms share behind their tubelet source: the still-image source and the limits checked, the rule's ``own``
+    arguments checked, one device, contiguous tensors, the launch.  Returns (R, ``_tn_call``'s flat outputs)."""
+    Ft = int(off[-1])
+    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
+    R = _tn_limits(C, T, Ft, top_still, cap)
+    scalars = _TN_RULES[rule][1](*own)
+    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
+    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
+    tboxes = None if tboxes is None else tboxes.contiguous()
+    still = None if still is None else tuple(x.contiguous() for x in still)
+    ctx = _ctx_for(ntracks, ctx)
+    return R, _tn_call(ctx, rule, scalars, off, C, T, R, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, sync)
+
+
+def _tn_single(rule, own, tracks, ntracks, score, tboxes, still, thresh, top_still, cap, sync, ctx):
+    """The single-video form of a rule: tensors or a tubelet dict in, the result dict with [C,R,F,...] views out."""
+    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
+    R, flat = _tn_run(rule, own, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still, thresh, top_still,
+                      cap, sync, ctx)
+    out = {k: flat[k].view((C, R, F) + ((per,) if per > 1 else ())) for k, per, _ in _TN_ROWS + _TN_RULES[rule][2]}
+    out.update(cnt=flat['cnt'], ntracks=flat['ntracks'].view(C))
+    return out
+
+
+def _tn_batch(rule, own, batch_out, score, still, thresh, top_still, cap, use_tboxes, sync, ctx):
+    """The batch form of a rule: a dict in ``video_batch``'s layout in, one out."""
+    b = _batch_read(batch_out)
+    sv = batch_out.get(score) if isinstance(score, str) else None
+    if not sv:
+        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
+    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
+    bv = batch_out.get('tboxes') if use_tboxes else None
+    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
+    R, flat = _tn_run(rule, own, b.off, b.C, b.T, b.tracks, b.ntracks, sc, tboxes, still, thresh, top_still, cap, sync, ctx)
+    out = {k: _batch_views(flat[k], b.off, b.C, R, per) for k, per, _ in _TN_ROWS + _TN_RULES[rule][2]}
+    out.update(cnt=flat['cnt'], ntracks=flat['ntracks'], frame_off=b.off)
+    return out
+
+
+def _tn_call(ctx, rule, scalars, off, C, T, R, tracks, ntracks, score, tboxes, still, B, kcap, top_still, thresh, sync):
+    """Allocate the outputs (flat, batch layout) and enqueue the one launch of ``rule``; every tensor contiguous and on one
+    device.  The arguments go in the order include/vdet_hip.h declares them: the common inputs, the rule's scalars, the common
+    outputs, the rule's outputs.  Returns the flat outputs by key: the per-row ones of ``_TN_ROWS`` and of the rule, ``cnt``
+    [C,Ftot] and ``ntracks`` [V,C]."""
+    V, Ft = len(off) - 1, int(off[-1])
+    dev = ntracks.device
+    name, _, own_rows = _TN_RULES[rule]
+    out = {k: torch.empty((C * R * Ft * per,), dtype=dt, device=dev) for k, per, dt in _TN_ROWS + own_rows}
+    out['cnt'] = torch.empty((C, Ft), dtype=torch.int32, device=dev)
+    out['ntracks'] = torch.empty((V, C), dtype=torch.int32, device=dev)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    sp = [ptr(x) for x in still] if still is not None and top_still > 0 else [None] * 4
+    inputs = (C, T, ptr(tracks), ntracks.data_ptr(), ptr(score), int(score.dtype == torch.float64), ptr(tboxes), sp[0], sp[1], B,
+              sp[2], sp[3], kcap, top_still if still is not None else 0, float(thresh), R)
+    common = tuple(out[k].data_ptr() for k, _, _ in _TN_ROWS) + (out['cnt'].data_ptr(), out['ntracks'].data_ptr())
+    args = inputs + tuple(scalars) + common + tuple(out[k].data_ptr() for k, _, _ in own_rows)
+    if V == 1:
+        ctx.check(getattr(ctx.lib, name)(ctx.h, Ft, *args))
+    else:
+        ctx.check(getattr(ctx.lib, name + '_batch')(ctx.h, off.ctypes.data, V, *args))
+    if sync:
+        ctx.sync()
+    return out
+
+
 def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None, sync=True, ctx=None):
     """Per-frame NMS of tubelet boxes together with still-image detections (``apply_vid_nms`` / ``vid_nms``, utils/nms.pyx:71-125,
     as arrays): one list of detections per frame and class, one launch, no host wait.
@@ -1685,17 +1760,7 @@ def nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh
     ``score`` [C,R,F] f64 (the source's own score), ``src`` [C,R,F] int32 (b >= 0: still-image box b; -(t+1): tubelet slot t;
     INT32_MIN behind the count), ``cnt`` [C,F] int32, ``ntracks`` [C] int32 -- NaN behind the counts.  ``tracks`` / ``ntracks`` /
     ``score`` feed every consumer of tubelets; ``DetEvaluator.add_detections`` takes the dict."""
-    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
-    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
-    R = _tn_limits(C, T, F, top_still, cap)
-    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
-    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
-    tboxes = None if tboxes is None else tboxes.contiguous()
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still, B, kcap,
-                                        top_still, thresh, R, sync)
-    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt, ntracks=ont.view(C))
+    return _tn_single('hard', (), tracks, ntracks, score, tboxes, still, thresh, top_still, cap, sync, ctx)
 
 
 def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_still=None, cap=None, use_tboxes=True, sync=True,
@@ -1706,22 +1771,7 @@ def nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_stil
     ``video_batch`` takes and returns).  Per video the bits are ``nms_tracks``' on that video alone.  Returns ``tracks`` /
     ``score`` / ``src`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot], ``ntracks`` [V,C]
     and ``frame_off``."""
-    b = _batch_read(batch_out)
-    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
-    sv = batch_out.get(score) if isinstance(score, str) else None
-    if not sv:
-        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
-    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
-    bv = batch_out.get('tboxes') if use_tboxes else None
-    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
-    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
-    R = _tn_limits(C, T, Ft, top_still, cap)
-    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync)
-    views = lambda flat, per: _batch_views(flat, off, C, R, per)
-    return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont, frame_off=off)
+    return _tn_batch('hard', (), batch_out, score, still, thresh, top_still, cap, use_tboxes, sync, ctx)
 
 
 _TUBE_NORMS = {'union': 0, 'shared': 1, 'min': 2}       # include/vdet_hip.h: VDET_TUBE_NORM_*
@@ -1880,25 +1930,6 @@ def nms_tubelets_batch(batch_out, score='det', thresh=0.5, norm='union', reduce=
     return out
 
 
-_SN_METHODS = ('linear', 'gauss')       # include/vdet_hip.h: vdet_soft_nms_tracks
-_SN_SIGMA_MIN = 1.0 / 64
-
-
-def _sn_settings(method, thresh, sigma, min_score):
-    """The scalar arguments of soft_nms_tracks, checked against the limits of include/vdet_hip.h: (method code, sigma, min_score)."""
-    if method not in _SN_METHODS:
-        raise ValueError("method must be 'linear' or 'gauss'")
-    try:
-        thresh, sigma, min_score = float(thresh), float(sigma), float(min_score)
-    except (TypeError, ValueError):
-        raise ValueError("thresh, sigma and min_score must be numbers")
-    if not math.isfinite(sigma) or sigma < _SN_SIGMA_MIN:
-        raise ValueError("sigma = %r; finite and at least 1/64" % sigma)
-    if math.isnan(thresh) or math.isnan(min_score):
-        raise ValueError("thresh and min_score must not be NaN")
-    return _SN_METHODS.index(method), sigma, min_score
-
-
 def soft_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, method='linear', thresh=0.3, sigma=0.5,
                     min_score=0.001, top_still=None, cap=None, sync=True, ctx=None):
     """Soft-NMS (Bodla et al., ICCV 2017) of the per-frame detection lists ``nms_tracks`` builds: a row that overlaps a better
@@ -1924,19 +1955,8 @@ def soft_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, m
     ``DetEvaluator.add_detections`` takes the dict; ``seq_nms`` / ``top_anchors`` / ``nms_tracks`` take its tracks / ntracks /
     score.  ``cap`` below a list's count raises ValueError at the wait (the counts are written), an evaluated zero-union pair
     ZeroDivisionError, a keep count or index out of range ValueError."""
-    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
-    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
-    R = _tn_limits(C, T, F, top_still, cap)
-    soft = _sn_settings(method, thresh, sigma, min_score)
-    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
-    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
-    tboxes = None if tboxes is None else tboxes.contiguous()
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont, os0 = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still, B,
-                                             kcap, top_still, thresh, R, sync, soft)
-    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), score0=os0.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt,
-                ntracks=ont.view(C))
+    return _tn_single('soft', (method, thresh, sigma, min_score), tracks, ntracks, score, tboxes, still, thresh, top_still, cap,
+                      sync, ctx)
 
 
 def soft_nms_tracks_batch(batch_out, score='pooled', still=None, method='linear', thresh=0.3, sigma=0.5, min_score=0.001,
@@ -1945,41 +1965,8 @@ def soft_nms_tracks_batch(batch_out, score='pooled', still=None, method='linear'
     ``nms_tracks_batch``.  Per video the bits are ``soft_nms_tracks``' on that video alone.  Returns ``tracks`` / ``score`` /
     ``score0`` / ``src`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot], ``ntracks`` [V,C]
     and ``frame_off``."""
-    b = _batch_read(batch_out)
-    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
-    sv = batch_out.get(score) if isinstance(score, str) else None
-    if not sv:
-        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
-    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
-    bv = batch_out.get('tboxes') if use_tboxes else None
-    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
-    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
-    R = _tn_limits(C, T, Ft, top_still, cap)
-    soft = _sn_settings(method, thresh, sigma, min_score)
-    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont, os0 = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R, sync,
-                                             soft)
-    views = lambda flat, per: _batch_views(flat, off, C, R, per)
-    return dict(tracks=views(ot, 5), score=views(osc, 1), score0=views(os0, 1), src=views(osrc, 1), cnt=ocnt, ntracks=ont,
-                frame_off=off)
-
-
-_VN_WEIGHTS = ('score', 'uniform')      # include/vdet_hip.h: vdet_vote_nms_tracks
-
-
-def _vn_settings(vote_thresh, weights):
-    """The scalar arguments of vote_nms_tracks, checked against the limits of include/vdet_hip.h: (vote_thresh, weights code)."""
-    if weights not in _VN_WEIGHTS:
-        raise ValueError("weights must be 'score' or 'uniform'")
-    try:
-        vote_thresh = float(vote_thresh)
-    except (TypeError, ValueError):
-        raise ValueError("vote_thresh must be a number")
-    if math.isnan(vote_thresh):
-        raise ValueError("vote_thresh must not be NaN")
-    return vote_thresh, _VN_WEIGHTS.index(weights)
+    return _tn_batch('soft', (method, thresh, sigma, min_score), batch_out, score, still, thresh, top_still, cap, use_tboxes,
+                     sync, ctx)
 
 
 def vote_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, thresh=0.5, top_still=None, cap=None,
@@ -2003,19 +1990,7 @@ def vote_nms_tracks(tracks, ntracks=None, score=None, tboxes=None, still=None, t
     ``votes`` [C,R,F] int32 (voters, the row itself included; 0 behind the count).  ``DetEvaluator.add_detections`` takes the
     dict; ``seq_nms`` / ``soft_nms_tracks`` / ``top_anchors`` / ``nms_tracks`` take its tracks / ntracks / score.  The errors at
     the wait are ``nms_tracks``': ``cap`` below a list's count, a zero-union pair the NMS evaluates, bad keep data."""
-    tracks, ntracks, score, tboxes, C, T, F = _tn_tubelets(tracks, ntracks, score, tboxes)
-    still, B, kcap, top_still = _tn_still(still, F, C, T, top_still)
-    R = _tn_limits(C, T, F, top_still, cap)
-    vote = _vn_settings(vote_thresh, weights)
-    _same_gpu([ntracks, tracks, score, tboxes] + list(still or ()), "every tensor")
-    tracks, ntracks, score = tracks.contiguous(), ntracks.contiguous(), score.contiguous()
-    tboxes = None if tboxes is None else tboxes.contiguous()
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont, ob0, ov = _tn_call(ctx, np.array([0, F], dtype=np.int64), C, T, tracks, ntracks, score, tboxes, still,
-                                                 B, kcap, top_still, thresh, R, sync, vote=vote)
-    return dict(tracks=ot.view(C, R, F, 5), score=osc.view(C, R, F), src=osrc.view(C, R, F), cnt=ocnt, ntracks=ont.view(C),
-                box0=ob0.view(C, R, F, 4), votes=ov.view(C, R, F))
+    return _tn_single('vote', (vote_thresh, weights), tracks, ntracks, score, tboxes, still, thresh, top_still, cap, sync, ctx)
 
 
 def vote_nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top_still=None, cap=None, vote_thresh=0.5,
@@ -2025,25 +2000,7 @@ def vote_nms_tracks_batch(batch_out, score='pooled', still=None, thresh=0.5, top
     ``src`` / ``box0`` / ``votes`` in the same layout with the rank as the slot axis ([C,R,F_v,...]), ``cnt`` [C,Ftot],
     ``ntracks`` [V,C] and ``frame_off``: a dict in ``video_batch``'s layout again, which ``DetEvaluator.add_detections``,
     ``seq_nms_batch``, ``soft_nms_tracks_batch`` (``score='score'``), ``nms_tracks_batch`` and ``top_anchors`` take as it is."""
-    b = _batch_read(batch_out)
-    off, V, Ft, C, T, tracks, ntracks = b.off, b.V, b.Ft, b.C, b.T, b.tracks, b.ntracks
-    sv = batch_out.get(score) if isinstance(score, str) else None
-    if not sv:
-        raise ValueError("score must name a per-video series of batch_out (e.g. 'pooled', 'det')")
-    sc = _batch_field(b, sv, 1, _F32_F64, score, 'batch_out')
-    bv = batch_out.get('tboxes') if use_tboxes else None
-    tboxes = _batch_field(b, bv, 4, _F32, 'tboxes', 'batch_out') if bv else None
-    still, B, kcap, top_still = _tn_still(still, Ft, C, T, top_still)
-    R = _tn_limits(C, T, Ft, top_still, cap)
-    vote = _vn_settings(vote_thresh, weights)
-    _same_gpu([ntracks, tracks, sc, tboxes] + list(still or ()), "every tensor")
-    still = None if still is None else tuple(x.contiguous() for x in still)
-    ctx = _ctx_for(ntracks, ctx)
-    ot, osc, osrc, ocnt, ont, ob0, ov = _tn_call(ctx, off, C, T, tracks, ntracks, sc, tboxes, still, B, kcap, top_still, thresh, R,
-                                                 sync, vote=vote)
-    views = lambda flat, per: _batch_views(flat, off, C, R, per)
-    return dict(tracks=views(ot, 5), score=views(osc, 1), src=views(osrc, 1), box0=views(ob0, 4), votes=views(ov, 1), cnt=ocnt,
-                ntracks=ont, frame_off=off)
+    return _tn_batch('vote', (vote_thresh, weights), batch_out, score, still, thresh, top_still, cap, use_tboxes, sync, ctx)
 
 
 _SQ_MAX_R, _SQ_MAX_SEQS = 256, 4096     # include/vdet_hip.h: vdet_seq_nms
