@@ -82,7 +82,11 @@
  *                                          per box, windows < 2^31 - 16, C*T*F < 2^31 - 16      VDET_EINVAL; more present tubelet
  *                                                                     boxes than cap: VDET_ECAP latched (vdet_sync), the count
  *                                                                     still written.  One path for every size
- *   device pixel tracker                   grid S a multiple of 4 in 4 .. 64, 1 <= radius R <= 16, step >= 1, max_frames >= 0,
+ *   device RoI pooling                     1 <= ph, pw <= 32, 1 <= sampling <= 8, Hf, Wf <= 32767, RoIs < 2^31 - 16,
+ *                                          RoIs * ceil(K / 64) ('max') or RoIs * ceil(K*ph*pw / 4096) ('align') < 2^31,
+ *                                          C*T*F < 2^31 - 16                                    VDET_EINVAL; the tubelet form's
+ *                                                                     cap as for the R-CNN windows.  One path for every size
+ *   device pixel tracker                  grid S a multiple of 4 in 4 .. 64, 1 <= radius R <= 16, step >= 1, max_frames >= 0,
  *                                          min_conf finite, H, W <= 32767, C*T*F < 2^31 - 16      VDET_EINVAL; an anchor frame
  *                                                                     outside 0..F, or an anchor box that is not finite, beyond
  *                                                                     2^20, empty or wholly outside the image: VDET_EINVAL latched
@@ -1190,6 +1194,55 @@ int vdet_tubelet_patches(vdet_ctx *ctx, const uint8_t *d_images, int64_t Fi, int
                          int tracks_f64, int64_t C, int T, int64_t F, int ld, const int32_t *d_ntracks, int64_t f0, int64_t f1,
                          int64_t cap, const double *d_mean, int S, int padding, int mode, int out_dtype, void *d_patches,
                          uint8_t *d_ok, int32_t *d_slot, int32_t *d_count);
+
+/* ---- RoI pooling on the device: the Fast R-CNN route ----------------------------------------------------------------------------
+ *
+ * The front half of fast_rcnn_cls (vdet/tubelet_cls.py:53-76) and fast_rcnn_det (vdet/image_det.py:22-33): the backbone runs
+ * once per frame and every box of the frame is pooled out of its feature map, one launch for all RoIs of a call.  BOTH rules
+ * below are restated from public code that was not at hand (Caffe's ROIPoolingLayer forward with Dtype = float; the RoIAlign
+ * forward of He et al. 2017 as the common detection libraries ship it) and could not be checked against it: the device is bit
+ * for bit the numpy statement in tests/roipool_spec.py, which is the definition.
+ *
+ * d_features [Fi,K,Hf,Wf], contiguous, feat_dtype VDET_FEAT_F32 / _F16 / _BF16 (16-bit features are widened to f32 exactly);
+ * boxes as they are (no 1-based shift).  A RoI is r = (float)((double)box * box_scale) per coordinate; s = (float)spatial_scale.
+ * Everything below is float32, every product and sum a separate operation.
+ *
+ * VDET_ROI_MAX.  x1c = round(r_x1 * s) (C round(): halves away from zero), y1c, x2c, y2c alike; rw = max(x2c - x1c + 1, 1), rh
+ * alike; bw = (float)rw / (float)pw, bh alike.  Bin (p,q) spans rows floor((float)p * bh) .. ceil((float)(p+1) * bh) and columns
+ * alike from q and bw, each shifted by y1c / x1c and clamped to [0, Hf] / [0, Wf].  A bin with end <= start on either axis is
+ * 0.  Otherwise best = -FLT_MAX and the cells, visited row-major, replace best iff v > best: NaN and -inf never win.
+ *
+ * VDET_ROI_ALIGN, sampling in 1 .. 8 samples per bin and axis (a fixed grid), off = aligned ? 0.5 : 0.  sx = r_x1 * s - off;
+ * rw = r_x2 * s - off - sx, raised to 1 when not aligned; bw = rw / (float)pw; y alike.  Sample (iy,ix) of bin (p,q) lies at
+ * y = sy + (float)p * bh + ((float)iy + 0.5f) * bh / (float)sampling, x alike.  A sample with y < -1, y > Hf, x < -1 or x > Wf
+ * contributes 0.  Otherwise y <= 0 becomes 0, lo = (int)y, hi = lo + 1; if lo >= Hf - 1 then lo = hi = Hf - 1 and y = lo;
+ * ly = y - lo, hy = 1 - ly; x alike; value = ((hy*hx*v[lo,lo] + hy*lx*v[lo,hi]) + ly*hx*v[hi,lo]) + ly*lx*v[hi,hi] (row, column).
+ * The samples are summed iy-major, then ix, from 0, and the sum is divided by (float)(sampling*sampling) once.
+ *
+ * Output: d_pooled [N,K,ph,pw] in feat_dtype, the f32 value rounded once to nearest even (-FLT_MAX becomes -inf in the 16-bit
+ * types).  d_ok [N] uint8: 0 -- and an all-zero block, no feature read -- when a coordinate of r is not finite, |r * s| > 2^24,
+ * or the image index is outside 0..Fi-1.  A RoI wholly off the map is ok with an all-zero block.
+ *
+ * vdet_roi_pool: d_boxes [N,4] f32 / f64, d_image_idx [N] int32 or NULL (image 0).
+ * vdet_tubelet_rois: d_tracks, d_ntracks, f0, f1, cap, d_slot, d_count exactly as vdet_tubelet_patches (the same compaction
+ * kernel and the same VDET_ECAP latch); d_features holds Fi = f1 - f0 maps, map f - f0 is frame f; block i of d_pooled
+ * [cap,K,ph,pw] / d_ok [cap] is slot i's box, behind the count zeros / 0.
+ *
+ * One launch (two for the tubelet form), on the context's stream, no host wait, inputs never modified; timed under "other".
+ * ctx NULL: VDET_EINVAL, nothing touched.  Not provided: backward / argmax, the adaptive RoIAlign grid, position-sensitive
+ * pooling, channels-last features.
+ */
+#define VDET_ROI_MAX 0
+#define VDET_ROI_ALIGN 1
+
+int vdet_roi_pool(vdet_ctx *ctx, const void *d_features, int feat_dtype, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf,
+                  const void *d_boxes, int boxes_f64, int64_t N, const int32_t *d_image_idx, double spatial_scale, int ph, int pw,
+                  double box_scale, int mode, int sampling, int aligned, void *d_pooled, uint8_t *d_ok);
+
+int vdet_tubelet_rois(vdet_ctx *ctx, const void *d_features, int feat_dtype, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf,
+                      const void *d_tracks, int tracks_f64, int64_t C, int T, int64_t F, int ld, const int32_t *d_ntracks, int64_t f0,
+                      int64_t f1, int64_t cap, double spatial_scale, int ph, int pw, double box_scale, int mode, int sampling,
+                      int aligned, void *d_pooled, uint8_t *d_ok, int32_t *d_slot, int32_t *d_count);
 
 /*
  * The SVM head of the CNN scorers on the device: rcnn_scoring / rcnn_sampling_scoring (vdet/tubelet_cls.py:102-194) AFTER the

@@ -111,6 +111,9 @@ SYMBOLS = {
     "vdet_rcnn_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "vdet_tubelet_patches": (_ci, [_vp, _vp, _i64, _i64, _i64, _vp, _ci, _i64, _ci, _i64, _ci, _vp, _i64, _i64, _i64, _vp, _ci, _ci,
                                    _ci, _ci, _vp, _vp, _vp, _vp]),
+    "vdet_roi_pool": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _i64, _vp, _ci, _i64, _vp, _f64, _ci, _ci, _f64, _ci, _ci, _ci, _vp, _vp]),
+    "vdet_tubelet_rois": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _i64, _vp, _ci, _i64, _ci, _i64, _ci, _vp, _i64, _i64, _i64, _f64, _ci,
+                                _ci, _f64, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "vdet_svm_head": (_ci, [_vp, _vp, _ci, _i64, _ci, _i64, _vp, _ci, _vp, _ci, _i64, _f64, _ci, _vp, _vp, _i64, _ci, _i64, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_svm_scores_dev_f64": (_ci, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),

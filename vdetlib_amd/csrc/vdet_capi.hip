@@ -42,6 +42,7 @@
 #include "votenms_kernels.hpp"
 #include "rescore_kernels.hpp"
 #include "patch_kernels.hpp"
+#include "roipool_kernels.hpp"
 #include "svmhead_kernels.hpp"
 #include "pixtrack_kernels.hpp"
 #include "motion_kernels.hpp"
@@ -447,7 +448,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadMerge) return fail(c, VDET_EINVAL, "merge 'max': two paired tubelets differ in the frames of their boxes or in their anchor frame");
     if (st & kStBadPropagate) return fail(c, VDET_EINVAL, "propagate_boxes: a keep_cnt outside 0..cap, a keep_idx outside 0..B-1, or a source box that is not finite or beyond 2^20 (the source writes NaN rows)");
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
-    if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
+    if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches / tubelet_rois: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
     if (st & kStSvmBad) return fail(c, VDET_EINVAL, "svm_head: a slot row outside shape or a class column outside W (the group is skipped, nothing is written for it)");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
@@ -4224,6 +4225,123 @@ int vdet_tubelet_patches(vdet_ctx *c, const uint8_t *d_images, int64_t Fi, int64
     g.mean = d_mean; g.S = S; g.padding = padding; g.square = mode == VDET_PATCH_SQUARE ? 1 : 0;
     g.M = cap; g.patches = d_patches; g.ok = d_ok;
     if ((rc = patch_launch(c, g, out_dtype))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// RoI pooling: the Fast R-CNN route (roipool_kernels.hpp)
+// ---------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+int roi_check(vdet_ctx *c, const void *d_features, int feat_dtype, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf, double spatial_scale,
+              int ph, int pw, double box_scale, int mode, int sampling, int64_t N, const void *d_pooled)
+{
+    if (feat_dtype != VDET_FEAT_F32 && feat_dtype != VDET_FEAT_F16 && feat_dtype != VDET_FEAT_BF16)
+        return fail(c, VDET_EINVAL, "feat_dtype must be VDET_FEAT_F32, VDET_FEAT_F16 or VDET_FEAT_BF16");
+    if (Fi < 1 || K < 1 || Hf < 1 || Wf < 1 || Hf > kRoiMaxHW || Wf > kRoiMaxHW || Fi > 0x7FFFFFF0ll || K > 0x7FFFFFF0ll)
+        return fail(c, VDET_EINVAL, "features must be [Fi,K,Hf,Wf] with Fi, K >= 1 and 1 <= Hf, Wf <= %d", kRoiMaxHW);
+    if (ph < 1 || pw < 1 || ph > kRoiMaxPooled || pw > kRoiMaxPooled) return fail(c, VDET_EINVAL, "pooled = (%d, %d); 1 .. %d each", ph, pw, kRoiMaxPooled);
+    if (mode != VDET_ROI_MAX && mode != VDET_ROI_ALIGN) return fail(c, VDET_EINVAL, "mode must be VDET_ROI_MAX or VDET_ROI_ALIGN");
+    if (mode == VDET_ROI_ALIGN && (sampling < 1 || sampling > kRoiMaxSampling)) return fail(c, VDET_EINVAL, "sampling = %d; 1 .. %d", sampling, kRoiMaxSampling);
+    if (!(spatial_scale > 0.0) || !(spatial_scale - spatial_scale == 0.0) || !((float)spatial_scale > 0.f) || !(box_scale - box_scale == 0.0))
+        return fail(c, VDET_EINVAL, "spatial_scale must be positive and finite (also as float32), box_scale finite");
+    if (N < 0 || N >= 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "too many RoIs (below 2^31 - 16)");
+    if (N && (!d_features || !d_pooled)) return fail(c, VDET_EINVAL, "null buffer");
+    return VDET_OK;
+}
+
+template <typename FeatT> void roi_launch_t(vdet_ctx *c, const RoiArgs &g, bool align, bool wpc, unsigned blocks)
+{
+    if (align && wpc) hipLaunchKernelGGL((roi_pool_kernel<FeatT, true, true>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else if (align) hipLaunchKernelGGL((roi_pool_kernel<FeatT, true, false>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else if (wpc) hipLaunchKernelGGL((roi_pool_kernel<FeatT, false, true>), dim3(blocks), dim3(256), 0, c->stream, g);
+    else hipLaunchKernelGGL((roi_pool_kernel<FeatT, false, false>), dim3(blocks), dim3(256), 0, c->stream, g);
+}
+
+// the order of a workgroup's elements (roipool_kernels.hpp), by measurement: 'max' a wave per channel, 'align'
+// lanes over the span.  VDET_ROIPOOL_ORDER = 1 / 2 forces span / wave per channel, for re-measuring
+#ifndef VDET_ROIPOOL_ORDER
+#define VDET_ROIPOOL_ORDER 0
+#endif
+bool roi_wave_per_channel(int mode) { return VDET_ROIPOOL_ORDER == 2 || (VDET_ROIPOOL_ORDER == 0 && mode == VDET_ROI_MAX); }
+
+// one workgroup per (RoI, chunk of its output span), on a 1-D grid
+int roi_launch(vdet_ctx *c, RoiArgs &g, int feat_dtype, int mode)
+{
+    if (g.N == 0) return VDET_OK;
+    g.span = g.K * g.ph * g.pw;
+    const bool wpc = roi_wave_per_channel(mode), align = mode == VDET_ROI_ALIGN;
+    const int64_t nchunks = wpc ? (g.K + kRoiWaveCh - 1) / kRoiWaveCh : (g.span + kRoiChunk - 1) / kRoiChunk;
+    if (!fits_upto(0x7FFFFFFFll, {g.N, nchunks})) return fail(c, VDET_EINVAL, "too many RoIs for one launch (N * ceil(K*ph*pw / %d) and N * ceil(K / %d) must stay below 2^31)", kRoiChunk, kRoiWaveCh);
+    g.nchunks = (int)nchunks;
+    const unsigned blocks = (unsigned)(g.N * nchunks);
+    StageTimer tm(c, ST_OTHER);
+    if (feat_dtype == VDET_FEAT_F32) roi_launch_t<float>(c, g, align, wpc, blocks);
+    else if (feat_dtype == VDET_FEAT_F16) roi_launch_t<_Float16>(c, g, align, wpc, blocks);
+    else roi_launch_t<PatchBf16>(c, g, align, wpc, blocks);
+    return VDET_OK;
+}
+
+void roi_fill(RoiArgs &g, const void *d_features, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf, double spatial_scale, int ph, int pw,
+              double box_scale, int sampling, int aligned, void *d_pooled, uint8_t *d_ok)
+{
+    g.features = d_features; g.Fi = (int)Fi; g.K = K; g.Hf = (int)Hf; g.Wf = (int)Wf;
+    g.spatial_scale = (float)spatial_scale; g.box_scale = box_scale;
+    g.ph = ph; g.pw = pw; g.sampling = sampling; g.aligned = aligned ? 1 : 0;
+    g.pooled = d_pooled; g.ok = d_ok;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int vdet_roi_pool(vdet_ctx *c, const void *d_features, int feat_dtype, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf, const void *d_boxes,
+                  int boxes_f64, int64_t N, const int32_t *d_image_idx, double spatial_scale, int ph, int pw, double box_scale, int mode,
+                  int sampling, int aligned, void *d_pooled, uint8_t *d_ok)
+{
+    if (!c) return VDET_EINVAL;
+    int rc = roi_check(c, d_features, feat_dtype, Fi, K, Hf, Wf, spatial_scale, ph, pw, box_scale, mode, sampling, N, d_pooled);
+    if (rc) return rc;
+    if (N == 0) return VDET_OK;
+    if (!d_boxes || !d_ok) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    RoiArgs g{};
+    roi_fill(g, d_features, Fi, K, Hf, Wf, spatial_scale, ph, pw, box_scale, sampling, aligned, d_pooled, d_ok);
+    g.boxes = d_boxes; g.boxes_f64 = boxes_f64 ? 1 : 0; g.ld = 4;
+    g.image_idx = d_image_idx; g.N = N;
+    if ((rc = roi_launch(c, g, feat_dtype, mode))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_tubelet_rois(vdet_ctx *c, const void *d_features, int feat_dtype, int64_t Fi, int64_t K, int64_t Hf, int64_t Wf,
+                      const void *d_tracks, int tracks_f64, int64_t C, int T, int64_t F, int ld, const int32_t *d_ntracks, int64_t f0,
+                      int64_t f1, int64_t cap, double spatial_scale, int ph, int pw, double box_scale, int mode, int sampling, int aligned,
+                      void *d_pooled, uint8_t *d_ok, int32_t *d_slot, int32_t *d_count)
+{
+    if (!c) return VDET_EINVAL;
+    if (C < 1 || T < 0 || F < 1 || ld < 4) return fail(c, VDET_EINVAL, "bad shape (tracks must be [C,T,F,>=4])");
+    if (f0 < 0 || f1 <= f0 || f1 > F) return fail(c, VDET_EINVAL, "frames must be a range 0 <= f0 < f1 <= F");
+    if (Fi != f1 - f0) return fail(c, VDET_EINVAL, "features must hold the f1 - f0 = %lld frames of the range", (long long)(f1 - f0));
+    if (!fits_below(0x7FFFFFF0ll, {C, std::max(T, 1), F})) return fail(c, VDET_EINVAL, "too many tubelet boxes (C*T*F must stay below 2^31 - 16)");
+    if (cap < 0) return fail(c, VDET_EINVAL, "cap must not be negative");
+    int rc = roi_check(c, d_features, feat_dtype, Fi, K, Hf, Wf, spatial_scale, ph, pw, box_scale, mode, sampling, cap, d_pooled);
+    if (rc) return rc;
+    if (!d_ntracks || !d_count || (T && !d_tracks) || (cap && (!d_slot || !d_ok))) return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(tubelet_slots_kernel, dim3(1), dim3(1024), 0, c->stream, d_tracks, tracks_f64 ? 1 : 0, ld, d_ntracks, (int)C, T,
+                           F, f0, f1, cap, d_slot, d_count, &c->d_cnt->status);
+    }
+    RoiArgs g{};
+    roi_fill(g, d_features, Fi, K, Hf, Wf, spatial_scale, ph, pw, box_scale, sampling, aligned, d_pooled, d_ok);
+    g.boxes = d_tracks; g.boxes_f64 = tracks_f64 ? 1 : 0; g.ld = ld;
+    g.slot = d_slot; g.T = T; g.F = F; g.f0 = f0; g.N = cap;
+    if ((rc = roi_launch(c, g, feat_dtype, mode))) return rc;
     HIPCHK(c, hipGetLastError());
     return VDET_OK;
 }

@@ -2481,6 +2481,50 @@ def _patch_common(images, crop_size, padding, mean, mode, dtype):
     return S, padding, _PATCH_MODES[mode], _PATCH_DTYPES[dtype], mean
 
 
+def _boxes_and_index(boxes, image_idx, Fi, single):
+    """The box / image_idx checks rcnn_patches and roi_pool share -> N: boxes f32 / f64 [N,4], image_idx int32 [N] (None needs
+    Fi == 1; ``single``: that layout, for the message), both contiguous."""
+    if not torch.is_tensor(boxes) or boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError("boxes must be float32 / float64 [N,4]")
+    N = boxes.shape[0]
+    if image_idx is None:
+        if Fi != 1:
+            raise ValueError("image_idx=None needs a single image (%s)" % single)
+    elif not torch.is_tensor(image_idx) or image_idx.dtype != torch.int32 or tuple(image_idx.shape) != (N,):
+        raise ValueError("image_idx must be int32 [N]")
+    if not all(x is None or x.is_contiguous() for x in (boxes, image_idx)):
+        raise ValueError("boxes and image_idx must be contiguous")
+    return N
+
+
+def _tubelet_range(tracks, ntracks, frames, cap, Fi, who):
+    """The tubelet checks tubelet_patches and tubelet_rois share -> (C, T, F, ld, f0, f1, cap): tracks f32 / f64 [C,T,F,>=4],
+    ntracks int32 [C], both contiguous; frames a range of the video that ``who`` (Fi entries) covers; cap a window count."""
+    if not torch.is_tensor(tracks) or tracks.dtype not in (torch.float32, torch.float64) or tracks.dim() != 4 or tracks.shape[3] < 4:
+        raise ValueError("tracks must be float32 / float64 [C,T,F,>=4]")
+    C, T, F, ld = tracks.shape
+    if C < 1 or F < 1:
+        raise ValueError("at least one class and one frame")
+    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
+        raise ValueError("ntracks must be int32 [C]")
+    if C * max(T, 1) * F >= 2 ** 31 - 16:
+        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16)")
+    try:
+        f0, f1 = (int(x) for x in frames)
+    except (TypeError, ValueError):
+        raise ValueError("frames must be (f0, f1)")
+    if not 0 <= f0 < f1 <= F:
+        raise ValueError("frames must be a range 0 <= f0 < f1 <= F (F = %d)" % F)
+    if Fi != f1 - f0:
+        raise ValueError("%s must hold the f1 - f0 = %d frames of the range" % (who, f1 - f0))
+    cap = int(cap)
+    if not 0 <= cap < 2 ** 31 - 16:
+        raise ValueError("cap must be 0 .. 2^31 - 17 windows")
+    if not tracks.is_contiguous() or not ntracks.is_contiguous():
+        raise ValueError("tracks and ntracks must be contiguous")
+    return C, T, F, ld, f0, f1, cap
+
+
 def rcnn_patches(images, boxes, image_idx=None, offsets=None, crop_size=224, padding=16, mean=(103.939, 116.779, 123.68),
                  mode='warp', dtype=torch.float32, sync=True, ctx=None):
     """The CNN scorers' input windows on the device (include/vdet_hip.h: vdet_rcnn_patches): ``rcnn_img_crop`` +
@@ -2498,14 +2542,7 @@ def rcnn_patches(images, boxes, image_idx=None, offsets=None, crop_size=224, pad
     and with offsets ``sboxes`` f64 [N,num+1,4], the boxes used.  Parity of the resize rule with OpenCV is unpinned (DESIGN.md
     10j); the bits are those of tests/patch_spec.py.  No CPU fallback."""
     S, padding, mcode, dcode, mean = _patch_common(images, crop_size, padding, mean, mode, dtype)
-    if not torch.is_tensor(boxes) or boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 2 or boxes.shape[1] != 4:
-        raise ValueError("boxes must be float32 / float64 [N,4]")
-    N = boxes.shape[0]
-    if image_idx is None:
-        if images.shape[0] != 1:
-            raise ValueError("image_idx=None needs a single image ([1,H,W,3])")
-    elif not torch.is_tensor(image_idx) or image_idx.dtype != torch.int32 or tuple(image_idx.shape) != (N,):
-        raise ValueError("image_idx must be int32 [N]")
+    N = _boxes_and_index(boxes, image_idx, images.shape[0], "[1,H,W,3]")
     num = 0
     if offsets is not None:
         if not torch.is_tensor(offsets) or offsets.dtype != torch.float64 or offsets.dim() != 3 or offsets.shape[0] != N or offsets.shape[2] != 4:
@@ -2516,8 +2553,8 @@ def rcnn_patches(images, boxes, image_idx=None, offsets=None, crop_size=224, pad
     M = N * (num + 1)
     if M >= 2 ** 31 - 16:
         raise ValueError("too many windows (below 2^31 - 16)")
-    if not all(x is None or x.is_contiguous() for x in (boxes, image_idx, offsets)):
-        raise ValueError("boxes, image_idx and offsets must be contiguous")
+    if offsets is not None and not offsets.is_contiguous():
+        raise ValueError("offsets must be contiguous")
     _same_gpu((images, boxes, image_idx, offsets), "images, boxes, image_idx and offsets")
     dev = images.device
     patches = torch.empty((M, 3, S, S), dtype=dtype, device=dev)
@@ -2554,28 +2591,7 @@ def tubelet_patches(images, tracks, ntracks, frames, cap, crop_size=224, padding
         series[c, t, f] = net(out['patches'][:n]).double()
         det, pooled, tboxes, src = rescore_tubelets(tracks, ntracks, boxes, scores, floor=series)"""
     S, padding, mcode, dcode, mean = _patch_common(images, crop_size, padding, mean, mode, dtype)
-    if not torch.is_tensor(tracks) or tracks.dtype not in (torch.float32, torch.float64) or tracks.dim() != 4 or tracks.shape[3] < 4:
-        raise ValueError("tracks must be float32 / float64 [C,T,F,>=4]")
-    C, T, F, ld = tracks.shape
-    if C < 1 or F < 1:
-        raise ValueError("at least one class and one frame")
-    if not torch.is_tensor(ntracks) or ntracks.dtype != torch.int32 or tuple(ntracks.shape) != (C,):
-        raise ValueError("ntracks must be int32 [C]")
-    if C * max(T, 1) * F >= 2 ** 31 - 16:
-        raise ValueError("too many tubelet boxes (C*T*F must stay below 2^31 - 16)")
-    try:
-        f0, f1 = (int(x) for x in frames)
-    except (TypeError, ValueError):
-        raise ValueError("frames must be (f0, f1)")
-    if not 0 <= f0 < f1 <= F:
-        raise ValueError("frames must be a range 0 <= f0 < f1 <= F (F = %d)" % F)
-    if images.shape[0] != f1 - f0:
-        raise ValueError("images must hold the f1 - f0 = %d frames of the range" % (f1 - f0))
-    cap = int(cap)
-    if not 0 <= cap < 2 ** 31 - 16:
-        raise ValueError("cap must be 0 .. 2^31 - 17 windows")
-    if not tracks.is_contiguous() or not ntracks.is_contiguous():
-        raise ValueError("tracks and ntracks must be contiguous")
+    C, T, F, ld, f0, f1, cap = _tubelet_range(tracks, ntracks, frames, cap, images.shape[0], "images")
     _same_gpu((images, tracks, ntracks), "images, tracks and ntracks")
     dev = images.device
     patches = torch.empty((cap, 3, S, S), dtype=dtype, device=dev)
@@ -2590,6 +2606,112 @@ def tubelet_patches(images, tracks, ntracks, frames, cap, crop_size=224, padding
     if sync:
         ctx.sync()
     return dict(patches=patches, slot=slot, count=count, ok=ok)
+
+
+_ROI_MODES = {'max': 0, 'align': 1}       # include/vdet_hip.h: VDET_ROI_MAX / VDET_ROI_ALIGN
+
+
+def _roi_common(features, spatial_scale, pooled, box_scale, mode, sampling):
+    """The checks roi_pool and tubelet_rois share: (feature dtype code, spatial_scale, ph, pw, box_scale, mode code, sampling)."""
+    if not torch.is_tensor(features) or features.dtype not in _PATCH_DTYPES or features.dim() != 4 or 0 in features.shape:
+        raise ValueError("features must be float32 / float16 / bfloat16 [Fi,K,Hf,Wf] with no empty dimension")
+    if not features.is_contiguous():
+        raise ValueError("features must be contiguous NCHW (channels_last is not supported)")
+    if not features.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if features.shape[2] > 32767 or features.shape[3] > 32767:
+        raise ValueError("feature maps of at most 32767 x 32767")
+    try:
+        ph, pw = (int(x) for x in pooled)
+    except (TypeError, ValueError):
+        raise ValueError("pooled must be (ph, pw)")
+    if not (1 <= ph <= 32 and 1 <= pw <= 32):
+        raise ValueError("pooled = (%d, %d); 1 .. 32 each" % (ph, pw))
+    if mode not in _ROI_MODES:
+        raise ValueError("mode must be 'max' or 'align'")
+    sampling = int(sampling)
+    if mode == 'align' and not 1 <= sampling <= 8:
+        raise ValueError("sampling = %d; 1 .. 8 (the adaptive grid is not provided)" % sampling)
+    spatial_scale, box_scale = float(spatial_scale), float(box_scale)
+    if not (0.0 < float(np.float32(spatial_scale)) < float('inf')) or not np.isfinite(box_scale):
+        raise ValueError("spatial_scale must be positive and finite, box_scale finite")
+    return _PATCH_DTYPES[features.dtype], spatial_scale, ph, pw, box_scale, _ROI_MODES[mode], sampling
+
+
+def roi_pool(features, boxes, image_idx=None, spatial_scale=1 / 16., pooled=(7, 7), box_scale=1.0, mode='max', sampling=2,
+             aligned=False, sync=True, ctx=None):
+    """RoI pooling on the device (include/vdet_hip.h: vdet_roi_pool): the front half of the Fast R-CNN route -- the backbone
+    runs once per image and every box is pooled out of its feature map, all RoIs of the call in one launch.
+
+    features f32 / f16 / bf16 [Fi,K,Hf,Wf], contiguous NCHW (anything else, channels_last included: ValueError); boxes [N,4]
+    f32 / f64 as they are (no 1-based shift); image_idx int32 [N] (None: a single image).  A RoI is
+    ``f32(f64(box) * box_scale)`` -- ``box_scale`` is the image resize factor of ``im_detect`` -- and ``spatial_scale`` maps
+    it to cells.  ``pooled = (ph, pw)``, 1 .. 32 each.  ``mode='max'``: Caffe's ROIPoolingLayer forward (rounded cell box, f32
+    bin edges, an empty bin is 0, NaN and -inf cells never win).  ``mode='align'``: RoIAlign with a fixed grid of
+    ``sampling`` x ``sampling`` (1 .. 8) bilinear samples per bin, ``aligned`` the half-pixel shift.  Both rules are RESTATED
+    from public code that was not at hand; the bits are those of tests/roipool_spec.py.
+
+    Returns a dict: ``pooled`` [N,K,ph,pw] in features.dtype (the f32 value rounded once), ``ok`` uint8 [N]: 0 -- and an
+    all-zero block -- where a RoI coordinate is not finite, exceeds 2^24 cells, or the image index is out of range.  A RoI
+    wholly off the map is ok and all zeros.  N = 0 is legal; N*K*ph*pw may exceed 2^31.  No CPU fallback."""
+    dcode, spatial_scale, ph, pw, box_scale, mcode, sampling = _roi_common(features, spatial_scale, pooled, box_scale, mode, sampling)
+    N = _boxes_and_index(boxes, image_idx, features.shape[0], "[1,K,Hf,Wf]")
+    if N >= 2 ** 31 - 16:
+        raise ValueError("too many RoIs (below 2^31 - 16)")
+    _same_gpu((features, boxes, image_idx), "features, boxes and image_idx")
+    Fi, K, Hf, Wf = features.shape
+    dev = features.device
+    out = torch.empty((N, K, ph, pw), dtype=features.dtype, device=dev)
+    ok = torch.empty((N,), dtype=torch.uint8, device=dev)
+    ctx = _ctx_for(features, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_roi_pool(ctx.h, features.data_ptr(), dcode, Fi, K, Hf, Wf, ptr(boxes), int(boxes.dtype == torch.float64), N,
+                                    ptr(image_idx), spatial_scale, ph, pw, box_scale, mcode, sampling, int(bool(aligned)), ptr(out),
+                                    ptr(ok)))
+    if sync:
+        ctx.sync()
+    return dict(pooled=out, ok=ok)
+
+
+def tubelet_rois(features, tracks, ntracks, frames, cap, spatial_scale=1 / 16., pooled=(7, 7), box_scale=1.0, mode='max', sampling=2,
+                 aligned=False, sync=True, ctx=None):
+    """``roi_pool`` for the tubelet boxes of the frames ``frames = (f0, f1)``, f0 <= f < f1, straight from device tubelets
+    (include/vdet_hip.h: vdet_tubelet_rois): the input of ``fast_rcnn_cls`` (vdet/tubelet_cls.py:53-76) for those frames.
+
+    tracks, ntracks, cap, ``slot``, ``count`` and the order of the compacted boxes (frames, classes, slots; present: t <
+    ntracks[c] and x1 not NaN) are ``tubelet_patches``'; features [f1-f0,K,Hf,Wf], features[f - f0] is frame f's map.
+    Returns a dict: ``pooled`` [cap,K,ph,pw], ``slot`` int32 [cap,3] rows (c,t,f), -1 behind the count, ``count`` int32 [1]:
+    the TRUE number of present boxes, ``ok`` uint8 [cap].  ``count > cap`` raises ValueError when the call -- with
+    ``sync=False`` a later ``ctx.sync()`` -- waits; the first ``cap`` blocks are valid then.  The other options are
+    ``roi_pool``'s.
+
+    The round trip for a chunk of frames, with any torch ``backbone`` and ``head`` (one score per pooled block)::
+
+        feats = backbone(images[f0:f1])                                   # [f1-f0,K,Hf,Wf], once per frame
+        out = tubelet_rois(feats, tracks, ntracks, (f0, f1), cap)
+        n = int(out['count']); c, t, f = out['slot'][:n].long().unbind(1)
+        series[c, t, f] = head(out['pooled'][:n]).double()                # series [C,T,F] f64, NaN where nothing is scored
+        det, pooled, tboxes, src = rescore_tubelets(tracks, ntracks, boxes, scores, floor=series)
+
+    or, for the TCN, the head's feature rows scattered the same way into the [C,T,F,ch] tensor that
+    ``tcn_tracks(wide={'feats': ...})`` reads."""
+    dcode, spatial_scale, ph, pw, box_scale, mcode, sampling = _roi_common(features, spatial_scale, pooled, box_scale, mode, sampling)
+    C, T, F, ld, f0, f1, cap = _tubelet_range(tracks, ntracks, frames, cap, features.shape[0], "features")
+    _same_gpu((features, tracks, ntracks), "features, tracks and ntracks")
+    Fi, K, Hf, Wf = features.shape
+    dev = features.device
+    out = torch.empty((cap, K, ph, pw), dtype=features.dtype, device=dev)
+    ok = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    slot = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    ctx = _ctx_for(features, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_tubelet_rois(ctx.h, features.data_ptr(), dcode, Fi, K, Hf, Wf, ptr(tracks), int(tracks.dtype == torch.float64),
+                                        C, T, F, ld, ntracks.data_ptr(), f0, f1, cap, spatial_scale, ph, pw, box_scale, mcode, sampling,
+                                        int(bool(aligned)), ptr(out), ptr(ok), ptr(slot), count.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(pooled=out, slot=slot, count=count, ok=ok)
 
 
 _FEAT_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}     # include/vdet_hip.h: VDET_FEAT_*

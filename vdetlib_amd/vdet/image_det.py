@@ -1,7 +1,9 @@
 """Still-image NMS wrapper (:117-123), the SVM scorer (:109-114) and the R-CNN feature loop of the reference's
 vdet/image_det.py: ``googlenet_features`` / ``googlenet_rcnn`` (:56-106) warp their windows on the GPU (``ops.rcnn_patches``,
 DESIGN.md section 10j) and drive any pycaffe-like ``net`` through the reference's blob protocol; the nets themselves are the
-caller's.  Out of scope: ``simple_crop`` / ``googlenet_det`` (:12-53, a fixed-point uint8 resize) and ``fast_rcnn_det``."""
+caller's.  ``fast_rcnn_det`` (:22-33) and the ``im_detect`` it calls run the Fast R-CNN route: any torch backbone and head of
+the caller's around ``ops.roi_pool``, the box decode on the host in numpy float64.
+Out of scope: ``simple_crop`` / ``googlenet_det`` (:12-53, a fixed-point uint8 resize)."""
 import numpy as np
 
 from ..utils.cython_nms import nms
@@ -62,6 +64,71 @@ def googlenet_features(img, boxes, net, blob_name):
                 logging.error("Unable to concatenate features.")
                 raise e
     return np.asarray(features)
+
+
+def bbox_transform_inv(boxes, deltas):
+    """The box decode of Fast R-CNN's ``im_detect``, restated (the public code was not at hand): boxes [N,4], deltas [N,4*Cn]
+    -> float64 [N,4*Cn].  Per box ``w = x2 - x1 + 1e-14``, ``ctr = x1 + 0.5*w``; per class ``pred_ctr = d*w + ctr``,
+    ``pred_w = exp(dw)*w``, corners ``pred_ctr -/+ 0.5*pred_w``; y alike.  numpy float64 on the host, as the reference does."""
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    deltas = np.asarray(deltas, dtype=np.float64)
+    pred = np.zeros(deltas.shape, dtype=np.float64)
+    if len(boxes) == 0:
+        return pred
+    w = boxes[:, 2] - boxes[:, 0] + 1e-14
+    h = boxes[:, 3] - boxes[:, 1] + 1e-14
+    cx, cy = boxes[:, 0] + 0.5 * w, boxes[:, 1] + 0.5 * h
+    pcx = deltas[:, 0::4] * w[:, None] + cx[:, None]
+    pcy = deltas[:, 1::4] * h[:, None] + cy[:, None]
+    pw = np.exp(deltas[:, 2::4]) * w[:, None]
+    ph = np.exp(deltas[:, 3::4]) * h[:, None]
+    pred[:, 0::4] = pcx - 0.5 * pw
+    pred[:, 1::4] = pcy - 0.5 * ph
+    pred[:, 2::4] = pcx + 0.5 * pw
+    pred[:, 3::4] = pcy + 0.5 * ph
+    return pred
+
+
+def clip_boxes(boxes, im_shape):
+    """x to [0, W-1], y to [0, H-1] (im_shape = (H, W, ...)) -> a new array."""
+    boxes = np.array(boxes, dtype=np.float64)
+    boxes[:, 0::2] = np.maximum(np.minimum(boxes[:, 0::2], im_shape[1] - 1), 0)
+    boxes[:, 1::2] = np.maximum(np.minimum(boxes[:, 1::2], im_shape[0] - 1), 0)
+    return boxes
+
+
+def im_detect(net, img, boxes):
+    """``fast_rcnn.test.im_detect``'s shape: (scores [N,Cn], pred_boxes [N,4*Cn]) as numpy, for the boxes [N,4] of ``img``
+    [H,W,3] (image coordinates, as they are).  A valid ``det_fun`` of ``video_det.fast_rcnn_det_vid``.
+
+    ``net`` is any object with ``prepare(img) -> (tensor [1,3,H',W'] on the GPU, im_scale)`` -- the mean subtraction and the
+    image resize are the caller's, as the net is -- ``backbone(x) -> [1,K,Hf,Wf]``, ``head(pooled) -> (scores, deltas)``,
+    ``spatial_scale`` and ``pooled``; optionally ``roi_mode`` ('max'), ``sampling`` and ``aligned`` (``ops.roi_pool``).  The
+    backbone runs once, every box is pooled out of its map on the device (``box_scale = im_scale``), the decode
+    (``bbox_transform_inv``, ``clip_boxes``) is numpy float64 on the host.  The reference de-duplicates RoIs that fall on the
+    same cells first; that changes no result and is left out.  ValueError for a box that is not finite."""
+    import torch
+    from .. import _lib, ops
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 4))
+    with torch.no_grad():
+        x, im_scale = net.prepare(img)
+        feat = net.backbone(x)
+        out = ops.roi_pool(feat.contiguous(), torch.from_numpy(boxes).to(feat.device), spatial_scale=net.spatial_scale,
+                           pooled=net.pooled, box_scale=im_scale, mode=getattr(net, 'roi_mode', 'max'),
+                           sampling=getattr(net, 'sampling', 2), aligned=getattr(net, 'aligned', False))
+        bad = (out['ok'] == 0).nonzero()
+        if bad.numel():
+            raise ValueError("im_detect: box %d is not finite (or beyond 2^24 cells)" % int(bad[0]))
+        scores, deltas = net.head(out['pooled'])
+    scores, deltas = scores.detach().cpu().numpy(), deltas.detach().cpu().numpy()
+    return scores, clip_boxes(bbox_transform_inv(boxes, deltas), np.shape(img))
+
+
+def fast_rcnn_det(img, boxes, net):
+    """:22-33 -- the scores of ``im_detect`` (there is no Caffe log level to lower here)."""
+    scores, _ = im_detect(net, img, np.array(boxes))
+    return scores
 
 
 def svm_scores(features, svm_model):

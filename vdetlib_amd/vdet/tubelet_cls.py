@@ -9,7 +9,10 @@ its windows are warped on the GPU (``ops.rcnn_patches``) and everything after it
 of the SVM, the max over a box's sampled windows, the winning box -- is ``ops.svm_head`` (DESIGN.md
 section 10k).
 
-Out of scope (external Caffe engines): fast_rcnn_cls, googlenet_cls (:53-100).
+``fast_rcnn_cls`` (:53-76) follows the reference's frame loop around ``image_det.im_detect``: backbone and head are
+the caller's torch callables, the pooling between them is ``ops.roi_pool``.
+
+Out of scope: googlenet_cls (:79-100, the fixed-point uint8 crop of ``googlenet_det``).
 ``rcnn_sampling_dets_scoring`` (:196-260) has no dict-level form; its half after the CNN is
 ``ops.rescore_tubelets(floor=...)`` on the scores ``ops.svm_head`` writes.
 """
@@ -18,11 +21,12 @@ from collections import defaultdict
 
 import numpy as np
 
-from ..utils.protocol import frame_path_at, tubelet_box_at_frame, tubelets_overlap, tubelets_proto_from_tracks_proto
+from ..utils.protocol import bbox_hash, frame_path_at, track_box_at_frame, tubelet_box_at_frame, tubelets_overlap, \
+    tubelets_proto_from_tracks_proto
 from ..utils.common import imread, svm_from_rcnn_model
 from ..utils.log import logger as logging
 from .dataset import imagenet_vdet_classes, index_vdet_to_det
-from .image_det import googlenet_features
+from .image_det import googlenet_features, im_detect
 from .. import hot
 
 
@@ -106,6 +110,28 @@ def score_conv_cls_batched(score_proto, net):
         for box, p in zip(tubelet['boxes'], probs):
             box['conv_score'] = float(p)
     return out
+
+
+def fast_rcnn_cls(video_proto, track_proto, net, class_idx, images=None):
+    """:53-76 -- per frame, the boxes of the tracks that have one there go through ``im_detect`` (one backbone pass, every box
+    pooled on the device) and each track gets {frame, bbox: the decoded box row (all classes, as the reference's
+    ``list(box)``), score: column ``class_idx``, hash}; a frame where a track has no box adds nothing to it.  ``net``: see
+    ``image_det.im_detect``.  ``images``: {frame id: uint8 [H,W,3]} instead of reading the frames' files.  A frame without
+    any box is skipped (the reference's ``im_detect`` has nothing to reshape there)."""
+    new_tracks = [[] for _ in track_proto['tracks']]
+    for frame in video_proto['frames']:
+        frame_id = frame['frame']
+        img = images[frame_id] if images is not None else imread(frame_path_at(video_proto, frame_id))
+        boxes = [track_box_at_frame(tracklet, frame_id) for tracklet in track_proto['tracks']]
+        valid_boxes = np.asarray([box for box in boxes if box is not None])
+        valid_index = [i for i in range(len(boxes)) if boxes[i] is not None]
+        if not valid_index:
+            continue
+        scores, pred_boxes = im_detect(net, img, valid_boxes)
+        for score, box, track_id in zip(scores, pred_boxes, valid_index):
+            new_tracks[track_id].append({"frame": frame_id, "bbox": list(box), "score": score[class_idx],
+                                         "hash": bbox_hash(video_proto['video'], frame_id, box)})
+    return new_tracks
 
 
 def sampling_boxes(orig_box, num, ratio=0.05, return_orig=True):
