@@ -39,6 +39,8 @@
  *   edges of one suppression graph         < 2^32                     VDET_ENOMEM
  *   survivors per (frame, class)           cap (caller's choice)      VDET_ECAP latched, count still written
  *   vdet_det_nms_volume top-k              1 <= topk <= 128           VDET_EINVAL
+ *   box decode (vdet_decode_boxes, vdet_det_nms_volume_deltas, vdet_tubelet_dets)   H, W >= 1; rois, deltas and box outputs
+ *                                          16-byte aligned; N*K <= 2^40 (vdet_decode_boxes), C*T*F < 2^31 - 16    VDET_EINVAL
  *   temporal window / taps                 odd, <= 31                 VDET_EINVAL (the one-pass volume kernel: 3 or 5, other
  *                                                                     windows run the separate kernels)
  *   frames per video, vdet_video_batch     none                       videos of more than 1536 frames re-score their tubelet
@@ -442,6 +444,63 @@ int vdet_nms_volume_topk(vdet_ctx *ctx, const float *d_boxes, const float *d_sco
 int vdet_det_nms_volume(vdet_ctx *ctx, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t K,
                         int class0, int use_score_thresh, float score_thresh, int topk, double nms_thresh,
                         float *d_dets, int32_t *d_sel_idx, int32_t *d_det_cnt, int32_t *d_keep, int32_t *d_keep_cnt);
+
+/*
+ * The Fast R-CNN box decode on the device: image_det.bbox_transform_inv followed by clip_boxes, per box and class.
+ * THE rule, bit for bit, is tests/decode_spec.py.  With the roi (x1,y1,x2,y2) widened exactly to f64 and the class's deltas
+ * (dx,dy,dw,dh) f32 widened exactly:
+ *     w = (x2 - x1) + 1e-14,  cx = x1 + 0.5*w,  pcx = dx*w + cx,  pw = E(dw)*w,  X1 = pcx - 0.5*pw,  X2 = pcx + 0.5*pw
+ * (y alike); every product and sum is one f64 operation (no fused multiply-add), then x is clipped to [0, W-1] and y to
+ * [0, H-1] -- clip(v, hi) = NaN if v is NaN, hi if v > hi, v if v > 0, else +0.0: numpy's maximum(minimum(v, hi), 0), a NaN
+ * stays and -0.0 becomes +0.0 -- and rounded ONCE to f32.  E is an exponential as a fixed sequence of f64 operations
+ * (k = rint(x*log2e), r = (x - k*ln2_hi) - k*ln2_lo, a degree-13 Horner polynomial with coefficients 1/n!, ldexp): within
+ * 2 units in the last place of exp; NaN -> NaN, x > 709 -> +inf, x < -708 -> +0.0.  dw is not clamped.  A roi or delta that
+ * is not finite gives NaN or clipped coordinates, never an error.
+ *   d_rois   [N,4] f32 or f64 (rois_f64), d_deltas [N,K,4] f32 (== the head's [N, 4K] rows), d_boxes [N,K,4] f32; all three
+ *   16-byte aligned (VDET_EINVAL otherwise).  H, W >= 1.  N*K up to 2^40; N = 0 or K = 0 is legal.  One launch.
+ */
+int vdet_decode_boxes(vdet_ctx *ctx, const void *d_rois, int rois_f64, const float *d_deltas, int64_t N, int64_t K, int64_t H,
+                      int64_t W, float *d_boxes);
+
+/*
+ * vdet_det_nms_volume reading the head's output instead of decoded boxes: d_rois [F,B,4] f32 or f64 (rois_f64), d_deltas
+ * [F,B,K,4] f32, both 16-byte aligned (VDET_EINVAL otherwise), H, W >= 1.  The selection is the same one, on the scores; the
+ * wave of a (frame, class) then decodes its <= topk candidates at the gather (vdet_decode_boxes' rule) and goes on as
+ * vdet_det_nms_volume does.  No [F,B,K,4] tensor exists at any point.  Every output, and every status vdet_sync reports, is
+ * bit for bit that of vdet_det_nms_volume on vdet_decode_boxes' output.  Limits and the remaining arguments are
+ * vdet_det_nms_volume's.
+ */
+int vdet_det_nms_volume_deltas(vdet_ctx *ctx, const void *d_rois, int rois_f64, const float *d_scores, const float *d_deltas,
+                               int64_t F, int64_t B, int64_t K, int64_t H, int64_t W, int class0, int use_score_thresh,
+                               float score_thresh, int topk, double nms_thresh, float *d_dets, int32_t *d_sel_idx,
+                               int32_t *d_det_cnt, int32_t *d_keep, int32_t *d_keep_cnt);
+
+/*
+ * The tubelet side of the decode (what fast_rcnn_cls computes per tubelet box): for the compact row n < count of
+ * vdet_tubelet_rois with d_slot[n] = (c,t,f) and col = d_cols[c] (d_cols NULL: c + 1, column 0 being the background)
+ *     d_det[c,t,f]    = (double)d_scores[n, col]
+ *     d_tboxes[c,t,f] = decode(d_tracks[c,t,f,0:4], d_deltas[n, 4*col : 4*col+4])          (vdet_decode_boxes' rule)
+ *   d_scores [N,K] f32, d_deltas [N,K,4] f32 (16-byte aligned), d_tracks [C,T,F,ld] f32 or f64 (tracks_f64), ld >= 4,
+ *   d_slot [N,3] int32, d_count [1] int32 or NULL (all N rows; rows behind the count are not read), d_cols [C] int32 or NULL,
+ *   d_det [C,T,F] f64, d_tboxes [C,T,F,4] f32 (16-byte aligned).  Slots that no row names are left untouched.
+ * A slot outside (C,T,F) or a column outside 0..K-1 latches VDET_EINVAL (reported by vdet_sync); that row is skipped.
+ * C, T, F >= 1, C*T*F < 2^31 - 16.  One launch, one thread per row.
+ */
+int vdet_tubelet_dets(vdet_ctx *ctx, const float *d_scores, const float *d_deltas, int64_t N, int64_t K, const void *d_tracks,
+                      int tracks_f64, int ld, const int32_t *d_slot, const int32_t *d_count, int64_t C, int T, int64_t F,
+                      const int32_t *d_cols, int64_t H, int64_t W, double *d_det, float *d_tboxes);
+
+/*
+ * vdet_det_nms_volume[_deltas]' outputs in the rank layout vdet_nms_tracks writes, C = K - class0 classes, R = topk ranks:
+ *   d_tracks [C,R,F,5] f32: the kept rows of (frame f, class class0 + c) in keep order (descending score),
+ *   d_score [C,R,F] f64 the row's score, d_src [C,R,F] int32 the row's box index (d_sel_idx), d_cnt [C,F] = d_keep_cnt,
+ *   d_ntracks [C] = the maximum of d_cnt over the frames (an integer atomic maximum).  Behind the counts: NaN, INT32_MIN.
+ * d_dets must be given ([F,K,topk,5]).  A keep count beyond topk is read as topk, a kept row outside 0..topk-1 as a row behind
+ * the count.  F, K >= 1, 0 <= class0 < K, 1 <= topk <= 128, K*topk*F < 2^31 - 16.  One launch (and a memset of d_ntracks).
+ */
+int vdet_dets_as_tracks(vdet_ctx *ctx, const float *d_dets, const int32_t *d_sel_idx, const int32_t *d_keep,
+                        const int32_t *d_keep_cnt, int64_t F, int64_t K, int topk, int class0, float *d_tracks, double *d_score,
+                        int32_t *d_src, int32_t *d_cnt, int32_t *d_ntracks);
 
 /*
  * vdet_nms_volume with the CALLER's order instead of the build's: d_order [F,C,B] uint16 lists every (frame, class)

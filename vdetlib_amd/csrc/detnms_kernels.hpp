@@ -37,7 +37,15 @@ struct DetNmsParams {
     int *status;
 };
 
-__global__ __launch_bounds__(256) void det_nms_kernel(const DetNmsParams prm)
+// where a candidate's box comes from: box_of(e, f, id) for box id of frame f, e = (f*B + id)*K + j its class slot.  This one
+// reads the [F,B,K] volume; decode_kernels.hpp has the one that decodes the head's deltas at the gather
+struct DetBoxFromVolume {
+    const float4 *boxes;
+    __device__ __forceinline__ float4 operator()(int64_t e, int, int) const { return boxes[e]; }
+};
+
+template <class BoxOf>
+__device__ __forceinline__ void det_nms_body(const DetNmsParams &prm, const BoxOf &box_of)
 {
     __shared__ float4 sbox[4][kDetMax];
     __shared__ int sidx[4][kDetMax];
@@ -64,7 +72,7 @@ __global__ __launch_bounds__(256) void det_nms_kernel(const DetNmsParams prm)
         sc[h] = 0.f;
         if (q < M) {
             const int64_t e = ((int64_t)f * prm.B + id[h]) * prm.K + j;
-            bx[h] = prm.boxes[e];
+            bx[h] = box_of(e, f, id[h]);
             sc[h] = prm.scores[e];
             sbox[w][q] = bx[h];
             sidx[w][q] = id[h];
@@ -164,6 +172,11 @@ __global__ __launch_bounds__(256) void det_nms_kernel(const DetNmsParams prm)
         prm.keep_cnt[p] = __popcll(klo) + __popcll(khi);
         if (bad) atomicOr(prm.status, kStDivZero);
     }
+}
+
+__global__ __launch_bounds__(256) void det_nms_kernel(const DetNmsParams prm)
+{
+    det_nms_body(prm, DetBoxFromVolume{prm.boxes});
 }
 
 }  // namespace vdet

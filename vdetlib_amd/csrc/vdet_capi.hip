@@ -21,6 +21,7 @@
 #include "binsort_kernels.hpp"
 #include "small_kernels.hpp"
 #include "detnms_kernels.hpp"
+#include "decode_kernels.hpp"
 #include "fused_kernels.hpp"
 #include "adjrows_kernels.hpp"
 #include "graphlists_kernels.hpp"
@@ -450,6 +451,7 @@ int translate_status(vdet_ctx *c, int st)
     if (st & kStBadKeep) return fail(c, VDET_EINVAL, "nms_tracks: a keep_cnt outside 0..cap or a keep_idx outside 0..B-1 (the entry is skipped)");
     if (st & kStPatchCap) return fail(c, VDET_ECAP, "tubelet_patches / tubelet_rois: more present tubelet boxes in the frame range than cap (the first cap windows are valid)");
     if (st & kStSvmBad) return fail(c, VDET_EINVAL, "svm_head: a slot row outside shape or a class column outside W (the group is skipped, nothing is written for it)");
+    if (st & kStDecodeBad) return fail(c, VDET_EINVAL, "tubelet_dets: a slot row outside shape or a class column outside K (the row is skipped, nothing is written for it)");
     if (st & kStEvalList) return fail(c, VDET_EINVAL, "a keep list holds a NaN score, an increasing score or a count / box index out of range");
     if (st & kStDivZero) return fail(c, VDET_EDIVZERO, "float division (zero union)");
     if (st & kStCap) return fail(c, VDET_ECAP, "more survivors than the output capacity");
@@ -2099,12 +2101,21 @@ int vdet_nms_volume_topk(vdet_ctx *c, const float *d_boxes, const float *d_score
 // The Fast R-CNN per-class flow (vdet/video_det.py:89-99 + vdet/image_det.py:117-123): every class suppresses its OWN
 // regressed boxes.  Selection (score > thresh, best topk) = the LSD sort's threshold + top-k on the [F,B,K] score
 // volume; then one wave per (frame, class) on its <= 128 selected boxes (detnms_kernels.hpp).
-int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t K, int class0,
-                        int use_score_thresh, float score_thresh, int topk, double nms_thresh, float *d_dets, int32_t *d_sel_idx,
-                        int32_t *d_det_cnt, int32_t *d_keep, int32_t *d_keep_cnt)
+// The boxes come from d_boxes [F,B,K,4], or -- dec given -- are decoded at the gather from the head's output (vdet_det_nms_volume_deltas).
+struct DetDecodeSrc {
+    const void *rois;
+    int rois_f64;
+    const float *deltas;
+    int64_t H, W;
+};
+
+static int det_nms_volume_impl(vdet_ctx *c, const float *d_boxes, const DetDecodeSrc *dec, const float *d_scores, int64_t F, int64_t B,
+                               int64_t K, int class0, int use_score_thresh, float score_thresh, int topk, double nms_thresh,
+                               float *d_dets, int32_t *d_sel_idx, int32_t *d_det_cnt, int32_t *d_keep, int32_t *d_keep_cnt)
 {
     if (!c) return VDET_EINVAL;
     if (F < 0 || B < 0 || K < 0 || class0 < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (dec && (dec->H < 1 || dec->W < 1)) return fail(c, VDET_EINVAL, "im_size: H and W must be at least 1");
     if (topk < 1 || topk > kDetMax) return fail(c, VDET_EINVAL, "topk = %d; the per-class NMS takes 1..%d boxes per (frame, class)", topk, kDetMax);
     if (F == 0 || K == 0) return VDET_OK;
     if (!d_det_cnt || !d_keep || !d_keep_cnt) return fail(c, VDET_EINVAL, "null output");
@@ -2117,8 +2128,13 @@ int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores
         HIPCHK(c, hipMemsetAsync(d_keep_cnt, 0, (size_t)(F * K) * 4, c->stream));
         return VDET_OK;
     }
-    if (!d_boxes || !d_scores) return fail(c, VDET_EINVAL, "null buffer");
-    if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    if (dec) {
+        if (!dec->rois || !dec->deltas || !d_scores) return fail(c, VDET_EINVAL, "null buffer");
+        if ((((uintptr_t)dec->rois | (uintptr_t)dec->deltas) & 15) != 0) return fail(c, VDET_EINVAL, "d_rois and d_deltas must be 16-byte aligned");
+    } else {
+        if (!d_boxes || !d_scores) return fail(c, VDET_EINVAL, "null buffer");
+        if (((uintptr_t)d_boxes & 15) != 0) return fail(c, VDET_EINVAL, "d_boxes must be 16-byte aligned");
+    }
     // (no suppression graph is shared between classes here)
     int rc = volume_groups(c, F, B);
     if (rc) return rc;
@@ -2137,7 +2153,127 @@ int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores
     dp.status = &c->d_cnt->status;
     {
         StageTimer tm(c, ST_WALK);
-        hipLaunchKernelGGL(det_nms_kernel, dim3((unsigned)((F * K + 3) / 4)), dim3(256), 0, c->stream, dp);
+        const dim3 grid((unsigned)((F * K + 3) / 4));
+        if (!dec) {
+            hipLaunchKernelGGL(det_nms_kernel, grid, dim3(256), 0, c->stream, dp);
+        } else if (dec->rois_f64) {
+            const DetBoxFromDeltas<true> src{dec->rois, reinterpret_cast<const float4 *>(dec->deltas), (int)B, (double)(dec->W - 1), (double)(dec->H - 1)};
+            hipLaunchKernelGGL(det_nms_deltas_kernel<true>, grid, dim3(256), 0, c->stream, dp, src);
+        } else {
+            const DetBoxFromDeltas<false> src{dec->rois, reinterpret_cast<const float4 *>(dec->deltas), (int)B, (double)(dec->W - 1), (double)(dec->H - 1)};
+            hipLaunchKernelGGL(det_nms_deltas_kernel<false>, grid, dim3(256), 0, c->stream, dp, src);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_det_nms_volume(vdet_ctx *c, const float *d_boxes, const float *d_scores, int64_t F, int64_t B, int64_t K, int class0,
+                        int use_score_thresh, float score_thresh, int topk, double nms_thresh, float *d_dets, int32_t *d_sel_idx,
+                        int32_t *d_det_cnt, int32_t *d_keep, int32_t *d_keep_cnt)
+{
+    return det_nms_volume_impl(c, d_boxes, nullptr, d_scores, F, B, K, class0, use_score_thresh, score_thresh, topk, nms_thresh, d_dets,
+                               d_sel_idx, d_det_cnt, d_keep, d_keep_cnt);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The box decode of the Fast R-CNN route (decode_kernels.hpp; THE rule: tests/decode_spec.py)
+static int decode_size_check(vdet_ctx *c, int64_t H, int64_t W)
+{
+    if (H < 1 || W < 1) return fail(c, VDET_EINVAL, "im_size: H and W must be at least 1");
+    return VDET_OK;
+}
+
+int vdet_decode_boxes(vdet_ctx *c, const void *d_rois, int rois_f64, const float *d_deltas, int64_t N, int64_t K, int64_t H, int64_t W,
+                      float *d_boxes)
+{
+    if (!c) return VDET_EINVAL;
+    if (N < 0 || K < 0 || K > 0x7FFFFFF0ll) return fail(c, VDET_EINVAL, "bad shape");
+    if (decode_size_check(c, H, W)) return VDET_EINVAL;
+    if (N == 0 || K == 0) return VDET_OK;
+    if (!fits_upto(1ll << 40, {N, K})) return fail(c, VDET_EINVAL, "too many boxes for one launch (N*K up to 2^40)");
+    if (!d_rois || !d_deltas || !d_boxes) return fail(c, VDET_EINVAL, "null buffer");
+    if ((((uintptr_t)d_rois | (uintptr_t)d_deltas | (uintptr_t)d_boxes) & 15) != 0)
+        return fail(c, VDET_EINVAL, "d_rois, d_deltas and d_boxes must be 16-byte aligned");
+    const int64_t blocks = (N * K + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return fail(c, VDET_EINVAL, "too many boxes for one launch");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    DecodeArgs a{};
+    a.rois = d_rois; a.deltas = reinterpret_cast<const float4 *>(d_deltas); a.N = N; a.K = (int)K;
+    a.wmax = (double)(W - 1); a.hmax = (double)(H - 1);
+    a.boxes = reinterpret_cast<float4 *>(d_boxes);
+    {
+        StageTimer tm(c, ST_OTHER);
+        if (rois_f64) hipLaunchKernelGGL(decode_boxes_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(decode_boxes_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_det_nms_volume_deltas(vdet_ctx *c, const void *d_rois, int rois_f64, const float *d_scores, const float *d_deltas, int64_t F,
+                               int64_t B, int64_t K, int64_t H, int64_t W, int class0, int use_score_thresh, float score_thresh,
+                               int topk, double nms_thresh, float *d_dets, int32_t *d_sel_idx, int32_t *d_det_cnt, int32_t *d_keep,
+                               int32_t *d_keep_cnt)
+{
+    const DetDecodeSrc dec{d_rois, rois_f64, d_deltas, H, W};
+    return det_nms_volume_impl(c, nullptr, &dec, d_scores, F, B, K, class0, use_score_thresh, score_thresh, topk, nms_thresh, d_dets,
+                               d_sel_idx, d_det_cnt, d_keep, d_keep_cnt);
+}
+
+int vdet_tubelet_dets(vdet_ctx *c, const float *d_scores, const float *d_deltas, int64_t N, int64_t K, const void *d_tracks,
+                      int tracks_f64, int ld, const int32_t *d_slot, const int32_t *d_count, int64_t C, int T, int64_t F,
+                      const int32_t *d_cols, int64_t H, int64_t W, double *d_det, float *d_tboxes)
+{
+    if (!c) return VDET_EINVAL;
+    if (N < 0 || K < 1 || K > 0x7FFFFFF0ll || ld < 4) return fail(c, VDET_EINVAL, "bad shape (N >= 0 rows, K >= 1 columns, ld >= 4)");
+    if (decode_size_check(c, H, W)) return VDET_EINVAL;
+    if (C < 1 || T < 1 || F < 1 || !fits_below(0x7FFFFFF0ll, {C, T, F}))
+        return fail(c, VDET_EINVAL, "shape must be C, T, F >= 1 with C*T*F below 2^31 - 16");
+    if (N == 0) return VDET_OK;
+    if (!fits_upto(1ll << 40, {N, K})) return fail(c, VDET_EINVAL, "too many rows (N*K up to 2^40)");
+    if (!d_scores || !d_deltas || !d_tracks || !d_slot || !d_det || !d_tboxes) return fail(c, VDET_EINVAL, "null buffer");
+    if ((((uintptr_t)d_deltas | (uintptr_t)d_tboxes) & 15) != 0) return fail(c, VDET_EINVAL, "d_deltas and d_tboxes must be 16-byte aligned");
+    const int64_t blocks = (N + 255) / 256;
+    if (blocks > 0x7FFFFFFFll) return fail(c, VDET_EINVAL, "too many rows for one launch");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    TubeletDetsArgs a{};
+    a.scores = d_scores; a.deltas = reinterpret_cast<const float4 *>(d_deltas); a.tracks = d_tracks; a.ld = ld;
+    a.slot = d_slot; a.count = d_count; a.cols = d_cols; a.N = N; a.K = (int)K; a.C = C; a.F = F; a.T = T;
+    a.wmax = (double)(W - 1); a.hmax = (double)(H - 1);
+    a.det = d_det; a.tboxes = reinterpret_cast<float4 *>(d_tboxes); a.status = &c->d_cnt->status;
+    {
+        StageTimer tm(c, ST_OTHER);
+        if (tracks_f64) hipLaunchKernelGGL(tubelet_dets_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(tubelet_dets_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
+}
+
+int vdet_dets_as_tracks(vdet_ctx *c, const float *d_dets, const int32_t *d_sel_idx, const int32_t *d_keep, const int32_t *d_keep_cnt,
+                        int64_t F, int64_t K, int topk, int class0, float *d_tracks, double *d_score, int32_t *d_src, int32_t *d_cnt,
+                        int32_t *d_ntracks)
+{
+    if (!c) return VDET_EINVAL;
+    if (F < 1 || K < 1 || class0 < 0 || class0 >= K) return fail(c, VDET_EINVAL, "bad shape (F >= 1 frames, K >= 1 classes, 0 <= first_class < K)");
+    if (topk < 1 || topk > kDetMax) return fail(c, VDET_EINVAL, "topk = %d; the per-class NMS takes 1..%d boxes per (frame, class)", topk, kDetMax);
+    if (!fits_below(0x7FFFFFF0ll, {K, (int64_t)topk, F})) return fail(c, VDET_EINVAL, "volume too large (K*topk*F must stay below 2^31 - 16)");
+    if (!d_dets || !d_sel_idx || !d_keep || !d_keep_cnt || !d_tracks || !d_score || !d_src || !d_cnt || !d_ntracks)
+        return fail(c, VDET_EINVAL, "null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    const int64_t C = K - class0;
+    DetsAsTracksArgs a{};
+    a.dets = d_dets; a.sel_idx = d_sel_idx; a.keep = d_keep; a.keep_cnt = d_keep_cnt;
+    a.F = F; a.K = (int)K; a.class0 = class0; a.R = topk;
+    a.tracks = d_tracks; a.score = d_score; a.src = d_src; a.cnt = d_cnt; a.ntracks = d_ntracks;
+    HIPCHK(c, hipMemsetAsync(d_ntracks, 0, (size_t)C * 4, c->stream));
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(dets_as_tracks_kernel, dim3((unsigned)((C * topk * F + 255) / 256)), dim3(256), 0, c->stream, a);
     }
     HIPCHK(c, hipGetLastError());
     return VDET_OK;

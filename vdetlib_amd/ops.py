@@ -119,6 +119,210 @@ def det_nms_volume(boxes, scores, score_thresh=0.05, topk=100, nms_thresh=0.3, f
     return dets, sel, det_cnt, keep, keep_cnt
 
 
+def _im_size(im_size):
+    try:
+        H, W = (int(x) for x in im_size[:2])
+    except (TypeError, ValueError):
+        raise ValueError("im_size must be (H, W)")
+    if H < 1 or W < 1:
+        raise ValueError("im_size: H and W must be at least 1")
+    return H, W
+
+
+def _head_output(rois, deltas, lead, names):
+    """K of a head's output: rois f32 / f64 ``lead + (4,)``, deltas f32 ``lead + (4K,)`` or ``lead + (K,4)`` (``lead``: the leading
+    shape, or its rank when rois define it).  Layout only; ``names`` is the leading shape as the messages spell it."""
+    if not torch.is_tensor(rois) or rois.dtype not in _F32_F64:
+        raise ValueError("rois must be a float32 / float64 tensor")
+    if not torch.is_tensor(deltas) or deltas.dtype != torch.float32:
+        raise ValueError("deltas must be a float32 tensor")
+    n = lead if isinstance(lead, int) else len(lead)
+    if rois.dim() != n + 1 or rois.shape[-1] != 4 or (not isinstance(lead, int) and tuple(rois.shape[:n]) != tuple(lead)):
+        raise ValueError("rois must be [%s,4]" % names)
+    lead = tuple(rois.shape[:n])
+    if deltas.dim() == n + 2 and tuple(deltas.shape[:n]) == lead and deltas.shape[-1] == 4:
+        return int(deltas.shape[n])
+    if deltas.dim() == n + 1 and tuple(deltas.shape[:n]) == lead and deltas.shape[-1] % 4 == 0:
+        return int(deltas.shape[-1]) // 4
+    raise ValueError("deltas must be [%s,4K] or [%s,K,4]" % (names, names))
+
+
+def _aligned16(tensors, who):
+    for t in tensors:
+        if t is not None and t.numel() and t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % who)
+
+
+def decode_boxes(rois, deltas, im_size, sync=True, ctx=None):
+    """The Fast R-CNN box decode on the device (include/vdet_hip.h: vdet_decode_boxes): ``image_det.bbox_transform_inv``
+    followed by ``clip_boxes`` for every box and class, one launch.
+
+    rois [F,B,4] f32 / f64 (image coordinates, as they are), deltas [F,B,4K] or [F,B,K,4] f32 (the head's output), im_size
+    (H, W).  Returns boxes [F,B,K,4] f32, the form ``det_nms_volume`` reads.  The arithmetic is float64, rounded once to float32,
+    with an exponential that is a fixed sequence of IEEE operations: the bits are those of tests/decode_spec.py (against the
+    host pair: at most one f32 ulp, on fewer than one element in 10^4).  A NaN stays a NaN; dw is not clamped.  rois and deltas
+    must be 16-byte aligned (ValueError).  No CPU fallback."""
+    K = _head_output(rois, deltas, 2, "F,B")
+    H, W = _im_size(im_size)
+    _same_gpu((rois, deltas), "rois and deltas")
+    rois, deltas = rois.contiguous(), deltas.contiguous()
+    _aligned16((rois, deltas), "rois and deltas")
+    F, B = rois.shape[:2]
+    boxes = torch.empty((F, B, K, 4), dtype=torch.float32, device=rois.device)
+    ctx = _ctx_for(rois, ctx)
+    ptr = lambda x: x.data_ptr() if x.numel() else None
+    ctx.check(ctx.lib.vdet_decode_boxes(ctx.h, ptr(rois), int(rois.dtype == torch.float64), ptr(deltas), F * B, K, H, W, ptr(boxes)))
+    if sync:
+        ctx.sync()
+    return boxes
+
+
+def det_nms_volume_deltas(rois, scores, deltas, im_size, score_thresh=0.05, topk=100, nms_thresh=0.3, first_class=1, sync=True,
+                          ctx=None, want_dets=True):
+    """``det_nms_volume`` straight from the head's output (include/vdet_hip.h: vdet_det_nms_volume_deltas): the selection runs on
+    the scores, and the wave of a (frame, class) decodes only its <= topk candidates, at the gather -- no [F,B,K,4] tensor exists.
+
+    rois [F,B,4] f32 / f64, scores [F,B,K] f32, deltas [F,B,4K] or [F,B,K,4] f32, im_size (H, W); rois and deltas 16-byte
+    aligned (ValueError).  Returns ``det_nms_volume``'s five outputs, bit for bit those of
+    ``det_nms_volume(decode_boxes(rois, deltas, im_size), scores, ...)``, ZeroDivisionError and every error raised at the wait
+    included.  The remaining arguments and the limits are ``det_nms_volume``'s.  Frames with fewer proposals: pad with NaN rois
+    and NaN scores (a NaN never passes ``> score_thresh``).  No CPU fallback."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t'")
+    if scores.dim() != 3:
+        raise ValueError("scores must be [F,B,K]")
+    F, B, K = scores.shape
+    if _head_output(rois, deltas, (F, B), "F,B") != K:
+        raise ValueError("deltas must be [F,B,4K] or [F,B,K,4] for scores [F,B,K]")
+    H, W = _im_size(im_size)
+    _same_gpu((rois, scores, deltas), "rois, scores and deltas")
+    rois, scores, deltas = rois.contiguous(), scores.contiguous(), deltas.contiguous()
+    _aligned16((rois, deltas), "rois and deltas")
+    topk = int(topk)
+    ctx = _ctx_for(rois, ctx)
+    dev = rois.device
+    dets = torch.full((F, K, topk, 5), float('nan'), dtype=torch.float32, device=dev) if want_dets else None
+    sel = torch.full((F, K, topk), -1, dtype=torch.int32, device=dev)
+    keep = torch.full((F, K, topk), -1, dtype=torch.int32, device=dev)
+    det_cnt = torch.zeros((F, K), dtype=torch.int32, device=dev)
+    keep_cnt = torch.zeros((F, K), dtype=torch.int32, device=dev)
+
+    def reset():
+        if dets is not None:
+            dets.fill_(float('nan'))
+        sel.fill_(-1); keep.fill_(-1)
+    _finish(ctx, lambda: ctx.check(ctx.lib.vdet_det_nms_volume_deltas(
+        ctx.h, rois.data_ptr(), int(rois.dtype == torch.float64), scores.data_ptr(), deltas.data_ptr(), F, B, K, H, W,
+        int(first_class), 0 if score_thresh is None else 1, 0.0 if score_thresh is None else float(score_thresh), topk,
+        float(nms_thresh), dets.data_ptr() if dets is not None else None, sel.data_ptr(), det_cnt.data_ptr(), keep.data_ptr(),
+        keep_cnt.data_ptr())), sync, reset=reset)
+    return dets, sel, det_cnt, keep, keep_cnt
+
+
+def tubelet_dets(scores, deltas, tracks, slot, count, im_size, cols=None, shape=None, out=None, sync=True, ctx=None):
+    """The tubelet side of the Fast R-CNN route after the head (include/vdet_hip.h: vdet_tubelet_dets; what ``fast_rcnn_cls``
+    computes per tubelet box): for the compact row n of ``tubelet_rois`` with ``slot[n] = (c,t,f)``
+
+        det[c,t,f] = f64(scores[n, cols[c]])        tboxes[c,t,f] = decode(tracks[c,t,f,:4], deltas[n, 4*cols[c] : +4])
+
+    scores [N,K] f32 and deltas [N,4K] or [N,K,4] f32 are the head's output for the N pooled rows; tracks [C,T,F,>=4] f32 / f64;
+    slot int32 [N,3] and count int32 [1] as ``tubelet_rois`` returns them (count None: all N; rows behind it are not read);
+    ``cols`` int32 [C] maps a class to its column of the head as in ``svm_head`` (default c + 1: column 0 is the background).
+    The decode is ``decode_boxes``' (tests/decode_spec.py).  ``shape`` = (C,T,F) defaults to tracks'.  ``out``: the dict of an
+    earlier call, written in place at this call's slots only (frame ranges of one video); ``out=None`` allocates NaN.
+
+    Returns a dict: ``det`` f64 [C,T,F] and ``tboxes`` f32 [C,T,F,4] -- what ``rescore_tubelets(floor=det)`` and
+    ``nms_tracks(tboxes=)`` take.  A slot outside ``shape`` or a column outside K raises ValueError when the call -- with
+    ``sync=False`` a later ``ctx.sync()`` -- waits; that row is skipped.  One launch.  No CPU fallback."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] < 1:
+        raise ValueError("scores must be float32 [N,K] with K >= 1")
+    N, K = scores.shape
+    if not torch.is_tensor(deltas) or deltas.dtype != torch.float32 or tuple(deltas.shape) not in ((N, 4 * K), (N, K, 4)):
+        raise ValueError("deltas must be float32 [N,4K] or [N,K,4]")
+    if not torch.is_tensor(tracks) or tracks.dtype not in _F32_F64 or tracks.dim() != 4 or tracks.shape[3] < 4:
+        raise ValueError("tracks must be float32 / float64 [C,T,F,>=4]")
+    if shape is not None and tuple(shape) != tuple(tracks.shape[:3]):
+        raise ValueError("shape differs from tracks'")
+    C, T, F, ld = (int(x) for x in tracks.shape)
+    if C < 1 or T < 1 or F < 1 or C * T * F >= 2 ** 31 - 16:
+        raise ValueError("shape must be C, T, F >= 1 with C*T*F below 2^31 - 16")
+    if not torch.is_tensor(slot) or slot.dtype != torch.int32 or tuple(slot.shape) != (N, 3):
+        raise ValueError("slot must be int32 [N,3]")
+    if count is not None and (not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1):
+        raise ValueError("count must be int32 [1]")
+    if cols is None:
+        if C + 1 > K:
+            raise ValueError("the default cols (c + 1) needs K >= C + 1 columns")
+    elif not torch.is_tensor(cols) or cols.dtype != torch.int32 or tuple(cols.shape) != (C,):
+        raise ValueError("cols must be int32 [C]")
+    H, W = _im_size(im_size)
+    if not all(x is None or x.is_contiguous() for x in (scores, deltas, tracks, slot, count, cols)):
+        raise ValueError("scores, deltas, tracks, slot, count and cols must be contiguous")
+    dev = scores.device
+    if out is not None:
+        if not isinstance(out, dict) or not torch.is_tensor(out.get('det')) or not torch.is_tensor(out.get('tboxes')):
+            raise ValueError("out must be the dict of an earlier tubelet_dets call")
+        det, tboxes = out['det'], out['tboxes']
+        if det.dtype != torch.float64 or tuple(det.shape) != (C, T, F) or tboxes.dtype != torch.float32 or \
+                tuple(tboxes.shape) != (C, T, F, 4) or not det.is_contiguous() or not tboxes.is_contiguous():
+            raise ValueError("out's det must be float64 [C,T,F] and its tboxes float32 [C,T,F,4], contiguous")
+    else:
+        det = tboxes = None
+    _same_gpu((scores, deltas, tracks, slot, count, cols, det, tboxes), "every tensor")
+    if det is None:
+        det = torch.full((C, T, F), float('nan'), dtype=torch.float64, device=dev)
+        tboxes = torch.full((C, T, F, 4), float('nan'), dtype=torch.float32, device=dev)
+    _aligned16((deltas, tboxes), "deltas and out's tboxes")
+    ctx = _ctx_for(scores, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    ctx.check(ctx.lib.vdet_tubelet_dets(ctx.h, ptr(scores), ptr(deltas), N, K, tracks.data_ptr(), int(tracks.dtype == torch.float64), ld,
+                                        ptr(slot), ptr(count), C, T, F, ptr(cols), H, W, det.data_ptr(), tboxes.data_ptr()))
+    if sync:
+        ctx.sync()
+    return dict(det=det, tboxes=tboxes)
+
+
+def dets_as_tracks(dets, sel_idx, keep, keep_cnt, first_class=1, sync=True, ctx=None):
+    """``det_nms_volume`` / ``det_nms_volume_deltas``' outputs in the rank layout ``nms_tracks`` returns (include/vdet_hip.h:
+    vdet_dets_as_tracks): per-class regressed boxes as a source of everything that reads that layout.
+
+    dets [F,K,topk,5] f32, sel_idx and keep [F,K,topk] int32, keep_cnt [F,K] int32.  With C = K - first_class and R = topk,
+    returns the dict ``tracks`` [C,R,F,5] f32 (the kept rows of class first_class + c in keep order), ``score`` [C,R,F] f64,
+    ``src`` [C,R,F] int32 (the row's box index; INT32_MIN behind the count), ``cnt`` [C,F] int32, ``ntracks`` [C] int32 (the
+    maximum of cnt over the frames) -- NaN behind the counts.  It goes as it is into ``DetEvaluator.add_detections``,
+    ``seq_nms`` and, as a tubelet dict, into ``nms_tracks`` / ``soft_nms_tracks`` / ``vote_nms_tracks`` (join it with real
+    tubelets through ``merge_tracks('combine')`` first).  One launch.  No CPU fallback."""
+    if not torch.is_tensor(dets) or dets.dtype != torch.float32 or dets.dim() != 4 or dets.shape[3] != 5:
+        raise ValueError("dets must be float32 [F,K,topk,5] (det_nms_volume with want_dets=True)")
+    F, K, R = (int(x) for x in dets.shape[:3])
+    for t, name in ((sel_idx, "sel_idx"), (keep, "keep")):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (F, K, R):
+            raise ValueError("%s must be int32 [F,K,topk]" % name)
+    if not torch.is_tensor(keep_cnt) or keep_cnt.dtype != torch.int32 or tuple(keep_cnt.shape) != (F, K):
+        raise ValueError("keep_cnt must be int32 [F,K]")
+    first_class = int(first_class)
+    if F < 1 or not 0 <= first_class < K:
+        raise ValueError("F >= 1 frames and 0 <= first_class < K")
+    if not 1 <= R <= 128:
+        raise ValueError("topk = %d; the per-class NMS takes 1..128 boxes per (frame, class)" % R)
+    if K * R * F >= 2 ** 31 - 16:
+        raise ValueError("volume too large (K*topk*F must stay below 2^31 - 16)")
+    _same_gpu((dets, sel_idx, keep, keep_cnt), "dets, sel_idx, keep and keep_cnt")
+    dets, sel_idx, keep, keep_cnt = dets.contiguous(), sel_idx.contiguous(), keep.contiguous(), keep_cnt.contiguous()
+    C, dev = K - first_class, dets.device
+    out = dict(tracks=torch.empty((C, R, F, 5), dtype=torch.float32, device=dev),
+               score=torch.empty((C, R, F), dtype=torch.float64, device=dev),
+               src=torch.empty((C, R, F), dtype=torch.int32, device=dev),
+               cnt=torch.empty((C, F), dtype=torch.int32, device=dev), ntracks=torch.empty((C,), dtype=torch.int32, device=dev))
+    ctx = _ctx_for(dets, ctx)
+    ctx.check(ctx.lib.vdet_dets_as_tracks(ctx.h, dets.data_ptr(), sel_idx.data_ptr(), keep.data_ptr(), keep_cnt.data_ptr(), F, K, R,
+                                          first_class, out['tracks'].data_ptr(), out['score'].data_ptr(), out['src'].data_ptr(),
+                                          out['cnt'].data_ptr(), out['ntracks'].data_ptr()))
+    if sync:
+        ctx.sync()
+    return out
+
+
 def nms_volume_ordered(boxes, order, ncand, thresh=0.3, cap=None, ctx=None, pad=True):
     """``nms_volume`` walking the CALLER's lists: order int16/uint16 [F,C,B] (box indices, e.g. ``argsort_volume``'s with
     ties rearranged as some machine's unstable ``scores.argsort()[::-1]`` left them, utils/nms.pyx:25), ncand int32 [F,C]

@@ -2,7 +2,8 @@
 vdet/image_det.py: ``googlenet_features`` / ``googlenet_rcnn`` (:56-106) warp their windows on the GPU (``ops.rcnn_patches``,
 DESIGN.md section 10j) and drive any pycaffe-like ``net`` through the reference's blob protocol; the nets themselves are the
 caller's.  ``fast_rcnn_det`` (:22-33) and the ``im_detect`` it calls run the Fast R-CNN route: any torch backbone and head of
-the caller's around ``ops.roi_pool``, the box decode on the host in numpy float64.
+the caller's around ``ops.roi_pool``, the box decode on the host in numpy float64
+(``video_det.fast_rcnn_det_vid_device`` keeps the head's output on the device: section 10z).
 Out of scope: ``simple_crop`` / ``googlenet_det`` (:12-53, a fixed-point uint8 resize)."""
 import numpy as np
 

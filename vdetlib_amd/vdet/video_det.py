@@ -164,3 +164,70 @@ def fast_rcnn_det_vid(net, vid_proto, box_proto, det_fun, class_names=imagenet_v
         logging.info('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(
             i + 1, len(frames), timers['im_detect'].average_time, timers['misc'].average_time))
     return all_boxes
+
+
+def fast_rcnn_det_vid_device(net, vid_proto, box_proto, class_names=imagenet_vdet_classes, max_per_image=100, thresh=0.05,
+                             nms_thresh=None, chunk=8, images=None):
+    """``fast_rcnn_det_vid(net, vid_proto, box_proto, image_det.im_detect, ...)`` with the head's output staying on the device
+    (DESIGN.md section 10z): per frame the backbone, ``ops.roi_pool`` and ``net.head`` on that frame's rows alone -- the shapes
+    ``im_detect`` gives the head -- then ``chunk`` frames at a time through ``ops.det_nms_volume_deltas``, which selects on the
+    scores and decodes only the selected boxes.  Frames with fewer proposals than the chunk's largest are padded with NaN rois
+    and NaN scores (a NaN never passes ``> thresh``).
+
+    ``net`` is ``im_detect``'s; ``images``: {frame id: uint8 [H,W,3]} instead of reading the frames' files.  Returns
+    ``all_boxes[cls][frame]`` float32 [n,5] as ``fast_rcnn_det_vid`` does; with ``nms_thresh`` also ``keeps[cls][frame]``, the
+    kept row positions in descending score order (``apply_image_nms`` of those rows).  The boxes follow tests/decode_spec.py:
+    against the host decode at most one float32 ulp, on fewer than one coordinate in 10^4; the scores are the head's bits.
+    ValueError for a box that is not finite, frames of different sizes, or ``max_per_image`` beyond 128."""
+    import torch
+    from .. import _lib, ops
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    frames = vid_proto['frames']
+    num_classes = len(class_names)
+    max_per_image, chunk = int(max_per_image), max(int(chunk), 1)
+    if not 1 <= max_per_image <= 128:
+        raise ValueError("max_per_image = %d; the per-class NMS on the device takes 1..128 boxes per (frame, class)" % max_per_image)
+    all_boxes = [[np.zeros((0, 5), np.float32) if j else [] for _ in frames] for j in range(num_classes)]
+    keeps = [[[] for _ in frames] for _ in range(num_classes)]
+    im_size = None
+    for i0 in range(0, len(frames), chunk):
+        rows = []
+        for frame in frames[i0:i0 + chunk]:
+            im = images[frame['frame']] if images is not None else imread(frame_path_at(vid_proto, frame['frame']))
+            if im_size is None:
+                im_size = tuple(np.shape(im)[:2])
+            elif tuple(np.shape(im)[:2]) != im_size:
+                raise ValueError("fast_rcnn_det_vid_device: the frames of a video must share one size")
+            proposals = np.array([box['bbox'] for box in boxes_at_frame(box_proto, frame['frame'])], dtype=np.float64).reshape(-1, 4)
+            with torch.no_grad():
+                x, im_scale = net.prepare(im)
+                feat = net.backbone(x)
+                rois = torch.from_numpy(np.ascontiguousarray(proposals)).to(feat.device)
+                out = ops.roi_pool(feat.contiguous(), rois, spatial_scale=net.spatial_scale, pooled=net.pooled, box_scale=im_scale,
+                                   mode=getattr(net, 'roi_mode', 'max'), sampling=getattr(net, 'sampling', 2),
+                                   aligned=getattr(net, 'aligned', False))
+                scores, deltas = net.head(out['pooled'])
+            rows.append((rois, scores.detach()[:, :num_classes].float(), deltas.detach()[:, :4 * num_classes].float(), out['ok']))
+        bad = (torch.cat([r[3] for r in rows]) == 0).nonzero()
+        if bad.numel():
+            raise ValueError("fast_rcnn_det_vid_device: a box of frames %d..%d is not finite (or beyond 2^24 cells)"
+                             % (i0, i0 + len(rows) - 1))
+        Fc, B, dev = len(rows), max(len(r[0]) for r in rows), rows[0][0].device
+        if B == 0:
+            continue
+        nan = float('nan')
+        v_rois = torch.full((Fc, B, 4), nan, dtype=torch.float64, device=dev)
+        v_scores = torch.full((Fc, B, num_classes), nan, dtype=torch.float32, device=dev)
+        v_deltas = torch.zeros((Fc, B, 4 * num_classes), dtype=torch.float32, device=dev)
+        for k, (rois, scores, deltas, _) in enumerate(rows):
+            n = len(rois)
+            v_rois[k, :n], v_scores[k, :n], v_deltas[k, :n] = rois, scores, deltas
+        dets, _, det_cnt, keep, keep_cnt = ops.det_nms_volume_deltas(
+            v_rois, v_scores, v_deltas, im_size, score_thresh=thresh, topk=max_per_image,
+            nms_thresh=0.3 if nms_thresh is None else nms_thresh, first_class=1)
+        dets, det_cnt, keep, keep_cnt = (t.cpu().numpy() for t in (dets, det_cnt, keep, keep_cnt))
+        for k in range(Fc):
+            for j in range(1, num_classes):
+                all_boxes[j][i0 + k] = dets[k, j, :det_cnt[k, j]].copy()
+                keeps[j][i0 + k] = keep[k, j, :keep_cnt[k, j]].tolist()
+    return all_boxes if nms_thresh is None else (all_boxes, keeps)
