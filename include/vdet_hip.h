@@ -41,6 +41,9 @@
  *   vdet_det_nms_volume top-k              1 <= topk <= 128           VDET_EINVAL
  *   box decode (vdet_decode_boxes, vdet_det_nms_volume_deltas, vdet_tubelet_dets)   H, W >= 1; rois, deltas and box outputs
  *                                          16-byte aligned; N*K <= 2^40 (vdet_decode_boxes), C*T*F < 2^31 - 16    VDET_EINVAL
+ *   RPN proposal layer (vdet_rpn_proposals)  1 <= A <= 64; Hf, Wf >= 1; Hf*Wf*A < 2^24; F*Hf*Wf*A < 2^31 - 16; stride >= 1;
+ *                                          1 <= post_nms_top_n <= pre_nms_top_n <= 16384; H, W >= 1; min_size, offset finite;
+ *                                          score frame stride >= A*Hf*Wf; d_rois 16-byte aligned    VDET_EINVAL
  *   temporal window / taps                 odd, <= 31                 VDET_EINVAL (the one-pass volume kernel: 3 or 5, other
  *                                                                     windows run the separate kernels)
  *   frames per video, vdet_video_batch     none                       videos of more than 1536 frames re-score their tubelet
@@ -512,6 +515,36 @@ int vdet_dets_as_tracks(vdet_ctx *ctx, const float *d_dets, const int32_t *d_sel
 int vdet_nms_volume_ordered(vdet_ctx *ctx, const float *d_boxes, const uint16_t *d_order, const int32_t *d_ncand,
                             int64_t F, int64_t B, int64_t C, double thresh, int32_t *d_keep_idx,
                             int32_t *d_keep_cnt, int64_t cap);
+
+/*
+ * The proposal layer of a region proposal network on the device (the boxes of the Faster R-CNN route): anchors, decode, clip,
+ * size filter, top-N, NMS, top-N, for F frames of one image size.  THE rule, bit for bit, is tests/rpn_spec.py; it restates
+ * the public py-faster-rcnn proposal layer, which was not at hand (parity with that code's f32 host arithmetic is unpinned).
+ *   d_scores   f32, frame f / anchor a / cell (h,w) at d_scores[f*score_frame_stride + (a*Hf + h)*Wf + w]: the foreground half
+ *              cls[:, A:] of a contiguous [F,2A,Hf,Wf] output goes in with a stride of 2*A*Hf*Wf and no copy.  Logits or
+ *              probabilities: only the ranking is used.
+ *   d_deltas   f32 [F,4A,Hf,Wf] contiguous, channel 4a+k component k of anchor a;  d_anchors f64 [A,4] (on the device).
+ * The candidate of flat index n = (h*Wf + w)*A + a is the anchor d_anchors[a] + (w,h,w,h)*stride (f64) decoded by
+ * vdet_decode_boxes' rule with the width term w = (x2 - x1) + offset (1.0: the RPN's; 1e-14: vdet_decode_boxes') and, with
+ * use_dw_max, a dw / dh GREATER than dw_max replaced by dw_max (NaN stays), clipped to (H, W), rounded once to f32.  It is valid
+ * when its score is not NaN and (X2 - X1) + 1 >= min_size and (Y2 - Y1) + 1 >= min_size on the f32 box, evaluated in f64.
+ * Valid candidates are ordered by descending score, equal scores (-0.0 == +0.0) by DESCENDING n; the first pre_nms_top_n are
+ * kept, greedy NMS at nms_thresh (vdet_nms_volume_ordered's arithmetic, one list per frame) runs over them in that order and
+ * the first post_nms_top_n survivors are the proposals; more survivors are no error.
+ *   d_rois [F,post,4] f32 (16-byte aligned), d_out_scores [F,post] f32, d_index [F,post] int32 (the flat index n), d_count [F]
+ *   int32; behind the count: NaN, NaN, -1 -- written by this call, the buffers need no initialisation.
+ *   d_cand_index [F,pre] int32 (-1 behind the count) / d_cand_cnt [F] int32: the candidates in order, or NULL.
+ * Three launches of its own (decode, select, gather) around those of vdet_nms_volume_ordered on [F,pre,4] boxes with one list per
+ * frame; scratch (a key and a box per anchor, the candidates, the keep list) is the context's.
+ * No host wait on a context set asynchronous (vdet_set_async) once the NMS's pool size is known, as for vdet_nms_volume.
+ * A frame with fewer than pre_nms_top_n candidates pads its NMS list with NaN boxes and takes the general predicate kernel.
+ * The resident suppression graph of the prep cache is dropped by this call.
+ */
+int vdet_rpn_proposals(vdet_ctx *ctx, const float *d_scores, int64_t score_frame_stride, const float *d_deltas,
+                       const double *d_anchors, int64_t F, int64_t A, int64_t Hf, int64_t Wf, int64_t H, int64_t W, int64_t stride,
+                       int64_t pre_nms_top_n, int64_t post_nms_top_n, double nms_thresh, double min_size, double offset,
+                       int use_dw_max, double dw_max, float *d_rois, float *d_out_scores, int32_t *d_index, int32_t *d_count,
+                       int32_t *d_cand_index, int32_t *d_cand_cnt);
 
 /*
  * Batched small videos (BASELINE configs[0] / [4] shapes: hundreds of frames x <= 300 boxes x 30 classes -- a single

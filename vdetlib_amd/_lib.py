@@ -53,6 +53,8 @@ SYMBOLS = {
     "vdet_tubelet_dets": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _ci, _ci, _vp, _vp, _i64, _ci, _i64, _vp, _i64, _i64, _vp, _vp]),
     "vdet_dets_as_tracks": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
     "vdet_nms_volume_ordered": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _vp, _vp, _i64]),
+    "vdet_rpn_proposals": (_ci, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f64, _f64, _f64, _ci,
+                                 _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vdet_argsort_volume": (_ci, [_vp, _vp, _ci, _i64, _i64, _i64, _ci, _f32, _vp, _vp]),
     "vdet_video_batch": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _ci, _f64, _ci, _vp, _vp, _vp, _i64, _vp, _vp,
                                _f64, _ci, _vp, _vp, _vp]),

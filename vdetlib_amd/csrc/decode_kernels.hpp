@@ -53,16 +53,25 @@ __device__ __forceinline__ double decode_clip(double v, double hi)
     return v != v ? v : (v > hi ? hi : (v > 0.0 ? v : 0.0));
 }
 
-// the roi widened exactly to f64, the class's deltas, wmax = W - 1, hmax = H - 1
-__device__ __forceinline__ float4 decode_box(double x1, double y1, double x2, double y2, float4 d, double wmax, double hmax)
+constexpr double kDecodeEps = 1e-14;    // the width term of the Fast R-CNN decode (tests/decode_spec.py: EPS)
+
+// the roi and the deltas in f64 (widened exactly), wmax = W - 1, hmax = H - 1, off the width term: w = (x2 - x1) + off
+__device__ __forceinline__ float4 decode_box_f64(double x1, double y1, double x2, double y2, double dx, double dy, double dw, double dh,
+                                                 double wmax, double hmax, double off)
 {
-    const double w = (x2 - x1) + 1e-14, h = (y2 - y1) + 1e-14;
+    const double w = (x2 - x1) + off, h = (y2 - y1) + off;
     const double cx = x1 + 0.5 * w, cy = y1 + 0.5 * h;
-    const double pcx = (double)d.x * w + cx, pcy = (double)d.y * h + cy;
-    const double pw = decode_exp((double)d.z) * w, ph = decode_exp((double)d.w) * h;
+    const double pcx = dx * w + cx, pcy = dy * h + cy;
+    const double pw = decode_exp(dw) * w, ph = decode_exp(dh) * h;
     const double hw = 0.5 * pw, hh = 0.5 * ph;
     return make_float4((float)decode_clip(pcx - hw, wmax), (float)decode_clip(pcy - hh, hmax),
                        (float)decode_clip(pcx + hw, wmax), (float)decode_clip(pcy + hh, hmax));
+}
+
+// the roi widened exactly to f64, the class's deltas; off is kDecodeEps for the Fast R-CNN callers, 1.0 for the RPN's anchors
+__device__ __forceinline__ float4 decode_box(double x1, double y1, double x2, double y2, float4 d, double wmax, double hmax, double off)
+{
+    return decode_box_f64(x1, y1, x2, y2, (double)d.x, (double)d.y, (double)d.z, (double)d.w, wmax, hmax, off);
 }
 
 // a roi row widened exactly to f64: rois [N,4] f32 (one 16-byte load) or f64 (two)
@@ -101,7 +110,7 @@ __global__ __launch_bounds__(256) void decode_boxes_kernel(const DecodeArgs a)
     double r[4];
     if (one_box) load_roi<F64>(a.rois, nb0, r);
     else load_roi<F64>(a.rois, nb, r);
-    a.boxes[i] = decode_box(r[0], r[1], r[2], r[3], d, a.wmax, a.hmax);
+    a.boxes[i] = decode_box(r[0], r[1], r[2], r[3], d, a.wmax, a.hmax, kDecodeEps);
 }
 
 // the box source of det_nms_body: decode box id of frame f for the class slot e at the gather
@@ -115,7 +124,7 @@ struct DetBoxFromDeltas {
     {
         double r[4];
         load_roi<F64>(rois, (int64_t)f * B + id, r);
-        return decode_box(r[0], r[1], r[2], r[3], deltas[e], wmax, hmax);
+        return decode_box(r[0], r[1], r[2], r[3], deltas[e], wmax, hmax, kDecodeEps);
     }
 };
 
@@ -167,7 +176,7 @@ __global__ __launch_bounds__(256) void tubelet_dets_kernel(const TubeletDetsArgs
         x1 = r[0]; y1 = r[1]; x2 = r[2]; y2 = r[3];
     }
     a.det[o] = (double)a.scores[e];
-    a.tboxes[o] = decode_box(x1, y1, x2, y2, a.deltas[e], a.wmax, a.hmax);
+    a.tboxes[o] = decode_box(x1, y1, x2, y2, a.deltas[e], a.wmax, a.hmax, kDecodeEps);
 }
 
 struct DetsAsTracksArgs {

@@ -22,6 +22,7 @@
 #include "small_kernels.hpp"
 #include "detnms_kernels.hpp"
 #include "decode_kernels.hpp"
+#include "proposal_kernels.hpp"
 #include "fused_kernels.hpp"
 #include "adjrows_kernels.hpp"
 #include "graphlists_kernels.hpp"
@@ -258,6 +259,10 @@ struct vdet_ctx {
     bool sq_lds = true;           // VDET_SEQNMS_LDS=0: the predecessor table in global scratch (the path of long videos)
     bool sq_attr_set = false;
     int sq_last_path = -1;        // vdet_query 14: 1 the table in LDS, 2 in global scratch
+    // RPN proposal layer (proposal_kernels.hpp): keys and boxes of every anchor, then per frame the candidates in order (boxes,
+    // scores, indices, the identity order list, the count) and the NMS keep list over them
+    DevBuf rpn_keys, rpn_boxes, rpn_cbox, rpn_cscore, rpn_cindex, rpn_order, rpn_ccnt, rpn_keep, rpn_keepcnt;
+    bool rpn_attr_set = false;
     DevBuf tube_scratch;          // NMS over whole tubelets (tubenms_kernels.hpp): scores, counts, extents and the bit rows per (video, class)
 };
 
@@ -1683,7 +1688,8 @@ int vdet_destroy(vdet_ctx *c)
                       &c->ev_dslot, &c->ev_bcnt, &c->ev_boff, &c->ev_key[0], &c->ev_key[1], &c->ev_val[0], &c->ev_val[1], &c->ev_hist,
                       &c->tcn_x, &c->tcn_frames, &c->tcn_base, &c->tcn_len, &c->tcn_scratch, &c->tcn_h0, &c->tcn_params.dev, &c->tcn_foff.dev, &c->tcn_segs.dev, &c->tcn_ovtab.dev, &c->interp_tab.dev,
                       &c->anchor_tab.dev, &c->topa_hist, &c->topa_state, &c->topa_cnt, &c->topa_nrec, &c->topa_rec, &c->svm_wt, &c->svm_wavebad,
-                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec, &c->sq_link, &c->sq_live, &c->sq_done, &c->sq_ptr, &c->tube_scratch};
+                      &c->ctxs_tab.dev, &c->ctxs_hist, &c->ctxs_state, &c->ctxs_rec, &c->sq_link, &c->sq_live, &c->sq_done, &c->sq_ptr, &c->tube_scratch,
+                      &c->rpn_keys, &c->rpn_boxes, &c->rpn_cbox, &c->rpn_cscore, &c->rpn_cindex, &c->rpn_order, &c->rpn_ccnt, &c->rpn_keep, &c->rpn_keepcnt};
     for (DevBuf *b : bufs) b->release();
     for (DevBuf &b : c->tmp) b.release();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -2280,8 +2286,9 @@ int vdet_dets_as_tracks(vdet_ctx *c, const float *d_dets, const int32_t *d_sel_i
 }
 
 // ---------------------------------------------------------------------------------------------
-int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d_order, const int32_t *d_ncand, int64_t F, int64_t B,
-                            int64_t C, double thresh, int32_t *d_keep_idx, int32_t *d_keep_cnt, int64_t cap)
+// (inner: a stage of another entry point, whose stage timers stay)
+static int nms_volume_ordered_impl(vdet_ctx *c, const float *d_boxes, const uint16_t *d_order, const int32_t *d_ncand, int64_t F, int64_t B,
+                                   int64_t C, double thresh, int32_t *d_keep_idx, int32_t *d_keep_cnt, int64_t cap, bool inner)
 {
     if (!c) return VDET_EINVAL;
     if (F < 0 || B < 0 || C < 0 || cap < 0) return fail(c, VDET_EINVAL, "bad shape");
@@ -2290,7 +2297,7 @@ int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d
     if (B > 32767) return fail(c, VDET_EINVAL, "B = %lld boxes per frame; the limit is 32767", (long long)B);
     if (!fits_upto(0x7FFFFFF0ll, {F, C}) || !fits_upto(0x7FFFFFF0ll, {F, B})) return fail(c, VDET_EINVAL, "volume too large");
     HIPCHK(c, hipSetDevice(c->device));
-    timing_reset(c);
+    if (!inner) timing_reset(c);
     if (B == 0) {
         HIPCHK(c, hipMemsetAsync(d_keep_cnt, 0, (size_t)(F * C) * 4, c->stream));
         return VDET_OK;
@@ -2309,6 +2316,100 @@ int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d
     a.order_in = d_order; a.ncand_in = c->ordncand.as<int32_t>();
     a.keep_idx = d_keep_idx; a.keep_cnt = d_keep_cnt; a.cap = cap;
     return launch_sort_walk(c, a, (int)B, F * C * B);
+}
+
+int vdet_nms_volume_ordered(vdet_ctx *c, const float *d_boxes, const uint16_t *d_order, const int32_t *d_ncand, int64_t F, int64_t B,
+                            int64_t C, double thresh, int32_t *d_keep_idx, int32_t *d_keep_cnt, int64_t cap)
+{
+    return nms_volume_ordered_impl(c, d_boxes, d_order, d_ncand, F, B, C, thresh, d_keep_idx, d_keep_cnt, cap, false);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The proposal layer of a region proposal network (proposal_kernels.hpp; THE rule: tests/rpn_spec.py): decode + keys, per-frame
+// select + sort, the ordered-list NMS over the candidates (one list per frame, identity order), gather.
+int vdet_rpn_proposals(vdet_ctx *c, const float *d_scores, int64_t score_frame_stride, const float *d_deltas, const double *d_anchors,
+                       int64_t F, int64_t A, int64_t Hf, int64_t Wf, int64_t H, int64_t W, int64_t stride, int64_t pre_nms_top_n,
+                       int64_t post_nms_top_n, double nms_thresh, double min_size, double offset, int use_dw_max, double dw_max,
+                       float *d_rois, float *d_out_scores, int32_t *d_index, int32_t *d_count, int32_t *d_cand_index,
+                       int32_t *d_cand_cnt)
+{
+    if (!c) return VDET_EINVAL;
+    if (F < 0) return fail(c, VDET_EINVAL, "bad shape");
+    if (A < 1 || A > kRpnMaxA) return fail(c, VDET_EINVAL, "A = %lld anchors per cell; 1 .. %d", (long long)A, kRpnMaxA);
+    if (Hf < 1 || Wf < 1 || !fits_below(1ll << 24, {Hf, Wf, A}))
+        return fail(c, VDET_EINVAL, "the feature map must be Hf, Wf >= 1 with Hf*Wf*A below 2^24");
+    const int64_t N = Hf * Wf * A;
+    if (!fits_below(0x7FFFFFF0ll, {F, N})) return fail(c, VDET_EINVAL, "volume too large (F*Hf*Wf*A must stay below 2^31 - 16)");
+    if (stride < 1 || stride > 0x7FFFFFFFll) return fail(c, VDET_EINVAL, "stride must be an integer >= 1");
+    if (post_nms_top_n < 1 || post_nms_top_n > pre_nms_top_n || pre_nms_top_n > kRpnMaxPre)
+        return fail(c, VDET_EINVAL, "1 <= post_nms_top_n <= pre_nms_top_n <= %d", kRpnMaxPre);
+    if (!fits_below(0x7FFFFFF0ll, {F, pre_nms_top_n})) return fail(c, VDET_EINVAL, "volume too large (F*pre_nms_top_n must stay below 2^31 - 16)");
+    if (decode_size_check(c, H, W)) return VDET_EINVAL;
+    if (!std::isfinite(min_size) || !std::isfinite(offset)) return fail(c, VDET_EINVAL, "min_size and offset must be finite");
+    if (use_dw_max && dw_max != dw_max) return fail(c, VDET_EINVAL, "dw_max must not be NaN");
+    if (score_frame_stride < N) return fail(c, VDET_EINVAL, "the scores' frame stride must be at least A*Hf*Wf elements");
+    if (F == 0) return VDET_OK;
+    if (!d_scores || !d_deltas || !d_anchors || !d_rois || !d_out_scores || !d_index || !d_count) return fail(c, VDET_EINVAL, "null buffer");
+    if (((uintptr_t)d_rois & 15) != 0) return fail(c, VDET_EINVAL, "d_rois must be 16-byte aligned");
+    const int pre = (int)pre_nms_top_n, post = (int)post_nms_top_n;
+    int p2 = 1;
+    while (p2 < pre) p2 <<= 1;
+    const size_t sel_lds = (size_t)p2 * 8;
+    if (sel_lds + 4096 > c->max_lds) return fail(c, VDET_EINVAL, "pre_nms_top_n = %d needs %zu B of LDS for the in-LDS sort", pre, sel_lds);
+    HIPCHK(c, hipSetDevice(c->device));
+    timing_reset(c);
+    if (!c->rpn_attr_set) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(rpn_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)std::min<size_t>((size_t)kRpnMaxPre * 8, c->max_lds - 4096)));
+        c->rpn_attr_set = true;
+    }
+    HIPCHK(c, c->rpn_keys.reserve((size_t)(F * N) * 4));
+    HIPCHK(c, c->rpn_boxes.reserve((size_t)(F * N) * 16));
+    HIPCHK(c, c->rpn_cbox.reserve((size_t)(F * pre) * 16));
+    HIPCHK(c, c->rpn_cscore.reserve((size_t)(F * pre) * 4));
+    HIPCHK(c, c->rpn_order.reserve((size_t)(F * pre) * 2));
+    HIPCHK(c, c->rpn_keep.reserve((size_t)(F * pre) * 4));
+    HIPCHK(c, c->rpn_keepcnt.reserve((size_t)F * 4));
+    if (!d_cand_index) { HIPCHK(c, c->rpn_cindex.reserve((size_t)(F * pre) * 4)); d_cand_index = c->rpn_cindex.as<int32_t>(); }
+    if (!d_cand_cnt) { HIPCHK(c, c->rpn_ccnt.reserve((size_t)F * 4)); d_cand_cnt = c->rpn_ccnt.as<int32_t>(); }
+
+    RpnDecodeArgs da{};
+    da.scores = d_scores; da.sstride = score_frame_stride; da.deltas = d_deltas; da.anchors = d_anchors;
+    da.A = (int)A; da.Hf = (int)Hf; da.Wf = (int)Wf; da.wtiles = (int)((Wf + 63) / 64); da.N = N;
+    da.stride = (double)stride; da.wmax = (double)(W - 1); da.hmax = (double)(H - 1); da.min_size = min_size; da.offset = offset;
+    da.use_dw_max = use_dw_max ? 1 : 0; da.dw_max = use_dw_max ? dw_max : 0.0;
+    da.keys = c->rpn_keys.as<uint32_t>(); da.boxes = c->rpn_boxes.as<float4>();
+    RpnSelectArgs sa{};
+    sa.keys = da.keys; sa.boxes = da.boxes; sa.scores = d_scores; sa.sstride = score_frame_stride; sa.A = (int)A; sa.HW = Hf * Wf; sa.N = N;
+    sa.pre = pre; sa.p2 = p2;
+    sa.cand_boxes = c->rpn_cbox.as<float4>(); sa.cand_scores = c->rpn_cscore.as<float>(); sa.cand_index = d_cand_index;
+    sa.order = c->rpn_order.as<uint16_t>(); sa.cand_cnt = d_cand_cnt;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(rpn_decode_kernel, dim3((unsigned)(F * Hf * da.wtiles)), dim3(256), 0, c->stream, da);
+    }
+    {
+        StageTimer tm(c, ST_SORT);
+        hipLaunchKernelGGL(rpn_select_kernel, dim3((unsigned)F), dim3(kRpnSelBlock), sel_lds, c->stream, sa);
+    }
+    HIPCHK(c, hipGetLastError());
+    // the candidates are the context's own scratch: a resident graph keyed on that address describes the call before
+    c->graph_valid = false;
+    const int rc = nms_volume_ordered_impl(c, c->rpn_cbox.as<float>(), sa.order, d_cand_cnt, F, pre, 1, nms_thresh, c->rpn_keep.as<int32_t>(),
+                                           c->rpn_keepcnt.as<int32_t>(), pre, true);      // (cap = pre: the cut at post is the gather's, no VDET_ECAP)
+    c->graph_valid = false;
+    if (rc) return rc;
+    RpnGatherArgs ga{};
+    ga.cand_boxes = sa.cand_boxes; ga.cand_scores = sa.cand_scores; ga.cand_index = d_cand_index;
+    ga.keep = c->rpn_keep.as<int32_t>(); ga.keep_cnt = c->rpn_keepcnt.as<int32_t>();
+    ga.F = F; ga.pre = pre; ga.post = post;
+    ga.rois = reinterpret_cast<float4 *>(d_rois); ga.scores = d_out_scores; ga.index = d_index; ga.count = d_count;
+    {
+        StageTimer tm(c, ST_OTHER);
+        hipLaunchKernelGGL(rpn_gather_kernel, dim3((unsigned)((F * post + 255) / 256)), dim3(256), 0, c->stream, ga);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VDET_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -323,6 +323,113 @@ def dets_as_tracks(dets, sel_idx, keep, keep_cnt, first_class=1, sync=True, ctx=
     return out
 
 
+def generate_anchors(base_size=16, ratios=(0.5, 1, 2), scales=(8, 16, 32)):
+    """The anchor table of a region proposal network on the host: float64 [A,4], ratio-major (A = len(ratios) * len(scales)),
+    ``np.round`` on the ratio widths and heights -- tests/rpn_spec.py's function (the public py-faster-rcnn
+    ``generate_anchors.py`` restated).  The defaults give the nine anchors (-84,-40,99,55) .. (-168,-344,183,359)."""
+    ratios, scales = np.asarray(ratios, np.float64).reshape(-1), np.asarray(scales, np.float64).reshape(-1)
+    size = np.float64(base_size)
+    ctr = np.float64(0.5) * (size - 1)
+    ws = np.round(np.sqrt(size * size / ratios))
+    hs = np.round(ws * ratios)
+    ws = (ws[:, None] * scales[None, :]).reshape(-1)
+    hs = (hs[:, None] * scales[None, :]).reshape(-1)
+    return np.stack([ctr - 0.5 * (ws - 1), ctr - 0.5 * (hs - 1), ctr + 0.5 * (ws - 1), ctr + 0.5 * (hs - 1)], axis=1)
+
+
+RPN_MAX_ANCHORS, RPN_MAX_PRE = 64, 16384
+
+
+def _rpn_common(scores, deltas, anchors, stride, pre, post, min_size, offset, dw_max):
+    """The checks of rpn_proposals: (F, A, Hf, Wf, the scores' frame stride, anchors on the device, scalars)."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 4:
+        raise ValueError("scores must be a float32 tensor [F,A,Hf,Wf]")
+    if not torch.is_tensor(deltas) or deltas.dtype != torch.float32 or deltas.dim() != 4:
+        raise ValueError("deltas must be a float32 tensor [F,4A,Hf,Wf]")
+    F, A, Hf, Wf = scores.shape
+    if tuple(deltas.shape) != (F, 4 * A, Hf, Wf):
+        raise ValueError("deltas must be [F,4A,Hf,Wf] for scores [F,A,Hf,Wf]")
+    if not scores.is_cuda:
+        raise ValueError("expected a CUDA/HIP tensor (vdetlib_amd has no CPU path)")
+    if not 1 <= A <= RPN_MAX_ANCHORS:
+        raise ValueError("A = %d anchors per cell; 1 .. %d" % (A, RPN_MAX_ANCHORS))
+    if Hf < 1 or Wf < 1 or Hf * Wf * A >= 2 ** 24:
+        raise ValueError("the feature map must be Hf, Wf >= 1 with Hf*Wf*A below 2^24")
+    if F * Hf * Wf * A >= 2 ** 31 - 16:
+        raise ValueError("volume too large (F*Hf*Wf*A must stay below 2^31 - 16)")
+    if torch.is_tensor(anchors):
+        if anchors.dtype != torch.float64 or tuple(anchors.shape) != (A, 4):
+            raise ValueError("anchors must be float64 [A,4]")
+        if anchors.is_cuda and anchors.device != scores.device:
+            raise ValueError("scores, deltas and anchors must be on the same GPU")
+        anchors = anchors.to(scores.device).contiguous()
+    else:
+        anchors = np.asarray(anchors)
+        if anchors.dtype != np.float64 or anchors.shape != (A, 4):
+            raise ValueError("anchors must be float64 [A,4]")
+        anchors = torch.from_numpy(np.array(anchors)).to(scores.device)
+    if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1 or int(stride) >= 2 ** 31:
+        raise ValueError("stride must be an integer >= 1")
+    if isinstance(pre, float) or isinstance(post, float) or not 1 <= int(post) <= int(pre) <= RPN_MAX_PRE:
+        raise ValueError("1 <= post_nms_top_n <= pre_nms_top_n <= %d" % RPN_MAX_PRE)
+    if F * int(pre) >= 2 ** 31 - 16:
+        raise ValueError("volume too large (F*pre_nms_top_n must stay below 2^31 - 16)")
+    min_size, offset = float(min_size), float(offset)
+    if not math.isfinite(min_size) or not math.isfinite(offset):
+        raise ValueError("min_size and offset must be finite")
+    if dw_max is not None and math.isnan(float(dw_max)):
+        raise ValueError("dw_max must not be NaN")
+    # the foreground half cls[:, A:] of a contiguous [F,2A,Hf,Wf] tensor goes in as it is: only the frame stride is free
+    st = scores.stride()
+    if F * A * Hf * Wf and (st[1:] != (Hf * Wf, Wf, 1) or (F > 1 and st[0] < A * Hf * Wf)):
+        scores = scores.contiguous()
+    sstride = scores.stride(0) if F > 1 else A * Hf * Wf
+    return scores, anchors, F, A, Hf, Wf, sstride, int(stride), int(pre), int(post), min_size, offset
+
+
+def rpn_proposals(scores, deltas, anchors, im_size, stride=16, pre_nms_top_n=6000, post_nms_top_n=300, nms_thresh=0.7, min_size=16,
+                  offset=1.0, dw_max=None, return_candidates=False, sync=True, ctx=None):
+    """The proposal layer of a region proposal network on the device (include/vdet_hip.h: vdet_rpn_proposals): anchors, decode,
+    clip, size filter, top-N, NMS, top-N for every frame of the call -- the boxes of the Faster R-CNN route.  The rule is
+    tests/rpn_spec.py, bit for bit; it RESTATES the public py-faster-rcnn proposal layer, which was not at hand.
+
+    scores [F,A,Hf,Wf] f32: the foreground scores, logits or probabilities (only the ranking is used); the slice ``cls[:, A:]``
+    of a contiguous [F,2A,Hf,Wf] tensor is read in place.  deltas [F,4A,Hf,Wf] f32 (channel 4a+k: component k of anchor a),
+    anchors float64 [A,4] (``generate_anchors``; numpy or tensor), im_size (H, W) of the network's input, ``stride`` the feature
+    stride.  The candidate of flat index ``n = (h*Wf + w)*A + a`` is ``anchors[a] + (w,h,w,h)*stride`` decoded as
+    ``decode_boxes`` does, with the width term ``(x2 - x1) + offset`` (1.0: the RPN's pixel convention; 1e-14 is
+    ``decode_boxes``') and, with ``dw_max``, a dw / dh greater than it clamped to it.  It is valid when its score is not NaN and
+    both sides of the clipped f32 box, plus 1, reach ``min_size``.  Valid candidates by descending score, equal scores by
+    DESCENDING n; the first ``pre_nms_top_n`` (at most 16384) go through greedy NMS at ``nms_thresh`` (utils/nms.pyx's arithmetic)
+    and the first ``post_nms_top_n`` survivors are the proposals.
+
+    Returns a dict: ``rois`` [F,post,4] f32, ``scores`` [F,post] f32 (both NaN behind the count), ``index`` [F,post] int32 (n; -1
+    behind the count), ``count`` [F] int32; with ``return_candidates`` also ``cand_index`` [F,pre] int32 (the candidates in
+    order, -1 behind) and ``cand_cnt`` [F].  ``rois.view(-1, 4)`` with an image index feeds ``roi_pool`` (a NaN row: ok = 0 and a
+    zero block), ``rois`` feeds ``det_nms_volume_deltas`` as its NaN-padded rois.  ValueError for a bad dtype, shape, device or
+    limit, before any launch.  No CPU fallback."""
+    H, W = _im_size(im_size)
+    scores, anchors, F, A, Hf, Wf, sstride, stride, pre, post, min_size, offset = _rpn_common(
+        scores, deltas, anchors, stride, pre_nms_top_n, post_nms_top_n, min_size, offset, dw_max)
+    _same_gpu((scores, deltas), "scores and deltas")
+    deltas = deltas.contiguous()
+    dev = scores.device
+    out = dict(rois=torch.empty((F, post, 4), dtype=torch.float32, device=dev),
+               scores=torch.empty((F, post), dtype=torch.float32, device=dev),
+               index=torch.empty((F, post), dtype=torch.int32, device=dev),
+               count=torch.empty((F,), dtype=torch.int32, device=dev))
+    if return_candidates:
+        out['cand_index'] = torch.empty((F, pre), dtype=torch.int32, device=dev)
+        out['cand_cnt'] = torch.empty((F,), dtype=torch.int32, device=dev)
+    ctx = _ctx_for(scores, ctx)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+    _finish(ctx, lambda: ctx.check(ctx.lib.vdet_rpn_proposals(
+        ctx.h, ptr(scores), sstride, ptr(deltas), ptr(anchors), F, A, Hf, Wf, H, W, stride, pre, post, float(nms_thresh), min_size,
+        offset, 0 if dw_max is None else 1, 0.0 if dw_max is None else float(dw_max), ptr(out['rois']), ptr(out['scores']),
+        ptr(out['index']), ptr(out['count']), ptr(out.get('cand_index')), ptr(out.get('cand_cnt')))), sync)
+    return out
+
+
 def nms_volume_ordered(boxes, order, ncand, thresh=0.3, cap=None, ctx=None, pad=True):
     """``nms_volume`` walking the CALLER's lists: order int16/uint16 [F,C,B] (box indices, e.g. ``argsort_volume``'s with
     ties rearranged as some machine's unstable ``scores.argsort()[::-1]`` left them, utils/nms.pyx:25), ncand int32 [F,C]

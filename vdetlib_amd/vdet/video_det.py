@@ -55,7 +55,8 @@ def det_vid_with_box(vid_proto, box_proto, det_fun, net, class_names=imagenet_vd
 
 def det_vid_without_box(vid_proto, det_fun, net, class_names=imagenet_vdet_classes):
     """Reference :34-40 generates the proposals with MATLAB selective search (vdet/proposal.py), an external
-    engine outside this build: supply a box_proto."""
+    engine outside this build: supply a box_proto (``proposal.rpn_vid_proposals`` makes one with a region proposal network;
+    ``faster_rcnn_det_vid_device`` is the route that needs none)."""
     raise RuntimeError("region proposals are an external engine (MATLAB selective search, "
                        "reference vdet/proposal.py); call det_vid_score with a box_proto")
 
@@ -222,12 +223,69 @@ def fast_rcnn_det_vid_device(net, vid_proto, box_proto, class_names=imagenet_vde
         for k, (rois, scores, deltas, _) in enumerate(rows):
             n = len(rois)
             v_rois[k, :n], v_scores[k, :n], v_deltas[k, :n] = rois, scores, deltas
-        dets, _, det_cnt, keep, keep_cnt = ops.det_nms_volume_deltas(
-            v_rois, v_scores, v_deltas, im_size, score_thresh=thresh, topk=max_per_image,
-            nms_thresh=0.3 if nms_thresh is None else nms_thresh, first_class=1)
-        dets, det_cnt, keep, keep_cnt = (t.cpu().numpy() for t in (dets, det_cnt, keep, keep_cnt))
-        for k in range(Fc):
-            for j in range(1, num_classes):
-                all_boxes[j][i0 + k] = dets[k, j, :det_cnt[k, j]].copy()
-                keeps[j][i0 + k] = keep[k, j, :keep_cnt[k, j]].tolist()
+        _chunk_dets(all_boxes, keeps, i0, v_rois, v_scores, v_deltas, im_size, thresh, max_per_image, nms_thresh)
+    return all_boxes if nms_thresh is None else (all_boxes, keeps)
+
+
+def _chunk_dets(all_boxes, keeps, i0, v_rois, v_scores, v_deltas, im_size, thresh, max_per_image, nms_thresh):
+    """the per-class selection, decode and NMS of a chunk's frames (``ops.det_nms_volume_deltas``) into the frames' lists"""
+    from .. import ops
+    dets, _, det_cnt, keep, keep_cnt = ops.det_nms_volume_deltas(
+        v_rois, v_scores, v_deltas, im_size, score_thresh=thresh, topk=max_per_image,
+        nms_thresh=0.3 if nms_thresh is None else nms_thresh, first_class=1)
+    dets, det_cnt, keep, keep_cnt = (t.cpu().numpy() for t in (dets, det_cnt, keep, keep_cnt))
+    for k in range(len(dets)):
+        for j in range(1, dets.shape[1]):
+            all_boxes[j][i0 + k] = dets[k, j, :det_cnt[k, j]].copy()
+            keeps[j][i0 + k] = keep[k, j, :keep_cnt[k, j]].tolist()
+
+
+def faster_rcnn_det_vid_device(net, vid_proto, class_names=imagenet_vdet_classes, max_per_image=100, thresh=0.05, nms_thresh=None,
+                               chunk=8, images=None, pre_nms_top_n=6000, post_nms_top_n=300, rpn_nms_thresh=0.7, min_size=16,
+                               dw_max=None):
+    """``fast_rcnn_det_vid_device`` without a ``box_proto`` -- the Faster R-CNN route: the proposals
+    are the net's own, made on the device by ``ops.rpn_proposals`` and handed on as they are.  Per chunk of frames: backbone
+    and ``net.rpn`` frame by frame (``proposal.rpn_chunk``), the proposal layer for the chunk, then per frame
+    ``ops.roi_pool(box_scale=1.0)`` on the frame's proposals (they are in the scaled image's coordinates already) and
+    ``net.head``, and ``ops.det_nms_volume_deltas`` on ``rois / im_scale``.  No box visits the host; the per-frame proposal
+    COUNTS do, once per chunk, so that the head sees the rows ``fast_rcnn_det_vid_device`` would give it.
+
+    ``net`` is ``proposal.rpn_vid_proposals``'; the RPN's settings are the trailing arguments.  Returns what
+    ``fast_rcnn_det_vid_device`` returns -- and, where ``im_scale`` is a power of two, the very bits it returns when fed
+    ``proposal.rpn_vid_proposals(..., integer_boxes=False)``."""
+    import torch
+    from .. import _lib, ops
+    from .proposal import rpn_chunk
+    _lib.get_context()        # no library or no GPU: RuntimeError
+    frames = vid_proto['frames']
+    num_classes = len(class_names)
+    max_per_image, chunk = int(max_per_image), max(int(chunk), 1)
+    if not 1 <= max_per_image <= 128:
+        raise ValueError("max_per_image = %d; the per-class NMS on the device takes 1..128 boxes per (frame, class)" % max_per_image)
+    all_boxes = [[np.zeros((0, 5), np.float32) if j else [] for _ in frames] for j in range(num_classes)]
+    keeps = [[[] for _ in frames] for _ in range(num_classes)]
+    im_size = None
+    for i0 in range(0, len(frames), chunk):
+        ims = [images[fr['frame']] if images is not None else imread(frame_path_at(vid_proto, fr['frame'])) for fr in frames[i0:i0 + chunk]]
+        for im in ims:
+            if im_size is None:
+                im_size = tuple(np.shape(im)[:2])
+            elif tuple(np.shape(im)[:2]) != im_size:
+                raise ValueError("faster_rcnn_det_vid_device: the frames of a video must share one size")
+        feats, prop, im_scale = rpn_chunk(net, ims, pre_nms_top_n, post_nms_top_n, rpn_nms_thresh, min_size, dw_max)
+        rois, count = prop['rois'], prop['count'].cpu().tolist()
+        Fc, B, dev = rois.shape[0], rois.shape[1], rois.device
+        nan = float('nan')
+        v_rois = rois.double() / im_scale                 # (NaN behind the counts stays NaN)
+        v_scores = torch.full((Fc, B, num_classes), nan, dtype=torch.float32, device=dev)
+        v_deltas = torch.zeros((Fc, B, 4 * num_classes), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for k, n in enumerate(count):
+                out = ops.roi_pool(feats[k], rois[k, :n], spatial_scale=net.spatial_scale, pooled=net.pooled, box_scale=1.0,
+                                   mode=getattr(net, 'roi_mode', 'max'), sampling=getattr(net, 'sampling', 2),
+                                   aligned=getattr(net, 'aligned', False))
+                scores, deltas = net.head(out['pooled'])
+                v_scores[k, :n] = scores.detach()[:, :num_classes].float()
+                v_deltas[k, :n] = deltas.detach()[:, :4 * num_classes].float()
+        _chunk_dets(all_boxes, keeps, i0, v_rois, v_scores, v_deltas, im_size, thresh, max_per_image, nms_thresh)
     return all_boxes if nms_thresh is None else (all_boxes, keeps)
